@@ -20,11 +20,21 @@ K = ONE part whose features are key-sharded over the ranks, every rank looks all
 location lists to the reads' owner ranks, union + candidates there (mc_candidates_from_partial_hits), gather to rank 0.
 `--pairs` = configs[3]'s reads: 2 x 150 bp pairs (fragment 300-500, seed 4100, maxWindowsInRange 4); a pair counts as 2 reads.
 
-Checker legs (rank 0, N = 1, after the timed region; oracle/ is loaded only here):
+A plain run sets up, warms up, times the K steps once and prints the headline line (value, ms_per_step, config).  Everything else
+runs only with `--full`:
+  roofline      per-kernel HIP-event timers over the timed region, the random-access microbenchmark (--gather-gib), the kernels
+                once more one batch at a time, the committed PMC summaries; `value_range` from --repeats timed regions.
+  host_fed      the same batches from pinned host memory (--host-fed).
+Checker legs (rank 0, N = 1, after the timed region, `--full` only; oracle/ is loaded only here):
   parity        the C oracle builds the buckets of a read sample's features ITSELF from the same collection (mco_db_build) and
                 classifies the sample; every candidate is compared with the GPU's.  configs[1]: the reference (oracle/_ref) on the
                 database files this repo wrote.
-  cpu_baseline  the same checker timed on the host cores, thread sweep, best value.
+  cpu_baseline  the same checker timed on the host cores, thread sweep, best value (+ reference_calibration, --calibrate-scale).
+  multi_gpu_selfcheck, e2e (see their options).
+
+`--dump-outputs DIR`: after the timed steps, the candidates of the last timed step (what a caller of the path receives: target, hits,
+first and last window per candidate slot) for a fixed, seeded sample of the reads, as DIR/<name>.npy in float64 (at most
+DUMP_MAX_BYTES in all).
 
 Prints ONE JSON line on rank 0.
 """
@@ -50,6 +60,8 @@ from metacache_amd import api, synth, synthdb  # noqa: E402
 from metacache_amd.distributed import gather_candidates_async  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E peak (MI355X_MICROARCH.md)
+DUMP_MAX_BYTES = 48 << 20      # --dump-outputs: all files together
+DUMP_SEED = 7
 READ_LEN = 150
 PAD_LEN = 152                  # every read starts 4-byte aligned
 KERNELS = ("plan", "sketch_probe", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128",
@@ -680,6 +692,20 @@ def run_multi_gpu_selfcheck(world: int, budget_s: float) -> dict:
         return {"ranks_seen": world, "ok": False, "error": repr(e)}
 
 
+def dump_outputs(out_dir: str, cands: torch.Tensor):
+    """--dump-outputs: cands = [rows, K, 4] int32 device tensor of the last timed step (api.cand_dtype fields tgt, hits, beg, end per
+    slot).  A fixed, seeded sample of the rows (all of them where they fit DUMP_MAX_BYTES) goes to out_dir as float64 arrays
+    (exact for every 32-bit field), one file per field, plus the sampled rows' numbers."""
+    rows, K = int(cands.shape[0]), int(cands.shape[1])
+    n = min(rows, DUMP_MAX_BYTES // (K * 4 * 8 + 8))
+    idx = np.arange(rows) if n == rows else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, n, replace=False))
+    c = cands[torch.from_numpy(idx).to(cands.device)].cpu().numpy().view(np.uint32).reshape(n, K, 4)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+    for f, name in enumerate(api.cand_dtype.names):
+        np.save(os.path.join(out_dir, f"cand_{name}.npy"), c[..., f].astype(np.float64))
+
+
 def self_launch_command(argv, gpus, port):
     """the command `python bench.py --gpus N <args>` re-executes itself as when it is not already a rank of a process group"""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
@@ -742,7 +768,13 @@ def main():
                     "where the box's memory allowance does not hold the full-scale file set; 0 = skip")
     ap.add_argument("--e2e-seconds", type=float, default=330.0, help="time limit of that process (it takes 140-200 s at full scale: 100 s to build and write the 174 GB file set, "
                     "20 + 10 s of loading for the two mcq runs)")
+    ap.add_argument("--full", action="store_true", help="also everything beyond the headline figure: roofline (kernel timers, --gather-gib, solo kernels, PMC "
+                    "summaries), --repeats, host_fed, the checker legs (parity, cpu_baseline, reference calibration), multi_gpu_selfcheck and e2e")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the candidates of the last timed step (a fixed, seeded sample of the "
+                    f"reads, at most {DUMP_MAX_BYTES >> 20} MiB in all) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.reference_files and not args.full:
+        sys.exit("--reference-files feeds the checker legs: only with --full")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -762,7 +794,7 @@ def main():
 
     if args.gather_gib < 0:
         args.gather_gib = 64.0 if args.config == 2 else 0.6
-    peak = gather_peak(args.gather_gib) if rank == 0 and args.gather_gib > 0 else None
+    peak = gather_peak(args.gather_gib) if args.full and rank == 0 and args.gather_gib > 0 else None
     K = args.maxcand
     cfg = args.config
     B = args.batch or ((250_000 if args.long_reads else 2_500_000 if args.pairs else 5_000_000) if cfg == 2 else 10_000_000)   # (5 M PAIRS ask for 2^32 pool entries per pipe: beyond the device)
@@ -786,7 +818,7 @@ def main():
         for i, gnm in enumerate(genomes):
             bld.add_target(gnm, f"SYN_{i:06d}.1", parent_taxid=1000 + i, filename=f"syn{i}.fa")
         db = bld.finish(load=True)
-        if rank == 0 and args.cpu_seconds > 0 and world == 1:
+        if args.full and rank == 0 and args.cpu_seconds > 0 and world == 1:
             dbdir = tempfile.mkdtemp(prefix="mcbench")
             taxa = [(1, 1, 20, "root")] + [(1000 + i, 1, 4, f"synthetic species {i}") for i in range(args.genomes)]
             bld.write(os.path.join(dbdir, "syn16"), taxa)
@@ -969,8 +1001,9 @@ def main():
     drain()
     torch.cuda.synchronize()
     first_batch[0] = args.warmup
-    db.timing(True)
-    db.timing_reset()
+    if args.full:
+        db.timing(True)
+        db.timing_reset()
 
     def timed_region():
         if world > 1:
@@ -992,44 +1025,70 @@ def main():
         return el
 
     elapsed = timed_region()                                 # THE timed region: exactly K steps, max over ranks -> value
-    db.timing(False)
-    kt_timed = {k: db.timing_get(k) for k in KERNELS + (KERNELS_MODE_K if mode == "K" else ())} if rank == 0 else {}
-    repeats = [elapsed] + [timed_region() for _ in range(max(0, args.repeats - 1))]   # the same K steps again: the spread (value_range)
-    # per-kernel durations WITHOUT another batch's kernels beside them: a few steps one batch at a time (two batches in flight share the
-    # device, the HIP events of the timed region bracket that sharing too)
-    kt_solo = None
-    if pipelined and rank == 0:
-        db.timing(True); db.timing_reset()
-        for i in range(min(3, args.steps)):
-            if args.long_reads:
-                lb = long_batches[i % nb]
-                r = db.query_device(lb["seq"].data_ptr(), lb["qinfo"].data_ptr(), nloc, lb["nchars"], max_win_ptr=lb["maxwin"].data_ptr())
-            else:
-                r = db.query_device(batches[i % nb].data_ptr(), qinfo.data_ptr(), nloc, nchars, max_win_uniform=max_win)
-            db.copy_results(out_bufs[0].data_ptr(), r.cands, nloc * K * 16)
-            db.synchronize()
+    last = (args.warmup + args.steps - 1) % nbuf              # the buffer that holds the last timed step's candidates
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, torch.cat(recv[last]) if recv is not None else out_bufs[last])
+    host_fed = kt_solo = kstats = None
+    repeats = [elapsed]
+    if args.full:
         db.timing(False)
-        kt_solo = {k: db.timing_get(k) for k in KERNELS}
-    host_fed = None
-    if pipelined and world == 1 and args.host_fed and not args.force_dist:
-        host_fed = host_fed_leg(db, batches if not args.long_reads else None, long_batches if args.long_reads else None, qinfo, nloc, nchars, max_win, K, args.steps, args.warmup, nb,
-                                2 if pairs else 1, elapsed / args.steps)
-    kstats = None
-    if mode == "K" and rank == 0 and world == 1:
-        # (the owner-side call resets the shard side's statistics: one more lookup pass for F and H of the line)
-        db.query_device(batches[0].data_ptr(), qinfo.data_ptr(), nloc, nchars, max_win_uniform=max_win, want_partial_hits=not numbers_wire, want_partial_numbers=numbers_wire)
-        db.synchronize()
-        kstats = db.last_batch_stats()
+        kt_timed = {k: db.timing_get(k) for k in KERNELS + (KERNELS_MODE_K if mode == "K" else ())} if rank == 0 else {}
+        repeats += [timed_region() for _ in range(max(0, args.repeats - 1))]   # the same K steps again: the spread (value_range)
+        # per-kernel durations WITHOUT another batch's kernels beside them: a few steps one batch at a time (two batches in flight share the
+        # device, the HIP events of the timed region bracket that sharing too)
+        if pipelined and rank == 0:
+            db.timing(True); db.timing_reset()
+            for i in range(min(3, args.steps)):
+                if args.long_reads:
+                    lb = long_batches[i % nb]
+                    r = db.query_device(lb["seq"].data_ptr(), lb["qinfo"].data_ptr(), nloc, lb["nchars"], max_win_ptr=lb["maxwin"].data_ptr())
+                else:
+                    r = db.query_device(batches[i % nb].data_ptr(), qinfo.data_ptr(), nloc, nchars, max_win_uniform=max_win)
+                db.copy_results(out_bufs[0].data_ptr(), r.cands, nloc * K * 16)
+                db.synchronize()
+            db.timing(False)
+            kt_solo = {k: db.timing_get(k) for k in KERNELS}
+        if pipelined and world == 1 and args.host_fed and not args.force_dist:
+            host_fed = host_fed_leg(db, batches if not args.long_reads else None, long_batches if args.long_reads else None, qinfo, nloc, nchars, max_win, K, args.steps, args.warmup, nb,
+                                    2 if pairs else 1, elapsed / args.steps)
+        if mode == "K" and rank == 0 and world == 1:
+            # (the owner-side call resets the shard side's statistics: one more lookup pass for F and H of the line)
+            db.query_device(batches[0].data_ptr(), qinfo.data_ptr(), nloc, nchars, max_win_uniform=max_win, want_partial_hits=not numbers_wire, want_partial_numbers=numbers_wire)
+            db.synchronize()
+            kstats = db.last_batch_stats()
     if world > 1:
         dist.barrier()
 
     if rank == 0:
+        per_read = 2 if pairs else 1                           # a pair counts as 2 reads (printing.cpp:605-608)
+        total_reads = world * args.steps * B * per_read
+        value = total_reads / elapsed * 60.0 / 1e6
+        result = {
+            "metric": "Mreads/min (long reads: 200-19000 bp, median 480)" if args.long_reads else "Mreads/min (150 bp)",
+            "value": round(value, 2), "unit": "Mreads/min", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": workload, "reads_per_step_per_gpu": B,
+                       "maxcand": K, "k": db.k, "sketchlen": db.s, "winlen": db.w, "winstride": db.stride,
+                       "db_targets": db_info[5], "db_locations": db_info[7], "db_build_s": round(build_s, 2), "db_build": build_info, "load_factor": lf,
+                       "hbm_used_GB": round((torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0]) / 1e9, 1),
+                       "mode": mode, "pairs": pairs,
+                       "parallelism": {"R": f"replicated DB x{world}, reads sharded, RCCL gather of top candidates",
+                                       "P": f"{world} parts, one per GPU; all reads against every part, RCCL all-gather of per-part candidates, merge",
+                                       "K": f"1 part key-sharded over {world} GPUs; every shard looks up the features it owns for all reads, RCCL all-to-all-v of the partial "
+                                            f"location lists ({args.wire} bytes per location), candidates on the read's owner, gather"}[mode],
+                       "batches_in_flight": 2 if pipelined else 1},
+        }
+        if args.long_reads:
+            tot_bases = sum(long_batches[(args.warmup + i) % nb]["bases"] for i in range(args.steps))
+            result["config"]["Gbases_per_s"] = round(world * tot_bases / elapsed / 1e9, 3)
+            result["config"]["mean_read_len"] = round(tot_bases / (args.steps * B), 1)
+    if rank == 0 and args.full:
         kt = kt_timed                                         # HIP events over THE timed region
         st = kstats or db.last_batch_stats()                  # of the last batch that went through the first pipe
         layout = db.table_layout()
         if cfg != 1:
             V = layout["location_bytes"]                       # SURVEY's V = bytes per location as the table holds them: 4 with the compact store
-        per_read = 2 if pairs else 1                           # a pair counts as 2 reads (printing.cpp:605-608)
         F, H = st["features"] / (nloc * per_read), st["locations"] / (nloc * per_read)
         bytes_per_read = algorithmic_bytes_per_read(F, H, K, V)
         if args.long_reads:                                    # SURVEY's formula with the reads' own lengths: ceil(L/4) + ceil(L/8) summed over the last timed batch
@@ -1050,43 +1109,25 @@ def main():
             if not same:                                       # a request count of another table layout is not this run's traffic
                 traffic, traffic_src, traffic_detail = None, None, {"refused": why}
         _, pmc_kernels = _pmc_rows(dom, pmc_tag)
-        total_reads = world * args.steps * B * per_read
-        value = total_reads / elapsed * 60.0 / 1e6
-        result = {
-            "metric": "Mreads/min (long reads: 200-19000 bp, median 480)" if args.long_reads else "Mreads/min (150 bp)",
-            "value": round(value, 2), "unit": "Mreads/min", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": workload, "reads_per_step_per_gpu": B,
-                       "maxcand": K, "k": db.k, "sketchlen": db.s, "winlen": db.w, "winstride": db.stride,
-                       "db_targets": db_info[5], "db_locations": db_info[7], "db_build_s": round(build_s, 2), "db_build": build_info, "load_factor": lf,
-                       "hbm_used_GB": round((torch.cuda.mem_get_info()[1] - torch.cuda.mem_get_info()[0]) / 1e9, 1),
-                       "mode": mode, "pairs": pairs,
-                       "parallelism": {"R": f"replicated DB x{world}, reads sharded, RCCL gather of top candidates",
-                                       "P": f"{world} parts, one per GPU; all reads against every part, RCCL all-gather of per-part candidates, merge",
-                                       "K": f"1 part key-sharded over {world} GPUs; every shard looks up the features it owns for all reads, RCCL all-to-all-v of the partial "
-                                            f"location lists ({args.wire} bytes per location), candidates on the read's owner, gather"}[mode]},
-            "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6),
-                         # the same bytes over the WHOLE step (all kernels, launches, the copy of the candidates)
-                         "step_frac": round(bytes_per_read * nloc * per_read / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 6),
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_detail": traffic_detail,
-                         # like for like with `traffic`: the dominant kernel's OWN share of the algorithmic bytes (kernel_bytes_per_read)
-                         # the kernel's whole name as the rocprofv3 summaries carry it (template arguments and all), where a summary of this workload exists
-                         "kernel_name": "mcamd::" + (sorted(pmc_kernels)[0] if pmc_kernels else KERNEL_FULL.get(dom, KERNEL_OF.get(dom, (dom,))[0])),
-                         "kernel_algorithmic_bytes": None if kbytes is None else round(kbytes),
-                         "kernel_frac": None if kbytes is None else round(kbytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
-                         "traffic_over_kernel_bytes": None if (kbytes is None or traffic is None) else round(traffic / kbytes, 3),
-                         "algorithmic_bytes_per_launch": round(bytes_per_read * nloc * per_read),
-                         "bytes_per_read": round(bytes_per_read, 1), "F": round(F, 3), "H": round(H, 3), "V": V,
-                         "table_location_bytes": layout["location_bytes"], "table_list_align": layout.get("list_align", 1), "table_list_entries": layout["list_locations"],
-                         "table_direct_index": bool(layout.get("direct_index", False)),
-                         "kernel_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in kt.items()}},
-        }
+        result["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBS, 6),
+                              # the same bytes over the WHOLE step (all kernels, launches, the copy of the candidates)
+                              "step_frac": round(bytes_per_read * nloc * per_read / (elapsed / args.steps) / 1e9 / HBM_PEAK_GBS, 6),
+                              "traffic": traffic, "traffic_source": traffic_src, "traffic_detail": traffic_detail,
+                              # like for like with `traffic`: the dominant kernel's OWN share of the algorithmic bytes (kernel_bytes_per_read)
+                              # the kernel's whole name as the rocprofv3 summaries carry it (template arguments and all), where a summary of this workload exists
+                              "kernel_name": "mcamd::" + (sorted(pmc_kernels)[0] if pmc_kernels else KERNEL_FULL.get(dom, KERNEL_OF.get(dom, (dom,))[0])),
+                              "kernel_algorithmic_bytes": None if kbytes is None else round(kbytes),
+                              "kernel_frac": None if kbytes is None else round(kbytes / (dom_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 6),
+                              "traffic_over_kernel_bytes": None if (kbytes is None or traffic is None) else round(traffic / kbytes, 3),
+                              "algorithmic_bytes_per_launch": round(bytes_per_read * nloc * per_read),
+                              "bytes_per_read": round(bytes_per_read, 1), "F": round(F, 3), "H": round(H, 3), "V": V,
+                              "table_location_bytes": layout["location_bytes"], "table_list_align": layout.get("list_align", 1), "table_list_entries": layout["list_locations"],
+                              "table_direct_index": bool(layout.get("direct_index", False)),
+                              "kernel_ms": {k: round(v[0] / max(v[1], 1), 4) for k, v in kt.items()}}
         vals = [total_reads / e * 60.0 / 1e6 for e in repeats]
         result["value_range"] = [round(min(vals), 1), round(max(vals), 1)]
         result["repeats_ms_per_step"] = [round(e / args.steps * 1e3, 3) for e in repeats]
-        result["config"]["batches_in_flight"] = 2 if pipelined else 1
         if host_fed is not None:
             result["host_fed"] = host_fed
         if kt_solo is not None:
@@ -1112,10 +1153,6 @@ def main():
             else:
                 ra["requests_per_s"] = None; ra["frac"] = None
             result["roofline"]["random_access"] = ra
-        if args.long_reads:
-            tot_bases = sum(long_batches[(args.warmup + i) % nb]["bases"] for i in range(args.steps))
-            result["config"]["Gbases_per_s"] = round(world * tot_bases / elapsed / 1e9, 3)
-            result["config"]["mean_read_len"] = round(tot_bases / (args.steps * B), 1)
         first_batch[0] = 0                                    # the checker legs look at batch 0
         if world == 1 and args.cpu_seconds > 0 and args.long_reads:
             cb, par = cpu_leg_long_reads(spec, db, long_batches[0], K, args.parity_reads, args.cpu_seconds, lambda: (step(0), drain(), db.synchronize()), out_cands)
@@ -1140,7 +1177,7 @@ def main():
             result["cpu_baseline"] = cb
             result["parity"] = par
     db.close()
-    if rank == 0 and world == 1 and cfg == 2 and mode == "R" and not pairs and not args.long_reads and args.cpu_seconds > 0 and args.calibrate_scale > 0 \
+    if args.full and rank == 0 and world == 1 and cfg == 2 and mode == "R" and not pairs and not args.long_reads and args.cpu_seconds > 0 and args.calibrate_scale > 0 \
             and "cpu_baseline" in result and not args.reference_files:
         torch.cuda.empty_cache()
         cal = reference_calibration(args.calibrate_scale, K, lf, local, args.cpu_seconds)
@@ -1150,7 +1187,7 @@ def main():
             result["cpu_baseline"]["reference_calibration"] = cal
     # ---- the sharded forms of the path on THESE N GPUs, checked against the oracle (outside every timing): its own job, rank 0 starts it
     # and the other ranks wait for it at the rendezvous store -- on the host, their GPUs are free for the job's ranks
-    if cfg == 2 and mode == "R" and args.selfcheck_seconds > 0 and (world > 1 or args.cpu_seconds > 0):
+    if args.full and cfg == 2 and mode == "R" and args.selfcheck_seconds > 0 and (world > 1 or args.cpu_seconds > 0):
         batches = out_bufs = None
         torch.cuda.empty_cache()
         store = dist.distributed_c10d._get_default_store() if dist.is_initialized() else None
@@ -1164,7 +1201,7 @@ def main():
                 store.wait(["mc_selfcheck_done"], timedelta(seconds=args.selfcheck_seconds + 120))
             except Exception:                                   # noqa: BLE001
                 pass
-    if rank == 0 and world == 1 and cfg == 2 and mode == "R" and not pairs and not args.long_reads and args.scale == 1.0 and args.shape == "default" \
+    if args.full and rank == 0 and world == 1 and cfg == 2 and mode == "R" and not pairs and not args.long_reads and args.scale == 1.0 and args.shape == "default" \
             and args.cpu_seconds > 0 and args.e2e_scale > 0:
         batches = out_bufs = mates = None                       # (the device belongs to the mcq processes now)
         torch.cuda.empty_cache()
