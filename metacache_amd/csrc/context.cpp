@@ -816,15 +816,15 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
     const uint32_t n = b.n;
     if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
     uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
-    if (!counterCopied) launch_words_to_host(nsorted, ws.midCount + 13, 1, st);
+    if (!counterCopied) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
     HIP_TRY(ctx, traced_sync(st));
     {   // MC_GW_DIAG=1: the batch's work-list counters on stderr (the classes of the filtered path)
         static const bool diag = [] { const char* e = std::getenv("MC_GW_DIAG"); return e && e[0] == '1'; }();
         if (diag) {
-            uint32_t mc[32];
+            uint32_t mc[kCounterWords];
             HIP_TRY(ctx, hipMemcpy(mc, ws.midCount, sizeof mc, hipMemcpyDeviceToHost));
             std::fprintf(stderr, "[gw diag] n %u filtered %u | stream filter %u | counted apart: 257..512 %u, 513..1024 %u | sorted %u\n",
-                         n, mc[9], mc[12], mc[14], mc[15], mc[13]);
+                         n, mc[kCntFilter], mc[kCntStream], mc[kCnt512], mc[kCnt1024], mc[kCntSorted]);
         }
     }
     if (!*nsorted) return MC_OK;
@@ -833,7 +833,7 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
     const uint32_t nseg = std::min(*nsorted, n);
     // the sorted class longest list first: the segmented sort (a block per segment) and the scan (a wave per list) take them in this order
     size_t ordBytes = 0;
-    if (launch_gw_order(3, ws, n, nseg, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists: size query failed");
+    if (launch_gw_order(kSideSorted, ws, n, nseg, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists: size query failed");
     if ((rc = ensure(ctx, P.bOrder, (size_t)3 * std::max<uint32_t>(n, 1) * 4 + ordBytes + 256))) return rc;
     size_t tmpBytes = 0;
     if (launch_gw_segsort(nullptr, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, poolEntries, ws, n, nseg, ctx->gwBits, st) != 0)
@@ -841,7 +841,7 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
     if ((rc = ensure(ctx, P.bSortTmp, tmpBytes + 256))) return rc;
     {
         ScopedTimer t(ctx, "gw_sort", st);
-        if (launch_gw_order(3, ws, n, nseg, (uint32_t*)P.bOrder.p, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists failed");
+        if (launch_gw_order(kSideSorted, ws, n, nseg, (uint32_t*)P.bOrder.p, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists failed");
         if (!P.sortSide.stream) {
             if (hipStreamCreateWithFlags(&P.sortSide.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&P.sortSide.fork, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&P.sortSide.join, hipEventDisableTiming) != hipSuccess) P.sortSide = GwSortSide{};
@@ -849,12 +849,12 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
         if (launch_gw_segsort(P.bSortTmp.p, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, poolEntries, ws, n, nseg, ctx->gwBits, st, &P.sortSide) != 0)
             return fail(ctx, MC_ERR_HIP, "segmented sort failed");
     }
-    { ScopedTimer t(ctx, "gw_sorted_cands", st); launch_big_cands(4, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    { ScopedTimer t(ctx, "gw_sorted_cands", st); launch_big_cands(FilterStep::SortedCands, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
     return MC_OK;
 }
 
 // The filtered candidate path on the work list the probing kernels (or, on the owner side of Mode K, owner_entries_kernel) left
-// in list 6: filter -> counting -> [segmented sort -> scan of the sorted lists].  poolEntries: entries of ws.bigPool (slices + overflow).
+// in kListFilter: filter -> counting -> [segmented sort -> scan of the sorted lists].  poolEntries: entries of ws.bigPool (slices + overflow).
 // deferSorted: the sorted class is left to the caller (mc_query_finish runs run_sorted_tail).
 static int run_filtered_path(mc_ctx* ctx, Pipe& P, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, Workspace& ws, uint32_t K,
                              const uint32_t* taxkey, bool compact, bool second, uint64_t poolEntries, hipStream_t st, bool deferSorted = false)
@@ -862,19 +862,19 @@ static int run_filtered_path(mc_ctx* ctx, Pipe& P, const BatchView& b, const Ske
     // timers carry the kernels' own names, one kernel each: compact store gw_filter_count_kernel (or gw_filter_kernel with "gw_fuse" 0), gw_filter2,
     // gw_compact (+ the ordering of the stream filter's reads), gw_filter_stream<fine>, gw_filter_stream (+ the second compaction),
     // gw_count_kernel<9>, <10>, <11>; 8-byte store: big_*
-    { ScopedTimer t(ctx, compact ? (ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", st); launch_big_cands(0, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    { ScopedTimer t(ctx, compact ? (ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", st); launch_big_cands(FilterStep::Filter, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
     // (compact store: gw_filter_kernel itself may leave reads to the second kernel -- it counts them on the device, after the
     // host's look at the counters: always launched, returns at once with nothing to do)
     if (compact) {                                             // (timers by kernel: a bench line's dominant "kernel" must be one)
-        { ScopedTimer t(ctx, "gw_filter2", st); launch_big_cands(3, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_compact", st); launch_big_cands(7, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream_fine", st); launch_big_cands(8, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream_mid", st); launch_big_cands(11, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream", st); launch_big_cands(9, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    } else if (second) { ScopedTimer t(ctx, "big_filter_2", st); launch_big_cands(3, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    { ScopedTimer t(ctx, compact ? "gw_count" : "big_count", st); launch_big_cands(1, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    if (compact) { ScopedTimer t(ctx, "gw_count_512", st); launch_big_cands(10, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    { ScopedTimer t(ctx, compact ? "gw_count_1024" : "big_count_2", st); launch_big_cands(2, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "gw_filter2", st); launch_big_cands(FilterStep::PairFilter, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "gw_compact", st); launch_big_cands(FilterStep::Compact, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "gw_filter_stream_fine", st); launch_big_cands(FilterStep::StreamFine, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "gw_filter_stream_mid", st); launch_big_cands(FilterStep::StreamMid, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "gw_filter_stream", st); launch_big_cands(FilterStep::Stream, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    } else if (second) { ScopedTimer t(ctx, "big_filter_2", st); launch_big_cands(FilterStep::BigFilter2, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    { ScopedTimer t(ctx, compact ? "gw_count" : "big_count", st); launch_big_cands(FilterStep::Count, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    if (compact) { ScopedTimer t(ctx, "gw_count_512", st); launch_big_cands(FilterStep::Count512, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    { ScopedTimer t(ctx, compact ? "gw_count_1024" : "big_count_2", st); launch_big_cands(FilterStep::Count1024, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
     if (compact && !deferSorted) return run_sorted_tail(ctx, P, b, sp, tab, ws, K, taxkey, poolEntries, false, st);
     return MC_OK;
 }
@@ -902,7 +902,7 @@ static int run_wave_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const SketchP
     };
     sketch_and_scan();
     uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
-    if (sortedPool) launch_words_to_host(nsorted, ws.midCount + 13, 1, st);
+    if (sortedPool) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
     HIP_TRY(ctx, traced_sync(st));
     if (sortedPool && *nsorted) {
         if ((rc = run_sorted_tail(ctx, P, b, sp, tab, ws, K, taxkey, *sortedPool, true, st))) return rc;
@@ -970,7 +970,7 @@ static int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool w
     if ((rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat)))) return rc;
     if ((rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4))) return rc;
     if ((rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4))) return rc;
-    if (lanePath && (rc = ensure(ctx, P.bMid, 128 + (size_t)8 * std::max<uint32_t>(n, 1) * 16))) return rc;
+    if (lanePath && (rc = ensure(ctx, P.bMid, work_lists_bytes(n)))) return rc;
     // pool of the filtered location lists (big_filter_kernel -> big_count_kernel): 384 per query on average, at least 4 MB
     // (tables whose features have few locations each never produce such lists: a token pool; a full pool sends lists to the wave kernel)
     const Part& T0 = ctx->parts[0];
@@ -979,11 +979,11 @@ static int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool w
     const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(longLists ? std::max<uint64_t>((uint64_t)n * 448, numChars * 3) : (uint64_t)n * 8,
                                                                                   (uint64_t)big_filter_grid(n, T0.compact, ctx->filterBpc) * 4 * std::min<uint64_t>(131072, std::max<uint64_t>(4096, 64 * (numChars / std::max<uint32_t>(n, 1))))));   // per wave: one full batch of gw_filter_kernel (2 112 numbers); long reads keep up to 65 535
     // compact store: behind the waves' slices an OVERFLOW region for filtered lists that may not fit their wave's slice (the longest
-    // reads of a batch keep 10^5 numbers): reserved with one atomic per such read (midCount[16..17])
+    // reads of a batch keep 10^5 numbers): reserved with one atomic per such read (kCntOverflow)
     const uint64_t ovfCap = T0.compact ? std::min<uint64_t>(0xFFFFFFF0ull - poolCap, std::max<uint64_t>(poolCap / 4, 8ull << 20)) : 0;
     if (lanePath && (rc = ensure(ctx, P.bBigPool, (poolCap + ovfCap) * (T0.compact ? 4 : 8)))) return rc;   // the pool holds the table's location form
     if (lanePath && (rc = ensure(ctx, P.bSliceFill, (size_t)big_filter_grid(n, T0.compact, ctx->filterBpc) * 4 * 4 + 64))) return rc;
-    if (lanePath && T0.compact && (rc = ensure(ctx, P.bSide, (size_t)5 * std::max<uint32_t>(n, 1) * 4))) return rc;
+    if (lanePath && T0.compact && (rc = ensure(ctx, P.bSide, (size_t)kSideRows * std::max<uint32_t>(n, 1) * 4))) return rc;
     if (lanePath && (rc = ensure(ctx, P.bChunkList, (size_t)(maxWindows + n + 1) * 8))) return rc;
     if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8))) return rc;
     if ((rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1)))) return rc;
@@ -1082,13 +1082,13 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
     ws.qstat = (QueryStat*)P.bQstat.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
     ws.scanTmp = P.bScan.p; ws.stats = (uint64_t*)P.bStats.p;
     if (lanePath) {
-        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = ws.midCount + 32;
+        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
         ws.bigMin = ctx->bigMin;
         ws.partialLists = wantPartial ? 1u : 0u;
         ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap; ws.bigOvfCap = (uint32_t)ovfCap;
         ws.sliceFill = (uint32_t*)P.bSliceFill.p;
         ws.sideList = (uint32_t*)P.bSide.p;
-        ws.chunkList = (flags & kQueryNoLongReads) ? nullptr : (uint2*)P.bChunkList.p;   // (null: no read is cut into chunks, launch_chunk_lanes launches nothing)
+        ws.chunkList = (flags & kQueryNoLongReads) ? nullptr : (uint2*)P.bChunkList.p;   // (null: no read is cut into chunks, the chunk launchers launch nothing)
     }
 
     BatchView b{in->seq, in->qinfo, in->max_win, in->max_win_uniform, n};
@@ -1116,7 +1116,7 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
     bool sortedInTail = false;                                   // the filtered path's sorted class is run_wave_tail's to look at
     if (lanePath) {
         // short reads: one lane per query for sketching and candidates, cooperative probing in between
-        if (!planSmall) HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, 128, st));
+        if (!planSmall) HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
         // sketching + probing in ONE kernel where the lookups wait for HBM (tables beyond the infinity cache: quad-cooperative fetches) -- the
         // sketching of some waves runs under the waiting of others (5.27 -> 5.08 ms per 5 x 10^6 reads at full scale); small tables keep
         // the two kernels (the ALU phase at the probe kernel's occupancy cost 5 % on configs[1]).  "lane_fusion" / MC_LANE_FUSION: 0 / 1 force it.
@@ -1126,23 +1126,24 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         const bool fuseSketch = !maskFeatures && (ctx->fuseLane >= 0 ? ctx->fuseLane != 0 : quadTable);
         if (fuseSketch) {
             { ScopedTimer t(ctx, "sketch_probe", st); launch_sketch_probe_lane(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
-            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_lanes(0, b, sp, tab, ws, ctx->quadLookup, st); }
-            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_lanes(1, b, sp, tab, ws, ctx->quadLookup, st); }
+            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
+            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
         } else {
             { ScopedTimer t(ctx, "sketch_lane", st); launch_sketch_lane(b, sp, ws, st); }
-            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_lanes(0, b, sp, tab, ws, ctx->quadLookup, st); }
+            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
             // a key shard's side of Mode K: only the features this shard owns are looked up (the others cannot be in its table)
             if (maskFeatures) {
                 ScopedTimer t(ctx, "mask_features", st);
                 launch_mask_foreign_features(ws.features, ws.winOff + n, sp.s, nfeat, ctx->cfg.key_shard_index, ctx->cfg.key_shard_count, st);
             }
-            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_lanes(1, b, sp, tab, ws, ctx->quadLookup, st); }
+            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
             { ScopedTimer t(ctx, "probe_cands", st); launch_probe_cands(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
         }
         // small batches take one look at the work lists and launch only the kernels with work (a launch costs as much as such a
         // batch's kernel: 0.37 -> 0.32 ms per 65 536 reads); large ones skip the round trip and launch everything
-        uint32_t all[16] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-        uint32_t none[16] = {0, 0, 0, 0, 0, 0, 1, 1, 0, 0, 0, 0, 0, 0, 0, 0};      // partial lists: no candidate kernels, the wave kernels for the rest
+        uint32_t all[kHostCounters], none[kHostCounters] = {};   // none (partial lists): no candidate kernels, the wave kernels for the rest
+        std::fill(all, all + kHostCounters, 1u);
+        none[kCntWaveSketch] = none[kCntWaveCands] = 1;
         uint32_t* hcnt = wantPartial ? none : all;
         // (MC_DEFER_TAIL: no look at the counters either -- everything is launched, the caller has another batch to enqueue)
         if (!wantPartial && n <= (1u << 20) && !(flags & MC_DEFER_TAIL)) {
@@ -1152,25 +1153,25 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
             HIP_TRY(ctx, traced_sync(st));
         }
         auto mid_and_hash = [&]() {
-            if (hcnt[0]) { ScopedTimer t(ctx, "mid_cands_64", st); launch_mid_cands(0, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[1]) { ScopedTimer t(ctx, "mid_cands_128", st); launch_mid_cands(1, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[2]) { ScopedTimer t(ctx, "mid_cands_256", st); launch_mid_cands(2, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[8]) { ScopedTimer t(ctx, "hash_cands_256", st); launch_hash_cands(5, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[3]) { ScopedTimer t(ctx, "hash_cands_512", st); launch_hash_cands(3, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[4]) { ScopedTimer t(ctx, "hash_cands_1024", st); launch_hash_cands(4, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntMid64]) { ScopedTimer t(ctx, "mid_cands_64", st); launch_mid_cands(kListMid64, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntMid128]) { ScopedTimer t(ctx, "mid_cands_128", st); launch_mid_cands(kListMid128, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntMid256]) { ScopedTimer t(ctx, "mid_cands_256", st); launch_mid_cands(kListMid256, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntHash256]) { ScopedTimer t(ctx, "hash_cands_256", st); launch_hash_cands(kListHash256, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntHash512]) { ScopedTimer t(ctx, "hash_cands_512", st); launch_hash_cands(kListHash512, b, tab, ws, K, taxkey, P.bCands.p, st); }
+            if (hcnt[kCntHash1024]) { ScopedTimer t(ctx, "hash_cands_1024", st); launch_hash_cands(kListHash1024, b, tab, ws, K, taxkey, P.bCands.p, st); }
         };
         mid_and_hash();
         bool waveDone = false;
-        if (T.compact && !wantPartial && hcnt[6]) {
+        if (T.compact && !wantPartial && hcnt[kCntWaveSketch]) {
             // compact store: the wave kernel's sketching and probing first, so that its reads can join the filtered path
             { ScopedTimer t(ctx, "query_wave", st); launch_query(b, sp, tab, fuse, false, ws, K, P.bCands.p, st); }
             launch_wave_rejoin(b, sp, tab, ws, st);
             waveDone = true;
         }
-        if (T.compact && !wantPartial && n <= (1u << 20) && (hcnt == all || hcnt[10])) {
+        if (T.compact && !wantPartial && n <= (1u << 20) && (hcnt == all || hcnt[kCntSecond])) {
             // reads beyond kGwSmallH locations (long reads): the stream filter takes them longest first (launch_gw_order)
             size_t ordBytes = 0;
-            if (launch_gw_order(0, ws, n, n, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the stream filter's reads: size query failed");
+            if (launch_gw_order(kSideStream, ws, n, n, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the stream filter's reads: size query failed");
             if ((rc = ensure(ctx, P.bOrder, (size_t)3 * std::max<uint32_t>(n, 1) * 4 + ordBytes + 256))) return rc;
             ws.orderScratch = (uint32_t*)P.bOrder.p; ws.orderTemp = ordBytes;
         }
@@ -1178,19 +1179,19 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         // filtered path, the segment sizes of the exact wave kernels' leftovers -- waits for mc_query_finish; this call returns with
         // the main kernels enqueued and NO synchronisation, so that the caller can enqueue the next batch on the other pipe first
         const bool defer = (flags & MC_DEFER_TAIL) != 0 && hcnt == all && !wantFeatures;
-        waveWork = wantPartial || hcnt[6] != 0 || hcnt[7] != 0 || hcnt[9] != 0;   // big_cands hands a few queries on to the wave kernels
+        waveWork = wantPartial || hcnt[kCntWaveSketch] != 0 || hcnt[kCntWaveCands] != 0 || hcnt[kCntFilter] != 0;   // big_cands hands a few queries on to the wave kernels
         // small batches: the sorted class's counter is looked at together with the wave tail's total (run_wave_tail: one round trip for both)
-        sortedInTail = hcnt != all && !defer && T.compact && waveWork && (hcnt[9] || waveDone);
-        if (hcnt[9] || waveDone) {
-            if ((rc = run_filtered_path(ctx, P, b, sp, tab, ws, K, taxkey, T.compact, hcnt[10] != 0, poolCap + ovfCap, st, defer || sortedInTail))) return rc;
+        sortedInTail = hcnt != all && !defer && T.compact && waveWork && (hcnt[kCntFilter] || waveDone);
+        if (hcnt[kCntFilter] || waveDone) {
+            if ((rc = run_filtered_path(ctx, P, b, sp, tab, ws, K, taxkey, T.compact, hcnt[kCntSecond] != 0, poolCap + ovfCap, st, defer || sortedInTail))) return rc;
         }
         skipWaveSketch = waveDone;
         if (defer) {
             Pipe::Tail& tl = P.tail;
             if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
             if (!tl.mainDone) HIP_TRY(ctx, hipEventCreateWithFlags(&tl.mainDone, hipEventDisableTiming));
-            tl.sortedPath = T.compact && (hcnt[9] || waveDone);
-            if (tl.sortedPath) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(P.hTotal + 9), ws.midCount + 13, 4, hipMemcpyDeviceToHost, st));
+            tl.sortedPath = T.compact && (hcnt[kCntFilter] || waveDone);
+            if (tl.sortedPath) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(P.hTotal + 9), ws.midCount + kCntSorted, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(ctx, hipEventRecord(tl.mainDone, st));
             tl.ws = ws; tl.b = b; tl.sp = sp; tl.tab = tab; tl.K = K; tl.taxkey = taxkey; tl.compact = T.compact; tl.fuse = fuse;
             tl.skipWaveSketch = skipWaveSketch; tl.poolEntries = poolCap + ovfCap; tl.st = st;
@@ -1309,7 +1310,7 @@ int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* i
         (rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1))) ||
         (rc = ensure(ctx, P.bPpay, ((size_t)S * (n + 2) + n + 1) * 8)) || (rc = ensure(ctx, P.bPsize, (size_t)(n + 1) * 4)) ||
         (rc = ensure(ctx, P.bWinOff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, P.bWinCount, (size_t)(n + 1) * 4)) ||
-        (rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bMid, 128 + (size_t)8 * std::max<uint32_t>(n, 1) * 16)))
+        (rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bMid, work_lists_bytes(n))))
         return rc;
     const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>((uint64_t)n * 448, (uint64_t)big_filter_grid(n, false, ctx->filterBpc) * 4 * 1024));
     if ((rc = ensure(ctx, P.bBigPool, poolCap * 8))) return rc;
@@ -1327,17 +1328,17 @@ int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* i
     // filter cannot take (more than 16 384 locations, wide window ranges) and what it hands back goes through the sort as before.
     const bool filtered = lane_candidates_supported(K) && ctx->useLanePath;
     if (filtered) {
-        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = ws.midCount + 32;
+        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
         ws.bigMin = ctx->bigMin; ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap;
         ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = srcStart + (size_t)S * (n + 2);
         ws.winOff = (uint32_t*)P.bWinOff.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitScan = (uint32_t*)P.bWinCount.p;
-        HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, 128, st));
+        HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
         launch_owner_classify(b, ws, std::max<uint32_t>(ctx->bigMin, 256u), st);
         DeviceTable utab{nullptr, ws.hits, 0, 0xFFFFFFFFu, 1};
         const SketchParams one{16, 1, 16, 1};                                  // step D finds a read's entry at winOff[q] * s = q
-        { ScopedTimer t(ctx, "big_filter", st); launch_big_cands(0, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "big_count", st); launch_big_cands(1, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "big_count_2", st); launch_big_cands(2, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "big_filter", st); launch_big_cands(FilterStep::Filter, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "big_count", st); launch_big_cands(FilterStep::Count, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
+        { ScopedTimer t(ctx, "big_count_2", st); launch_big_cands(FilterStep::Count1024, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
     }
     DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
     {
@@ -1427,9 +1428,9 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     if ((rc = ensure(ctx, P.bPsize, ((size_t)n * S + 4) * 4)) || (rc = ensure(ctx, P.bPpay, ((size_t)n * S + (size_t)S * (n + 2) + 4) * 8)) ||
         (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) || (rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4)) ||
         (rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1))) ||
-        (rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bMid, 128 + (size_t)8 * std::max<uint32_t>(n, 1) * 16)) ||
+        (rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bMid, work_lists_bytes(n))) ||
         (rc = ensure(ctx, P.bBigPool, (poolCap + ovfCap) * 4)) || (rc = ensure(ctx, P.bSliceFill, (size_t)big_filter_grid(n, true, ctx->filterBpc) * 4 * 4 + 64)) ||
-        (rc = ensure(ctx, P.bSide, (size_t)5 * std::max<uint32_t>(n, 1) * 4)) ||
+        (rc = ensure(ctx, P.bSide, (size_t)kSideRows * std::max<uint32_t>(n, 1) * 4)) ||
         (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))))
         return rc;
     Workspace ws{};
@@ -1438,7 +1439,7 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     uint64_t* srcStart = ws.ppay + (size_t)n * S + 2;                 // [S][n + 1] exclusive scans of the sources' counts
     ws.qstat = (QueryStat*)P.bQstat.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
     ws.scanTmp = P.bScan.p;
-    ws.midCount = (uint32_t*)P.bMid.p; ws.midList = ws.midCount + 32;
+    ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
     ws.bigMin = ctx->bigMin;
     ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap; ws.bigOvfCap = (uint32_t)ovfCap;
     ws.sliceFill = (uint32_t*)P.bSliceFill.p; ws.sideList = (uint32_t*)P.bSide.p;
@@ -1449,7 +1450,7 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
     KeyshardBases bases{};
     for (uint32_t s = 0; s < S; ++s) bases.b[s] = in->source_offsets[s];
-    HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, 128, st));
+    HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
     {
         ScopedTimer t(ctx, "owner_entries", st);
         for (uint32_t s = 0; s < S; ++s) launch_scan_u32(in->counts + (size_t)s * n, 1, n, nullptr, srcStart + (size_t)s * (n + 1), ws.scanTmp, st);
@@ -1461,7 +1462,7 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     launch_scan_u32(ws.hitScan, 1, n, nullptr, ws.hitOff, ws.scanTmp, st);
     if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
     HIP_TRY(ctx, hipMemcpyAsync(P.hTotal, ws.hitOff + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(P.hTotal + 10, ws.midCount + 9, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(P.hTotal + 10, ws.midCount + kCntFilter, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));
     ctx->ownerStats[0] += n; ctx->ownerStats[1] += *reinterpret_cast<const uint32_t*>(P.hTotal + 10); ctx->ownerStats[2] += totalIn; ctx->ownerStats[3] += *P.hTotal;
     const size_t hb = (size_t)(*P.hTotal + 1) * 8;
@@ -1585,7 +1586,7 @@ int mc_last_batch_stats(mc_ctx* ctx, uint64_t stats[8])
     Workspace ws{};
     ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
     ws.qstat = (QueryStat*)P.bQstat.p; ws.winOff = (uint32_t*)P.bWinOff.p; ws.stats = (uint64_t*)P.bStats.p;
-    if (P.bMid.p) { ws.midCount = (uint32_t*)P.bMid.p; ws.midList = ws.midCount + 32; }
+    if (P.bMid.p) { ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords); }
     launch_batch_stats(ws, P.lastN, ctx->stream);
     HIP_TRY(ctx, hipMemcpyAsync(stats, ws.stats, 64, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));

@@ -226,9 +226,8 @@ constexpr uint32_t kGwSmallH = 2048;      // compact store: reads with more loca
 constexpr uint32_t kGwMaxKept = kMaxHitsPerQuery;   // longest filtered list handed on (gw_filter kernels)
 // a filtered list (n2 numbers, window range maxWin) that is sorted instead of counted
 __host__ __device__ inline bool gw_sorted_class(uint32_t n2, uint32_t maxWin) { return n2 <= kGwMaxKept && (n2 > kBigMaxFilteredCount || maxWin > kHashWin); }
-// (stage 4 of launch_gw_cands: candidates of the sorted lists; needs ws.bigPool2 filled by launch_gw_segsort, kernels.h)
-// gw_kernels.hip: the filtered path of tables with the compact location store (stages as launch_big_cands)
-void launch_gw_cands(uint32_t stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+// gw_kernels.hip: the filtered path of tables with the compact location store (FilterStep::SortedCands needs ws.bigPool2 filled by launch_gw_segsort)
+void launch_gw_cands(FilterStep step, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                      const uint32_t* taxkey, void* cands, hipStream_t st);
 
 }  // namespace mcamd

@@ -6,7 +6,7 @@
 //   * gw - d is "the same target, d windows earlier" or no location at all;
 //   * the order of the numbers is the order of (target, window) (database.hpp:151-156), so "hits descending, then the smaller
 //     number" is the insertion order of the reference's top list (candidate_generation.hpp:172-201).
-// One WAVE per read throughout, persistent grids over the work list probe_cands_kernel / chunk_finish_kernel leave (list 6).
+// One WAVE per read throughout, persistent grids over the work list probe_cands_kernel / chunk_finish_kernel leave (kListFilter).
 //
 //   gw_filter_kernel   keeps the locations that have a neighbour (another location of the read less than maxWindowsInRange away):
 //                      only those can be part of a window range with two or more hits.  RefSeq scale: 1 271 locations per 150 bp read,
@@ -337,7 +337,7 @@ __device__ __forceinline__ void gw_take_rounds_packed(const uint32_t* bits, cons
     for (uint32_t u = 0; u < kGwLoads; ++u) if (u < nl) gw_take4<Bloom, CHECK>(bits, F, S, x[u], (int32_t)((packed >> (3u * u)) & 7u));
 }
 
-constexpr uint32_t kGwDefer = 0xFFFFFFFEu;                 // record of list 7: left to gw_filter_stream_kernel
+constexpr uint32_t kGwDefer = 0xFFFFFFFEu;                 // record of kListFiltered: left to gw_filter_stream_kernel
 constexpr uint32_t kGwFallback = 0xFFFFFFFFu;              // ... handed to the wave kernel
 
 }  // namespace
@@ -357,9 +357,9 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_kernel(BatchView b,
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (uniform: the wave's pointers and counters live in scalar registers)
     uint32_t* bits = bitS[wave];
     uint64_t* T = roundS[wave];
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
-    uint4* __restrict__ outRec = reinterpret_cast<uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    uint4* __restrict__ outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     const uint32_t w0 = blockIdx.x * WAVES + wave;
     auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0, 0); };
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_kernel(BatchView b,
     }
     if (lane == 0) {
         if (ws.sliceFill) ws.sliceFill[w0] = (uint32_t)sliceUsed;
-        if (deferred) atomicAdd(&ws.midCount[10], deferred);       // (one atomic per wave that met such reads at all)
+        if (deferred) atomicAdd(&ws.midCount[kCntSecond], deferred);   // (one atomic per wave that met such reads at all)
     }
 }
 
@@ -439,14 +439,14 @@ __global__ __launch_bounds__(WAVES * 64, T2LOG2 == TLOG2 ? MC_GW_FILTER_WPE : 6)
     __shared__ uint32_t bitS[WAVES][Bloom::kWords];
     __shared__ uint64_t roundS[WAVES][kGwRounds];
     __shared__ uint32_t scanS[WAVES][kGwRounds];                   // scratch of the round tables' max-scan
-    if (ws.midCount[10] == 0) return;                              // nothing was left
+    if (ws.midCount[kCntSecond] == 0) return;                      // nothing was left
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t* bits = bitS[wave];
     uint64_t* T = roundS[wave];
     uint32_t* E = scanS[wave];
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
-    uint4* outRec = reinterpret_cast<uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    uint4* outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     const uint32_t w0 = blockIdx.x * WAVES + wave;
     const uint64_t sliceCap = ws.bigPoolCap / nWaves;
@@ -529,19 +529,19 @@ __global__ __launch_bounds__(256) void gw_compact_kernel(Workspace ws, uint32_t 
 {
     // a block takes a contiguous stretch of the records: it counts its members of every class first, reserves their places with ONE
     // atomic per class (78 000 atomics on one counter -- one per 64 records -- took 0.4 ms), then writes them in record order
-    constexpr uint32_t kC = 4;                                     // classes = side lists; class kC: none
+    constexpr uint32_t kC = kSideRows;                             // classes = side lists; class kC: none
     __shared__ uint32_t cnt[4][kC], base[kC];
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ rec7 = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ rec7 = ws.midList + list_at(kListFiltered, n);
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t per = ((total + gridDim.x - 1) / gridDim.x + 255u) / 256u * 256u;          // records per block, whole 256-record steps
     const uint32_t lo = blockIdx.x * per, hi = min(total, lo + per);
     auto class_of = [&](uint32_t i) -> uint32_t {
         if (i >= hi) return kC;
         const uint4 r = rec7[i];
-        if (stage == 0) return r.z == kGwDefer ? 0u : kC;
-        if (gw_sorted_class(r.z, r.w)) return 3u;
-        if (r.z <= kBigMaxFilteredCount && r.w <= kHashWin) return r.z > 512u ? 2u : r.z > 256u ? 1u : kC;
+        if (stage == 0) return r.z == kGwDefer ? kSideStream : kC;
+        if (gw_sorted_class(r.z, r.w)) return kSideSorted;
+        if (r.z <= kBigMaxFilteredCount && r.w <= kHashWin) return r.z > 512u ? kSide1024 : r.z > 256u ? kSide512 : kC;
         return kC;
     };
     uint32_t mine[kC];
@@ -556,7 +556,7 @@ __global__ __launch_bounds__(256) void gw_compact_kernel(Workspace ws, uint32_t 
     __syncthreads();
     if (threadIdx.x < kC) {
         const uint32_t k = threadIdx.x, tot = cnt[0][k] + cnt[1][k] + cnt[2][k] + cnt[3][k];
-        base[k] = tot ? atomicAdd(&ws.midCount[k == 0 ? 12u : k == 1 ? 14u : k == 2 ? 15u : 13u], tot) : 0u;
+        base[k] = tot ? atomicAdd(&ws.midCount[side_counter(k)], tot) : 0u;
     }
     __syncthreads();
     // second pass: step s of the block holds records lo + s * 256 .. ; within a step the waves' members follow each other
@@ -576,7 +576,7 @@ __global__ __launch_bounds__(256) void gw_compact_kernel(Workspace ws, uint32_t 
         for (uint32_t k = 0; k < kC; ++k) {
             uint32_t before = 0, all = 0;
             for (uint32_t w = 0; w < 4; ++w) { before += w < wave ? cnt[w][k] : 0u; all += cnt[w][k]; }
-            if (c == k) ws.sideList[(size_t)k * n + run[k] + before + __popcll(m[k] & ((1ull << lane) - 1ull))] = i;
+            if (c == k) ws.sideList[list_at(k, n) + run[k] + before + __popcll(m[k] & ((1ull << lane) - 1ull))] = i;
             run[k] += all;
         }
     }
@@ -585,7 +585,7 @@ __global__ __launch_bounds__(256) void gw_compact_kernel(Workspace ws, uint32_t 
 // Everything else: reads with more than 64 found features, lists of more than kGwRounds rounds, more than kGwSmallH locations (long
 // reads: thousands to tens of thousands).  Entries in chunks of 64, rounds in batches of kGwRounds, two passes over the lists (the
 // second one finds them in the L2 / infinity cache), filters sized for tens of thousands of keys.  Same waves, same pool slices
-// (ws.sliceFill) as gw_filter_kernel, after which it runs; returns at once when the batch has no such read (midCount[10]).
+// (ws.sliceFill) as gw_filter_kernel, after which it runs; returns at once when the batch has no such read (kCntStream).
 // Two instances by the read's locations H in (hMin, hMax].  FINE (reads beyond kGwBigH locations -- 4 kbp and more: 1.7 % of configs[4]'s
 // reads with an eighth of its locations): with tens of thousands of locations in 1.4 x 10^9 numbers every block of 64 D numbers holds a
 // second location and the block filter keeps nearly all of them (a 19 kbp read kept 10^5 of its 1.6 x 10^5: these lists were 90 of the
@@ -607,12 +607,12 @@ __global__ __launch_bounds__(WAVES * 64) void gw_filter_stream_kernel(BatchView 
     __shared__ uint32_t scanS[WAVES][kGwRounds];                   // scratch of the round tables' max-scan (round 6: gw_fill_rounds_scan_at)
     __shared__ uint32_t n2S;
     __shared__ unsigned long long ovfS;
-    if (ws.midCount[12] == 0) return;
+    if (ws.midCount[kCntStream] == 0) return;
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint64_t* T = roundS[wave];
     uint32_t* E = scanS[wave];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
-    uint4* outRec = reinterpret_cast<uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    uint4* outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t w0 = blockIdx.x * WAVES;                        // the block's first slice
     const uint64_t sliceCap = ws.bigPoolCap / nSlices;
     const uint32_t mySlices = w0 < nSlices ? min(WAVES, nSlices - w0) : 0u;
@@ -621,8 +621,8 @@ __global__ __launch_bounds__(WAVES * 64) void gw_filter_stream_kernel(BatchView 
 #pragma unroll
     for (uint32_t k = 0; k < WAVES; ++k) used[k] = k < mySlices ? (ws.sliceFill ? ws.sliceFill[w0 + k] : 0u) : sliceCap;
     const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
-    const uint32_t mine = ws.midCount[12];
-    const uint32_t* __restrict__ side = ws.sideList;
+    const uint32_t mine = ws.midCount[kCntStream];
+    const uint32_t* __restrict__ side = ws.sideList;                  // (kSideStream: the first row)
     for (uint32_t i = blockIdx.x; i < mine; i += gridDim.x) {
         const uint32_t w = side[i];
         const uint4 rec = work[w];
@@ -643,7 +643,7 @@ __global__ __launch_bounds__(WAVES * 64) void gw_filter_stream_kernel(BatchView 
         uint64_t listAt = 0; uint32_t room = 0;
         if (k >= 0) { listAt = (uint64_t)(w0 + (uint32_t)k) * sliceCap + used[k]; room = (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - used[k]); }
         else {
-            if (threadIdx.x == 0) ovfS = atomicAdd(reinterpret_cast<unsigned long long*>(ws.midCount + 16), (unsigned long long)H);
+            if (threadIdx.x == 0) ovfS = atomicAdd(reinterpret_cast<unsigned long long*>(ws.midCount + kCntOverflow), (unsigned long long)H);
             __syncthreads();
             const unsigned long long at = ovfS;
             if (at + H <= ws.bigOvfCap) { listAt = (uint64_t)ws.bigPoolCap + at; room = H; }
@@ -917,11 +917,11 @@ struct GwPend {
 
 // Rows 8-10 for ONE read on its filtered list of n2 <= 2^LOG2S / 2 numbers, window ranges up to kHashWin: getv(r) hands this lane its
 // r-th number (position r * 64 + lane; kGwNone past the end).  slots: the wave's table of 2^LOG2S {number, count} slots, ck: room for
-// the slots of the distinct numbers, T: a round table (step D; may share memory with slots or ck).  w: the read's record in work list 6.
+// the slots of the distinct numbers, T: a round table (step D; may share memory with slots or ck).  w: the read's record in kListFilter.
 // DEFER: the winners' target lookup waits in P for the caller's next read (see GwPend; the caller finishes the last one).
 // LONG (first instance's table only): the list may hold up to 2^LOG2S numbers as long as no more than half of them are DISTINCT (a filtered
 // list of 400 numbers has about 100 distinct ones); a list with more goes to the exact wave kernel.
-// entf(): where step D finds the read's entries -- {first entry slot in ws.psize / ws.ppay, entries} (the record of work list 6)
+// entf(): where step D finds the read's entries -- {first entry slot in ws.psize / ws.ppay, entries} (the record of kListFilter)
 template <uint32_t LOG2S, bool TAX, bool DEFER, bool LONG = false, class GetV, class EntF>
 __device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, const uint32_t n2, const uint32_t maxWin, GetV&& getv,
                                               uint2* slots, uint32_t* ck, uint64_t* T, const uint32_t lane, const uint32_t grp, const uint32_t sub4,
@@ -1112,11 +1112,11 @@ __global__ __launch_bounds__(WAVES * 64, LOG2S == 9 ? MC_GW_COUNT_WPE : LOG2S ==
     uint2* slots = slotS[wave];
     uint32_t* ck = ckS[wave];
     uint64_t* T = reinterpret_cast<uint64_t*>(slotS[wave]);
-    // the records gw_filter_kernel left (list 7, one per read of work list 6); this instance takes the filtered lists that fit its
+    // the records gw_filter_kernel left (kListFiltered, one per read of kListFilter); this instance takes the filtered lists that fit its
     // table: n2 in (minN2, kList], window ranges up to kHashWin
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * b.n;
-    const uint4* __restrict__ work6 = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ work = ws.midList + list_at(kListFiltered, b.n);
+    const uint4* __restrict__ work6 = ws.midList + list_at(kListFilter, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     const uint32_t w0 = blockIdx.x * WAVES + wave;
     const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
@@ -1133,15 +1133,15 @@ __global__ __launch_bounds__(WAVES * 64, LOG2S == 9 ? MC_GW_COUNT_WPE : LOG2S ==
         }
     };
     // the first instance (most reads) takes ALL records, 64 per step; the others get theirs from the compact lists gw_compact_kernel
-    // made (ws.sideList [1] / [2]), 8 per step: with few of them every wave should have some.  The first two instances defer the
+    // made (kSide512 / kSide1024), 8 per step: with few of them every wave should have some.  The first two instances defer the
     // winners' target lookup behind the next read's counting (GwPend).
     constexpr bool kDefer = LOG2S <= 10;
     GwPend P;
-    const uint32_t nmine = LOG2S == 9 ? total : ws.midCount[LOG2S == 10 ? 14 : 15];
+    const uint32_t nmine = LOG2S == 9 ? total : ws.midCount[LOG2S == 10 ? kCnt512 : kCnt1024];
     // (few records -- the small batches of the host slots --: fewer per step, so that every wave of the grid has one before any wave has two;
     // eight reads of ~25 us each one after the other on five waves were the longest kernel of a 4 096-read batch)
     const uint32_t kStep = LOG2S == 9 ? 64u : min(8u, max(1u, (nmine + nWaves - 1) / nWaves));
-    const uint32_t* __restrict__ side = ws.sideList + (size_t)(LOG2S == 10 ? 1 : 2) * b.n;
+    const uint32_t* __restrict__ side = ws.sideList + list_at(LOG2S == 10 ? kSide512 : kSide1024, b.n);
     for (uint32_t chunk = w0 * kStep; chunk < nmine; chunk += nWaves * kStep) {
       const bool inb = lane < kStep && chunk + lane < nmine;
       const uint32_t myW = LOG2S == 9 ? chunk + lane : (inb ? side[chunk + lane] : 0u);
@@ -1167,7 +1167,7 @@ __global__ __launch_bounds__(WAVES * 64, LOG2S == 9 ? MC_GW_COUNT_WPE : LOG2S ==
     if constexpr (kDefer) { P.bases(tab); P.template finish<TAX>(lane, K, tab, ws, cands); }
 }
 
-constexpr uint32_t kGwCounted = 0x80000000u;      // record of list 7: the read was counted inside the filter kernel (| kept numbers)
+constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: the read was counted inside the filter kernel (| kept numbers)
 
 // FUSED filter + counting (the common case of a 150 bp read at RefSeq scale in ONE kernel): gw_filter_kernel's two phases on the read's
 // lists in registers, the kept numbers to LDS instead of the pool (up to 512), gw_count_read on them right there -- no round trip of
@@ -1199,9 +1199,9 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     uint32_t* bits = bitS[wave];
     uint64_t* T = kSeven ? reinterpret_cast<uint64_t*>(bits) : roundS[kSeven ? 0 : wave];
     uint32_t* kept = keptS[wave];
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
-    uint4* __restrict__ outRec = reinterpret_cast<uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    uint4* __restrict__ outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     const uint32_t w0 = blockIdx.x * WAVES + wave;
     auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0, 0); };
@@ -1315,7 +1315,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     P.bases(tab); P.template finish<TAX>(lane, K, tab, ws, cands);
     if (lane == 0) {
         if (ws.sliceFill) ws.sliceFill[w0] = (uint32_t)sliceUsed;
-        if (deferred) atomicAdd(&ws.midCount[10], deferred);
+        if (deferred) atomicAdd(&ws.midCount[kCntSecond], deferred);
     }
 }
 
@@ -1456,7 +1456,7 @@ __device__ __forceinline__ uint32_t gw_sorted_rounds(LaneCand (&top)[kLaneK], ui
 
 // BIG = false: one wave per read.  The work list is in descending order of the lists' lengths (launch_gw_order): the longest lists beyond
 // kGwBigSorted numbers -- up to kGwFewBig of them: the rare 10-19 kbp reads of a mixed batch keep 10^5 numbers at RefSeq scale, and the one
-// wave on such a list kept running long after all others had finished -- are left to the second launch (their count: midCount[18]).
+// wave on such a list kept running long after all others had finished -- are left to the second launch (their count: kCntSortedBig).
 // The rest keeps one wave per read: sixteen waves per list cost more than they gain when every CU has work anyway (20 000 reads of
 // 10 kbp: 3.9 ms with one wave each, 6.5 ms with sixteen).
 // BIG = true (second launch): one BLOCK of sixteen waves per such read, its list cut into sixteen runs of whole chunks, one per wave.
@@ -1474,8 +1474,8 @@ __global__ __launch_bounds__(BIG ? 1024 : 256) void gw_sorted_cands_kernel(Batch
     __shared__ uint32_t ptaxS[kWaves][kLaneK];
     const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t* ring = ringS[wave];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * b.n;
-    const uint32_t* __restrict__ side = ws.sideList + (size_t)3 * b.n;
+    const uint4* __restrict__ work = ws.midList + list_at(kListFiltered, b.n);
+    const uint32_t* __restrict__ side = ws.sideList + list_at(kSideSorted, b.n);
     auto finish = [&](uint32_t q, uint32_t strong) {
         if (lane == 0) {
             if (strong < K) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
@@ -1484,12 +1484,12 @@ __global__ __launch_bounds__(BIG ? 1024 : 256) void gw_sorted_cands_kernel(Batch
     };
     if constexpr (!BIG) {
         const uint32_t nWaves = gridDim.x * 4, w0 = blockIdx.x * 4 + wave;
-        const uint32_t nmine = ws.midCount[13];
+        const uint32_t nmine = ws.midCount[kCntSorted];
         // how many lists are longer than kGwBigSorted (descending order: a binary search, the same in every wave)
         uint32_t lo = 0, hi = nmine;
         while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (work[side[mid]].z > kGwBigSorted) lo = mid + 1u; else hi = mid; }
         const uint32_t nbig = min(lo, kGwFewBig);                  // the longest of them
-        if (w0 == 0 && lane == 0) ws.midCount[18] = nbig;
+        if (w0 == 0 && lane == 0) ws.midCount[kCntSortedBig] = nbig;
         for (uint32_t i = nbig + w0; i < nmine; i += nWaves) {
             const uint32_t w = side[i];
             const uint4 rec = work[w];
@@ -1504,7 +1504,7 @@ __global__ __launch_bounds__(BIG ? 1024 : 256) void gw_sorted_cands_kernel(Batch
             finish(q, strong);
         }
     } else {
-        const uint32_t nbig = ws.midCount[18];
+        const uint32_t nbig = ws.midCount[kCntSortedBig];
         for (uint32_t i = blockIdx.x; i < nbig; i += gridDim.x) {
             const uint4 rec = work[side[i]];
             const uint32_t q = rec.x, n = rec.z, maxWin = rec.w;
@@ -1543,13 +1543,13 @@ static uint32_t gw_env(const char* name, uint32_t dflt)
     return e ? (uint32_t)std::max(1, std::atoi(e)) : dflt;
 }
 
-void launch_gw_cands(uint32_t stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+void launch_gw_cands(FilterStep step, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                      const uint32_t* taxkey, void* cands, hipStream_t st)
 {
     if (b.n == 0) return;
     mc_candidate_dev* c = (mc_candidate_dev*)cands;
     const uint32_t fgrid = big_filter_grid(b.n, true, ws.filterBpc);               // blocks of 4 waves: the pool is cut into one slice per wave
-    if (stage == 0) {
+    if (step == FilterStep::Filter) {
         // the filter with the counting of lists up to 512 numbers fused in (gw_filter_count_kernel); "gw_fuse" 0: the two kernels apart
         if (ws.gwFuse == 0) hipLaunchKernelGGL((gw_filter_kernel<4, 14, 5>), dim3(fgrid), dim3(256), 0, st, b, tab, ws);   // (compiled for five waves per SIMD: 96 registers)
         // (round 6: occupancy is what this kernel answers to -- the compiler sizes its registers by what the LDS allows, so the LDS was cut:
@@ -1562,40 +1562,40 @@ void launch_gw_cands(uint32_t stage, const BatchView& b, const SketchParams& sp,
         else if (ws.gwFuse == 5) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 4>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
         else if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
         else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-    } else if (stage == 3) {
+    } else if (step == FilterStep::PairFilter) {
         // reads of up to 2 x kGwRounds rounds (read pairs): two register batches
         // ("gw_fuse" 5 also brings back the pair filter of rounds 3-5: both filter halves of 2^15 bits, 38 KB per block, four waves per SIMD)
         if (ws.gwFuse == 5) hipLaunchKernelGGL((gw_filter2_kernel<4, 15>), dim3(fgrid), dim3(256), 0, st, b, tab, ws);
         else hipLaunchKernelGGL((gw_filter2_kernel<4, 15, 13>), dim3(fgrid), dim3(256), 0, st, b, tab, ws);
-    } else if (stage == 7) {
+    } else if (step == FilterStep::Compact) {
         // the records the register filters left -> the stream filter's list, longest reads first
         const uint32_t cgrid = std::min<uint32_t>((b.n + 255) / 256, 2048u);
         hipLaunchKernelGGL(gw_compact_kernel, dim3(cgrid), dim3(256), 0, st, ws, b.n, 0u);
-        if (ws.orderScratch) { size_t tb = ws.orderTemp; (void)launch_gw_order(0, ws, b.n, b.n, ws.orderScratch, tb, st); }
-    } else if (stage == 8) {
+        if (ws.orderScratch) { size_t tb = ws.orderTemp; (void)launch_gw_order(kSideStream, ws, b.n, b.n, ws.orderScratch, tb, st); }
+    } else if (step == FilterStep::StreamFine) {
         // reads with more than kGwSmallH locations: the ones beyond kGwBigH first (one block of sixteen waves per read, 2^19 + 2^17 filter bits:
         // blocks x 16 = the same waves, the same pool slices; tuning switch "gw_big_h"; 0xFFFFFFFF: one instance for all reads, as round 3)
         const uint32_t nSlices = 4u * fgrid;
         if (ws.gwBigH != 0xFFFFFFFFu) hipLaunchKernelGGL((gw_filter_stream_kernel<16, 19, 17, true>), dim3((nSlices + 15u) / 16u), dim3(1024), 0, st, b, tab, ws, ws.gwBigH, 0xFFFFFFFFu, nSlices);
-    } else if (stage == 11) {
+    } else if (step == FilterStep::StreamMid) {
         const uint32_t nSlices = 4u * fgrid;
         const uint32_t midH = std::min(ws.gwMidH, ws.gwBigH);
         if (midH) hipLaunchKernelGGL((gw_filter_stream_kernel<2, 16, 13>), dim3(2 * fgrid), dim3(128), 0, st, b, tab, ws, 0u, midH, nSlices);
-    } else if (stage == 9) {
+    } else if (step == FilterStep::Stream) {
         // ... the others: 2^17 + 2^15 filter bits per block of two waves (20 KB), twice the blocks
         // (2^16 + 2^15 bits instead: more waves per CU, but more false positives to sort -- 612 against 676 Mreads/min on configs[4]'s reads;
         // four waves per block and pair of filters -- 24 waves per CU: 5.01 -> 4.87 ms per 250 000 long reads: left at two; a single-pass
         // instance in front of this kernel was measured slower: DESIGN section 10 of round 4)
         const uint32_t nSlices = 4u * fgrid;
         const uint32_t cgrid = std::min<uint32_t>((b.n + 255) / 256, 2048u);
-        // (stage 11, "gw_mid_h" > 0: the reads of up to that many locations through an instance with 2^16 + 2^13 filter bits -- 9 KB instead of
+        // (StreamMid, "gw_mid_h" > 0: the reads of up to that many locations through an instance with 2^16 + 2^13 filter bits -- 9 KB instead of
         // 20 per block, six waves per SIMD where this instance runs at three.  Measured at 8 192: filters 3.35 -> 3.0 ms per 250 000 long reads,
         // and the sort, the scan and the counting of what the smaller filters keep too much +0.35: off by default)
-        const uint32_t midH = std::min(ws.gwMidH, ws.gwBigH);      // (stage 11, before this one)
+        const uint32_t midH = std::min(ws.gwMidH, ws.gwBigH);      // (StreamMid, before this one)
         hipLaunchKernelGGL((gw_filter_stream_kernel<2, 17, 15>), dim3(2 * fgrid), dim3(128), 0, st, b, tab, ws, midH, ws.gwBigH, nSlices);
         hipLaunchKernelGGL(gw_compact_kernel, dim3(cgrid), dim3(256), 0, st, ws, b.n, 1u);
-    } else if (stage == 1 || stage == 10) {
-        // filtered lists up to 256 (stage 1: 4 KB of LDS per wave), then 257 .. 512 (stage 10)
+    } else if (step == FilterStep::Count || step == FilterStep::Count512) {
+        // filtered lists up to 256 (Count: 4 KB of LDS per wave), then 257 .. 512 (Count512)
         // (eight blocks per CU are resident; a grid of exactly that many left the waves with 9 or 10 steps of 64 records each and the CU waiting
         // for the last one: 5.9 ms per 5 x 10^6 reads; 16 / 24 / 32 blocks per CU: 5.23 / 5.19 / 5.15)
         static const uint32_t bpcEnv = gw_env("MC_BIG_COUNT_BPC", 24u);
@@ -1603,14 +1603,14 @@ void launch_gw_cands(uint32_t stage, const BatchView& b, const SketchParams& sp,
         // (second instance: 40 KB of LDS per block = four blocks per CU at a time; its grid in whole rounds of four)
         static const uint32_t bpc1 = gw_env("MC_BIG_COUNT1_BPC", 16u);
         const uint32_t grid = std::min<uint32_t>(256 * bpc, (b.n + 3) / 4), grid1 = std::min<uint32_t>(256 * bpc1, (b.n + 3) / 4);
-        if (stage == 1) {
+        if (step == FilterStep::Count) {
             if (taxkey) hipLaunchKernelGGL((gw_count_kernel<9, 4, true>), dim3(grid), dim3(256), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, 0u);
             else        hipLaunchKernelGGL((gw_count_kernel<9, 4, false>), dim3(grid), dim3(256), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, 0u);
         } else {
             if (taxkey) hipLaunchKernelGGL((gw_count_kernel<10, 4, true>), dim3(grid1), dim3(256), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, 256u);
             else        hipLaunchKernelGGL((gw_count_kernel<10, 4, false>), dim3(grid1), dim3(256), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, 256u);
         }
-    } else if (stage == 4) {                                   // candidates of the sorted lists (after launch_gw_segsort)
+    } else if (step == FilterStep::SortedCands) {             // candidates of the sorted lists (after launch_gw_segsort)
         const uint32_t grid = std::min<uint32_t>(256 * 8, (b.n + 3) / 4);
         if (taxkey) {
             hipLaunchKernelGGL((gw_sorted_cands_kernel<true, false>), dim3(grid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
@@ -1619,7 +1619,7 @@ void launch_gw_cands(uint32_t stage, const BatchView& b, const SketchParams& sp,
             hipLaunchKernelGGL((gw_sorted_cands_kernel<false, false>), dim3(grid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
             hipLaunchKernelGGL((gw_sorted_cands_kernel<false, true>), dim3(std::min<uint32_t>(grid, 512u)), dim3(1024), 0, st, b, tab, ws, maxCand, taxkey, c);
         }
-    } else if (stage == 2) {
+    } else if (step == FilterStep::Count1024) {
         static const uint32_t bpc2 = gw_env("MC_BIG_COUNT2_BPC", 4u);  // 32 KB per block of two waves
         const uint32_t grid = std::min<uint32_t>(256 * bpc2, (b.n + 1) / 2);
         if (taxkey) hipLaunchKernelGGL((gw_count_kernel<11, 2, true>), dim3(grid), dim3(128), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, 512u);

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void gw_sort_plan_kernel(Workspace ws, uint32_
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     uint32_t len = 0;
-    if (i < nseg && i < ws.midCount[13]) len = (reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n)[ws.sideList[(size_t)3 * n + i]].z;
+    if (i < nseg && i < ws.midCount[kCntSorted]) len = (ws.midList + list_at(kListFiltered, n))[ws.sideList[list_at(kSideSorted, n) + i]].z;
     if (i < nseg) { items[i] = len <= kWholeMax ? 0u : (len + kChunk - 1u) / kChunk; tiles[i] = len <= kChunk ? 0u : (len + kTile - 1u) / kTile; }
     // how many lists every instance takes: the lists come longest first (launch_gw_order: classes of 256 lengths whose borders are the
     // instances'), so instance c's lists are the places [sum of the counts before, + count) -- nobody walks over the others' lists
@@ -157,8 +157,8 @@ __global__ __launch_bounds__(THREADS) void gw_sort_lists_kernel(Workspace ws, ui
                                                                 const uint32_t* __restrict__ in, uint32_t* __restrict__ out)
 {
     __shared__ uint32_t s[padded(THREADS * 16)];
-    const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n;
-    const uint32_t* __restrict__ side = ws.sideList + (size_t)3 * n;
+    const uint4* __restrict__ rec = ws.midList + list_at(kListFiltered, n);
+    const uint32_t* __restrict__ side = ws.sideList + list_at(kSideSorted, n);
     uint32_t first = 0;
     for (uint32_t c = 0; c < cls; ++c) first += classCount[c];
     const uint32_t end = first + classCount[cls];
@@ -183,8 +183,8 @@ __global__ __launch_bounds__(1024) void gw_sort_chunk_kernel(Workspace ws, uint3
 {
     __shared__ uint32_t s[padded(kChunk)];
     __shared__ uint32_t listS;
-    const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n;
-    const uint32_t* __restrict__ side = ws.sideList + (size_t)3 * n;
+    const uint4* __restrict__ rec = ws.midList + list_at(kListFiltered, n);
+    const uint32_t* __restrict__ side = ws.sideList + list_at(kSideSorted, n);
     const uint32_t total = itemOff[nseg];
     for (uint32_t x = blockIdx.x; x < total; x += gridDim.x) {
         if (threadIdx.x == 0) listS = list_of(itemOff, nseg, x);
@@ -223,8 +223,8 @@ __global__ __launch_bounds__(256) void gw_merge_pass_kernel(Workspace ws, uint32
 {
     __shared__ uint32_t s[padded(kTile) + 32];
     __shared__ uint32_t cutS[4];
-    const uint4* __restrict__ rec = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n;
-    const uint32_t* __restrict__ side = ws.sideList + (size_t)3 * n;
+    const uint4* __restrict__ rec = ws.midList + list_at(kListFiltered, n);
+    const uint32_t* __restrict__ side = ws.sideList + list_at(kSideSorted, n);
     const uint32_t total = tileOff[nseg];
     const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
     for (uint32_t x = blockIdx.x; x < total; x += gridDim.x) {
@@ -266,12 +266,12 @@ constexpr uint32_t kOrderClasses = 4096, kOrderSlots = 256 * 17;   // + one clas
 __device__ __forceinline__ uint32_t order_class(uint32_t key) { return key ? kOrderClasses - 1u - min((key - 1u) >> 8, kOrderClasses - 1u) : kOrderClasses; }   // descending
 __device__ __forceinline__ uint32_t order_key(const Workspace& ws, uint32_t n, uint32_t list, uint32_t i)
 {
-    // list 3 (sorted class): the numbers its filtered list holds; list 0 (reads of gw_filter_stream_kernel): the read's locations.
+    // kSideSorted: the numbers its filtered list holds; kSideStream (reads of gw_filter_stream_kernel): the read's locations.
     // Entries beyond the list's length (device-side count) get key 0 and end up last.
-    const uint32_t len = ws.midCount[list == 3 ? 13 : 12];
+    const uint32_t len = ws.midCount[list == kSideSorted ? kCntSorted : kCntStream];
     if (i >= len) return 0u;
-    const uint32_t w = ws.sideList[(size_t)list * n + i];
-    return list == 3 ? (reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n)[w].z : (reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * n)[w].z >> 12;
+    const uint32_t w = ws.sideList[list_at(list, n) + i];
+    return list == kSideSorted ? (ws.midList + list_at(kListFiltered, n))[w].z : (ws.midList + list_at(kListFilter, n))[w].z >> 12;
 }
 __global__ __launch_bounds__(256) void order_hist_kernel(Workspace ws, uint32_t n, uint32_t list, uint32_t count, uint32_t* __restrict__ hist)
 {
@@ -315,13 +315,13 @@ __global__ __launch_bounds__(256) void order_scatter_kernel(Workspace ws, uint32
     __syncthreads();
     for (uint32_t j = threadIdx.x; j < kOrderClasses; j += 256) { const uint32_t v = cnt[j]; if (v) cnt[j] = atomicAdd(&cursor[j], v); }
     __syncthreads();
-    if (key) outv[cnt[c] + local] = ws.sideList[(size_t)list * n + i];
+    if (key) outv[cnt[c] + local] = ws.sideList[list_at(list, n) + i];
 }
 // back to the side list: the list's own entries only (what lies behind its end stays as it is)
 __global__ __launch_bounds__(256) void order_copy_kernel(Workspace ws, uint32_t n, uint32_t list, uint32_t count, const uint32_t* __restrict__ outv)
 {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i < count && i < ws.midCount[list == 3 ? 13 : 12]) ws.sideList[(size_t)list * n + i] = outv[i];
+    if (i < count && i < ws.midCount[list == kSideSorted ? kCntSorted : kCntStream]) ws.sideList[list_at(list, n) + i] = outv[i];
 }
 
 }  // namespace
@@ -329,11 +329,11 @@ __global__ __launch_bounds__(256) void order_copy_kernel(Workspace ws, uint32_t 
 // Longest first.  The kernels that take ONE read per wave (or block) over a strided work list -- the stream filter, the sort's blocks,
 // the scan of the sorted lists -- finished when the wave that happened to hold several 19 kbp reads did: with the records in descending
 // order of their work a stride hands every wave the same mix.  scratch: count words + tempBytes (size query: scratch == nullptr).
-int launch_gw_order(uint32_t list, const Workspace& ws, uint32_t n, uint32_t count, uint32_t* scratch, size_t& tempBytes, hipStream_t st)
+int launch_gw_order(SideRow row, const Workspace& ws, uint32_t n, uint32_t count, uint32_t* scratch, size_t& tempBytes, hipStream_t st)
 {
     if (!scratch) { tempBytes = (size_t)kOrderSlots * 4 + 256; return 0; }
     if (count == 0) return 0;
-    uint32_t* side = ws.sideList + (size_t)list * n;
+    const uint32_t list = row;
     uint32_t* outv = scratch;
     uint32_t* hist = reinterpret_cast<uint32_t*>((reinterpret_cast<uintptr_t>(scratch + count) + 255u) & ~(uintptr_t)255u);
     if (hipMemsetAsync(hist, 0, (size_t)kOrderSlots * 4, st) != hipSuccess) return 1;
@@ -344,7 +344,7 @@ int launch_gw_order(uint32_t list, const Workspace& ws, uint32_t n, uint32_t cou
     return (int)hipGetLastError();
 }
 
-// segments = the first nseg records of the sorted class (ws.sideList[3]); temp: caller's buffer (size query with temp == nullptr)
+// segments = the first nseg records of the sorted class (kSideSorted); temp: caller's buffer (size query with temp == nullptr)
 int launch_gw_segsort(void* temp, size_t& tempBytes, const uint32_t* in, uint32_t* out, uint64_t poolCap, const Workspace& ws, uint32_t n, uint32_t nseg,
                       uint32_t endBit, hipStream_t st, const GwSortSide* side2)
 {

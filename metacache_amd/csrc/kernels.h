@@ -147,21 +147,19 @@ struct Workspace {           // device buffers sized by the host for this batch
     uint32_t* qflag;         // [n]        0 = done, 1 = needs sketch+probe (wave), 2 = needs candidates (wave),
                              //            4 = sketched by a lane (probe_cands_kernel takes it from there), 5 = on a work list of mid_cands_kernel,
                              //            6 = long read handled by the chunk lane kernels
-    uint32_t* midCount;      // [32]; [8] = third work list of hash_cands_kernel (129..256);       lengths of the three work lists of mid_cands_kernel, [3], [4] = of hash_cands_kernel, [5] = chunk records, [6], [7] = queries left for the wave kernels (launch_flag_count) (zeroed per batch)
+    uint32_t* midCount;      // [kCounterWords] work-list counters, zeroed per batch (slots: kCnt* below)
     uint2*    chunkList;     // [W + n]    {query, chunk}: long single reads, cut into one-window chunks for the chunk lane kernels
     uint32_t  partialLists;  // 1: every lane-path query hands its entry table over and ends there (MC_WANT_PARTIAL_HITS: gather_lists_kernel copies the lists)
-    uint32_t  bigMin;        // lists longer than this (and > 256) from <= 64 found features go to big_filter_kernel (midCount[9], list 6), which
-                             // hands their filtered parts (bigPool, cursor midCount[11]) to big_count_kernel (midCount[10] / [12], lists 7 / 8)
+    uint32_t  bigMin;        // lists longer than this (and > 64) from few enough found features take the filtered path (class kClassFilter)
     uint32_t* sliceFill;     // [waves of big_filter_kernel] entries each wave's pool slice holds after the first instance (nullptr: single instance)
     uint64_t* bigPool;       // [bigPoolCap] filtered locations of a batch
-    uint32_t* sideList;      // [5][n] ([4]: the sorted class' lists gw_count_block_kernel takes, midCount[19]) compact store: record numbers (list 6 / 7) of the reads gw_filter_stream_kernel takes ([0], length midCount[12]), of the
-                             // filtered lists of 257 .. 512 ([1], midCount[14]) and 513 .. 1024 numbers ([2], midCount[15]) and of the sorted ones ([3], midCount[13])
+    uint32_t* sideList;      // [kSideRows][n] compact store: record numbers of the filtered path (rows: kSide* below)
     uint32_t* bigPool2;      // [bigPoolCap] compact store: the filtered lists that are sorted (gw_sort.hip), at their pool offsets
     uint32_t* orderScratch;  // compact store, batches up to 2^20 reads: scratch of launch_gw_order for the stream filter's list (3 n words + orderTemp bytes); nullptr: no ordering
     size_t    orderTemp;
     uint32_t  bigPoolCap;
-    uint32_t  bigOvfCap;     // compact store: entries behind bigPoolCap for filtered lists that may not fit their wave's slice (cursor: midCount[16..17] as u64)
-    uint32_t* midList;       // [8][n] x uint4 {query, first entry slot, entries | locations << 8, maxWindowsInRange}: lists of 33..64 / 65..128 / 129..256
+    uint32_t  bigOvfCap;     // compact store: entries behind bigPoolCap for filtered lists that may not fit their wave's slice (cursor: kCntOverflow)
+    uint4*    midList;       // [kWorkLists][n] {query, first entry slot, entries | locations << 12, maxWindowsInRange} (lists: kList* below)
     uint32_t* hitScan;       // [n]        hits that need a segment in 'hits' (all, or only lists too long for LDS)
     uint64_t* hitOff;        // [n+1]      exclusive scan of hitScan
     uint64_t* hits;          // [H]        gathered + sorted locations
@@ -174,6 +172,45 @@ struct Workspace {           // device buffers sized by the host for this batch
     uint32_t  gwBigH = 32768;     // reads beyond this many locations take the stream filter's fine-block instance (gw_kernels.hip kGwBigH; 0xFFFFFFFF: none)
     int32_t   filterBpc = 0, countBpc = 0, gwFuse = 1;   // gwFuse: gw_filter_count_kernel (1) or gw_filter_kernel + gw_count_kernel (0)
 };
+
+// ---- the lane path's work lists: who hands which reads to whom ------------------------------------------------------------------------
+// The probing kernels sort every read into a CLASS: classes 0 .. 5 are the midList lists of the same number, kClassWave the wave kernels
+// (no list), kClassFilter the filtered path (list kListFilter).  A list's length is a counter slot of ws.midCount; the host copies the
+// first kHostCounters slots (launch_flag_count_host) and launches only the kernels with work.  "8-byte" / "compact": the location stores.
+//   slot  name            holds                                               written by                         read by
+//   0-2   kCntMid*        lengths of kListMid64 / 128 / 256                   probe_cands_one                    mid_cands_kernel, host
+//   3-4   kCntHash512/1024 lengths of kListHash512 / 1024                    probe_cands_one                    hash_cands_kernel<10/11>, host
+//   5     kCntChunks      chunk records in ws.chunkList                       lane_chunk_records                 chunk_sketch / probe / finish kernels
+//   6-7   kCntWave*       reads left to the wave kernels: to sketch / with     flag_count(_small)_kernel          host
+//                         a list in HBM
+//   8     kCntHash256     length of kListHash256                              probe_cands_one                    hash_cands_kernel<9>, host
+//   9     kCntFilter      length of kListFilter (and of kListFiltered)        probe_cands_one, chunk_finish,     every filter and count kernel,
+//                                                                             wave_rejoin, owner_classify,       big_stats_kernel, host
+//                                                                             owner_entries
+//   10    kCntSecond      8-byte: reads with more than kBigEnt entries        as kCntFilter                      big_filter_kernel<EPL > 1>, host
+//                         compact: reads beyond kGwSmallH locations, + the     + gw_filter(_count)_kernel          gw_filter2_kernel, host
+//                         reads the register filters defer
+//   12    kCntStream      length of kSideStream                               gw_compact_kernel (stage 0)        gw_filter_stream_kernel, launch_gw_order
+//   13    kCntSorted      length of kSideSorted                               gw_compact_kernel (stage 1)        gw_sort.hip, gw_sorted_cands_kernel, host
+//   14-15 kCnt512/1024    lengths of kSide512 / kSide1024                     gw_compact_kernel (stage 1)        gw_count_kernel<10> / <11>
+//   16-17 kCntOverflow    u64 cursor of the pool's overflow region            gw_filter_stream_kernel
+//   18    kCntSortedBig   sorted lists left to the 16-wave instance           gw_sorted_cands_kernel<BIG=false>  gw_sorted_cands_kernel<BIG=true>
+constexpr uint32_t kCntMid64 = 0, kCntMid128 = 1, kCntMid256 = 2, kCntHash512 = 3, kCntHash1024 = 4, kCntChunks = 5, kCntWaveSketch = 6,
+                   kCntWaveCands = 7, kCntHash256 = 8, kCntFilter = 9, kCntSecond = 10, kCntStream = 12, kCntSorted = 13, kCnt512 = 14,
+                   kCnt1024 = 15, kCntOverflow = 16, kCntSortedBig = 18;
+constexpr uint32_t kCounterWords = 32, kCounterBytes = kCounterWords * 4, kHostCounters = 16;   // midList = midCount + kCounterWords
+// midList: records {query, first entry slot, entries | locations << 12, maxWindowsInRange}; kListFiltered holds, at the place of the
+// read's kListFilter record, what the filter kept {query, pool offset, kept numbers (or kGwDefer / kGwFallback), maxWindowsInRange}
+enum WorkList : uint32_t { kListMid64, kListMid128, kListMid256, kListHash512, kListHash1024, kListHash256, kListFilter, kListFiltered, kWorkLists };
+constexpr uint32_t kClassWave = 6, kClassFilter = 7;
+__host__ __device__ __forceinline__ constexpr uint32_t class_counter(uint32_t c) { return c < 5 ? c : c == 5 ? kCntHash256 : kCntFilter; }
+__host__ __device__ __forceinline__ constexpr uint32_t class_list(uint32_t c) { return c == kClassFilter ? kListFilter : c; }
+// sideList (compact store): record numbers of kListFilter / kListFiltered for the kernels that take few of them, made by gw_compact_kernel
+enum SideRow : uint32_t { kSideStream, kSide512, kSide1024, kSideSorted, kSideRows };   // the stream filter's reads, 257 .. 512 / 513 .. 1024 kept, the sorted class
+__host__ __device__ __forceinline__ constexpr uint32_t side_counter(uint32_t r) { return r == kSideStream ? kCntStream : r == kSide512 ? kCnt512 : r == kSide1024 ? kCnt1024 : kCntSorted; }
+// where list / row `list` of a batch of n reads begins in midList / sideList
+__host__ __device__ __forceinline__ constexpr size_t list_at(uint32_t list, uint32_t n) { return (size_t)list * n; }
+inline size_t work_lists_bytes(uint32_t n) { return kCounterBytes + (size_t)kWorkLists * (n ? n : 1) * 16; }   // counters + lists, one buffer
 
 // launchers (all asynchronous on 'st')
 // Results of a batch of the host slots to the slots' own PINNED host buffers by ONE kernel (uint4 stores over the host link): every
@@ -228,27 +265,41 @@ void launch_table_values(const uint32_t* keys, const uint8_t* sizes, uint32_t n,
 // compact store: dst32[...] = gwBase[tgt] + win; a location outside its target's windows (or of an unknown target) raises *rangeErr instead
 void launch_table_values_compact(const uint32_t* keys, const uint8_t* sizes, uint32_t n, LoadFilter lf, const uint32_t* fileOff, const uint32_t* storeOff,
                                  const uint8_t* vals, uint32_t tb, uint64_t totalFileVals, uint32_t* dst32, GwLayout gw, unsigned int* rangeErr, hipStream_t st);
-void launch_chunk_lanes(int stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, int quadMode, hipStream_t st);
+void launch_chunk_sketch(const BatchView& b, const SketchParams& sp, const Workspace& ws, hipStream_t st);
+void launch_chunk_probe(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, int quadMode, hipStream_t st);
 void launch_sketch_probe_lane(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                               const uint32_t* taxkey, void* cands, int quadMode, hipStream_t st);
 // up to 16 candidate lists per read ([n][K] each, device), merged in list order through the CPU's top-list insert; K <= 4.  -1: not supported
 int launch_merge_parts(const void* const* lists, uint32_t nlists, uint32_t n, uint32_t K, const uint32_t* taxkey, void* out, hipStream_t st);
 void launch_flag_count(const Workspace& ws, uint32_t n, hipStream_t st);
-// compact store: reads sketched and probed by the wave kernel join the filtered path's work list (list 6) where it can take them
+// compact store: reads sketched and probed by the wave kernel join the filtered path's work list (kListFilter) where it can take them
 void launch_wave_rejoin(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, hipStream_t st);
-void launch_hash_cands(uint32_t cls, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand, const uint32_t* taxkey, void* cands, hipStream_t st);
-void launch_big_cands(uint32_t stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+void launch_hash_cands(WorkList list, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand, const uint32_t* taxkey, void* cands, hipStream_t st);
+// the filtered path's launches in the order run_filtered_path makes them: the 8-byte store (big_* kernels) takes Filter, BigFilter2,
+// Count and Count1024, the compact store (gw_kernels.hip) all others
+enum class FilterStep {
+    Filter,           // big_filter_kernel / gw_filter_count_kernel (gw_filter_kernel with "gw_fuse" 0)
+    BigFilter2,       // 8-byte: big_filter_kernel's second instance (reads with more than kBigEnt entries)
+    PairFilter,       // compact: gw_filter2_kernel (read pairs: two register batches)
+    Compact,          // compact: gw_compact_kernel, the stream filter's reads (+ launch_gw_order)
+    StreamFine, StreamMid, Stream,   // compact: gw_filter_stream_kernel's instances (Stream: + gw_compact_kernel, the counting classes)
+    Count,            // big_count_kernel<10> (up to 512 kept) / gw_count_kernel<9> (up to 256)
+    Count512,         // compact: gw_count_kernel<10> (257 .. 512)
+    Count1024,        // big_count_kernel<11> / gw_count_kernel<11> (513 .. 1024)
+    SortedCands       // compact: gw_sorted_cands_kernel (after launch_gw_segsort)
+};
+void launch_big_cands(FilterStep step, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                       const uint32_t* taxkey, void* cands, hipStream_t st);
 void launch_gather_lists(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t* numbers, hipStream_t st);
-// gw_sort.hip: the filtered lists that are sorted instead of counted (the first nseg records of ws.sideList[3]), pool -> out at the same
+// gw_sort.hip: the filtered lists that are sorted instead of counted (the first nseg records of kSideSorted), pool -> out at the same
 // offsets; temp == nullptr: size query
 struct GwSortSide { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };   // a second stream for the sort's independent instances (the caller's: a Pipe's)
 int launch_gw_segsort(void* temp, size_t& tempBytes, const uint32_t* in, uint32_t* out, uint64_t poolCap, const Workspace& ws, uint32_t n, uint32_t nseg,
                       uint32_t endBit, hipStream_t st, const GwSortSide* side2 = nullptr);
-// ws.sideList[list] (list 0: the stream filter's reads, 3: the sorted class) in descending order of the records' work; scratch == nullptr: size query
-int launch_gw_order(uint32_t list, const Workspace& ws, uint32_t n, uint32_t count, uint32_t* scratch, size_t& tempBytes, hipStream_t st);
+// a side list (kSideStream or kSideSorted) in descending order of the records' work; scratch == nullptr: size query
+int launch_gw_order(SideRow row, const Workspace& ws, uint32_t n, uint32_t count, uint32_t* scratch, size_t& tempBytes, hipStream_t st);
 uint32_t big_filter_grid(uint32_t n, bool compact, int bpcOverride = 0);     // (bpcOverride: mc_set_tuning "filter_bpc" of the context) blocks of 4 waves the filter kernels run with (compact: the gw kernels): the pool is cut into one slice per wave
-void launch_mid_cands(uint32_t cls, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+void launch_mid_cands(WorkList list, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                       const uint32_t* taxkey, void* cands, hipStream_t st);
 void launch_cands_from_hits(const BatchView& b, const DeviceTable& tab, const Workspace& ws, const uint32_t* taxkey, uint32_t maxCand,
                             void* cands, hipStream_t st);

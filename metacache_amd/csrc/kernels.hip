@@ -703,9 +703,9 @@ __global__ __launch_bounds__(256) void owner_classify_kernel(BatchView b, Worksp
     if (big) {
         const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
         uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&ws.midCount[9], (uint32_t)__popcll(mask));
+        if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(mask));
         base = __shfl(base, leader);
-        reinterpret_cast<uint4*>(ws.midList)[(size_t)6 * b.n + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q, 1u | (H << 12), mw);
+        ws.midList[list_at(kListFilter, b.n) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q, 1u | (H << 12), mw);
     }
 }
 void launch_owner_classify(const BatchView& b, const Workspace& ws, uint32_t minLen, hipStream_t st)
@@ -1297,7 +1297,7 @@ __device__ __forceinline__ uint32_t lane_chunk_records(const BatchView& b, const
     const uint32_t total = rdlane(incl, 63);
     if (total) {
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(&ws.midCount[5], total);
+        if (lane == 0) base = atomicAdd(&ws.midCount[kCntChunks], total);
         base = rdlane(base, 0);
         // the wave writes its records together (64 consecutive ones per round); record r belongs to the first lane with incl > r
         for (uint32_t r0 = 0; r0 < total; r0 += 64) {
@@ -1333,7 +1333,7 @@ __global__ __launch_bounds__(256) void sketch_lane_kernel(BatchView b, SketchPar
 // one lane per chunk: the window sketches of its <= kChunkWins windows
 __global__ __launch_bounds__(128) void chunk_sketch_kernel(BatchView b, SketchParams sp, Workspace ws)
 {
-    const uint32_t total = ws.midCount[5];
+    const uint32_t total = ws.midCount[kCntChunks];
     for (uint32_t id = blockIdx.x * 128 + threadIdx.x; id < total; id += gridDim.x * 128) {
         const uint2 rec = ws.chunkList[id];
         const uint32_t q = rec.x, c = rec.y;
@@ -1397,7 +1397,7 @@ uint32_t build_record_windows() { return kBuildRecWins; }
 template <bool QUAD>
 __global__ __launch_bounds__(128) void chunk_probe_kernel(BatchView b, uint32_t s, DeviceTable tab, Workspace ws)
 {
-    const uint32_t total = ws.midCount[5];
+    const uint32_t total = ws.midCount[kCntChunks];
     for (uint32_t base = blockIdx.x * 128; base < total; base += gridDim.x * 128) {   // block-uniform: quads stay together
         const uint32_t id = base + threadIdx.x;
         uint2 rec = make_uint2(0, 0);
@@ -1481,7 +1481,7 @@ __global__ __launch_bounds__(128) void chunk_probe_kernel(BatchView b, uint32_t 
 // slots, found or not, as the entries) instead of the wave kernel's sort of everything.
 __global__ __launch_bounds__(256) void chunk_finish_kernel(uint32_t s, Workspace ws, BatchView b, DeviceTable tab)
 {
-    const uint32_t total = ws.midCount[5];
+    const uint32_t total = ws.midCount[kCntChunks];
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t nWaves = gridDim.x * 4, waveId = blockIdx.x * 4 + (threadIdx.x >> 6);
     for (uint32_t base = waveId * 64; base < total; base += nWaves * 64) {
@@ -1523,12 +1523,12 @@ __global__ __launch_bounds__(256) void chunk_finish_kernel(uint32_t s, Workspace
         if (fm) {
             const uint32_t leader = __ffsll((unsigned long long)fm) - 1;
             uint32_t at = 0;
-            if (lane == leader) at = atomicAdd(&ws.midCount[9], (uint32_t)__popcll(fm));
+            if (lane == leader) at = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(fm));
             at = __shfl(at, leader);
             if (filtered)
-                reinterpret_cast<uint4*>(ws.midList)[(size_t)6 * b.n + at + __popcll(fm & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (myH << 12), mw);
+                ws.midList[list_at(kListFilter, b.n) + at + __popcll(fm & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (myH << 12), mw);
             const uint64_t wm = __ballot(wide);
-            if (wm && lane == leader) atomicAdd(&ws.midCount[10], (uint32_t)__popcll(wm));
+            if (wm && lane == leader) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wm));
         }
     }
 }
@@ -1814,34 +1814,35 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
         // lists of up to 256 locations: work lists of mid_cands_kernel (4 / 8 / 16 lanes per query); one atomic per wave and class
         // ... and of hash_cands_kernel (257 .. 1024 locations, one wave per query, no sort); longer ones, wide window ranges -> wave kernel
         const uint32_t mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-        // work list slots: 0 / 1 / 2 mid_cands (64 / 128 / 256), 3 / 4 / 5 hash_cands (512 / 1024 / 256), 6 = wave kernel.  From 129 locations
-        // on counting beats sorting (measured per list: 3.3 vs 4.7 ns at 129..256); below, the register sort wins (1.6 vs 2 ns)
+        // (classes: kernels.h).  From 129 locations on counting beats sorting (measured per list: 3.3 vs 4.7 ns at 129..256); below, the
+        // register sort wins (1.6 vs 2 ns)
         const bool hashOK = nent <= kHashEnt && mw <= kHashWin;
-        // 7 = big_cands_kernel (filter first): lists beyond ws.bigMin locations from at most kBigEnt found features
+        // kClassFilter = the filtered path (filter first): lists beyond ws.bigMin locations from at most kBigEnt found features
         // (compact store: any number of entries the record can name, any window range the gap between two targets covers; filtered lists
         // the counting kernels do not take are sorted, gw_sorted_cands_kernel)
         const bool bigOK = H > ws.bigMin && H > 64u &&              // (lists up to 64 are sorted in registers, mid_cands_kernel)
                            (tab.values32 ? (nent <= 0xFFFu && mw <= tab.gwGap && H <= kMaxHitsPerQuery) : (nent <= kBigEnt * kBigEPL && mw <= kHashWin));
-        const uint32_t cls = bigOK ? 7u : H <= 64 ? 0u : H <= 128 ? (hashOK ? 5u : 1u) : H <= kMidMax ? (hashOK ? 5u : 2u) : (H <= kHashMax && hashOK) ? (H <= kHashMax / 2 ? 3u : 4u) : 6u;
-        ws.qflag[q] = cls != 6 ? kFlagMid : kFlagCands;
-        if (cls >= 3 && cls != 6) ws.hitScan[q] = 0u;                            // no segment in HBM
+        const uint32_t cls = bigOK ? kClassFilter : H <= 64 ? kListMid64 : H <= 128 ? (hashOK ? kListHash256 : kListMid128) : H <= kMidMax ? (hashOK ? kListHash256 : kListMid256)
+                           : (H <= kHashMax && hashOK) ? (H <= kHashMax / 2 ? kListHash512 : kListHash1024) : kClassWave;
+        ws.qflag[q] = cls != kClassWave ? kFlagMid : kFlagCands;
+        if (cls >= kListHash512 && cls != kClassWave) ws.hitScan[q] = 0u;                            // no segment in HBM
         const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
         for (uint32_t c = 0; c < 8; ++c) {
-            if (c == 6) continue;
+            if (c == kClassWave) continue;
             const uint64_t mask = __ballot(cls == c);
             if (cls == c) {
                 const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
                 uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&ws.midCount[c < 5 ? c : c == 5 ? 8u : 9u], (uint32_t)__popcll(mask));
+                if (lane == leader) base = atomicAdd(&ws.midCount[class_counter(c)], (uint32_t)__popcll(mask));
                 base = __shfl(base, leader);
-                reinterpret_cast<uint4*>(ws.midList)[(size_t)(c == 7 ? 6u : c) * b.n + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, fbase, nent | (H << 12), b.maxWin ? b.maxWin[q] : b.maxWinUniform);
+                ws.midList[list_at(class_list(c), b.n) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, fbase, nent | (H << 12), b.maxWin ? b.maxWin[q] : b.maxWinUniform);
             }
         }
-        {   // [10]: how many of the filter's queries have more than kBigEnt entries (its second instance runs only for those)
+        {   // kCntSecond: how many of the filter's queries have more than kBigEnt entries (its second instance runs only for those)
             // (compact store: how many have more than kGwSmallH locations -- gw_filter_kernel's second instance)
-            const uint64_t wide = __ballot(cls == 7 && (tab.values32 ? H > kGwSmallH : nent > kBigEnt));
-            if (wide && lane == (uint32_t)__ffsll((unsigned long long)wide) - 1) atomicAdd(&ws.midCount[10], (uint32_t)__popcll(wide));
+            const uint64_t wide = __ballot(cls == kClassFilter && (tab.values32 ? H > kGwSmallH : nent > kBigEnt));
+            if (wide && lane == (uint32_t)__ffsll((unsigned long long)wide) - 1) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wide));
         }
         return;
     }
@@ -1944,17 +1945,18 @@ void launch_sketch_lane(const BatchView& b, const SketchParams& sp, const Worksp
     if (b.n == 0) return;
     hipLaunchKernelGGL(sketch_lane_kernel, dim3((b.n + 255) / 256), dim3(256), 0, st, b, sp, ws);
 }
-void launch_chunk_lanes(int stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, int quadMode, hipStream_t st)
+// persistent grids over the chunk work list (usually empty: its length stays on the device)
+void launch_chunk_sketch(const BatchView& b, const SketchParams& sp, const Workspace& ws, hipStream_t st)
+{
+    if (b.n && ws.chunkList) hipLaunchKernelGGL(chunk_sketch_kernel, dim3(2048), dim3(128), 0, st, b, sp, ws);
+}
+void launch_chunk_probe(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, int quadMode, hipStream_t st)
 {
     if (b.n == 0 || !ws.chunkList) return;
-    // persistent grids over the chunk work list (usually empty: its length stays on the device)
-    if (stage == 0) hipLaunchKernelGGL(chunk_sketch_kernel, dim3(2048), dim3(128), 0, st, b, sp, ws);
-    else {
-        const bool quad = quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
-        if (quad) hipLaunchKernelGGL(chunk_probe_kernel<true>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
-        else      hipLaunchKernelGGL(chunk_probe_kernel<false>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
-        hipLaunchKernelGGL(chunk_finish_kernel, dim3(1024), dim3(256), 0, st, sp.s, ws, b, tab);
-    }
+    const bool quad = quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
+    if (quad) hipLaunchKernelGGL(chunk_probe_kernel<true>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
+    else      hipLaunchKernelGGL(chunk_probe_kernel<false>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
+    hipLaunchKernelGGL(chunk_finish_kernel, dim3(1024), dim3(256), 0, st, sp.s, ws, b, tab);
 }
 // Mode K, shard side: the location lists of the lane path's queries as they are (any order inside a list; the owner rank sorts the
 // union), copied from the table to ws.hits + hitOff[q].  One wave per 64 queries' flags, then one query at a time: its found
@@ -2112,8 +2114,8 @@ __global__ __launch_bounds__(256) void mid_cands_kernel(BatchView b, DeviceTable
     uint64_t* buf = listS[wave] + qi * (G * ROW);            // this query's list, padded: element i at mid_ix(i)
     uint32_t* sg = segS[wave] + qi * (G * ROW);              // entry offsets while gathering, then the query's segments
 
-    const uint32_t total = ws.midCount[cls];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)cls * b.n;
+    const uint32_t total = ws.midCount[cls];                      // (kListMid*: the list's counter slot is its number)
+    const uint4* __restrict__ work = ws.midList + list_at(cls, b.n);
     const uint32_t nWaves = gridDim.x * 4;
     // two-deep software pipeline over the work list: the record of iteration t+2 and the first kRounds x G entries of iteration
     // t+1 are requested while iteration t is processed (three dependent HBM round trips per query otherwise)
@@ -2327,15 +2329,15 @@ static void launch_mid_g(uint32_t grid, uint32_t cls, const BatchView& b, const 
     else        hipLaunchKernelGGL((mid_cands_kernel<G, false>), dim3(grid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands, cls);
 }
 
-void launch_mid_cands(uint32_t cls, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+void launch_mid_cands(WorkList list, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                       const uint32_t* taxkey, void* cands, hipStream_t st)
 {
     if (b.n == 0) return;
     // persistent grids: the work lists are usually short (their lengths stay on the device); 3 blocks fit a CU (53 KB of LDS each)
     const uint32_t blocks = 256 * 3;
-    if (cls == 0)      launch_mid_g<4>(std::min<uint32_t>(blocks, (b.n + 63) / 64), 0u, b, tab, ws, maxCand, taxkey, cands, st);
-    else if (cls == 1) launch_mid_g<8>(std::min<uint32_t>(blocks, (b.n + 31) / 32), 1u, b, tab, ws, maxCand, taxkey, cands, st);
-    else               launch_mid_g<16>(std::min<uint32_t>(blocks, (b.n + 15) / 16), 2u, b, tab, ws, maxCand, taxkey, cands, st);
+    if (list == kListMid64)       launch_mid_g<4>(std::min<uint32_t>(blocks, (b.n + 63) / 64), list, b, tab, ws, maxCand, taxkey, cands, st);
+    else if (list == kListMid128) launch_mid_g<8>(std::min<uint32_t>(blocks, (b.n + 31) / 32), list, b, tab, ws, maxCand, taxkey, cands, st);
+    else                          launch_mid_g<16>(std::min<uint32_t>(blocks, (b.n + 15) / 16), kListMid256, b, tab, ws, maxCand, taxkey, cands, st);
 }
 // ================================================================================================
 // hash_cands_kernel: location lists of 257 .. 1024 entries (RefSeq-scale tables: 32-bit features collide, a 150 bp read collects
@@ -2504,8 +2506,8 @@ __global__ __launch_bounds__(WAVES * 64) void hash_cands_kernel(BatchView b, Dev
     uint32_t* cnts = cntS[wave];
     uint64_t* entPay = entPayS[wave];
     uint32_t* entOff = entOffS[wave];
-    const uint32_t total = ws.midCount[cls < 5 ? cls : 8u];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)cls * b.n;
+    const uint32_t total = ws.midCount[cls < kListHash256 ? cls : kCntHash256];
+    const uint4* __restrict__ work = ws.midList + list_at(cls, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0, 0); };
     uint32_t esz[kRounds]; uint64_t epay[kRounds];
@@ -2711,7 +2713,7 @@ __device__ __forceinline__ void big_sweep(const BigTables& T, const DeviceTable&
 
 // No atomics on global memory: a wave appends its filtered lists to ITS OWN slice of the pool (a million waves bumping one cursor
 // cost more than the sweeps: 43 ms instead of 14), and the record for big_count_kernel goes to the place of the query's own work
-// record (list 7 runs parallel to list 6; n2 = 0xFFFF marks lists that went to the wave kernel instead).
+// record (kListFiltered runs parallel to kListFilter; n2 = 0xFFFF marks lists that went to the wave kernel instead).
 #ifdef MC_BIG_WPE
 #define MC_BIG_WPE_ATTR __attribute__((amdgpu_waves_per_eu(MC_BIG_WPE, MC_BIG_WPE)))
 #else
@@ -2736,10 +2738,10 @@ __global__ __launch_bounds__(WAVES * 64) MC_BIG_WPE_ATTR void big_filter_kernel(
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     uint32_t* bits = bitS[wave];
     BigTables& T = tabS[wave];
-    const uint32_t total = ws.midCount[9];
-    if (EPL > 1 && ws.midCount[10] == 0) return;                  // no query with more than kBigEnt entries in this batch
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)6 * b.n;
-    uint4* __restrict__ outRec = reinterpret_cast<uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    if (EPL > 1 && ws.midCount[kCntSecond] == 0) return;          // no query with more than kBigEnt entries in this batch
+    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    uint4* __restrict__ outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0, 0); };
     auto mine = [](uint32_t nent) { return EPL == 1 ? nent <= kBigEnt : nent > kBigEnt; };
@@ -2876,10 +2878,10 @@ __global__ __launch_bounds__(WAVES * 64) void big_count_kernel(BatchView b, uint
     pool_t* keys = keyS[wave];
     uint32_t* cnts = cntS[wave];
     BigTables& T = *reinterpret_cast<BigTables*>(keyS[wave]);      // (10 KB instead of 13 KB of LDS per wave: 16 waves per CU instead of 12)
-    // the records big_filter_kernel left (list 7, one per query of work list 6); this instance takes the filtered lists that fit its
+    // the records big_filter_kernel left (kListFiltered, one per query of kListFilter); this instance takes the filtered lists that fit its
     // table: n2 in (minN2, kList]
-    const uint32_t total = ws.midCount[9];
-    const uint4* __restrict__ work = reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * b.n;
+    const uint32_t total = ws.midCount[kCntFilter];
+    const uint4* __restrict__ work = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0xFFFFu, 0); };
     const uint32_t w0 = blockIdx.x * WAVES + wave;
@@ -3012,28 +3014,28 @@ __global__ __launch_bounds__(WAVES * 64) void big_count_kernel(BatchView b, uint
     }
 }
 
-void launch_big_cands(uint32_t stage, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
+void launch_big_cands(FilterStep step, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                       const uint32_t* taxkey, void* cands, hipStream_t st)
 {
     if (b.n == 0) return;
     // tables with the compact location store (global window numbers): their own kernels, gw_kernels.hip
-    if (tab.values32) { launch_gw_cands(stage, b, sp, tab, ws, maxCand, taxkey, cands, st); return; }
+    if (tab.values32) { launch_gw_cands(step, b, sp, tab, ws, maxCand, taxkey, cands, st); return; }
     mc_candidate_dev* c = (mc_candidate_dev*)cands;
-    // persistent grids.  stage 0: the filter; 1: counting of filtered lists up to 512; 2: 513 .. 1024
+    // persistent grids
     auto count = [&](auto log2s, auto waves, uint32_t grid, uint32_t minN2) {
         constexpr uint32_t L = decltype(log2s)::value, W = decltype(waves)::value;
         if (taxkey) hipLaunchKernelGGL((big_count_kernel<L, W, true>), dim3(grid), dim3(W * 64), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, minN2);
         else        hipLaunchKernelGGL((big_count_kernel<L, W, false>), dim3(grid), dim3(W * 64), 0, st, b, sp.s, tab, ws, maxCand, taxkey, c, minN2);
     };
-    if (stage == 0) {
+    if (step == FilterStep::Filter) {
         hipLaunchKernelGGL((big_filter_kernel<4, 1, false, kBigT1Log2, kBigT2Log2>), dim3(big_filter_grid(b.n, false, ws.filterBpc)), dim3(256), 0, st, b, tab, ws);
-    } else if (stage == 3) {                                   // the filter's second instance: queries with 65 .. 192 found features
+    } else if (step == FilterStep::BigFilter2) {              // the filter's second instance: queries with 65 .. 192 found features
         // two waves per block, twice the blocks: the same number of waves -- and so the same pool slices -- as the first instance
         hipLaunchKernelGGL((big_filter_kernel<2, kBigEPL, true, MC_BIG_POS_T1, MC_BIG_POS_T2>), dim3(2 * big_filter_grid(b.n, false, ws.filterBpc)), dim3(128), 0, st, b, tab, ws);
-    } else if (stage == 1) {
+    } else if (step == FilterStep::Count) {
         // blocks per CU by LDS: 40 KB per block
         count(std::integral_constant<uint32_t, 10>{}, std::integral_constant<uint32_t, 4>{}, std::min<uint32_t>(256 * big_count_bpc(false), (b.n + 3) / 4), 0u);
-    } else if (stage == 2) {
+    } else if (step == FilterStep::Count1024) {
         static const uint32_t env2 = [] { const char* e = std::getenv("MC_BIG_COUNT2_BPC"); return e ? (uint32_t)std::max(1, std::atoi(e)) : 0u; }();
         const uint32_t bpc2 = env2 ? env2 : 4u;
         count(std::integral_constant<uint32_t, 11>{}, std::integral_constant<uint32_t, 2>{}, std::min<uint32_t>(256 * bpc2, (b.n + 1) / 2), 512u);
@@ -3052,16 +3054,17 @@ uint32_t big_filter_grid(uint32_t n, bool compact, int bpcOverride)
     return std::min<uint32_t>(256 * bpc, (n + 3) / 4);
 }
 
-void launch_hash_cands(uint32_t cls, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand, const uint32_t* taxkey, void* cands,
+void launch_hash_cands(WorkList list, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand, const uint32_t* taxkey, void* cands,
                        hipStream_t st)
 {
     if (b.n == 0) return;
+    const uint32_t cls = list;
     // persistent grids; LDS per block: 52 KB (512), 50 KB (1024), 40 KB (256)
-    if (cls == 3) {
+    if (list == kListHash512) {
         const uint32_t grid = std::min<uint32_t>(256 * 3, (b.n + 3) / 4);
         if (taxkey) hipLaunchKernelGGL((hash_cands_kernel<10, 4, true>), dim3(grid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands, cls);
         else        hipLaunchKernelGGL((hash_cands_kernel<10, 4, false>), dim3(grid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands, cls);
-    } else if (cls == 4) {
+    } else if (list == kListHash1024) {
         const uint32_t grid = std::min<uint32_t>(256 * 3, (b.n + 1) / 2);
         if (taxkey) hipLaunchKernelGGL((hash_cands_kernel<11, 2, true>), dim3(grid), dim3(128), 0, st, b, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands, cls);
         else        hipLaunchKernelGGL((hash_cands_kernel<11, 2, false>), dim3(grid), dim3(128), 0, st, b, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands, cls);
@@ -3087,12 +3090,12 @@ __global__ __launch_bounds__(256) void wave_rejoin_kernel(BatchView b, uint32_t 
     if (!m) return;
     const uint32_t leader = __ffsll((unsigned long long)m) - 1;
     uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&ws.midCount[9], (uint32_t)__popcll(m));
+    if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(m));
     base = __shfl(base, leader);
     const uint64_t large = __ballot(join && H > kGwSmallH);
-    if (large && lane == leader) atomicAdd(&ws.midCount[10], (uint32_t)__popcll(large));
+    if (large && lane == leader) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(large));
     if (join) {
-        reinterpret_cast<uint4*>(ws.midList)[(size_t)6 * b.n + base + __popcll(m & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (H << 12), mw);
+        ws.midList[list_at(kListFilter, b.n) + base + __popcll(m & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (H << 12), mw);
         ws.hitScan[q] = 0u; ws.qflag[q] = kFlagMid;
     }
 }
@@ -3140,8 +3143,8 @@ int launch_merge_parts(const void* const* lists, uint32_t nlists, uint32_t n, ui
     return 0;
 }
 
-// after the lane kernels: how many queries are left for the wave kernels (midCount[6]: to be sketched, [7]: candidates from a list in
-// HBM).  The host reads the eight counters once and launches only the kernels that have work -- a batch of 65 536 short reads spent
+// after the lane kernels: how many queries are left for the wave kernels (kCntWaveSketch: to be sketched, kCntWaveCands: candidates from
+// a list in HBM).  The host reads the counters once and launches only the kernels that have work -- a batch of 65 536 short reads spent
 // a fifth of its device time on launches of kernels with nothing to do.
 __global__ __launch_bounds__(256) void flag_count_kernel(const uint32_t* __restrict__ qflag, uint32_t n, uint32_t* __restrict__ counts)
 {
@@ -3151,15 +3154,15 @@ __global__ __launch_bounds__(256) void flag_count_kernel(const uint32_t* __restr
         a += f == kFlagSketch; c += f == kFlagCands;
     }
     const uint64_t ma = __ballot(a != 0), mc = __ballot(c != 0);
-    if (ma) { for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[6], a); }
-    if (mc) { for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[7], c); }
+    if (ma) { for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[kCntWaveSketch], a); }
+    if (mc) { for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[kCntWaveCands], c); }
 }
 
 void launch_flag_count(const Workspace& ws, uint32_t n, hipStream_t st)
 {
     if (n) hipLaunchKernelGGL(flag_count_kernel, dim3(std::min<uint32_t>((n + 255) / 256, 1024u)), dim3(256), 0, st, ws.qflag, n, ws.midCount);
 }
-// small batches: ONE block counts, and hands the sixteen work-list counters to the host (pinned memory) itself
+// small batches: ONE block counts, and hands the kHostCounters work-list counters to the host (pinned memory) itself
 __global__ __launch_bounds__(256) void flag_count_small_kernel(const uint32_t* __restrict__ qflag, uint32_t n, uint32_t* __restrict__ counts, uint32_t* __restrict__ hostCounts)
 {
     uint32_t a = 0, c = 0;
@@ -3168,17 +3171,17 @@ __global__ __launch_bounds__(256) void flag_count_small_kernel(const uint32_t* _
         a += f == kFlagSketch; c += f == kFlagCands;
     }
     const uint64_t ma = __ballot(a != 0), mc = __ballot(c != 0);
-    if (ma) { for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[6], a); }
-    if (mc) { for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[7], c); }
+    if (ma) { for (int off = 32; off > 0; off >>= 1) a += __shfl_down(a, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[kCntWaveSketch], a); }
+    if (mc) { for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off); if ((threadIdx.x & 63) == 0) atomicAdd(&counts[kCntWaveCands], c); }
     __threadfence();
     __syncthreads();
-    if (threadIdx.x < 16) { hostCounts[threadIdx.x] = __hip_atomic_load(&counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __threadfence_system(); }
+    if (threadIdx.x < kHostCounters) { hostCounts[threadIdx.x] = __hip_atomic_load(&counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __threadfence_system(); }
 }
 void launch_flag_count_host(const Workspace& ws, uint32_t n, uint32_t* hostCounts, hipStream_t st)
 {
     if (n && n <= kSmallPlan) { hipLaunchKernelGGL(flag_count_small_kernel, dim3(1), dim3(256), 0, st, ws.qflag, n, ws.midCount, hostCounts); return; }
     launch_flag_count(ws, n, st);
-    launch_words_to_host(hostCounts, ws.midCount, 16, st);
+    launch_words_to_host(hostCounts, ws.midCount, kHostCounters, st);
 }
 
 // A few words of device memory to PINNED HOST memory by a one-wave kernel on the batch's own stream: what the host looks at inside a
@@ -3240,11 +3243,11 @@ __global__ __launch_bounds__(256) void batch_stats_kernel(const QueryStat* __res
     }
 }
 
-// the filtered path's records of the batch (list 7): [5] = locations kept by the filter, [6] = reads that took the filtered path |
+// the filtered path's records of the batch (kListFiltered): [5] = locations kept by the filter, [6] = reads that took the filtered path |
 // those with more than 512 kept << 32, [7] = reads the first filter kernel left to the second (compact store) | handed to the wave kernel << 32
 __global__ __launch_bounds__(256) void big_stats_kernel(const uint32_t* __restrict__ midCount, const uint4* __restrict__ list7, uint64_t* __restrict__ stats, uint32_t overMin)
 {
-    const uint32_t total = midCount[9];
+    const uint32_t total = midCount[kCntFilter];
     unsigned long long kept = 0; uint32_t over = 0, fb = 0;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         uint32_t n2 = list7[i].z;
@@ -3254,7 +3257,7 @@ __global__ __launch_bounds__(256) void big_stats_kernel(const uint32_t* __restri
     atomicAdd((unsigned long long*)&stats[5], kept);
     atomicAdd((unsigned long long*)&stats[6], (unsigned long long)over << 32);
     atomicAdd((unsigned long long*)&stats[7], (unsigned long long)fb << 32);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { atomicAdd((unsigned long long*)&stats[6], (unsigned long long)total); atomicAdd((unsigned long long*)&stats[7], (unsigned long long)midCount[10]); }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { atomicAdd((unsigned long long*)&stats[6], (unsigned long long)total); atomicAdd((unsigned long long*)&stats[7], (unsigned long long)midCount[kCntSecond]); }
 }
 
 void launch_batch_stats(const Workspace& ws, uint32_t n, hipStream_t st)
@@ -3265,7 +3268,7 @@ void launch_batch_stats(const Workspace& ws, uint32_t n, hipStream_t st)
     hipLaunchKernelGGL(batch_stats_kernel, dim3(blocks), dim3(256), 0, st, ws.qstat, ws.winOff, n, ws.stats);
     // ("more than 512 kept"; MC_STATS_OVER=n: another threshold, for looking at the distribution of the filtered lists' lengths)
     static const uint32_t overMin = [] { const char* e = std::getenv("MC_STATS_OVER"); return e ? (uint32_t)std::max(0, std::atoi(e)) : 512u; }();
-    if (ws.midCount) hipLaunchKernelGGL(big_stats_kernel, dim3(blocks), dim3(256), 0, st, ws.midCount, reinterpret_cast<const uint4*>(ws.midList) + (size_t)7 * n, ws.stats, overMin);
+    if (ws.midCount) hipLaunchKernelGGL(big_stats_kernel, dim3(blocks), dim3(256), 0, st, ws.midCount, ws.midList + list_at(kListFiltered, n), ws.stats, overMin);
 }
 
 }  // namespace mcamd

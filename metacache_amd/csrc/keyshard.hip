@@ -9,7 +9,7 @@
 //                                        order (the piece for the owner of reads [lo, hi) is ONE contiguous range) + per-read counts
 //   owner side   owner_entries         : NO union copy -- the receive buffer stands in for the table's location store, the piece of
 //                                        every source is one ENTRY of the read (what a found feature's bucket list is in the
-//                                        replicated mode); reads the filtered path takes become records of its work list (list 6)
+//                                        replicated mode); reads the filtered path takes become records of its work list (kListFilter)
 //                decode_union          : the rest (short lists, what the filtered path hands back): pieces -> (target, window) lists
 //                                        for the sort of cands_from_hits_kernel
 // Replaces the reference's per-part forwarding chain between its GPUs (query_batch.cu:464-527, :638-652, gpu_hashmap.cu:1255-1290).
@@ -122,12 +122,12 @@ __global__ __launch_bounds__(256) void owner_entries_kernel(BatchView b, DeviceT
     if (take) {
         const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
         uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&ws.midCount[9], (uint32_t)__popcll(mask));
+        if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(mask));
         base = __shfl(base, leader);
-        reinterpret_cast<uint4*>(ws.midList)[(size_t)6 * m + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q * S, S | (H << 12), mw);
+        ws.midList[list_at(kListFilter, m) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q * S, S | (H << 12), mw);
     }
     const uint64_t wmask = __ballot(wide);
-    if (wmask && lane == (uint32_t)__ffsll((unsigned long long)wmask) - 1) atomicAdd(&ws.midCount[10], (uint32_t)__popcll(wmask));
+    if (wmask && lane == (uint32_t)__ffsll((unsigned long long)wmask) - 1) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wmask));
 }
 void launch_owner_entries(const BatchView& b, const DeviceTable& tab, const Workspace& ws, const uint32_t* counts, const uint64_t* srcStart,
                           const KeyshardBases& bases, uint32_t S, hipStream_t st)
