@@ -19,7 +19,7 @@
 //   -taxids -taxids-only -omit-ranks -separate-cols -separator -comment -lineage -pairfiles -pairseq -insertsize -min-readlen
 //   -max-readlen -query-limit -sketchlen -winlen -winstride -max-locations-per-feature -remove-overpopulated-features -max-load-fac
 //   -no-query-params -no-summary -no-err -threads -batch-size -abundances [file] -abundance-per <rank> -hits-per-ref [file]
-//   -ground-truth -precision -taxon-coverage.  Not offered: -cov-percentile, -align.
+//   -ground-truth -precision -taxon-coverage -cov-percentile.  Not offered: -align.
 #include "mcq_build.h"
 
 #include <fcntl.h>
@@ -334,6 +334,23 @@ uint32_t classify(const Options& o, const Taxonomy& tx, const std::vector<Cand>&
     return lca;
 }
 
+// lowest_ranked_ancestor of a target's taxon: on rank 'lowest' or the closest one above it (0: none, or not a target)
+uint32_t lowest_ranked_ancestor(const Taxonomy& tx, uint32_t tgt, int lowest)
+{
+    if (tgt >= tx.numTargets) return 0;
+    const uint32_t* lin = tx.targetLineages + (size_t)tgt * kNumRanks;
+    if (lowest <= 0) return lin[0];
+    for (int rk = lowest; rk < kNumRanks; ++rk) if (lin[rk]) return lin[rk];
+    return 0;
+}
+
+// one query's device candidate list (K entries, the used ones first) as Cands
+void device_candidates(const mc_candidate* c, uint32_t K, const Taxonomy& tx, int lowest, std::vector<Cand>& out)
+{
+    out.clear();
+    for (uint32_t j = 0; j < K && c[j].hits != 0; ++j) out.push_back(Cand{c[j].tgt, c[j].hits, c[j].beg, c[j].end, lowest_ranked_ancestor(tx, c[j].tgt, lowest)});
+}
+
 // ---- database session: the loaded context is kept between jobs (interactive mode) as long as its load-time settings fit ----
 // Rows 9-10 on the host for ONE read's sorted location list: the reference's loop (for_all_contiguous_window_ranges,
 // candidate_generation.hpp:47-108) and its sorted insert without a limit (:172-231, same std:: calls so that equal hit counts fall
@@ -343,12 +360,7 @@ static void host_candidates(const mc_location* h, uint64_t n, uint32_t maxWin, c
     top.clear();
     auto greater = [](const Cand& a, const Cand& b) { return a.hits > b.hits; };
     auto insert = [&](Cand c) {
-        c.tax = 0;
-        if (c.tgt < tx.numTargets) {
-            const uint32_t* lin = tx.targetLineages + (size_t)c.tgt * kNumRanks;
-            if (lowest > 0) { for (int rk = lowest; rk < kNumRanks; ++rk) if (lin[rk]) { c.tax = lin[rk]; break; } }
-            else c.tax = lin[0];
-        }
+        c.tax = lowest_ranked_ancestor(tx, c.tgt, lowest);
         if (!c.tax) return;
         if (lowest <= 0) { top.insert(std::upper_bound(top.begin(), top.end(), c, greater), c); return; }
         auto i = std::find_if(top.begin(), top.end(), [&](const Cand& x) { return x.tax == c.tax; });
@@ -371,6 +383,17 @@ static void host_candidates(const mc_location* h, uint64_t n, uint32_t maxWin, c
         }
     }
     insert(best);
+}
+
+void read_taxa(mc_ctx* ctx, Taxonomy& tx)                                  // the taxa of a context's metadata
+{
+    uint64_t nt = 0; mc_db_num_taxa(ctx, &nt); tx.taxa.resize(nt);
+    for (uint64_t i = 0; i < nt; ++i) {
+        uint32_t rk; const char* nm;
+        mc_db_taxon(ctx, i, &tx.taxa[i].id, &tx.taxa[i].parent, &rk, &nm);
+        tx.taxa[i].rank = int(rk); tx.taxa[i].name = nm;
+        mc_db_taxon_source(ctx, i, nullptr, nullptr, &tx.taxa[i].windows);
+    }
 }
 
 struct Session {
@@ -446,13 +469,7 @@ struct Session {
             } else if (mc_partset_open(o.db.c_str(), &c, o.residentParts, o.gpus.empty() ? nullptr : o.gpus.data(), (uint32_t)o.gpus.size(), &partset) != MC_OK)
                 throw std::runtime_error(mc_partset_last_error(nullptr));
             if (mc_open_metadata(o.db.c_str(), &ctx) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
-            uint64_t nt = 0; mc_db_num_taxa(ctx, &nt); tx.taxa.resize(nt);
-            for (uint64_t i = 0; i < nt; ++i) {
-                uint32_t rk; const char* nm;
-                mc_db_taxon(ctx, i, &tx.taxa[i].id, &tx.taxa[i].parent, &rk, &nm);
-                tx.taxa[i].rank = int(rk); tx.taxa[i].name = nm;
-                mc_db_taxon_source(ctx, i, nullptr, nullptr, &tx.taxa[i].windows);
-            }
+            read_taxa(ctx, tx);
         } else if (built) {
             // add_to_database_and_query (mode_build_query.cpp:41-77): a query context over the builder's arrays
             for (mc_builder* b : built->bs) if (mc_build_set_query_config(b, &c) != MC_OK) throw std::runtime_error(mc_build_last_error(b));
@@ -469,13 +486,7 @@ struct Session {
                     throw std::runtime_error(std::string("-replicate ") + std::to_string(nrep) + ": GPU " + std::to_string(r) + ": " + mc_last_error(nullptr));
                 replicas.push_back(rc);
             }
-            uint64_t nt = 0; mc_db_num_taxa(ctx, &nt); tx.taxa.resize(nt);
-            for (uint64_t i = 0; i < nt; ++i) {
-                uint32_t rk; const char* nm;
-                mc_db_taxon(ctx, i, &tx.taxa[i].id, &tx.taxa[i].parent, &rk, &nm);
-                tx.taxa[i].rank = int(rk); tx.taxa[i].name = nm;
-                mc_db_taxon_source(ctx, i, nullptr, nullptr, &tx.taxa[i].windows);
-            }
+            read_taxa(ctx, tx);
         }
         cfg = c; db = o.db;
         uint64_t info[8]; mc_db_info(ctx, info);
@@ -502,100 +513,177 @@ struct Session {
 // merge mode (mode_merge.cpp): the candidates come from result files instead of the database
 struct MergedInput { std::vector<std::string> files, headers; std::vector<std::vector<Cand>> cands; };
 
-void run_job(Session& S, Options o, const std::vector<std::string>& infiles, const std::string& outfile, const std::string& targetsFile,
-             const std::string& abundanceFile, const MergedInput* merged = nullptr)
+// ---- per-query statistics: classification_statistics (classification_statistics.hpp), queries per taxon, matches per target ----------
+struct Cover { uint32_t tgt; uint64_t qid; uint32_t beg, end, hits; };
+
+struct Tally {
+    uint64_t assigned[kNumRanks + 1] = {}, known[kNumRanks + 1] = {}, correct[kNumRanks + 1] = {}, wrong[kNumRanks + 1] = {};
+    uint64_t covFalsePos[kNumRanks + 1] = {}, covDomain = 0;
+    std::map<uint32_t, double> counts;                                      // taxon (index + 1) -> queries classified as it
+    std::vector<Cover> covers;                                              // matches_per_target
+    Tally& operator+=(const Tally& t)
+    {
+        for (int r = 0; r <= kNumRanks; ++r) { assigned[r] += t.assigned[r]; known[r] += t.known[r]; correct[r] += t.correct[r]; wrong[r] += t.wrong[r]; covFalsePos[r] += t.covFalsePos[r]; }
+        covDomain += t.covDomain;
+        for (const auto& kv : t.counts) counts[kv.first] += kv.second;
+        covers.insert(covers.end(), t.covers.begin(), t.covers.end());
+        return *this;
+    }
+    uint64_t classified() const { uint64_t n = 0; for (int r = 0; r < kNumRanks; ++r) n += assigned[r]; return n; }
+    uint64_t unclassified() const { return assigned[kNumRanks]; }
+    uint64_t total() const { return classified() + unclassified(); }
+};
+
+// ---- one query: classification, statistics, mapping line (classify_and_evaluate, classification.cpp:470-559) ------------------------
+struct MappingWriter {
+    const Options& o; const Taxonomy& tx; const uint32_t stride, winlen;
+    const bool deferred;                     // -cov-percentile: the workers keep the candidates, the lines come after the coverage filter
+    Tally& tally;
+    // the text show_taxon writes for a classification (taxon, or target for sequence-level results): the same few thousand over and
+    // over -- its lineage walk (hash lookups up the taxonomy, taxonomy.hpp:576-597) is done once per worker and taxon
+    std::unordered_map<uint64_t, std::string> taxText = {};
+
+    template <class OS>
+    void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits)
+    {
+        bool isTarget; uint32_t tgt;
+        const uint32_t best = classify(o, tx, cands, isTarget, tgt);
+        const int bestRank = best ? tx.taxon(best)->rank : kNumRanks;
+        ++tally.assigned[bestRank];
+        uint32_t truth = 0;
+        if (o.determineGroundTruth) truth = ground_truth(tx, std::string(header.p, header.n));
+        if (o.precision) {                                       // evaluate_classification, classification.cpp:272-295
+            const int knownRank = truth ? tx.taxon(truth)->rank : kNumRanks;
+            int correctRank = kNumRanks;                         // rank of the ranked LCA of mapping and truth
+            if (best && truth) {
+                const Lineage la = tx.ranks_of(best), lb = tx.ranks_of(truth);
+                for (int r = 0; r < kNumRanks; ++r) if (la[r] && la[r] == lb[r]) { correctRank = tx.taxon(la[r])->rank; break; }
+            }
+            // assign_known_correct (classification_statistics.hpp:86-106)
+            if (correctRank < bestRank) correctRank = bestRank;
+            if (correctRank < knownRank) correctRank = knownRank;
+            ++tally.known[knownRank];
+            if (knownRank != kNumRanks) {
+                ++tally.correct[correctRank];
+                if (correctRank > knownRank && correctRank > bestRank) ++tally.wrong[correctRank - 1];
+            }
+            if (o.taxonCoverage && truth) {                       // update_coverage_statistics, classification.cpp:242-265
+                for (uint32_t t : tx.ranks_of(truth)) {
+                    if (!t) continue;
+                    const int r = tx.taxon(t)->rank;
+                    const bool classifiedOnRank = best && r >= bestRank;
+                    if (!tx.covers(t) && classifiedOnRank) ++tally.covFalsePos[r];
+                    if (r == 19) ++tally.covDomain;
+                }
+            }
+        }
+        if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];             // classify_and_evaluate, classification.cpp:552-554
+        if (o.hitsPerRef && !deferred)                           // matches_per_target::insert (matches_per_target.hpp:100-110)
+            for (const Cand& c : cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits});
+        if (o.mapView == Options::mv_none || (o.mapView == Options::mv_mapped && !best)) return;
+        if (o.queryIds) out << id << o.column;
+        const void* sp = memchr(header.p, ' ', header.n);
+        out.write(header.p, sp ? (const char*)sp - header.p : (std::streamsize)header.n);
+        out << o.column;
+        if (o.showGroundTruth) { show_taxon(out, o, tx, truth, false, 0); out << o.column; }
+        if (o.allhits) { if (hits) show_matches(out, o, tx, hits, nhits); out << o.column; }
+        if (o.tophits) { show_candidates(out, o, tx, cands); out << o.column; }
+        if (o.locations) {                                       // show_candidate_ranges, printing.cpp:370-380
+            for (const Cand& c : cands) out << '[' << (uint64_t)stride * c.beg << ',' << (uint64_t)stride * c.end + winlen << "] ";
+            out << o.column;
+        }
+        {
+            const uint64_t key = isTarget ? ((1ull << 32) | tgt) : (uint64_t)best;
+            auto it = taxText.find(key);
+            if (it == taxText.end()) {
+                FastOut t;
+                show_taxon(t, o, tx, best, isTarget, tgt);
+                it = taxText.emplace(key, std::move(t.s)).first;
+            }
+            out << it->second;
+        }
+        out << '\n';
+    }
+};
+
+// fn(0) on the calling thread, fn(1) .. fn(n - 1) on threads of their own; back when all are through
+template <class Fn>
+void run_workers(unsigned n, Fn&& fn)
 {
-        if (!merged) S.open(o);
-        mc_ctx* ctx = S.ctx;
-        const Taxonomy& tx = S.tx;
-        const mc_config& cfg = S.cfg;
-        const uint32_t dbStride = S.dbStride, dbSketch = S.dbSketch;
-        const unsigned threads = S.threads, workers = S.workers;
-        const bool unlimited = o.maxCand < 1;
-        if (o.hitsMin < 1) o.hitsMin = dbSketch >= 6 ? int(dbSketch / 3.0) : (dbSketch >= 4 ? 2 : 1);        // querying.cpp:257-268
-        o.infiles = infiles;
+    std::vector<std::thread> pool;
+    for (unsigned w = 1; w < n; ++w) pool.emplace_back(fn, w);
+    fn(0);
+    for (auto& t : pool) t.join();
+}
 
-        std::ofstream fout;
-        if (!outfile.empty()) { fout.open(outfile); if (!fout.good()) throw std::runtime_error("Could not write to file " + outfile); }
-        std::ostream& os = outfile.empty() ? std::cout : fout;
-        std::ofstream ftargets, ftaxa;                                          // process_input_files, querying.cpp:84-112
-        if (!targetsFile.empty()) { ftargets.open(targetsFile); if (!ftargets.good()) throw std::runtime_error("Could not write to file " + targetsFile); }
-        if (!abundanceFile.empty()) { ftaxa.open(abundanceFile); if (!ftaxa.good()) throw std::runtime_error("Could not write to file " + abundanceFile); }
-        std::ostream& perTargetOut = targetsFile.empty() ? os : ftargets;
-        std::ostream& perTaxonOut = abundanceFile.empty() ? os : ftaxa;
-        const bool taxCountsWanted = o.abundances || o.abundancePer != kNumRanks;
-        struct Cover { uint32_t tgt; uint64_t qid; uint32_t beg, end, hits; };
-        std::vector<Cover> covers;                                              // matches_per_target, all workers
-        std::map<uint32_t, double> bestCounts;                                  // taxon (index + 1) -> queries classified as it
+// ---- the batches: runs of consecutive queries of one file (pair of files), ids continuing across files -----------------------------
+// Batches are produced while the workers already run: plain files are indexed chunk by chunk (SeqFile::stream_*), and a batch goes out
+// as soon as its records are known -- the first one after a few megabytes instead of after the whole file.
+struct Deferred { uint64_t id; View header; std::vector<Cand> cands; };
+struct Batch {
+    size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast;
+    std::vector<Deferred> deferred;                                         // -cov-percentile: its reads' candidates
+    std::vector<mc_candidate> carried;                                      // part groups: its reads' candidate lists from the groups so far
+};
+struct Records { View h1, s1, h2, s2; std::string scratch1, scratch2; };    // one query's records (scratch: multi-line sequences)
 
-        if (o.showQueryParams) {                                                 // printing.cpp:47-131
-            if (o.mapView != Options::mv_none) {
-                os << o.comment << "Reporting per-read mappings (non-mapping lines start with '" << o.comment << "').\n";
-                os << o.comment << (o.lineage ? "The complete lineage will be reported starting with the lowest match.\n" : "Only the lowest matching rank will be reported.\n");
-            } else os << o.comment << "Per-Read mappings will not be shown.\n";
-            if (o.minReadLen > 0) os << o.comment << "Only reads with a minimum length of " << o.minReadLen << " bp will be mapped.\n";
-            if (o.maxReadLen < std::numeric_limits<uint64_t>::max()) os << o.comment << "Only reads with a maximum length of " << o.maxReadLen << " bp will be mapped.\n";
-            os << o.comment << "Classification will be constrained to ranks from '" << kRankNames[o.lowest] << "' to '" << kRankNames[o.highest] << "'.\n";
-            os << o.comment << "Classification hit threshold is " << o.hitsMin << " per query\n";
-            os << o.comment << "At maximum " << (unlimited ? std::numeric_limits<size_t>::max() : o.maxCand) << " classification candidates will be considered per query.\n";
-            if (o.pairing == Options::files) os << o.comment << "File based paired-end mode:\n" << o.comment << "  Reads from two consecutive files will be interleaved.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
-            else if (o.pairing == Options::sequences) os << o.comment << "Per file paired-end mode:\n" << o.comment << "  Reads from two consecutive sequences in each file will be paired up.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
-            if (o.hitsPerRef) os << o.comment << "A list of hits per reference sequence will be generated after the read mapping.\n";
-            if (o.abundances) os << o.comment << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
-            if (o.abundancePer != kNumRanks) os << o.comment << "A list of absolute and relative abundances for each '" << kRankNames[o.abundancePer] << "' will be generated after the read mapping.\n";
-            os << o.comment << "Using " << threads << " threads\n";
+struct BatchQueue {
+    const Options& o; const unsigned workers; const std::chrono::steady_clock::time_point t0;
+    std::vector<std::unique_ptr<SeqFile>> files;
+    std::vector<std::unique_ptr<std::vector<uint64_t>>> selections;
+    std::deque<Batch> batches;                                              // grows at the back only: references stay valid
+    std::mutex mu; std::condition_variable cv;
+    size_t next = 0; bool producing = true;                                 // (under mu)
+    std::atomic<bool> stopped{false}; std::string producerError, firstError;
+    double tIndexed = 0; std::thread producer;
+
+    BatchQueue(const Options& o, unsigned workers, std::chrono::steady_clock::time_point t0) : o(o), workers(workers), t0(t0) {}
+    void start()
+    {
+        files.reserve(o.infiles.size() + 2);                                // workers read files[...] while the producer appends
+        producer = std::thread([this] { produce(); });
+    }
+    void finish() { { std::lock_guard<std::mutex> l(mu); } cv.notify_all(); producer.join(); }
+    // the next batch, or false when none is left (or the job has failed)
+    bool take(size_t& b, Batch*& B)
+    {
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return stopped || next < batches.size() || !producing; });
+        if (stopped || next >= batches.size()) return false;
+        b = next++;
+        B = &batches[b];                                                    // (under the lock: operator[] walks the deque's map, which push_back may reallocate)
+        return true;
+    }
+    void rewind() { std::lock_guard<std::mutex> l(mu); next = 0; }          // the next part group's pass
+    void fail(const std::string& m) { std::lock_guard<std::mutex> l(mu); if (!stopped.exchange(true)) firstError = m; }
+    bool failed() const { return stopped; }
+    void rethrow() const { if (!producerError.empty()) throw std::runtime_error(producerError); if (stopped) throw std::runtime_error(firstError); }
+    // One query's records by pairing mode and its id: the reader's index after the read (database_query.hpp:264); a last pair without its
+    // second sequence does not advance the index (sequence_io.cpp:312-318), so it shares the id of the pair before it
+    uint64_t read(const Batch& B, size_t q, Records& r) const
+    {
+        const size_t qi = B.sel ? (size_t)(*B.sel)[q] : q;                  // query index inside the file (pair)
+        const bool halfPair = B.halfLast && q + 1 == B.qEnd;
+        r.h2 = r.s2 = View{};
+        if (o.pairing == Options::sequences) {
+            files[B.f1]->record(2 * qi, r.h1, r.s1, r.scratch1);
+            if (!halfPair) files[B.f1]->record(2 * qi + 1, r.h2, r.s2, r.scratch2);
+        } else {
+            files[B.f1]->record(qi, r.h1, r.s1, r.scratch1);
+            if (o.pairing == Options::files) files[B.f2]->record(qi, r.h2, r.s2, r.scratch2);
         }
-        if (merged) {                                                            // merge_result_files, mode_merge.cpp:266-269
-            os << o.comment << "Merging " << merged->files.size() << " files:\n";
-            for (const auto& f : merged->files) os << o.comment << f << '\n';
-        }
-        if (o.mapView != Options::mv_none) {                                     // show_query_mapping_header, classification.cpp:432-460
-            os << o.comment << "TABLE_LAYOUT: ";
-            if (o.queryIds) os << "query_id" << o.column;
-            os << "query_header" << o.column;
-            const int rmax = o.lineage ? o.highest : o.lowest;
-            auto taxon_header = [&](const std::string& prefix) {              // show_taxon_header, printing.cpp:133-172
-                auto hdr = [&](int r, bool named) {
-                    if (o.showRank) os << prefix << (named ? kRankNames[r] : "rank") << o.rankSuffix;
-                    if (o.showName) { os << prefix << "taxname"; if (o.showId) os << o.idPrefix << prefix << "taxid" << o.idSuffix; }
-                    else if (o.showId) os << prefix << "taxid";
-                };
-                if (o.lowest == rmax) hdr(o.lowest, false);
-                else for (int r = o.lowest; r <= rmax; ++r) { hdr(r, true); if (r < rmax) os << o.taxSep; }
-            };
-            if (o.showGroundTruth) { taxon_header("truth_"); os << o.column; }
-            if (o.allhits) os << "all_hits" << o.column;
-            if (o.tophits) os << "top_hits" << o.column;
-            if (o.locations) os << "candidate_locations" << o.column;
-            taxon_header("");
-            os << '\n';
-        }
+        return B.idBase + qi + (halfPair ? 0 : 1);
+    }
 
-        const auto t0 = std::chrono::steady_clock::now();
-        uint64_t assigned[kNumRanks + 1] = {};                                   // classification_statistics (classification_statistics.hpp)
-        uint64_t known[kNumRanks + 1] = {}, correct[kNumRanks + 1] = {}, wrong[kNumRanks + 1] = {}, covFalsePos[kNumRanks + 1] = {};
-        uint64_t covTotalDomain = 0;
-
-        // ---- all inputs are indexed first: batches = runs of consecutive queries, ids continue across files -------------
-        // Batches are produced while the workers already run: plain files are indexed chunk by chunk (SeqFile::stream_*), and a batch
-        // goes out as soon as its records are known -- the first one after a few megabytes instead of after the whole file.
-        struct Batch { size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast; };
-        std::vector<std::unique_ptr<SeqFile>> files;
-        files.reserve(o.infiles.size() + 2);                                   // workers read files[...] while the producer appends
-        std::vector<std::unique_ptr<std::vector<uint64_t>>> selections;
-        std::deque<Batch> batches;                                             // grows at the back only: references stay valid
-        std::mutex batchMtx;
-        std::condition_variable batchCv;
-        bool producing = true;
-        std::string producerError;
-        auto push_batch = [&](Batch&& B) {
-            { std::lock_guard<std::mutex> l(batchMtx); batches.push_back(std::move(B)); }
-            batchCv.notify_all();
-        };
+    void push(size_t f1, size_t f2, size_t qBeg, size_t qEnd, uint64_t idBase, const std::string& prefix, const std::vector<uint64_t>* sel, bool halfLast)
+    {
+        { std::lock_guard<std::mutex> l(mu); batches.push_back(Batch{f1, f2, qBeg, qEnd, idBase, prefix, sel, halfLast, {}, {}}); }
+        cv.notify_all();
+    }
+    void produce()
+    {
         const bool lengthFilter = o.minReadLen > 0 || o.maxReadLen < std::numeric_limits<uint64_t>::max();
-        double tIndexed = 0;
-        auto produce = [&]() {
-          try {
+        try {
             uint64_t idOffset = 0;
             const size_t stride = o.pairing == Options::files ? 2 : 1;
             for (size_t fi = 0; fi < o.infiles.size(); fi += stride) {
@@ -604,13 +692,11 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
                 if (o.pairing == Options::files) prefix += " + " + o.infiles[fi + 1];
                 prefix += '\n';
                 size_t nq = 0, f1 = files.size(), f2 = files.size();
-                bool streamed = false;
                 try {
                     files.emplace_back(new SeqFile(o.infiles[fi]));
                     SeqFile& F = *files.back();
                     if (F.can_stream() && o.pairing != Options::files && !lengthFilter && o.queryLimit >= (int64_t)1 << 62 && !std::getenv("MCQ_NO_STREAM")) {
                         // streaming: batches of this file go out while its later chunks are still being indexed
-                        streamed = true;
                         const size_t per = o.pairing == Options::sequences ? 2 : 1;
                         F.stream_begin(std::max(1u, std::min(workers, 16u)));
                         size_t q = 0;
@@ -622,16 +708,16 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
                             while (q + o.batchSize <= qAvail || (done && q < qAvail)) {
                                 const size_t qe = std::min(qAvail, q + o.batchSize);
                                 const bool half = done && per == 2 && qe == qAvail && (F.records() & 1u);
-                                push_batch(Batch{f1, f2, q, qe, idOffset, first ? prefix : std::string(), nullptr, half});
+                                push(f1, f2, q, qe, idOffset, first ? prefix : std::string(), nullptr, half);
                                 first = false; q = qe;
                             }
                             if (done) break;
                         }
                         F.stream_end();
-                        if (first) push_batch(Batch{f1, f2, 0, 0, idOffset, prefix, nullptr, false});     // no records: the file's comment line only
+                        if (first) push(f1, f2, 0, 0, idOffset, prefix, nullptr, false);             // no records: the file's comment line only
                         nq = (F.records() + per - 1) / per;
                         size_t nread = nq;
-                        if (per == 2 && nq > 0 && (F.records() & 1u)) --nread;                           // (the half pair did not count)
+                        if (per == 2 && nq > 0 && (F.records() & 1u)) --nread;                       // (the half pair did not count)
                         idOffset += nread;
                         continue;
                     }
@@ -651,26 +737,21 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
                 size_t nsel = std::min<uint64_t>(nq, (uint64_t)o.queryLimit), nread = nsel;
                 if (lengthFilter && nq > 0) {
                     std::vector<uint32_t> len(nq);
-                    {
-                        std::vector<std::thread> pool;
-                        const size_t per = (nq + workers - 1) / workers;
-                        for (unsigned t = 0; t < workers; ++t)
-                            pool.emplace_back([&, t] {
-                                View h, sq; std::string scratch;
-                                for (size_t q = t * per; q < std::min(nq, (t + 1) * per); ++q) {
-                                    files[f1]->record(o.pairing == Options::sequences ? 2 * q : q, h, sq, scratch);
-                                    len[q] = (uint32_t)std::min<size_t>(sq.n, 0xFFFFFFFFu);
-                                }
-                            });
-                        for (auto& th : pool) th.join();
-                    }
+                    const size_t per = (nq + workers - 1) / workers;
+                    run_workers(workers, [&](unsigned t) {
+                        View h, sq; std::string scratch;
+                        for (size_t q = t * per; q < std::min(nq, (t + 1) * per); ++q) {
+                            files[f1]->record(o.pairing == Options::sequences ? 2 * q : q, h, sq, scratch);
+                            len[q] = (uint32_t)std::min<size_t>(sq.n, 0xFFFFFFFFu);
+                        }
+                    });
                     auto fails = [&](size_t q) { return len[q] < o.minReadLen || len[q] > o.maxReadLen; };
                     selections.emplace_back(new std::vector<uint64_t>());
                     auto& kept = *selections.back();
-                    size_t q = 0, discarded = 0;
+                    size_t q = 0;
                     for (int64_t limit = o.queryLimit; q < nq && limit >= 1; --limit) {
                         size_t cur = q++;
-                        while (fails(cur)) { ++discarded; if (q >= nq) break; cur = q++; }
+                        while (fails(cur)) { if (q >= nq) break; cur = q++; }
                         kept.push_back(cur);
                     }
                     nread = q; nsel = kept.size(); sel = &kept;
@@ -680,585 +761,505 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
                     const size_t qe = std::min<size_t>(nsel, q + o.batchSize);
                     // the file's last query is a half pair: when it is among the selected ones, it is the last of them
                     const bool half = oddFile && qe == nsel && nsel > 0 && (sel ? (*sel)[nsel - 1] : nsel - 1) == nq - 1;
-                    push_batch(Batch{f1, f2, q, qe, idOffset, q == 0 ? prefix : std::string(), sel, half});
+                    push(f1, f2, q, qe, idOffset, q == 0 ? prefix : std::string(), sel, half);
                     if (nsel == 0) break;
                 }
                 if (oddFile && nread == nq) --nread;                             // (the half pair did not count)
                 idOffset += nread;                                               // reader.index(): records (pairs) consumed
             }
-          } catch (std::exception& e) { std::lock_guard<std::mutex> l(batchMtx); producerError = e.what(); }
-          tIndexed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-          { std::lock_guard<std::mutex> l(batchMtx); producing = false; }
-          batchCv.notify_all();
-        };
+        } catch (std::exception& e) { std::lock_guard<std::mutex> l(mu); producerError = e.what(); }
+        tIndexed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        { std::lock_guard<std::mutex> l(mu); producing = false; }
+        cv.notify_all();
+    }
+};
 
-        const bool profile = std::getenv("MCQ_PROFILE") != nullptr;              // phase times on stderr (development aid)
-        std::atomic<uint64_t> nsParse{0}, nsSubmit{0}, nsWait{0}, nsClassify{0};
-        auto now_ns = [] { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        // one query: classification, statistics, mapping line (classify_and_evaluate, classification.cpp:470-559)
-        struct Acc {
-            uint64_t mine[kNumRanks + 1] = {}, known[kNumRanks + 1] = {}, correct[kNumRanks + 1] = {}, wrong[kNumRanks + 1] = {}, falsePos[kNumRanks + 1] = {}, covDomain = 0;
-            std::map<uint32_t, double> counts;
-            std::vector<Cover> covers;
-            // the text show_taxon writes for a classification (taxon, or target for sequence-level results): the same few thousand over and
-            // over -- its lineage walk (hash lookups up the taxonomy, taxonomy.hpp:576-597) is done once per worker and taxon
-            std::unordered_map<uint64_t, std::string> taxText;
-        };
-        // -cov-percentile (map_queries_to_targets_default, classification.cpp:747-838): nothing is classified while the reads are
-        // queried; every read's candidates are kept, the targets are filtered by their coverage afterwards, and the reads are
-        // classified from the candidates that are left
-        const bool covMode = o.covPercentile > 0 && !merged;
-        struct Deferred { uint64_t id; View header; std::vector<Cand> cands; };
-        std::deque<std::vector<Deferred>> deferred;                              // [batch]; grown (under batchMtx) when a worker takes a batch
-        auto emit = [&](Acc& A, auto& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits) {
-            bool isTarget; uint32_t tgt;
-            const uint32_t best = classify(o, tx, cands, isTarget, tgt);
-            const int bestRank = best ? tx.taxon(best)->rank : kNumRanks;
-            ++A.mine[bestRank];
-            uint32_t truth = 0;
-            if (o.determineGroundTruth) truth = ground_truth(tx, std::string(header.p, header.n));
-            if (o.precision) {                                       // evaluate_classification, classification.cpp:272-295
-                const int knownRank = truth ? tx.taxon(truth)->rank : kNumRanks;
-                int correctRank = kNumRanks;                         // rank of the ranked LCA of mapping and truth
-                if (best && truth) {
-                    const Lineage la = tx.ranks_of(best), lb = tx.ranks_of(truth);
-                    for (int r = 0; r < kNumRanks; ++r) if (la[r] && la[r] == lb[r]) { correctRank = tx.taxon(la[r])->rank; break; }
-                }
-                // assign_known_correct (classification_statistics.hpp:86-106)
-                if (correctRank < bestRank) correctRank = bestRank;
-                if (correctRank < knownRank) correctRank = knownRank;
-                ++A.known[knownRank];
-                if (knownRank != kNumRanks) {
-                    ++A.correct[correctRank];
-                    if (correctRank > knownRank && correctRank > bestRank) ++A.wrong[correctRank - 1];
-                }
-                if (o.taxonCoverage && truth) {                       // update_coverage_statistics, classification.cpp:242-265
-                    for (uint32_t t : tx.ranks_of(truth)) {
-                        if (!t) continue;
-                        const int r = tx.taxon(t)->rank;
-                        const bool classifiedOnRank = best && r >= bestRank;
-                        if (!tx.covers(t) && classifiedOnRank) ++A.falsePos[r];
-                        if (r == 19) ++A.covDomain;
-                    }
-                }
-            }
-            if (taxCountsWanted && best) ++A.counts[best];           // classify_and_evaluate, classification.cpp:552-554
-            if (o.hitsPerRef && !covMode)                            // matches_per_target::insert (matches_per_target.hpp:100-110)
-                for (const Cand& c : cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) A.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits});
-            if (o.mapView == Options::mv_none || (o.mapView == Options::mv_mapped && !best)) return;
-            if (o.queryIds) out << id << o.column;
-            const void* sp = memchr(header.p, ' ', header.n);
-            out.write(header.p, sp ? (const char*)sp - header.p : (std::streamsize)header.n);
-            out << o.column;
-            if (o.showGroundTruth) { show_taxon(out, o, tx, truth, false, 0); out << o.column; }
-            if (o.allhits) { if (hits) show_matches(out, o, tx, hits, nhits); out << o.column; }
-            if (o.tophits) { show_candidates(out, o, tx, cands); out << o.column; }
-            if (o.locations) {                                       // show_candidate_ranges, printing.cpp:370-380
-                for (const Cand& c : cands) out << '[' << (uint64_t)dbStride * c.beg << ',' << (uint64_t)dbStride * c.end + S.dbWinlen << "] ";
-                out << o.column;
-            }
-            {
-                const uint64_t key = isTarget ? ((1ull << 32) | tgt) : (uint64_t)best;
-                auto it = A.taxText.find(key);
-                if (it == A.taxText.end()) {
-                    FastOut t;
-                    show_taxon(t, o, tx, best, isTarget, tgt);
-                    it = A.taxText.emplace(key, std::move(t.s)).first;
-                }
-                out << it->second;
-            }
-            out << '\n';
-        };
-        auto collect = [&](const Acc& A) {
-            for (int r = 0; r <= kNumRanks; ++r) {
-                assigned[r] += A.mine[r]; known[r] += A.known[r]; correct[r] += A.correct[r]; wrong[r] += A.wrong[r]; covFalsePos[r] += A.falsePos[r];
-            }
-            covTotalDomain += A.covDomain;
-            for (const auto& kv : A.counts) bestCounts[kv.first] += kv.second;
-            covers.insert(covers.end(), A.covers.begin(), A.covers.end());
-        };
-        // ---- workers: one batch slot each; output delivered in batch order -------------------------------------------------
-        size_t nextBatch = 0;                                                   // under batchMtx
-        std::mutex outMtx, errMtx;
-        std::map<size_t, std::string> finished;
-        size_t nextToWrite = 0;
-        std::string firstError;
-        std::atomic<bool> failed{false};
-        // Output file: the batches' texts go out in batch order, but not one after the other -- under the lock a finished batch only gets its
-        // place in the file (the sizes of the batches before it are known then); the bytes are written by the worker that formatted them,
-        // side by side with the others' (pwrite).  10^7 lines of `-tophits -queryids` are 1.1 GB: one thread copying them into the page cache
-        // was a quarter of a second of a 0.3 s query phase.  (No file: std::cout, in order, as before.)
-        int outFd = -1;
-        uint64_t outOff = 0;
-        std::vector<std::string> bufPool;                                       // written batches' buffers, for the next batches (a fresh 7 MB buffer per batch is 1 700 page faults)
-        auto take_buffer = [&](std::string& into) {
-            std::lock_guard<std::mutex> lock(outMtx);
-            if (!bufPool.empty()) { into = std::move(bufPool.back()); bufPool.pop_back(); into.clear(); }
-        };
-        if (!outfile.empty()) {
-            fout.flush();
-            const std::streamoff at = fout.tellp();
-            if (at >= 0) { outFd = ::open(outfile.c_str(), O_WRONLY); outOff = (uint64_t)at; }
-        }
-        auto deliver = [&](size_t b, std::string&& text) {
-            std::vector<std::pair<uint64_t, std::string>> mine;
-            {
-                std::lock_guard<std::mutex> lock(outMtx);
-                finished.emplace(b, std::move(text));
-                for (auto it = finished.begin(); it != finished.end() && it->first == nextToWrite; it = finished.erase(it), ++nextToWrite) {
-                    if (outFd >= 0) { const uint64_t n = it->second.size(); mine.emplace_back(outOff, std::move(it->second)); outOff += n; }
-                    else os.write(it->second.data(), (std::streamsize)it->second.size());
-                }
-            }
-            for (auto& m : mine) {
-                const char* p = m.second.data();
-                struct Recycle { std::string& s; std::mutex& mu; std::vector<std::string>& pool; ~Recycle() { s.clear(); std::lock_guard<std::mutex> l(mu); if (pool.size() < 64) pool.push_back(std::move(s)); } } recycle{m.second, outMtx, bufPool};
-                uint64_t left = m.second.size(), at = m.first;
-                while (left) {
-                    const ssize_t w = ::pwrite(outFd, p, (size_t)std::min<uint64_t>(left, 1ull << 30), (off_t)at);
-                    if (w <= 0) { std::lock_guard<std::mutex> l(errMtx); if (!failed.exchange(true)) firstError = "Could not write to file " + outfile; break; }
-                    p += w; left -= (uint64_t)w; at += (uint64_t)w;
-                }
-            }
-        };
-        auto work = [&](unsigned worker) {
-            const unsigned slot = worker / S.replication;
-            mc_ctx* const ctx = S.replica(worker % S.replication);
-            struct Meta { uint64_t id; View header; bool empty; uint64_t len; };
-            std::vector<Meta> metas;
-            std::vector<Cand> cands;
-            std::string scratch1, scratch2;
-            FastOut out;
-            Acc A;
-            auto fail = [&](const std::string& m) { std::lock_guard<std::mutex> l(errMtx); if (!failed.exchange(true)) firstError = m; };
-            for (;;) {
-                size_t b;
-                const Batch* Bp = nullptr;
-                std::vector<Deferred>* Dp = nullptr;                             // taken under the lock: operator[] walks the deque's map, which emplace_back may reallocate
-                {
-                    std::unique_lock<std::mutex> l(batchMtx);
-                    batchCv.wait(l, [&] { return failed || nextBatch < batches.size() || !producing; });
-                    if (failed || nextBatch >= batches.size()) break;           // (no batch left and the producer is through)
-                    b = nextBatch++;
-                    Bp = &batches[b];
-                    if (covMode) { while (deferred.size() <= b) deferred.emplace_back(); Dp = &deferred[b]; }
-                }
-                const Batch& B = *Bp;
-                out.s.clear();
-                if (out.s.capacity() < 64) take_buffer(out.s);                     // (a moved-from string keeps its 15-character SSO capacity, never 0)
-                out << B.prefix;
-                size_t q = B.qBeg;
-                while (q < B.qEnd && !failed) {
-                    metas.clear();
-                    const uint64_t tp0 = now_ns();
-                    for (; q < B.qEnd; ++q) {
-                        View h1, s1, h2, s2;
-                        const size_t qi = B.sel ? (size_t)(*B.sel)[q] : q;          // query index inside the file (pair)
-                        if (o.pairing == Options::sequences) {
-                            files[B.f1]->record(2 * qi, h1, s1, scratch1);
-                            if (!(B.halfLast && q + 1 == B.qEnd)) files[B.f1]->record(2 * qi + 1, h2, s2, scratch2);
-                        } else {
-                            files[B.f1]->record(qi, h1, s1, scratch1);
-                            if (o.pairing == Options::files) files[B.f2]->record(qi, h2, s2, scratch2);
-                        }
-                        if (std::max(s1.n, s2.n) >= 0xFFFFFFF0ull) { fail("sequence too long"); break; }
-                        const uint32_t maxWin = (uint32_t)(2 + std::max<uint64_t>(s1.n + s2.n, o.insertMax) / dbStride);   // candidate_structs.hpp:143-145
-                        const bool tooBig = s1.n + s2.n + 8 > cfg.slot_max_chars;
-                        const int rc = tooBig ? MC_BATCH_FULL : mc_batch_add(ctx, slot, s1.p, (uint32_t)s1.n, s2.p, (uint32_t)s2.n, maxWin);
-                        if (rc == MC_BATCH_FULL) {
-                            if (!tooBig && !metas.empty()) break;                 // submit what is there, then retry this query
-                            std::cerr << "query batch is too small for a single read!\n";                                    // database_query.hpp:103
-                            continue;
-                        }
-                        if (rc < 0) { fail(mc_last_error(ctx)); break; }
-                        // query id = the reader's index after the read (database_query.hpp:264); a last pair without its second
-                        // sequence does not advance the index (sequence_io.cpp:312-318), so it shares the id of the pair before it
-                        const bool halfPair = B.halfLast && q + 1 == B.qEnd;
-                        metas.push_back(Meta{B.idBase + qi + (halfPair ? 0 : 1), h1, h1.empty() || s1.empty(), (uint64_t)s1.n + s2.n});
-                    }
-                    if (failed) break;
-                    mc_results r;
-                    const uint64_t tp1 = now_ns();
-                    if (mc_batch_submit(ctx, slot, o.lowest) != MC_OK) { fail(mc_last_error(ctx)); break; }
-                    const uint64_t tp2 = now_ns();
-                    if (mc_batch_wait(ctx, slot, &r) != MC_OK) { fail(mc_last_error(ctx)); break; }
-                    const uint64_t tp3 = now_ns();
-                    for (uint32_t i = 0; i < r.num_queries; ++i) {
-                        const Meta& m = metas[i];
-                        if (m.empty) continue;                                    // processQuery, classification.cpp:780
-                        cands.clear();
-                        for (uint32_t j = 0; j < r.max_candidates; ++j) {
-                            const mc_candidate& c = r.cands[(size_t)i * r.max_candidates + j];
-                            if (c.hits == 0) break;
-                            Cand x{c.tgt, c.hits, c.beg, c.end, 0};
-                            if (c.tgt < tx.numTargets) {
-                                const uint32_t* lin = tx.targetLineages + (size_t)c.tgt * kNumRanks;
-                                if (o.lowest > 0) { for (int rk = o.lowest; rk < kNumRanks; ++rk) if (lin[rk]) { x.tax = lin[rk]; break; } }   // lowest_ranked_ancestor
-                                else x.tax = lin[0];
-                            }
-                            cands.push_back(x);
-                        }
-                        if (o.maxCand < 1 && cands.size() == r.max_candidates) {   // list full: there may be more candidates than it holds
-                            const uint32_t mw = (uint32_t)(2 + std::max<uint64_t>(m.len, o.insertMax) / dbStride);
-                            host_candidates(r.hits + r.hit_offsets[i], r.hit_offsets[i + 1] - r.hit_offsets[i], mw, tx, o.lowest, cands);
-                        }
-                        if (covMode) Dp->push_back(Deferred{m.id, m.header, cands});
-                        else emit(A, out, m.id, m.header, cands, o.allhits ? r.hits + r.hit_offsets[i] : nullptr, o.allhits ? r.hit_offsets[i + 1] - r.hit_offsets[i] : 0);
-                    }
-                    mc_batch_clear(ctx, slot);
-                    if (profile) { nsParse += tp1 - tp0; nsSubmit += tp2 - tp1; nsWait += tp3 - tp2; nsClassify += now_ns() - tp3; }
-                }
-                deliver(b, std::move(out.s));
-            }
-            std::lock_guard<std::mutex> l(errMtx);
-            collect(A);
-        };
-        // -shard keys / -resident-parts / -gpus: the batches STREAM -- worker threads cut the records out of the files side by side, one at a
-        // time hands its batch to mc_keyset_classify / mc_partset_classify_resident (the sets take one call at a time), then formats
-        // its lines.  A partitioned database is gone through part group by part group (mc_partset_select_group: the next group loads
-        // behind this one's queries); between the groups a batch keeps nothing but its reads' candidate lists (`carried`), the last
-        // group's pass prints.  (Round 3 collected all reads on one thread first: 2.5 s per 10^7 reads.)
+// ---- the mapping lines of the batches, in batch order ---------------------------------------------------------------------------
+// Output file: the batches' texts go out in batch order, but not one after the other -- under the lock a finished batch only gets its
+// place in the file (the sizes of the batches before it are known then); the bytes are written by the worker that formatted them,
+// side by side with the others' (pwrite).  10^7 lines of `-tophits -queryids` are 1.1 GB: one thread copying them into the page cache
+// was a quarter of a second of a 0.3 s query phase.  (No file: std::cout, in order.)
+struct OrderedOut {
+    std::ostream& os; std::ofstream& fout; const std::string name;
+    int fd = -1; uint64_t off = 0;                                          // where the next batch goes (under mu)
+    std::mutex mu; std::map<size_t, std::string> finished; size_t next = 0;
+    std::vector<std::string> pool;                                          // written batches' buffers, for the next batches (a fresh 7 MB buffer per batch is 1 700 page faults)
 
-        std::deque<std::vector<mc_candidate>> carried;                          // [batch]; grown under batchMtx when a worker takes a batch
-        bool setHasPrior = false, setLastPass = true;                           // the part group pass the workers are in
-        auto work_keyset = [&](unsigned) {
-            struct Meta { uint64_t id; View header; bool empty; };
-            std::vector<Meta> metas;
-            std::string seq1, seq2, scratch1, scratch2;
-            std::vector<uint64_t> off1, off2;
-            std::vector<mc_candidate> all;
-            std::vector<Cand> cands;
-            FastOut out;
-            Acc A;
-            const bool paired = o.pairing != Options::unpaired;
-            const uint32_t K = cfg.max_candidates;
-            auto fail = [&](const std::string& m) { std::lock_guard<std::mutex> l(errMtx); if (!failed.exchange(true)) firstError = m; };
-            for (;;) {
-                size_t b;
-                const Batch* Bp = nullptr;
-                std::vector<mc_candidate>* slot = nullptr;
-                {
-                    std::unique_lock<std::mutex> l(batchMtx);
-                    batchCv.wait(l, [&] { return failed || nextBatch < batches.size() || !producing; });
-                    if (failed || nextBatch >= batches.size()) break;
-                    b = nextBatch++;
-                    Bp = &batches[b];
-                    if (S.partset) { if (carried.size() <= b) carried.resize(b + 1); slot = &carried[b]; }   // (a deque: the element stays where it is)
-                }
-                const Batch& B = *Bp;
-                metas.clear(); seq1.clear(); seq2.clear(); off1.assign(1, 0); off2.assign(1, 0);
-                for (size_t q = B.qBeg; q < B.qEnd; ++q) {
-                    View h1, s1, h2, s2;
-                    const size_t qi = B.sel ? (size_t)(*B.sel)[q] : q;
-                    if (o.pairing == Options::sequences) {
-                        files[B.f1]->record(2 * qi, h1, s1, scratch1);
-                        if (!(B.halfLast && q + 1 == B.qEnd)) files[B.f1]->record(2 * qi + 1, h2, s2, scratch2);
-                    } else {
-                        files[B.f1]->record(qi, h1, s1, scratch1);
-                        if (o.pairing == Options::files) files[B.f2]->record(qi, h2, s2, scratch2);
-                    }
-                    const bool halfPair = B.halfLast && q + 1 == B.qEnd;
-                    if (s1.n + s2.n + 8 > cfg.slot_max_chars) { std::cerr << "query batch is too small for a single read!\n"; continue; }
-                    metas.push_back(Meta{B.idBase + qi + (halfPair ? 0 : 1), h1, h1.empty() || s1.empty()});
-                    seq1.append(s1.p, s1.n); off1.push_back(seq1.size());
-                    if (paired) { seq2.append(s2.p, s2.n); off2.push_back(seq2.size()); }
-                }
-                const size_t n = metas.size();
-                if (slot && setHasPrior) all.swap(*slot);              // what the earlier part groups left for this batch's reads
-                else all.assign(n * K, mc_candidate{});
-                if (all.size() != n * K) { fail("internal: a batch changed between two part groups"); break; }
-                seq1.push_back('\0'); seq2.push_back('\0');
-                if (n && S.keyset) {
-                    // (the key set shares its two lanes among the callers, as the part set does: this worker's batch runs beside another worker's)
-                    if (mc_keyset_classify(S.keyset, seq1.data(), off1.data(), paired ? seq2.data() : nullptr, paired ? off2.data() : nullptr, n, o.lowest,
-                                           o.insertMax, all.data()) != MC_OK) { fail(mc_keyset_last_error(S.keyset)); break; }
-                } else if (n) {
-                    // (the part set shares its two device lanes among the callers: this worker's batch runs beside another worker's,
-                    // its upload under the other's kernels)
-                    if (mc_partset_classify_resident(S.partset, seq1.data(), off1.data(), paired ? seq2.data() : nullptr, paired ? off2.data() : nullptr, n,
-                                                     o.lowest, o.insertMax, setHasPrior ? 1 : 0, all.data()) != MC_OK) { fail(mc_partset_last_error(S.partset)); break; }
-                }
-                if (!setLastPass) { slot->swap(all); continue; }            // more part groups to come: nothing is printed yet
-                out.s.clear();
-                if (out.s.capacity() < 64) take_buffer(out.s);                     // (a moved-from string keeps its 15-character SSO capacity, never 0)
-                out << B.prefix;
-                for (size_t i = 0; i < n; ++i) {
-                    const Meta& m = metas[i];
-                    if (m.empty) continue;
-                    cands.clear();
-                    for (uint32_t j = 0; j < K; ++j) {
-                        const mc_candidate& c = all[i * K + j];
-                        if (c.hits == 0) break;
-                        Cand x{c.tgt, c.hits, c.beg, c.end, 0};
-                        if (c.tgt < tx.numTargets) {
-                            const uint32_t* lin = tx.targetLineages + (size_t)c.tgt * kNumRanks;
-                            if (o.lowest > 0) { for (int rk = o.lowest; rk < kNumRanks; ++rk) if (lin[rk]) { x.tax = lin[rk]; break; } }
-                            else x.tax = lin[0];
-                        }
-                        cands.push_back(x);
-                    }
-                    emit(A, out, m.id, m.header, cands, nullptr, 0);
-                }
-                deliver(b, std::move(out.s));
+    OrderedOut(std::ostream& os, std::ofstream& fout, const std::string& name) : os(os), fout(fout), name(name)
+    {
+        if (name.empty()) return;
+        const std::streamoff at = fout.flush().tellp();
+        if (at >= 0) { fd = ::open(name.c_str(), O_WRONLY); off = (uint64_t)at; }
+    }
+    void take_buffer(std::string& into)
+    {
+        std::lock_guard<std::mutex> l(mu);
+        if (!pool.empty()) { into = std::move(pool.back()); pool.pop_back(); into.clear(); }
+    }
+    // batch b's text; false when the file could not be written
+    bool deliver(size_t b, std::string&& text)
+    {
+        std::vector<std::pair<uint64_t, std::string>> mine;
+        {
+            std::lock_guard<std::mutex> l(mu);
+            finished.emplace(b, std::move(text));
+            for (auto it = finished.begin(); it != finished.end() && it->first == next; it = finished.erase(it), ++next) {
+                if (fd >= 0) { const uint64_t n = it->second.size(); mine.emplace_back(off, std::move(it->second)); off += n; }
+                else os.write(it->second.data(), (std::streamsize)it->second.size());
             }
-            std::lock_guard<std::mutex> l(errMtx);
-            collect(A);
+        }
+        bool ok = true;
+        for (auto& m : mine) {
+            const char* p = m.second.data();
+            uint64_t left = m.second.size(), at = m.first;
+            while (left) {
+                const ssize_t w = ::pwrite(fd, p, (size_t)std::min<uint64_t>(left, 1ull << 30), (off_t)at);
+                if (w <= 0) { ok = false; break; }
+                p += w; left -= (uint64_t)w; at += (uint64_t)w;
+            }
+            m.second.clear();
+            std::lock_guard<std::mutex> l(mu);
+            if (pool.size() < 64) pool.push_back(std::move(m.second));
+        }
+        return ok;
+    }
+    void close() { if (fd >= 0) { ::close(fd); fout.seekp((std::streamoff)off); } }   // (the stream goes on behind the batches' lines)
+};
+
+// ---- the device steps: a batch's queries in, their candidate lists out (emit(queries, results) once or more) ----------------------
+struct Query { uint64_t id; View header; bool empty; uint64_t len; };
+
+struct Profile {                                                            // MCQ_PROFILE: phase times on stderr (development aid)
+    const bool on = std::getenv("MCQ_PROFILE") != nullptr;
+    std::atomic<uint64_t> parse{0}, submit{0}, wait{0}, classify{0};
+};
+uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// maxWindowsInRange (candidate_structs.hpp:143-145)
+uint32_t max_windows(uint64_t len, uint64_t insertMax, uint32_t stride) { return (uint32_t)(2 + std::max<uint64_t>(len, insertMax) / stride); }
+
+// The slot path: the worker's own batch slot on one replica (worker w: replica w % n, slot w / n).  A batch goes through it in as many
+// rounds as the slot needs: parse -> mc_batch_add -> submit -> wait -> emit -> clear.
+struct SlotStep {
+    const Session& S; const Options& o; BatchQueue& Q; Profile& P; mc_ctx* const ctx; const unsigned slot;
+    const bool prints = true;
+    std::vector<Query> queries = {}; Records rec = {};
+
+    template <class Emit>
+    bool operator()(Batch& B, Emit&& emit)
+    {
+        for (size_t q = B.qBeg; q < B.qEnd;) {
+            if (Q.failed()) return false;
+            queries.clear();
+            const uint64_t tp0 = now_ns();
+            for (; q < B.qEnd; ++q) {
+                const uint64_t id = Q.read(B, q, rec);
+                if (std::max(rec.s1.n, rec.s2.n) >= 0xFFFFFFF0ull) { Q.fail("sequence too long"); return false; }
+                const uint64_t len = (uint64_t)rec.s1.n + rec.s2.n;
+                const bool tooBig = len + 8 > S.cfg.slot_max_chars;
+                const int rc = tooBig ? MC_BATCH_FULL : mc_batch_add(ctx, slot, rec.s1.p, (uint32_t)rec.s1.n, rec.s2.p, (uint32_t)rec.s2.n, max_windows(len, o.insertMax, S.dbStride));
+                if (rc == MC_BATCH_FULL) {
+                    if (!tooBig && !queries.empty()) break;                   // submit what is there, then retry this query
+                    std::cerr << "query batch is too small for a single read!\n";                                    // database_query.hpp:103
+                    continue;
+                }
+                if (rc < 0) { Q.fail(mc_last_error(ctx)); return false; }
+                queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len});
+            }
+            if (Q.failed()) return false;
+            mc_results r;
+            const uint64_t tp1 = now_ns();
+            if (mc_batch_submit(ctx, slot, o.lowest) != MC_OK) { Q.fail(mc_last_error(ctx)); return false; }
+            const uint64_t tp2 = now_ns();
+            if (mc_batch_wait(ctx, slot, &r) != MC_OK) { Q.fail(mc_last_error(ctx)); return false; }
+            const uint64_t tp3 = now_ns();
+            emit(queries, r);
+            mc_batch_clear(ctx, slot);
+            if (P.on) { P.parse += tp1 - tp0; P.submit += tp2 - tp1; P.wait += tp3 - tp2; P.classify += now_ns() - tp3; }
+        }
+        return true;
+    }
+};
+
+// The set path (-shard keys / -resident-parts / -gpus): a batch's records are packed and go to mc_keyset_classify or
+// mc_partset_classify_resident in one call.  The sets share their two device lanes among the callers: this worker's batch runs beside
+// another worker's, its upload under the other's kernels.  A partitioned database is gone through part group by part group (the job
+// selects the group: the next one loads behind this one's queries); between the groups a batch keeps nothing but its reads' candidate
+// lists (Batch::carried), and only the last group's pass prints.
+struct SetStep {
+    const Session& S; const Options& o; BatchQueue& Q;
+    const bool hasPrior, prints;                                            // the part group pass: after another one; the last one
+    std::vector<Query> queries = {}; Records rec = {};
+    std::string seq1 = {}, seq2 = {}; std::vector<uint64_t> off1 = {}, off2 = {}; std::vector<mc_candidate> all = {};
+
+    template <class Emit>
+    bool operator()(Batch& B, Emit&& emit)
+    {
+        const bool paired = o.pairing != Options::unpaired;
+        const uint32_t K = S.cfg.max_candidates;
+        queries.clear(); seq1.clear(); seq2.clear(); off1.assign(1, 0); off2.assign(1, 0);
+        for (size_t q = B.qBeg; q < B.qEnd; ++q) {
+            const uint64_t id = Q.read(B, q, rec);
+            const uint64_t len = (uint64_t)rec.s1.n + rec.s2.n;
+            if (len + 8 > S.cfg.slot_max_chars) { std::cerr << "query batch is too small for a single read!\n"; continue; }
+            queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len});
+            seq1.append(rec.s1.p, rec.s1.n); off1.push_back(seq1.size());
+            if (paired) { seq2.append(rec.s2.p, rec.s2.n); off2.push_back(seq2.size()); }
+        }
+        const size_t n = queries.size();
+        if (hasPrior) all.swap(B.carried);                                  // what the earlier part groups left for this batch's reads
+        else all.assign(n * K, mc_candidate{});
+        if (all.size() != n * K) { Q.fail("internal: a batch changed between two part groups"); return false; }
+        seq1.push_back('\0'); seq2.push_back('\0');
+        const char* s2 = paired ? seq2.data() : nullptr;
+        const uint64_t* o2 = paired ? off2.data() : nullptr;
+        const int rc = !n ? MC_OK
+                     : S.keyset ? mc_keyset_classify(S.keyset, seq1.data(), off1.data(), s2, o2, n, o.lowest, o.insertMax, all.data())
+                                : mc_partset_classify_resident(S.partset, seq1.data(), off1.data(), s2, o2, n, o.lowest, o.insertMax, hasPrior ? 1 : 0, all.data());
+        if (rc != MC_OK) { Q.fail(S.keyset ? mc_keyset_last_error(S.keyset) : mc_partset_last_error(S.partset)); return false; }
+        if (!prints) { B.carried.swap(all); return true; }                  // more part groups to come: nothing is printed yet
+        mc_results r{};
+        r.num_queries = (uint32_t)n; r.max_candidates = K; r.cands = all.data();
+        emit(queries, r);
+        return true;
+    }
+};
+
+// One worker: batches until none is left.  The device step classifies a batch's queries; here their candidates become lines in a buffer,
+// which goes to the ordered writer whole (a batch the job failed in is not written).
+template <class Step>
+void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step)
+{
+    const Options& o = L.o;
+    const bool unlimited = o.maxCand < 1;
+    FastOut out;
+    std::vector<Cand> cands;
+    size_t b; Batch* B;
+    while (Q.take(b, B)) {
+        // (a moved-from string keeps its 15-character SSO capacity, never 0)
+        if (step.prints) { out.s.clear(); if (out.s.capacity() < 64) W.take_buffer(out.s); out << B->prefix; }
+        const bool done = step(*B, [&](const std::vector<Query>& queries, const mc_results& r) {
+            for (uint32_t i = 0; i < r.num_queries; ++i) {
+                const Query& m = queries[i];
+                if (m.empty) continue;                                      // processQuery, classification.cpp:780
+                device_candidates(r.cands + (size_t)i * r.max_candidates, r.max_candidates, L.tx, o.lowest, cands);
+                const mc_location* hits = nullptr; uint64_t nhits = 0;
+                if (o.allhits || unlimited) { hits = r.hits + r.hit_offsets[i]; nhits = r.hit_offsets[i + 1] - r.hit_offsets[i]; }
+                if (unlimited && cands.size() == r.max_candidates)          // list full: there may be more candidates than it holds
+                    host_candidates(hits, nhits, max_windows(m.len, o.insertMax, L.stride), L.tx, o.lowest, cands);
+                if (L.deferred) B->deferred.push_back(Deferred{m.id, m.header, cands});
+                else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0);
+            }
+        });
+        if (!done) break;
+        if (step.prints && !W.deliver(b, std::move(out.s))) Q.fail("Could not write to file " + W.name);
+    }
+}
+
+// ---- reports ----------------------------------------------------------------------------------------------------------------------
+void show_query_params(std::ostream& os, const Options& o, unsigned threads)   // printing.cpp:47-131
+{
+    if (o.mapView != Options::mv_none) {
+        os << o.comment << "Reporting per-read mappings (non-mapping lines start with '" << o.comment << "').\n";
+        os << o.comment << (o.lineage ? "The complete lineage will be reported starting with the lowest match.\n" : "Only the lowest matching rank will be reported.\n");
+    } else os << o.comment << "Per-Read mappings will not be shown.\n";
+    if (o.minReadLen > 0) os << o.comment << "Only reads with a minimum length of " << o.minReadLen << " bp will be mapped.\n";
+    if (o.maxReadLen < std::numeric_limits<uint64_t>::max()) os << o.comment << "Only reads with a maximum length of " << o.maxReadLen << " bp will be mapped.\n";
+    os << o.comment << "Classification will be constrained to ranks from '" << kRankNames[o.lowest] << "' to '" << kRankNames[o.highest] << "'.\n";
+    os << o.comment << "Classification hit threshold is " << o.hitsMin << " per query\n";
+    os << o.comment << "At maximum " << (o.maxCand < 1 ? std::numeric_limits<size_t>::max() : o.maxCand) << " classification candidates will be considered per query.\n";
+    if (o.pairing == Options::files) os << o.comment << "File based paired-end mode:\n" << o.comment << "  Reads from two consecutive files will be interleaved.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
+    else if (o.pairing == Options::sequences) os << o.comment << "Per file paired-end mode:\n" << o.comment << "  Reads from two consecutive sequences in each file will be paired up.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
+    if (o.hitsPerRef) os << o.comment << "A list of hits per reference sequence will be generated after the read mapping.\n";
+    if (o.abundances) os << o.comment << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
+    if (o.abundancePer != kNumRanks) os << o.comment << "A list of absolute and relative abundances for each '" << kRankNames[o.abundancePer] << "' will be generated after the read mapping.\n";
+    os << o.comment << "Using " << threads << " threads\n";
+}
+
+void show_mapping_header(std::ostream& os, const Options& o)               // show_query_mapping_header, classification.cpp:432-460
+{
+    os << o.comment << "TABLE_LAYOUT: ";
+    if (o.queryIds) os << "query_id" << o.column;
+    os << "query_header" << o.column;
+    const int rmax = o.lineage ? o.highest : o.lowest;
+    auto taxon_header = [&](const std::string& prefix) {                  // show_taxon_header, printing.cpp:133-172
+        auto hdr = [&](int r, bool named) {
+            if (o.showRank) os << prefix << (named ? kRankNames[r] : "rank") << o.rankSuffix;
+            if (o.showName) { os << prefix << "taxname"; if (o.showId) os << o.idPrefix << prefix << "taxid" << o.idSuffix; }
+            else if (o.showId) os << prefix << "taxid";
         };
-        if (S.keyset) {
-            std::thread producer(produce);
-            std::vector<std::thread> pool;
-            for (unsigned w = 1; w < workers; ++w) pool.emplace_back(work_keyset, w);
-            work_keyset(0);
-            for (auto& t : pool) t.join();
-            { std::lock_guard<std::mutex> l(batchMtx); }
-            batchCv.notify_all();
-            producer.join();
-        } else if (S.partset) {
-            uint64_t pinfo[6] = {0, 0, 1, 0, 0, 0};
-            mc_partset_info(S.partset, pinfo);
-            const uint32_t groups = (uint32_t)std::max<uint64_t>(pinfo[2], 1);
-            std::thread producer(produce);                                       // (the first pass streams behind the files' indexing)
-            for (uint32_t g = 0; g < groups && !failed; ++g) {
-                if (mc_partset_select_group(S.partset, g) != MC_OK) { std::lock_guard<std::mutex> l(errMtx); if (!failed.exchange(true)) firstError = mc_partset_last_error(S.partset); break; }
-                { std::lock_guard<std::mutex> l(batchMtx); nextBatch = 0; }
-                setHasPrior = g > 0; setLastPass = g + 1 == groups;
-                std::vector<std::thread> pool;
-                for (unsigned w = 1; w < workers; ++w) pool.emplace_back(work_keyset, w);
-                work_keyset(0);
-                for (auto& t : pool) t.join();
-            }
-            { std::lock_guard<std::mutex> l(batchMtx); }
-            batchCv.notify_all();
-            producer.join();
-        } else {
-            std::thread producer(produce);
-            std::vector<std::thread> pool;
-            for (unsigned w = 1; w < workers; ++w) pool.emplace_back(work, w);
-            work(0);
-            for (auto& t : pool) t.join();
-            { std::lock_guard<std::mutex> l(batchMtx); }
-            batchCv.notify_all();
-            producer.join();
-        }
-        if (outFd >= 0) { ::close(outFd); fout.seekp((std::streamoff)outOff); }   // (the stream goes on behind the batches' lines)
-        if (!producerError.empty()) throw std::runtime_error(producerError);
-        if (failed) throw std::runtime_error(firstError);
-        if (covMode) {
-            // The reference keeps (target -> candidates) in std::unordered_map objects: one per batch of -batch-size reads (4096 unless
-            // given, options.hpp:232; batches do not span input files), merged into a global one batch after batch
-            // (matches_per_target.hpp:100-125).  filter_targets_by_coverage (classification.cpp:591-634) then walks the global map
-            // in ITS iteration order, sums float coverages in that order, std::sorts them and erases targets from the low end: the order
-            // of equal coverages and the rounding of the sums come from the containers.  Same containers, same insertion sequence here
-            // (the reference's -threads 1 order), so the same targets go.
-            const size_t refBatch = o.refBatchSize ? o.refBatchSize : 4096;
-            std::unordered_map<uint32_t, std::vector<Cover>> tgtMatches;
-            {
-                std::unordered_map<uint32_t, std::vector<Cover>> batchMap;
-                size_t inBatch = 0, curFile = (size_t)-1;
-                auto flush = [&]() {
-                    for (auto& m : batchMap) { auto& t = tgtMatches[m.first]; t.insert(t.end(), m.second.begin(), m.second.end()); }
-                    batchMap = std::unordered_map<uint32_t, std::vector<Cover>>();
-                    inBatch = 0;
-                };
-                for (size_t b = 0; b < batches.size() && b < deferred.size(); ++b) {
-                    if (batches[b].f1 != curFile || batches[b].qBeg == 0) { if (inBatch) flush(); curFile = batches[b].f1; }
-                    for (const Deferred& d : deferred[b]) {
-                        for (const Cand& c : d.cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) batchMap[c.tgt].push_back(Cover{c.tgt, d.id, c.beg, c.end, c.hits});
-                        if (++inBatch == refBatch) flush();
-                    }
-                }
-                if (inBatch) flush();
-            }
-            {
-                using CovP = std::pair<uint32_t, float>;
-                std::vector<CovP> cov;
-                cov.reserve(tgtMatches.size());
-                float sum = 0;
-                for (const auto& m : tgtMatches) {
-                    const Lineage lin = tx.target_ranks(m.first);
-                    const uint32_t targetSize = tx.taxon(lin[0]) ? (uint32_t)tx.taxon(lin[0])->windows : 0u;
-                    std::unordered_set<uint32_t> hitWindows;
-                    for (const Cover& c : m.second) for (uint32_t w = c.beg; w <= c.end; ++w) hitWindows.emplace(w);
-                    const float covP = float(hitWindows.size()) / targetSize;
-                    sum += covP;
-                    cov.emplace_back(m.first, covP);
-                }
-                std::sort(cov.begin(), cov.end(), [](CovP& a, CovP& b) { return a.second < b.second; });
-                float part = 0;
-                for (auto it = cov.begin(); it != cov.end(); ++it) {
-                    part += it->second;
-                    if (part > o.covPercentile * sum) break;
-                    tgtMatches.erase(it->first);
-                }
-            }
-            // redo_classification_batched: candidates of erased targets go, then classification and output as usual
-            Acc A;
-            std::ostringstream out;
-            std::vector<Cand> left;
-            for (size_t b = 0; b < batches.size() && b < deferred.size(); ++b) {
-                for (const Deferred& d : deferred[b]) {
-                    left.clear();
-                    for (const Cand& c : d.cands) if (tgtMatches.find(c.tgt) != tgtMatches.end()) left.push_back(c);
-                    emit(A, out, d.id, d.header, left, nullptr, 0);
-                }
-                os << out.str();
-                out.str(std::string());
-            }
-            collect(A);
-            for (const auto& m : tgtMatches) covers.insert(covers.end(), m.second.begin(), m.second.end());
-        }
-        if (merged) {                                                            // map_candidates_to_targets, classification.cpp:891-911
-            Acc A;
-            std::ostringstream out;
-            for (size_t i = 0; i < merged->headers.size(); ++i) {
-                const std::string& h = merged->headers[i];
-                emit(A, out, i + 1, View{h.data(), h.size()}, merged->cands[i], nullptr, 0);
-            }
-            os << out.str();
-            collect(A);
-        }
-        if (profile)
-            std::cerr << "mcq profile: index " << tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
-                      << " ms; summed over " << workers << " workers: parse+add " << nsParse / 1e6 << " ms, submit " << nsSubmit / 1e6 << " ms, wait "
-                      << nsWait / 1e6 << " ms, classify+format " << nsClassify / 1e6 << " ms; batches " << batches.size() << "\n";
+        if (o.lowest == rmax) hdr(o.lowest, false);
+        else for (int r = o.lowest; r <= rmax; ++r) { hdr(r, true); if (r < rmax) os << o.taxSep; }
+    };
+    if (o.showGroundTruth) { taxon_header("truth_"); os << o.column; }
+    if (o.allhits) os << "all_hits" << o.column;
+    if (o.tophits) os << "top_hits" << o.column;
+    if (o.locations) os << "candidate_locations" << o.column;
+    taxon_header("");
+    os << '\n';
+}
 
-        uint64_t nAssigned = 0;
-        for (int r = 0; r < kNumRanks; ++r) nAssigned += assigned[r];
-        const uint64_t nUnassigned = assigned[kNumRanks], nTotal = nAssigned + nUnassigned;
-
-        if (o.hitsPerRef) {                                                      // show_matches_per_targets, printing.cpp:385-420
-            std::sort(covers.begin(), covers.end(), [](const Cover& a, const Cover& b) {   // per target: by window range, then query id
-                if (a.tgt != b.tgt) return a.tgt < b.tgt;
-                if (a.beg != b.beg) return a.beg < b.beg;
-                if (a.end != b.end) return a.end < b.end;
-                return a.qid < b.qid;
-            });
-            perTargetOut << o.comment << "--- list of hits for each reference sequence ---\n"
-                         << o.comment << "window start position within sequence = window_index * window_stride(=" << dbStride << ")\n";
-            perTargetOut << o.comment << "TABLE_LAYOUT: " << " sequence " << o.column << " windows_in_sequence " << o.column
-                         << "queryid/first_window_index+additional_windows:hits,queryid/...\n";
-            for (size_t i = 0; i < covers.size();) {
-                const uint32_t tgt = covers[i].tgt;
-                const Lineage lin = tx.target_ranks(tgt);
-                show_lineage(perTargetOut, o, tx, lin, 0, o.lineage ? o.highest : 0);
-                perTargetOut << o.column << (tx.taxon(lin[0]) ? tx.taxon(lin[0])->windows : 0) << o.column;
-                for (bool first = true; i < covers.size() && covers[i].tgt == tgt; ++i, first = false) {
-                    if (!first) perTargetOut << ',';
-                    perTargetOut << covers[i].qid << '/' << covers[i].beg << '+' << (covers[i].end - covers[i].beg) << ':' << covers[i].hits;
-                }
-                perTargetOut << '\n';
+// -cov-percentile (map_queries_to_targets_default, classification.cpp:747-838): nothing is classified while the reads are queried; every
+// read's candidates are kept (Batch::deferred), the targets are filtered by their coverage afterwards, and the reads are classified from
+// the candidates that are left.
+// The reference keeps (target -> candidates) in std::unordered_map objects: one per batch of -batch-size reads (4096 unless given,
+// options.hpp:232; batches do not span input files), merged into a global one batch after batch (matches_per_target.hpp:100-125).
+// filter_targets_by_coverage (classification.cpp:591-634) then walks the global map in ITS iteration order, sums float coverages in that
+// order, std::sorts them and erases targets from the low end: the order of equal coverages and the rounding of the sums come from the
+// containers.  Same containers, same insertion sequence here (the reference's -threads 1 order), so the same targets go.
+void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L)
+{
+    const Taxonomy& tx = L.tx;
+    const size_t refBatch = o.refBatchSize ? o.refBatchSize : 4096;
+    std::unordered_map<uint32_t, std::vector<Cover>> tgtMatches;
+    {
+        std::unordered_map<uint32_t, std::vector<Cover>> batchMap;
+        size_t inBatch = 0, curFile = (size_t)-1;
+        auto flush = [&]() {
+            for (auto& m : batchMap) { auto& t = tgtMatches[m.first]; t.insert(t.end(), m.second.begin(), m.second.end()); }
+            batchMap = std::unordered_map<uint32_t, std::vector<Cover>>();
+            inBatch = 0;
+        };
+        for (const Batch& B : batches) {
+            if (B.f1 != curFile || B.qBeg == 0) { if (inBatch) flush(); curFile = B.f1; }
+            for (const Deferred& d : B.deferred) {
+                for (const Cand& c : d.cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) batchMap[c.tgt].push_back(Cover{c.tgt, d.id, c.beg, c.end, c.hits});
+                if (++inBatch == refBatch) flush();
             }
         }
+        if (inBatch) flush();
+    }
+    {
+        using CovP = std::pair<uint32_t, float>;
+        std::vector<CovP> cov;
+        cov.reserve(tgtMatches.size());
+        float sum = 0;
+        for (const auto& m : tgtMatches) {
+            const Lineage lin = tx.target_ranks(m.first);
+            const uint32_t targetSize = tx.taxon(lin[0]) ? (uint32_t)tx.taxon(lin[0])->windows : 0u;
+            std::unordered_set<uint32_t> hitWindows;
+            for (const Cover& c : m.second) for (uint32_t w = c.beg; w <= c.end; ++w) hitWindows.emplace(w);
+            const float covP = float(hitWindows.size()) / targetSize;
+            sum += covP;
+            cov.emplace_back(m.first, covP);
+        }
+        std::sort(cov.begin(), cov.end(), [](CovP& a, CovP& b) { return a.second < b.second; });
+        float part = 0;
+        for (auto it = cov.begin(); it != cov.end(); ++it) {
+            part += it->second;
+            if (part > o.covPercentile * sum) break;
+            tgtMatches.erase(it->first);
+        }
+    }
+    // redo_classification_batched: candidates of erased targets go, then classification and output as usual
+    std::ostringstream out;
+    std::vector<Cand> left;
+    for (const Batch& B : batches) {
+        for (const Deferred& d : B.deferred) {
+            left.clear();
+            for (const Cand& c : d.cands) if (tgtMatches.find(c.tgt) != tgtMatches.end()) left.push_back(c);
+            L(out, d.id, d.header, left, nullptr, 0);
+        }
+        os << out.str();
+        out.str(std::string());
+    }
+    for (const auto& m : tgtMatches) L.tally.covers.insert(L.tally.covers.end(), m.second.begin(), m.second.end());
+}
 
-        if (taxCountsWanted) {
-            // taxon_count_map (classification.hpp:48-56): higher ranks first, then ascending taxon id
-            auto higher = [&tx](uint32_t a, uint32_t b) {
-                const Taxon* x = tx.taxon(a); const Taxon* y = tx.taxon(b);
-                if (x->rank != y->rank) return x->rank > y->rank;
-                return x->id < y->id;
-            };
-            std::map<uint32_t, double, decltype(higher)> counts(higher);
-            for (const auto& kv : bestCounts) counts[kv.first] = kv.second;
-            auto table = [&]() {                                                 // show_abundance_table, printing.cpp:424-468
-                perTaxonOut << o.comment << "rank" << o.rankSuffix << "name" << o.column << "taxid" << o.column << "number of reads" << o.column
-                            << "abundance\n";
-                double ipart = 0.0;
-                for (const auto& tc : counts) {
-                    const Taxon* t = tx.taxon(tc.first);
-                    perTaxonOut << (t->rank == kNumRanks ? "none" : kRankNames[t->rank]) << o.rankSuffix << t->name << o.column;
-                    perTaxonOut << (t->rank == 0 ? t->parent : t->id) << o.column;
-                    if (std::modf(tc.second, &ipart) == 0.0) perTaxonOut << ipart;
-                    else perTaxonOut << std::setprecision(15) << tc.second << std::setprecision(6);
-                    perTaxonOut << o.column << (tc.second / double(nTotal) * 100) << "%\n";
-                }
-                perTaxonOut << "unclassified" << o.column << "--" << o.column << '0' << o.column << nUnassigned << o.column
-                            << (nTotal > 0 ? nUnassigned / double(nTotal) : 0.0) * 100 << "%\n";
-            };
-            if (o.abundances) { perTaxonOut << o.comment << "query summary: number of queries mapped per taxon\n"; table(); }
-            if (o.abundancePer != kNumRanks) {
-                // estimate_abundance (classification.cpp:304-374)
-                const int rank = o.abundancePer;
-                auto first_ancestor = [&](uint32_t t, int from, auto&& accept) -> uint32_t {
-                    const Lineage lin = tx.ranks_of(t);
-                    for (int r = from; r < kNumRanks; ++r) if (lin[r] && accept(lin[r])) return lin[r];
-                    return 0;
-                };
-                if (rank != 0) {
-                    // counts below the estimation rank move up to the closest ancestor on or above it (first position that is not
-                    // "higher" than an imaginary taxon of rank-1 with id 0)
-                    auto it = counts.begin();
-                    while (it != counts.end()) {
-                        const Taxon* t = tx.taxon(it->first);
-                        if (t->rank > rank - 1 || (t->rank == rank - 1 && t->id < 0)) ++it; else break;
-                    }
-                    while (it != counts.end()) {
-                        const uint32_t anc = first_ancestor(it->first, rank, [](uint32_t) { return true; });
-                        if (anc) { counts[anc] += it->second; it = counts.erase(it); } else ++it;
-                    }
-                }
-                std::unordered_map<uint32_t, std::vector<uint32_t>> children;
-                std::unordered_map<uint32_t, uint64_t> weight;
-                for (const auto& tc : counts) weight[tc.first] = 0;
-                for (auto it = counts.rbegin(); it != counts.rend(); ++it) {   // leaves to root: own count + weight go to the closest counted ancestor
-                    const uint32_t parent = first_ancestor(it->first, tx.taxon(it->first)->rank + 1, [&](uint32_t a) { return weight.count(a) > 0; });
-                    if (parent) {
-                        weight[parent] = (uint64_t)(weight[parent] + (weight[it->first] + it->second));
-                        children[parent].push_back(it->first);
-                    }
-                }
-                for (auto it = counts.begin(); it != counts.end();) {            // root to leaves: a parent's count is shared out proportionally
-                    auto ch = children.find(it->first);
-                    if (ch != children.end()) {
-                        const uint64_t sumChildren = weight[it->first];
-                        for (uint32_t c : ch->second) counts[c] += it->second * (counts[c] + weight[c]) / sumChildren;
-                        it = counts.erase(it);
-                    } else ++it;
-                }
-                perTaxonOut << o.comment << "estimated abundance (number of queries) per " << kRankNames[rank] << "\n";
-                table();
-            }
+void show_hits_per_ref(std::ostream& os, const Options& o, const Taxonomy& tx, uint32_t stride, std::vector<Cover>& covers)   // show_matches_per_targets, printing.cpp:385-420
+{
+    std::sort(covers.begin(), covers.end(), [](const Cover& a, const Cover& b) {   // per target: by window range, then query id
+        if (a.tgt != b.tgt) return a.tgt < b.tgt;
+        if (a.beg != b.beg) return a.beg < b.beg;
+        if (a.end != b.end) return a.end < b.end;
+        return a.qid < b.qid;
+    });
+    os << o.comment << "--- list of hits for each reference sequence ---\n"
+       << o.comment << "window start position within sequence = window_index * window_stride(=" << stride << ")\n";
+    os << o.comment << "TABLE_LAYOUT: " << " sequence " << o.column << " windows_in_sequence " << o.column
+       << "queryid/first_window_index+additional_windows:hits,queryid/...\n";
+    for (size_t i = 0; i < covers.size();) {
+        const uint32_t tgt = covers[i].tgt;
+        const Lineage lin = tx.target_ranks(tgt);
+        show_lineage(os, o, tx, lin, 0, o.lineage ? o.highest : 0);
+        os << o.column << (tx.taxon(lin[0]) ? tx.taxon(lin[0])->windows : 0) << o.column;
+        for (bool first = true; i < covers.size() && covers[i].tgt == tgt; ++i, first = false) {
+            if (!first) os << ',';
+            os << covers[i].qid << '/' << covers[i].beg << '+' << (covers[i].end - covers[i].beg) << ':' << covers[i].hits;
         }
-        if (o.showSummary) {                                                     // show_summary, printing.cpp:601-620
-            const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            uint64_t nassigned = 0;
-            for (int r = 0; r < kNumRanks; ++r) nassigned += assigned[r];
-            const uint64_t unassigned = assigned[kNumRanks], total = nassigned + unassigned;
-            const uint64_t nq = o.pairing == Options::unpaired ? total : 2 * total;
-            os << o.comment << "queries: " << nq << '\n' << o.comment << "time:    " << (long long)(s * 1000) << " ms\n"
-               << o.comment << "speed:   " << nq / (s / 60.0) << " queries/min\n";
-            if (total > 0) {                                                     // show_taxon_statistics, printing.cpp:502-535
-                if (nassigned < 1) os << "None of the input sequences could be classified.\n";
-                else {
-                    if (unassigned > 0) os << o.comment << "unclassified: " << (100 * (unassigned / double(total))) << "% (" << unassigned << ")\n";
-                    os << o.comment << "classified:\n";
-                    const int shown[] = {0, 3, 4, 6, 10, 12, 14, 16, 18, 19, 20};
-                    auto upto = [](const uint64_t* a, int r) { uint64_t s = 0; for (int x = 0; x <= r; ++x) s += a[x]; return s; };
-                    auto padded = [](int r) { std::string rn = kRankNames[r]; rn.resize(11, ' '); return rn; };
-                    for (int r : shown)
-                        if (upto(assigned, r) > 0) os << o.comment << "  " << padded(r) << (100 * (upto(assigned, r) / double(total))) << "% (" << upto(assigned, r) << ")\n";
-                    if (upto(known, kNumRanks - 1) > 0) {                         // ground truth block, printing.cpp:537-592
-                        if (known[kNumRanks] > 0) os << o.comment << "ground truth unknown: " << (100 * (known[kNumRanks] / double(total))) << "% (" << known[kNumRanks] << ")\n";
-                        os << o.comment << "ground truth known:\n";
-                        for (int r : shown) if (upto(assigned, r) > 0) os << o.comment << "  " << padded(r) << (100 * (upto(known, r) / double(total))) << "% (" << upto(known, r) << ")\n";
-                        os << o.comment << "correctly classified:\n";
-                        for (int r : shown) if (upto(assigned, r) > 0) os << o.comment << "  " << padded(r) << upto(correct, r) << '\n';
-                        auto wrongFrom = [&](int r) { uint64_t s = 0; for (int x = r; x < kNumRanks; ++x) s += wrong[x]; return s; };
-                        os << o.comment << "precision (correctly classified / classified) if ground truth known:\n";
-                        for (int r : shown) if (upto(assigned, r) > 0) {
-                            const double tot = double(upto(correct, r)) + double(wrongFrom(r));
-                            os << o.comment << "  " << padded(r) << (100 * (tot > 0 ? upto(correct, r) / tot : 0.0)) << "%\n";
-                        }
-                        os << o.comment << "sensitivity (correctly classified / all) if ground truth known:\n";
-                        for (int r : shown) if (upto(assigned, r) > 0)
-                            os << o.comment << "  " << padded(r) << (100 * (upto(known, r) > 0 ? upto(correct, r) / double(upto(known, r)) : 0.0)) << "%\n";
-                        if (covTotalDomain > 0) {
-                            os << o.comment << "false positives (hit on taxa not covered in DB):\n";
-                            for (int r : shown) if (upto(assigned, r) > 0) os << o.comment << "  " << padded(r) << covFalsePos[r] << "\n";
-                        }
-                    }
-                }
-            } else std::cerr << o.comment << "No valid query sequences found.\n";
+        os << '\n';
+    }
+}
+
+// -abundances: queries per taxon; -abundance-per: the estimate for one rank (estimate_abundance, classification.cpp:304-374)
+void show_abundances(std::ostream& os, const Options& o, const Taxonomy& tx, const Tally& T)
+{
+    const uint64_t nUnassigned = T.unclassified(), nTotal = T.total();
+    // taxon_count_map (classification.hpp:48-56): higher ranks first, then ascending taxon id
+    auto higher = [&tx](uint32_t a, uint32_t b) {
+        const Taxon* x = tx.taxon(a); const Taxon* y = tx.taxon(b);
+        if (x->rank != y->rank) return x->rank > y->rank;
+        return x->id < y->id;
+    };
+    std::map<uint32_t, double, decltype(higher)> counts(higher);
+    for (const auto& kv : T.counts) counts[kv.first] = kv.second;
+    auto table = [&]() {                                                    // show_abundance_table, printing.cpp:424-468
+        os << o.comment << "rank" << o.rankSuffix << "name" << o.column << "taxid" << o.column << "number of reads" << o.column << "abundance\n";
+        double ipart = 0.0;
+        for (const auto& tc : counts) {
+            const Taxon* t = tx.taxon(tc.first);
+            os << (t->rank == kNumRanks ? "none" : kRankNames[t->rank]) << o.rankSuffix << t->name << o.column;
+            os << (t->rank == 0 ? t->parent : t->id) << o.column;
+            if (std::modf(tc.second, &ipart) == 0.0) os << ipart;
+            else os << std::setprecision(15) << tc.second << std::setprecision(6);
+            os << o.column << (tc.second / double(nTotal) * 100) << "%\n";
         }
+        os << "unclassified" << o.column << "--" << o.column << '0' << o.column << nUnassigned << o.column
+           << (nTotal > 0 ? nUnassigned / double(nTotal) : 0.0) * 100 << "%\n";
+    };
+    if (o.abundances) { os << o.comment << "query summary: number of queries mapped per taxon\n"; table(); }
+    if (o.abundancePer == kNumRanks) return;
+    const int rank = o.abundancePer;
+    auto first_ancestor = [&](uint32_t t, int from, auto&& accept) -> uint32_t {
+        const Lineage lin = tx.ranks_of(t);
+        for (int r = from; r < kNumRanks; ++r) if (lin[r] && accept(lin[r])) return lin[r];
+        return 0;
+    };
+    if (rank != 0) {
+        // counts below the estimation rank move up to the closest ancestor on or above it (first position that is not
+        // "higher" than an imaginary taxon of rank-1 with id 0)
+        auto it = counts.begin();
+        while (it != counts.end()) {
+            const Taxon* t = tx.taxon(it->first);
+            if (t->rank > rank - 1 || (t->rank == rank - 1 && t->id < 0)) ++it; else break;
+        }
+        while (it != counts.end()) {
+            const uint32_t anc = first_ancestor(it->first, rank, [](uint32_t) { return true; });
+            if (anc) { counts[anc] += it->second; it = counts.erase(it); } else ++it;
+        }
+    }
+    std::unordered_map<uint32_t, std::vector<uint32_t>> children;
+    std::unordered_map<uint32_t, uint64_t> weight;
+    for (const auto& tc : counts) weight[tc.first] = 0;
+    for (auto it = counts.rbegin(); it != counts.rend(); ++it) {           // leaves to root: own count + weight go to the closest counted ancestor
+        const uint32_t parent = first_ancestor(it->first, tx.taxon(it->first)->rank + 1, [&](uint32_t a) { return weight.count(a) > 0; });
+        if (parent) {
+            weight[parent] = (uint64_t)(weight[parent] + (weight[it->first] + it->second));
+            children[parent].push_back(it->first);
+        }
+    }
+    for (auto it = counts.begin(); it != counts.end();) {                  // root to leaves: a parent's count is shared out proportionally
+        auto ch = children.find(it->first);
+        if (ch != children.end()) {
+            const uint64_t sumChildren = weight[it->first];
+            for (uint32_t c : ch->second) counts[c] += it->second * (counts[c] + weight[c]) / sumChildren;
+            it = counts.erase(it);
+        } else ++it;
+    }
+    os << o.comment << "estimated abundance (number of queries) per " << kRankNames[rank] << "\n";
+    table();
+}
+
+void show_summary(std::ostream& os, const Options& o, const Tally& T, double seconds)   // show_summary, printing.cpp:601-620
+{
+    const uint64_t nassigned = T.classified(), unassigned = T.unclassified(), total = T.total();
+    const uint64_t nq = o.pairing == Options::unpaired ? total : 2 * total;
+    os << o.comment << "queries: " << nq << '\n' << o.comment << "time:    " << (long long)(seconds * 1000) << " ms\n"
+       << o.comment << "speed:   " << nq / (seconds / 60.0) << " queries/min\n";
+    if (total == 0) { std::cerr << o.comment << "No valid query sequences found.\n"; return; }
+    // show_taxon_statistics, printing.cpp:502-535
+    if (nassigned < 1) { os << "None of the input sequences could be classified.\n"; return; }
+    if (unassigned > 0) os << o.comment << "unclassified: " << (100 * (unassigned / double(total))) << "% (" << unassigned << ")\n";
+    os << o.comment << "classified:\n";
+    const int shown[] = {0, 3, 4, 6, 10, 12, 14, 16, 18, 19, 20};
+    auto upto = [](const uint64_t* a, int r) { uint64_t s = 0; for (int x = 0; x <= r; ++x) s += a[x]; return s; };
+    auto padded = [](int r) { std::string rn = kRankNames[r]; rn.resize(11, ' '); return rn; };
+    for (int r : shown)
+        if (upto(T.assigned, r) > 0) os << o.comment << "  " << padded(r) << (100 * (upto(T.assigned, r) / double(total))) << "% (" << upto(T.assigned, r) << ")\n";
+    if (upto(T.known, kNumRanks - 1) == 0) return;
+    // ground truth block, printing.cpp:537-592
+    if (T.known[kNumRanks] > 0) os << o.comment << "ground truth unknown: " << (100 * (T.known[kNumRanks] / double(total))) << "% (" << T.known[kNumRanks] << ")\n";
+    os << o.comment << "ground truth known:\n";
+    for (int r : shown) if (upto(T.assigned, r) > 0) os << o.comment << "  " << padded(r) << (100 * (upto(T.known, r) / double(total))) << "% (" << upto(T.known, r) << ")\n";
+    os << o.comment << "correctly classified:\n";
+    for (int r : shown) if (upto(T.assigned, r) > 0) os << o.comment << "  " << padded(r) << upto(T.correct, r) << '\n';
+    auto wrongFrom = [&](int r) { uint64_t s = 0; for (int x = r; x < kNumRanks; ++x) s += T.wrong[x]; return s; };
+    os << o.comment << "precision (correctly classified / classified) if ground truth known:\n";
+    for (int r : shown) if (upto(T.assigned, r) > 0) {
+        const double tot = double(upto(T.correct, r)) + double(wrongFrom(r));
+        os << o.comment << "  " << padded(r) << (100 * (tot > 0 ? upto(T.correct, r) / tot : 0.0)) << "%\n";
+    }
+    os << o.comment << "sensitivity (correctly classified / all) if ground truth known:\n";
+    for (int r : shown) if (upto(T.assigned, r) > 0)
+        os << o.comment << "  " << padded(r) << (100 * (upto(T.known, r) > 0 ? upto(T.correct, r) / double(upto(T.known, r)) : 0.0)) << "%\n";
+    if (T.covDomain > 0) {
+        os << o.comment << "false positives (hit on taxa not covered in DB):\n";
+        for (int r : shown) if (upto(T.assigned, r) > 0) os << o.comment << "  " << padded(r) << T.covFalsePos[r] << "\n";
+    }
+}
+
+// ---- one query job: the files of one command (or of one -split-out group) -> mapping lines and reports --------------------------------
+void run_job(Session& S, Options o, const std::vector<std::string>& infiles, const std::string& outfile, const std::string& targetsFile,
+             const std::string& abundanceFile, const MergedInput* merged = nullptr)
+{
+    if (!merged) S.open(o);
+    const Taxonomy& tx = S.tx;
+    if (o.hitsMin < 1) o.hitsMin = S.dbSketch >= 6 ? int(S.dbSketch / 3.0) : (S.dbSketch >= 4 ? 2 : 1);     // querying.cpp:257-268
+    o.infiles = infiles;
+    std::ofstream fout, ftargets, ftaxa;                                    // process_input_files, querying.cpp:84-112
+    if (!outfile.empty()) { fout.open(outfile); if (!fout.good()) throw std::runtime_error("Could not write to file " + outfile); }
+    if (!targetsFile.empty()) { ftargets.open(targetsFile); if (!ftargets.good()) throw std::runtime_error("Could not write to file " + targetsFile); }
+    if (!abundanceFile.empty()) { ftaxa.open(abundanceFile); if (!ftaxa.good()) throw std::runtime_error("Could not write to file " + abundanceFile); }
+    std::ostream& os = outfile.empty() ? std::cout : fout;
+    std::ostream& perTargetOut = targetsFile.empty() ? os : ftargets;
+    std::ostream& perTaxonOut = abundanceFile.empty() ? os : ftaxa;
+
+    if (o.showQueryParams) show_query_params(os, o, S.threads);
+    if (merged) {                                                           // merge_result_files, mode_merge.cpp:266-269
+        os << o.comment << "Merging " << merged->files.size() << " files:\n";
+        for (const auto& f : merged->files) os << o.comment << f << '\n';
+    }
+    if (o.mapView != Options::mv_none) show_mapping_header(os, o);
+
+    const auto t0 = std::chrono::steady_clock::now();
+    const bool covMode = o.covPercentile > 0 && !merged;
+    Profile P;
+    BatchQueue Q(o, S.workers, t0);
+    OrderedOut W(os, fout, outfile);
+    std::vector<Tally> tallies(S.workers);
+    auto worker = [&](unsigned w, auto&& step) { MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]}; work(Q, W, L, step); };
+    Q.start();                                                              // (with part groups: the first pass streams behind the files' indexing)
+    if (S.keyset) run_workers(S.workers, [&](unsigned w) { worker(w, SetStep{S, o, Q, false, true}); });
+    else if (S.partset) {
+        uint64_t pinfo[6] = {0, 0, 1, 0, 0, 0};
+        mc_partset_info(S.partset, pinfo);
+        const uint32_t groups = (uint32_t)std::max<uint64_t>(pinfo[2], 1);
+        for (uint32_t g = 0; g < groups && !Q.failed(); ++g) {
+            if (mc_partset_select_group(S.partset, g) != MC_OK) { Q.fail(mc_partset_last_error(S.partset)); break; }
+            Q.rewind();
+            run_workers(S.workers, [&](unsigned w) { worker(w, SetStep{S, o, Q, g > 0, g + 1 == groups}); });
+        }
+    } else run_workers(S.workers, [&](unsigned w) { worker(w, SlotStep{S, o, Q, P, S.replica(w % S.replication), w / S.replication}); });
+    Q.finish();
+    W.close();
+    Q.rethrow();
+
+    Tally T;
+    for (const Tally& t : tallies) T += t;
+    if (covMode) { MappingWriter L{o, tx, S.dbStride, S.dbWinlen, true, T}; classify_by_coverage(os, o, Q.batches, L); }
+    if (merged) {                                                           // map_candidates_to_targets, classification.cpp:891-911
+        MappingWriter L{o, tx, S.dbStride, S.dbWinlen, false, T};
+        std::ostringstream out;
+        for (size_t i = 0; i < merged->headers.size(); ++i) L(out, i + 1, View{merged->headers[i].data(), merged->headers[i].size()}, merged->cands[i], nullptr, 0);
+        os << out.str();
+    }
+    if (P.on)
+        std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
+                  << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
+                  << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    if (o.hitsPerRef) show_hits_per_ref(perTargetOut, o, tx, S.dbStride, T.covers);
+    if (o.abundances || o.abundancePer != kNumRanks) show_abundances(perTaxonOut, o, tx, T);
+    if (o.showSummary) show_summary(os, o, T, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 }
 
 // ---- merge mode (mode_merge.cpp): result files of queries against single database parts -> one classification ------------------
@@ -1468,14 +1469,11 @@ int info_main(const std::vector<std::string>& args)
     struct Guard { mc_ctx* c; ~Guard() { mc_destroy(c); } } guard{ctx};
     uint64_t info[8]; mc_db_info(ctx, info);
     Taxonomy tx;
-    std::vector<std::string> srcFile; std::vector<uint64_t> srcIndex;
-    uint64_t nt = 0; mc_db_num_taxa(ctx, &nt);
-    tx.taxa.resize(nt); srcFile.resize(nt); srcIndex.resize(nt);
-    for (uint64_t i = 0; i < nt; ++i) {
-        uint32_t rk; const char *nm, *fn;
-        mc_db_taxon(ctx, i, &tx.taxa[i].id, &tx.taxa[i].parent, &rk, &nm);
-        tx.taxa[i].rank = int(rk); tx.taxa[i].name = nm;
-        mc_db_taxon_source(ctx, i, &fn, &srcIndex[i], &tx.taxa[i].windows);
+    read_taxa(ctx, tx);
+    std::vector<std::string> srcFile(tx.taxa.size()); std::vector<uint64_t> srcIndex(tx.taxa.size());
+    for (size_t i = 0; i < tx.taxa.size(); ++i) {
+        const char* fn;
+        mc_db_taxon_source(ctx, i, &fn, &srcIndex[i], nullptr);
         srcFile[i] = fn;
         tx.byId.emplace(tx.taxa[i].id, (uint32_t)i);
         if (tx.taxa[i].rank == 0 && tx.taxa[i].id < 0) tx.targetByName.emplace(tx.taxa[i].name, (uint32_t)i + 1);
