@@ -427,6 +427,26 @@ int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, 
  * test_gpu_reference_midscale.py run them against the goldens, the oracle and the reference). */
 int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value);
 
+/* semi-global alignment of reads to subjects on the device, as `metacache query -align` computes it on the host (alignment.hpp:177-276,
+ * make_semi_global_alignment classification.cpp:76-100): match +2, mismatch -1, gap -1 on the characters as they are; free end gaps; ties
+ * fall to diag, then above, then left; the end cell is the corner unless a cell of the last column, then of the last row, is strictly
+ * greater.  Problem i is read i = reads[read_off[i] .. read_off[i+1]), its mate (mates may be NULL: no mates; an empty mate counts as
+ * none) and subject i.  Read 1 is aligned forward and reverse-complemented (case kept, U -> A); the mate's two scores are added to
+ * them as unsigned 64-bit numbers (a negative score wraps, as in the reference), forward is shown when its sum is strictly greater:
+ * reversed[i] = 0, else 1.  score_fwd / score_rev are read 1's own scores, mate_fwd / mate_rev the mate's (0 without one).
+ * The shown alignment's two strings (gaps are '_', equal lengths, at least one column) go to aligned[aligned_off[i] .. aligned_off[i+1]):
+ * first half the aligned read, second half the aligned subject; aligned_off (n + 1 numbers) is FILLED by the call, aligned_cap must be
+ * at least the sum of 2 * max(1, len_read + len_subject).  Works on any context, with or without a loaded table, from several threads at
+ * once.  A call goes to the device in sub-batches whose output and scratch stay under mc_set_tuning "align_scratch_mb" (default 512;
+ * one problem alone always goes): reads up to 256 against subjects up to 512 characters keep their trace in LDS, longer ones in device
+ * scratch, 2 bits per cell. */
+int mc_align_semiglobal(mc_ctx* ctx, const char* reads, const uint64_t* read_off, const char* mates, const uint64_t* mate_off,
+                        const char* subjects, const uint64_t* subj_off, uint64_t n, int32_t* score_fwd, int32_t* score_rev,
+                        int32_t* mate_fwd, int32_t* mate_rev, uint8_t* reversed, char* aligned, uint64_t aligned_cap, uint64_t* aligned_off);
+/* stats[0..3] = problems aligned on this context, matrix cells of read 1 (len_read * len_subject summed), nanoseconds of the alignment
+ * kernels (HIP events around each sub-batch's launches), sub-batches */
+int mc_align_stats(const mc_ctx* ctx, uint64_t stats[4]);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with

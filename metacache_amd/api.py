@@ -73,7 +73,7 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_timing_enable", "mc_timing_reset", "mc_timing_get", "mc_last_batch_stats", "mc_set_tuning", "mc_copy_results_on",
            "mc_build_begin", "mc_build_add_target", "mc_build_add_target_src", "mc_build_add_target_device", "mc_build_flush", "mc_build_reserve",
            "mc_build_table_begin", "mc_build_table_add", "mc_build_table_end", "mc_build_set_parent", "mc_build_target_windows", "mc_build_remove_ambiguous", "mc_build_counts", "mc_build_add_existing_target", "mc_build_add_locations", "mc_build_finish", "mc_build_finish_shards", "mc_build_write_shards", "mc_build_write", "mc_build_write_begin", "mc_build_write_add", "mc_build_write_end", "mc_build_free", "mc_build_last_error",
-           "mc_build_set_query_config"]
+           "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats"]
 
 _lib = None
 
@@ -128,6 +128,9 @@ def lib() -> C.CDLL:
         L.mc_timing_reset.argtypes = [C.c_void_p]
         L.mc_timing_get.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
         L.mc_last_batch_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
+        L.mc_align_semiglobal.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p]
+        L.mc_align_stats.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -710,3 +713,86 @@ class Builder:
         if self.h:
             lib().mc_build_free(self.h)
             self.h = None
+
+
+# ---- semi-global alignment (mc_align_semiglobal) -------------------------------------------------------------------------------
+def _packed(seqs):
+    """byte strings -> (characters, n + 1 offsets) as the C ABI takes them"""
+    seqs = [x.encode() if isinstance(x, str) else bytes(x) for x in seqs]
+    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+    if seqs:
+        off[1:] = np.cumsum([len(x) for x in seqs], dtype=np.uint64)
+    chars = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+    return chars, off
+
+
+class Aligner:
+    """A context without a table for align_semiglobal (any Database's handle does as well)."""
+
+    def __init__(self, handle=None, **kw):
+        self.own = handle is None
+        if self.own:
+            cfg = default_config(**kw)
+            h = C.c_void_p()
+            rc = lib().mc_create(C.byref(cfg), C.byref(h))
+            if rc != MC_OK:
+                raise McError(f"mc_create -> {rc}: {lib().mc_last_error(None).decode()}")
+            handle = h.value
+        self.h = C.c_void_p(handle)
+
+    def close(self):
+        if self.own and self.h:
+            lib().mc_destroy(self.h)
+        self.h = None
+
+    def set_tuning(self, name: str, value: int):
+        if lib().mc_set_tuning(self.h, name.encode(), value) < 0:
+            raise McError(lib().mc_last_error(self.h).decode())
+
+    def stats(self):
+        """[problems, cells of read 1's matrices, nanoseconds of the kernels, sub-batches] since the context was made"""
+        st = np.zeros(4, dtype=np.uint64)
+        lib().mc_align_stats(self.h, st.ctypes.data_as(C.c_void_p))
+        return list(map(int, st))
+
+    def align_packed(self, rc, ro, sc, so, mc=None, mo=None):
+        """packed arrays in (uint8 characters, uint64 offsets), arrays out: raw[n, 4] int32 = read 1 forward, reverse, mate forward,
+        reverse; reversed[n] uint8; aligned characters and their n + 1 offsets (first half of a problem's range: the read)"""
+        n = len(ro) - 1
+        raw = np.zeros((4, max(n, 1)), dtype=np.int32)
+        rev = np.zeros(max(n, 1), dtype=np.uint8)
+        lq = (ro[1:] - ro[:-1]).astype(np.int64); ls = (so[1:] - so[:-1]).astype(np.int64)
+        cap = int(2 * np.maximum(1, lq + ls).sum()) if n else 0
+        aligned = np.zeros(cap + 1, dtype=np.uint8)
+        aoff = np.zeros(n + 1, dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        r = lib().mc_align_semiglobal(self.h, p(rc), p(ro), p(mc), p(mo), p(sc), p(so), n, p(raw[0]), p(raw[1]), p(raw[2]), p(raw[3]), p(rev), p(aligned), cap, p(aoff))
+        if r < 0:
+            raise McError(f"mc_align_semiglobal -> {r}: {lib().mc_last_error(self.h).decode()}")
+        return raw[:, :n].T.copy(), rev[:n], aligned, aoff
+
+    def align(self, reads, subjects, mates=None):
+        if len(reads) != len(subjects) or (mates is not None and len(mates) != len(reads)):
+            raise ValueError("align_semiglobal: one subject (and mate) per read")
+        rc, ro = _packed(reads); sc, so = _packed(subjects)
+        mc, mo = _packed([m if m is not None else b"" for m in mates]) if mates is not None else (None, None)
+        raw, rev, aligned, aoff = self.align_packed(rc, ro, sc, so, mc, mo)
+        out = []
+        buf = aligned.tobytes()
+        for i in range(len(reads)):
+            a, b = int(aoff[i]), int(aoff[i + 1])
+            h = (b - a) // 2
+            out.append((int(raw[i, 1] if rev[i] else raw[i, 0]), bool(rev[i]), buf[a:a + h], buf[a + h:b]))
+        return out, raw
+
+
+def align_semiglobal(reads, subjects, mates=None, handle=None, scratch_mb=None):
+    """Semi-global alignment of reads[i] (with mates[i], if given) to subjects[i] on the GPU, as `query -align` shows it.
+    -> ([(score, reversed, aligned_query, aligned_target)], raw[n, 4] int32: read 1 forward, reverse, mate forward, reverse)"""
+    A = Aligner(handle)
+    try:
+        if scratch_mb is not None:
+            A.set_tuning("align_scratch_mb", int(scratch_mb))
+        return A.align(reads, subjects, mates)
+    finally:
+        A.close()

@@ -135,6 +135,10 @@ uint64_t cut_batch_to_target_range(const mc_ctx* ctx, uint8_t* sizes, uint8_t* v
 // error text for failures that have no context yet (mc_last_error(NULL))
 void set_global_error(const std::string& msg);
 
+// align.hip: the device workspaces of mc_align_semiglobal callers (one per caller at a time), freed with the context
+struct AlignWork;
+void free_align_works(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -209,6 +213,12 @@ struct mc_ctx {
 
     uint64_t loadStats[4] = {0, 0, 0, 0};  // mc_load_stats: bytes read from the database files, nanoseconds of the load, of its index pass, the feeder waited for the readers
     uint64_t ownerStats[4] = {0, 0, 0, 0}; // mc_owner_stats: reads, reads on the filtered path, numbers received, locations decoded for the sort
+
+    // mc_align_semiglobal (align.hip): workspaces nobody is using, the sub-batch budget (mc_set_tuning "align_scratch_mb"), mc_align_stats
+    std::mutex alignMtx;
+    std::vector<mcamd::AlignWork*> alignWorks;
+    int64_t alignScratchMb = 512;
+    std::atomic<uint64_t> alignProblems{0}, alignCells{0}, alignKernelNs{0}, alignSubBatches{0};
 
     // timing
     bool timing = false;

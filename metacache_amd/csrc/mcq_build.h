@@ -496,7 +496,7 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
                     std::cerr << "Warning: duplicate sequence id! '" << seqId << "' already in database - '" << filename << "/" << r
                               << "' inserted as '" << sid << "'\n";
                 name2tgt.emplace(sid, tgt);
-                Taxon t; t.id = -(int64_t)tgt - 1; t.parent = parent; t.rank = 0; t.name = sid;
+                Taxon t; t.id = -(int64_t)tgt - 1; t.parent = parent; t.rank = 0; t.name = sid; t.srcFile = filename; t.srcIndex = r;
                 mc_build_target_windows(db.bs[0], tgt, &t.windows);
                 db.targets.push_back(std::move(t));
                 if (o.info == BuildOptions::verbose) {

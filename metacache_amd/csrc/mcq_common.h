@@ -67,7 +67,8 @@ inline int rank_from_dump_name(std::string n)
     return kNumRanks;
 }
 
-struct Taxon { int64_t id = 0, parent = 0; int rank = kNumRanks; std::string name; uint64_t windows = 0; };
+struct Taxon { int64_t id = 0, parent = 0; int rank = kNumRanks; std::string name; uint64_t windows = 0;
+               std::string srcFile; uint64_t srcIndex = 0; };   // targets: the file the sequence came from, its record number there (0-based)
 using Lineage = std::array<uint32_t, kNumRanks>;     // taxon index + 1, 0 = none
 
 struct Taxonomy {

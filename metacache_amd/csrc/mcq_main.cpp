@@ -19,7 +19,7 @@
 //   -taxids -taxids-only -omit-ranks -separate-cols -separator -comment -lineage -pairfiles -pairseq -insertsize -min-readlen
 //   -max-readlen -query-limit -sketchlen -winlen -winstride -max-locations-per-feature -remove-overpopulated-features -max-load-fac
 //   -no-query-params -no-summary -no-err -threads -batch-size -abundances [file] -abundance-per <rank> -hits-per-ref [file]
-//   -ground-truth -precision -taxon-coverage -cov-percentile.  Not offered: -align.
+//   -ground-truth -precision -taxon-coverage -cov-percentile -align (alignment on the device: mc_align_semiglobal).
 #include "mcq_build.h"
 
 #include <fcntl.h>
@@ -60,6 +60,7 @@ struct Options {
     int64_t queryLimit = std::numeric_limits<int64_t>::max();
     bool hitsPerRef = false, abundances = false;
     bool showGroundTruth = false, determineGroundTruth = false, precision = false, taxonCoverage = false;
+    bool align = false;                  // -align: the read against its best candidate's range of the target record (classification.cpp:384-426)
     int abundancePer = kNumRanks;                    // none
     std::string targetsFile, abundanceFile;
 };
@@ -100,6 +101,7 @@ Options parse(const std::vector<std::string>& args, Options o)
         else if (a == "-allhits" || a == "-all-hits") o.allhits = true;
         else if (a == "-locations") { o.locations = true; o.tophits = true; }
         else if (a == "-queryids" || a == "-query-ids") o.queryIds = true;
+        else if (a == "-align" || a == "-alignment") o.align = true;
         else if (a == "-ground-truth") { o.determineGroundTruth = true; o.showGroundTruth = true; }
         else if (a == "-precision") { o.precision = true; o.determineGroundTruth = true; }
         else if (a == "-taxon-coverage") { o.taxonCoverage = true; o.precision = true; o.determineGroundTruth = true; }
@@ -392,7 +394,9 @@ void read_taxa(mc_ctx* ctx, Taxonomy& tx)                                  // th
         uint32_t rk; const char* nm;
         mc_db_taxon(ctx, i, &tx.taxa[i].id, &tx.taxa[i].parent, &rk, &nm);
         tx.taxa[i].rank = int(rk); tx.taxa[i].name = nm;
-        mc_db_taxon_source(ctx, i, nullptr, nullptr, &tx.taxa[i].windows);
+        const char* src = nullptr;
+        mc_db_taxon_source(ctx, i, &src, &tx.taxa[i].srcIndex, &tx.taxa[i].windows);
+        if (src) tx.taxa[i].srcFile = src;
     }
 }
 
@@ -534,6 +538,12 @@ struct Tally {
     uint64_t total() const { return classified() + unclassified(); }
 };
 
+// -align: where a batch's text gets alignment lines (behind a mapping line's taxon text, before its '\n'), for which query of the
+// batch, against which candidate; the Aligner below turns these into problems for the device and into lines
+struct AlignWant { size_t at, q; Cand c; };
+inline size_t out_pos(const FastOut& o) { return o.s.size(); }
+inline size_t out_pos(std::ostringstream& o) { return (size_t)o.tellp(); }
+
 // ---- one query: classification, statistics, mapping line (classify_and_evaluate, classification.cpp:470-559) ------------------------
 struct MappingWriter {
     const Options& o; const Taxonomy& tx; const uint32_t stride, winlen;
@@ -542,9 +552,10 @@ struct MappingWriter {
     // the text show_taxon writes for a classification (taxon, or target for sequence-level results): the same few thousand over and
     // over -- its lineage walk (hash lookups up the taxonomy, taxonomy.hpp:576-597) is done once per worker and taxon
     std::unordered_map<uint64_t, std::string> taxText = {};
+    std::vector<AlignWant>* wants = nullptr;    // -align: the printed lines of classified reads ask for their alignment here
 
     template <class OS>
-    void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits)
+    void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits, size_t q = 0)
     {
         bool isTarget; uint32_t tgt;
         const uint32_t best = classify(o, tx, cands, isTarget, tgt);
@@ -602,6 +613,7 @@ struct MappingWriter {
             }
             out << it->second;
         }
+        if (wants && best && !cands.empty()) wants->push_back(AlignWant{out_pos(out), q, cands[0]});   // show_query_mapping, classification.cpp:521-523
         out << '\n';
     }
 };
@@ -619,7 +631,7 @@ void run_workers(unsigned n, Fn&& fn)
 // ---- the batches: runs of consecutive queries of one file (pair of files), ids continuing across files -----------------------------
 // Batches are produced while the workers already run: plain files are indexed chunk by chunk (SeqFile::stream_*), and a batch goes out
 // as soon as its records are known -- the first one after a few megabytes instead of after the whole file.
-struct Deferred { uint64_t id; View header; std::vector<Cand> cands; };
+struct Deferred { uint64_t id; View header; std::vector<Cand> cands; size_t q; };   // (q: the query's place in its batch, BatchQueue::read)
 struct Batch {
     size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast;
     std::vector<Deferred> deferred;                                         // -cov-percentile: its reads' candidates
@@ -774,6 +786,103 @@ struct BatchQueue {
     }
 };
 
+// ---- -align (show_alignment, classification.cpp:384-426) ---------------------------------------------------------------------------
+// The target records a run aligns to, by file name and record number: loaded through SeqFile on first use and kept for the run (the
+// reference opens the file again for every read); a file that cannot be read is remembered as such.
+struct TargetCache {
+    const bool showErrors;
+    std::mutex mu;
+    std::map<std::string, std::unique_ptr<SeqFile>> files;                  // (null: could not be read)
+    std::map<std::pair<std::string, uint64_t>, std::unique_ptr<std::string>> recs;   // (null: no such record)
+    explicit TargetCache(bool showErrors) : showErrors(showErrors) {}
+    const std::string* get(const std::string& file, uint64_t index)
+    {
+        std::lock_guard<std::mutex> l(mu);
+        const auto key = std::make_pair(file, index);
+        auto it = recs.find(key);
+        if (it != recs.end()) return it->second.get();
+        auto f = files.find(file);
+        if (f == files.end()) {
+            std::unique_ptr<SeqFile> sf;
+            try { sf.reset(new SeqFile(file)); sf->index(1); }
+            catch (std::exception& e) { if (showErrors) std::cerr << e.what() << '\n'; sf.reset(); }
+            f = files.emplace(file, std::move(sf)).first;
+        }
+        std::unique_ptr<std::string> rec;
+        if (f->second && index < f->second->records()) {
+            View h, sq; std::string scratch;
+            f->second->record((size_t)index, h, sq, scratch);
+            rec.reset(new std::string(sq.p, sq.n));
+        }
+        return recs.emplace(key, std::move(rec)).first->second.get();
+    }
+};
+
+// One batch's alignments: the lines that asked for one (MappingWriter::wants) become problems -- read 1, its mate, the candidate's window
+// range cut out of the target's record (make_view_from_window_range, classification.cpp:56-65) -- for ONE mc_align_semiglobal call, and
+// the three lines per read are put into the batch's text.  The target's record is number srcIndex of its file, counted from 0 as the
+// database stores it (the reference reads the record before it: DESIGN.md 7a).
+struct Aligner {
+    mc_ctx* const ctx; const Options& o; const Taxonomy& tx; TargetCache& cache; const BatchQueue& Q; const uint64_t stride, winlen;
+    std::vector<AlignWant> wants = {};
+    struct Job { size_t at; const Taxon* t; uint32_t beg, end; };
+    std::vector<Job> jobs = {};
+    std::string reads = {}, mates = {}, subjects = {}, aligned = {}, spliced = {};
+    std::vector<uint64_t> roff = {}, moff = {}, soff = {}, aoff = {};
+    std::vector<int32_t> sc[4] = {};
+    std::vector<uint8_t> rev = {};
+    Records rec = {};
+    bool noReads = false;       // -cov-percentile: the reference keeps id, header and candidates of a read for the pass after the coverage filter, not its
+                                // sequences (classification.cpp:790-799), and so aligns an EMPTY query there: score 0, one column of gaps.  Kept as it is.
+
+    // false: the device call failed (err)
+    bool finish(const Batch& B, std::string& text, std::string& err)
+    {
+        jobs.clear(); reads.clear(); mates.clear(); subjects.clear(); roff.assign(1, 0); moff.assign(1, 0); soff.assign(1, 0);
+        uint64_t cap = 0;
+        for (const AlignWant& w : wants) {
+            const Taxon* t = tx.taxon(w.c.tax);
+            if (!t || t->rank != 0) continue;                               // candidates above sequence level (-lowest): nothing to align to
+            const std::string* target = cache.get(t->srcFile, t->srcIndex);
+            if (!target) continue;
+            const uint64_t sb = std::min<uint64_t>(stride * w.c.beg, target->size()), se = std::max(sb, std::min<uint64_t>(stride * w.c.end + winlen, target->size()));
+            if (noReads) rec = Records{}; else Q.read(B, w.q, rec);
+            reads.append(rec.s1.p, rec.s1.n); roff.push_back(reads.size());
+            mates.append(rec.s2.p, rec.s2.n); moff.push_back(mates.size());
+            subjects.append(*target, (size_t)sb, (size_t)(se - sb)); soff.push_back(subjects.size());
+            cap += 2 * std::max<uint64_t>(1, rec.s1.n + (se - sb));
+            jobs.push_back(Job{w.at, t, w.c.beg, w.c.end});
+        }
+        wants.clear();
+        const size_t n = jobs.size();
+        if (n == 0) return true;
+        for (auto& v : sc) v.resize(n);
+        rev.resize(n); aoff.resize(n + 1); aligned.resize(cap);
+        if (mc_align_semiglobal(ctx, reads.data(), roff.data(), mates.empty() ? nullptr : mates.data(), moff.data(), subjects.data(), soff.data(), n,
+                                sc[0].data(), sc[1].data(), sc[2].data(), sc[3].data(), rev.data(), &aligned[0], cap, aoff.data()) != MC_OK) {
+            err = mc_last_error(ctx);
+            return false;
+        }
+        FastOut out;
+        out.s.swap(spliced); out.s.clear();
+        size_t from = 0;
+        for (size_t j = 0; j < n; ++j) {
+            const Job& J = jobs[j];
+            out.write(text.data() + from, (std::streamsize)(J.at - from)); from = J.at;
+            const uint64_t half = (aoff[j + 1] - aoff[j]) / 2;
+            out << '\n' << o.comment << "  score  " << (rev[j] ? sc[1][j] : sc[0][j]) << "  aligned to " << J.t->srcFile << " #" << J.t->srcIndex
+                << " in range [" << stride * J.beg << ',' << stride * J.end + stride << "]\n" << o.comment << "  query  ";
+            out.write(aligned.data() + aoff[j], (std::streamsize)half);
+            out << '\n' << o.comment << "  target ";
+            out.write(aligned.data() + aoff[j] + half, (std::streamsize)half);
+        }
+        out.write(text.data() + from, (std::streamsize)(text.size() - from));
+        text.swap(out.s);
+        spliced.swap(out.s);
+        return true;
+    }
+};
+
 // ---- the mapping lines of the batches, in batch order ---------------------------------------------------------------------------
 // Output file: the batches' texts go out in batch order, but not one after the other -- under the lock a finished batch only gets its
 // place in the file (the sizes of the batches before it are known then); the bytes are written by the worker that formatted them,
@@ -827,7 +936,7 @@ struct OrderedOut {
 };
 
 // ---- the device steps: a batch's queries in, their candidate lists out (emit(queries, results) once or more) ----------------------
-struct Query { uint64_t id; View header; bool empty; uint64_t len; };
+struct Query { uint64_t id; View header; bool empty; uint64_t len; size_t q; };   // (q: its place in the batch, BatchQueue::read)
 
 struct Profile {                                                            // MCQ_PROFILE: phase times on stderr (development aid)
     const bool on = std::getenv("MCQ_PROFILE") != nullptr;
@@ -864,7 +973,7 @@ struct SlotStep {
                     continue;
                 }
                 if (rc < 0) { Q.fail(mc_last_error(ctx)); return false; }
-                queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len});
+                queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len, q});
             }
             if (Q.failed()) return false;
             mc_results r;
@@ -902,7 +1011,7 @@ struct SetStep {
             const uint64_t id = Q.read(B, q, rec);
             const uint64_t len = (uint64_t)rec.s1.n + rec.s2.n;
             if (len + 8 > S.cfg.slot_max_chars) { std::cerr << "query batch is too small for a single read!\n"; continue; }
-            queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len});
+            queries.push_back(Query{id, rec.h1, rec.h1.empty() || rec.s1.empty(), len, q});
             seq1.append(rec.s1.p, rec.s1.n); off1.push_back(seq1.size());
             if (paired) { seq2.append(rec.s2.p, rec.s2.n); off2.push_back(seq2.size()); }
         }
@@ -928,7 +1037,7 @@ struct SetStep {
 // One worker: batches until none is left.  The device step classifies a batch's queries; here their candidates become lines in a buffer,
 // which goes to the ordered writer whole (a batch the job failed in is not written).
 template <class Step>
-void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step)
+void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* aligner = nullptr)
 {
     const Options& o = L.o;
     const bool unlimited = o.maxCand < 1;
@@ -947,11 +1056,15 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step)
                 if (o.allhits || unlimited) { hits = r.hits + r.hit_offsets[i]; nhits = r.hit_offsets[i + 1] - r.hit_offsets[i]; }
                 if (unlimited && cands.size() == r.max_candidates)          // list full: there may be more candidates than it holds
                     host_candidates(hits, nhits, max_windows(m.len, o.insertMax, L.stride), L.tx, o.lowest, cands);
-                if (L.deferred) B->deferred.push_back(Deferred{m.id, m.header, cands});
-                else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0);
+                if (L.deferred) B->deferred.push_back(Deferred{m.id, m.header, cands, m.q});
+                else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0, m.q);
             }
         });
         if (!done) break;
+        if (aligner && step.prints && !L.deferred) {                        // the batch's alignments: one device call, then the lines go into its text
+            std::string err;
+            if (!aligner->finish(*B, out.s, err)) { Q.fail(err); break; }
+        }
         if (step.prints && !W.deliver(b, std::move(out.s))) Q.fail("Could not write to file " + W.name);
     }
 }
@@ -970,6 +1083,7 @@ void show_query_params(std::ostream& os, const Options& o, unsigned threads)   /
     os << o.comment << "At maximum " << (o.maxCand < 1 ? std::numeric_limits<size_t>::max() : o.maxCand) << " classification candidates will be considered per query.\n";
     if (o.pairing == Options::files) os << o.comment << "File based paired-end mode:\n" << o.comment << "  Reads from two consecutive files will be interleaved.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
     else if (o.pairing == Options::sequences) os << o.comment << "Per file paired-end mode:\n" << o.comment << "  Reads from two consecutive sequences in each file will be paired up.\n" << o.comment << "  Max insert size considered " << o.insertMax << ".\n";
+    if (o.align) os << o.comment << "Query sequences will be aligned to best candidate target => SLOW!\n";
     if (o.hitsPerRef) os << o.comment << "A list of hits per reference sequence will be generated after the read mapping.\n";
     if (o.abundances) os << o.comment << "A list of absolute and relative abundances per taxon will be generated after the read mapping.\n";
     if (o.abundancePer != kNumRanks) os << o.comment << "A list of absolute and relative abundances for each '" << kRankNames[o.abundancePer] << "' will be generated after the read mapping.\n";
@@ -1007,7 +1121,7 @@ void show_mapping_header(std::ostream& os, const Options& o)               // sh
 // filter_targets_by_coverage (classification.cpp:591-634) then walks the global map in ITS iteration order, sums float coverages in that
 // order, std::sorts them and erases targets from the low end: the order of equal coverages and the rounding of the sums come from the
 // containers.  Same containers, same insertion sequence here (the reference's -threads 1 order), so the same targets go.
-void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L)
+void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L, Aligner* aligner = nullptr)
 {
     const Taxonomy& tx = L.tx;
     const size_t refBatch = o.refBatchSize ? o.refBatchSize : 4096;
@@ -1058,9 +1172,11 @@ void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<B
         for (const Deferred& d : B.deferred) {
             left.clear();
             for (const Cand& c : d.cands) if (tgtMatches.find(c.tgt) != tgtMatches.end()) left.push_back(c);
-            L(out, d.id, d.header, left, nullptr, 0);
+            L(out, d.id, d.header, left, nullptr, 0, d.q);
         }
-        os << out.str();
+        std::string text = out.str(), err;
+        if (aligner && !aligner->finish(B, text, err)) throw std::runtime_error(err);
+        os << text;
         out.str(std::string());
     }
     for (const auto& m : tgtMatches) L.tally.covers.insert(L.tally.covers.end(), m.second.begin(), m.second.end());
@@ -1227,7 +1343,14 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     BatchQueue Q(o, S.workers, t0);
     OrderedOut W(os, fout, outfile);
     std::vector<Tally> tallies(S.workers);
-    auto worker = [&](unsigned w, auto&& step) { MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]}; work(Q, W, L, step); };
+    TargetCache targets(o.showErrors);                                      // -align: the target records of this job
+    const bool aligning = o.align && !merged;
+    auto worker = [&](unsigned w, auto&& step) {
+        MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]};
+        Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
+        if (aligning && !covMode) L.wants = &A.wants;
+        work(Q, W, L, step, aligning ? &A : nullptr);
+    };
     Q.start();                                                              // (with part groups: the first pass streams behind the files' indexing)
     if (S.keyset) run_workers(S.workers, [&](unsigned w) { worker(w, SetStep{S, o, Q, false, true}); });
     else if (S.partset) {
@@ -1246,7 +1369,13 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
 
     Tally T;
     for (const Tally& t : tallies) T += t;
-    if (covMode) { MappingWriter L{o, tx, S.dbStride, S.dbWinlen, true, T}; classify_by_coverage(os, o, Q.batches, L); }
+    if (covMode) {
+        MappingWriter L{o, tx, S.dbStride, S.dbWinlen, true, T};
+        Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
+        A.noReads = true;
+        if (aligning) L.wants = &A.wants;
+        classify_by_coverage(os, o, Q.batches, L, aligning ? &A : nullptr);
+    }
     if (merged) {                                                           // map_candidates_to_targets, classification.cpp:891-911
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, false, T};
         std::ostringstream out;
