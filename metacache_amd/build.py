@@ -2,6 +2,7 @@
 
     libmetacache_amd.so   the product: HIP kernels (gfx950) + C-ABI host code   [hipcc]
     bin/mcq               `metacache query` command line above the C ABI         [g++]
+    libmckharness.so      tests/cpp/kernel_harness.hip: the tests' way to the launchers   [hipcc]
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the build container and on the GPU box.
 """
@@ -67,6 +68,7 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     build_synth(force=force, verbose=verbose)
     build_gather_peak(force=force, verbose=verbose)
     build_slot_driver(force=force, verbose=verbose)
+    build_kernel_harness(force=force, verbose=verbose)
     return LIB
 
 
@@ -123,6 +125,22 @@ def build_slot_driver(force: bool = False, verbose: bool = False) -> str:
             print("+", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     return SLOTDRV_LIB
+
+
+HARNESS_LIB = os.path.join(LIBDIR, "libmckharness.so")
+
+
+def build_kernel_harness(force: bool = False, verbose: bool = False) -> str:
+    """tests/cpp/kernel_harness.hip -> libmckharness.so: drives the sorted path's launchers (csrc/kernels.h) with inputs a test chooses
+    (test infrastructure, tests/kernel_harness.py; links the product library, adds nothing to it)"""
+    src = os.path.join(ROOT, "tests", "cpp", "kernel_harness.hip")
+    if force or _stale(HARNESS_LIB, [src, LIB, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "device_common.h")]):
+        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "-I", os.path.join(ROOT, "include"),
+               "-I", CSRC, "-Wno-unused-result", src, "-o", HARNESS_LIB, "-L", LIBDIR, "-lmetacache_amd", "-Wl,-rpath,$ORIGIN"]
+        if verbose:
+            print("+", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return HARNESS_LIB
 
 
 def build_cli(force: bool = False, verbose: bool = False) -> str:

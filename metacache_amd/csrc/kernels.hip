@@ -240,10 +240,11 @@ void launch_scan_u32(const uint32_t* in, uint32_t stride, uint32_t n, uint32_t* 
         hipLaunchKernelGGL(scan_small_kernel, dim3(1), dim3(kSmallScanBlock), 0, st, in, stride, n, out32, out64, hostTotal);
         return;
     }
-    struct TotalOut { uint64_t* host; uint64_t* out64; uint32_t n; hipStream_t st; ~TotalOut() { if (host && out64) launch_words_to_host(reinterpret_cast<uint32_t*>(host), reinterpret_cast<const uint32_t*>(out64 + n), 2, st); } } totalOut{hostTotal, out64, n, st};
     uint32_t nblocks = (n + kScanTile - 1) / kScanTile;
     if (nblocks == 0) nblocks = 1;
     uint64_t* sums = (uint64_t*)tmp;
+    // (the grand total is sums[nblocks] after scan_of_sums: a caller that wants only out32 gets its host total as well, as below kSmallScan)
+    struct TotalOut { uint64_t* host; const uint64_t* total; hipStream_t st; ~TotalOut() { if (host) launch_words_to_host(reinterpret_cast<uint32_t*>(host), reinterpret_cast<const uint32_t*>(total), 2, st); } } totalOut{hostTotal, sums + nblocks, st};
     hipLaunchKernelGGL(scan_block_sums, dim3(nblocks), dim3(kScanBlock), 0, st, in, stride, n, sums);
     hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(kScanBlock), 0, st, sums, nblocks);
     hipLaunchKernelGGL(scan_apply, dim3(nblocks), dim3(kScanBlock), 0, st, in, stride, n, sums, nblocks, out32, out64);
