@@ -447,6 +447,54 @@ int mc_align_semiglobal(mc_ctx* ctx, const char* reads, const uint64_t* read_off
  * kernels (HIP events around each sub-batch's launches), sub-batches */
 int mc_align_stats(const mc_ctx* ctx, uint64_t stats[4]);
 
+/* ---- classification: one taxon per read from its top candidates ---------------------------------
+ * The reference's ranked-LCA vote (classification.cpp:146-189; -hitmin, -hitdiff, -lowest, -highest) on the device, for candidate
+ * lists of any producer: mc_query_device (either pipe), mc_candidates_from_*, mc_merge_part_candidates, or -- with MC_CLASSIFY_HOST --
+ * the host arrays of mc_batch_wait, mc_partset_* and mc_keyset_*.  Needs the lineage table (mc_open_database reads it from the .meta
+ * file; mc_set_lineages otherwise); a slot's index in a lineage is the taxon's rank.
+ *   A read's list is cands[i * stride .. i * stride + stride) up to the first entry with hits == 0; an empty list is unclassified.
+ *   tax(c) = lineage slot 0 of c.tgt for lowest_rank 0, else its first non-zero slot at lowest_rank or above; a tgt beyond the
+ *   lineage table has a lineage of zeros.  No tax(cand[0]), or cand[0].hits < hits_min: unclassified.
+ *   threshold = cand[0].hits > hits_min ? (float)(cand[0].hits - hits_min) * hits_diff : 0.0f  (unsigned difference, one float
+ *   multiply); candidates 1, 2, ... vote as long as (float)hits > threshold, the first one that is not ends the vote.  hits_diff is the
+ *   FACTOR: the command line's rule "a value above 1 is a percentage" (options.cpp:1312) is the caller's.
+ *   Every voter moves the result up the top candidate's lineage: from the current rank r (at first the slot tax(cand[0]) came from) to the
+ *   first r' >= r where the top candidate's lineage is non-zero and equal to the voter's.  None, or r' > highest_rank: unclassified.
+ *   At the end r > highest_rank is unclassified as well; otherwise the read is assigned the top candidate's lineage slot r. */
+typedef struct {
+    uint32_t hits_min;               /* -hitmin */
+    float    hits_diff;              /* -hitdiff as a factor; finite, >= 0 */
+    int32_t  lowest_rank;            /* -lowest,  0 .. MC_NUM_RANKS - 1 */
+    int32_t  highest_rank;           /* -highest, lowest_rank .. MC_NUM_RANKS - 1 */
+} mc_classify_options;
+void mc_classify_options_default(mc_classify_options* opt);      /* {0, 1.0f, 0, MC_NUM_RANKS - 1} */
+
+typedef struct {
+    uint32_t taxon;                  /* taxon index + 1 as in the lineage table; 0 = unclassified */
+    uint32_t info;                   /* bits 0-7: rank (MC_NUM_RANKS = unclassified); bits 8-15: voters = candidates that entered the vote,
+                                        the top one included (0 if unclassified; 255 stands for 255 and more) */
+} mc_assignment;
+
+#define MC_CLASSIFY_HOST  1          /* cands / out are HOST arrays: staged through device buffers of the context, the call returns when out is filled */
+#define MC_CLASSIFY_TALLY 2          /* add this call's reads to the context's tallies (mc_classify_tally) */
+/* out[i] = the assignment of read i.  Without MC_CLASSIFY_HOST cands and out are DEVICE pointers (8-byte aligned) and the call is
+ * asynchronous on 'stream' (a hipStream_t; NULL = the context's own): enqueued behind the call that made the candidates it needs no
+ * synchronisation in between.  out must not overlap cands.  Calls on different streams may run -- and tally -- at the same time.
+ * The lineage table goes to the device with the first call and again after a later mc_set_lineages (which also clears the tallies;
+ * no classification may be in flight then).
+ * MC_ERR_INVALID (checked first): NULL ctx or options, NULL arrays with num_queries > 0, stride == 0, a rank outside
+ * 0 .. MC_NUM_RANKS - 1, lowest_rank > highest_rank, hits_diff negative or not finite, unknown flags, out overlapping cands.
+ * num_queries == 0: MC_OK, nothing is done.  MC_ERR_STATE: a context without lineages, or without a device (mc_open_metadata). */
+int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* opt, const mc_candidate* cands, uint32_t num_queries,
+                           uint32_t stride, int flags, mc_assignment* out, void* stream);
+/* the tallies of all MC_CLASSIFY_TALLY calls since the last reset, exact 64-bit sums: assigned[r] = reads whose result has rank r
+ * (assigned[MC_NUM_RANKS] = unclassified reads); taxon_counts[x] = reads assigned to the taxon with lineage entry x (= taxon index + 1;
+ * what -abundances counts per taxon), of which the first min(capacity, *num_counts) are copied; *num_counts = 1 + the largest entry of
+ * the lineage table.  assigned, taxon_counts (with capacity 0) and num_counts may be NULL.  Waits for the context's own streams; a caller
+ * that classified on streams of its own synchronises them first.  reset != 0 clears the counters after they have been read. */
+int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t* taxon_counts, uint64_t capacity,
+                      uint64_t* num_counts, int reset);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with

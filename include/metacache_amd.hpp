@@ -135,12 +135,26 @@ public:
             s.first = tops_.data() + i * K; s.last = s.first + K;
             return s;
         }
-        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; }        // query_batch.cuh:255-259
+        // one taxon per query of this batch from its top candidates (after wait_for_results): the ranked-LCA vote of
+        // classification.cpp:146-189 on the device (mc_classify_candidates on the slot's host arrays); tally: the queries are added to
+        // the context's per-rank / per-taxon counts (mc_classify_tally).  Valid until the next classify() or clear().
+        span<mc_assignment> classify(const mc_classify_options& opt, bool tally = false)
+        {
+            assigned_.resize(res_.num_queries);
+            if (mc_classify_candidates(ctx_, &opt, res_.cands, res_.num_queries, res_.max_candidates,
+                                       MC_CLASSIFY_HOST | (tally ? MC_CLASSIFY_TALLY : 0), assigned_.data(), nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            span<mc_assignment> s;
+            s.first = assigned_.data(); s.last = s.first + assigned_.size();
+            return s;
+        }
+        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
         mc_ctx* ctx_ = nullptr; std::uint32_t slot_ = 0;
         mc_results res_{};
         std::vector<match_candidate> tops_;
+        std::vector<mc_assignment> assigned_;
     };
 
     query_batch(const database& db, unsigned numHostThreads) : ctx_(db.ctx_), hosts_(numHostThreads)

@@ -18,6 +18,8 @@ NUM_RANKS = 21
 cand_dtype = np.dtype([("tgt", "<u4"), ("hits", "<u4"), ("beg", "<u4"), ("end", "<u4")])
 loc_dtype = np.dtype([("win", "<u4"), ("tgt", "<u4")])
 qstat_dtype = np.dtype([("hits", "<u4"), ("nfeat", "<u4"), ("nfound", "<u4"), ("nsteps", "<u4")])
+assignment_dtype = np.dtype({"names": ["taxon", "rank", "voters"], "formats": ["<u4", "u1", "u1"], "offsets": [0, 4, 5], "itemsize": 8})   # mc_assignment, info split into its bytes
+CLASSIFY_HOST, CLASSIFY_TALLY = 1, 2
 
 
 class McConfig(C.Structure):
@@ -59,6 +61,23 @@ class McDevicePartialNumbersIn(C.Structure):
                 ("num_queries", C.c_uint32), ("num_sources", C.c_uint32)]
 
 
+class McClassifyOptions(C.Structure):
+    _fields_ = [("hits_min", C.c_uint32), ("hits_diff", C.c_float), ("lowest_rank", C.c_int32), ("highest_rank", C.c_int32)]
+
+
+def hitdiff_factor(hitdiff: float) -> float:
+    """-hitdiff as the command line reads it (options.cpp:1312): the value is kept as a float, one above 1 is a percentage --
+    times 0.01 in double, rounded back to float"""
+    v = np.float32(hitdiff)
+    if v > np.float32(1):
+        v = np.float32(np.float64(v) * 0.01)
+    return float(v)
+
+
+def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1) -> McClassifyOptions:
+    return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
+
+
 class McDeviceResults(C.Structure):
     _fields_ = [("cands", C.c_void_p), ("hit_counts", C.c_void_p), ("hit_offsets", C.c_void_p), ("hits", C.c_void_p),
                 ("features", C.c_void_p), ("win_offsets", C.c_void_p)]
@@ -73,7 +92,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_timing_enable", "mc_timing_reset", "mc_timing_get", "mc_last_batch_stats", "mc_set_tuning", "mc_copy_results_on",
            "mc_build_begin", "mc_build_add_target", "mc_build_add_target_src", "mc_build_add_target_device", "mc_build_flush", "mc_build_reserve",
            "mc_build_table_begin", "mc_build_table_add", "mc_build_table_end", "mc_build_set_parent", "mc_build_target_windows", "mc_build_remove_ambiguous", "mc_build_counts", "mc_build_add_existing_target", "mc_build_add_locations", "mc_build_finish", "mc_build_finish_shards", "mc_build_write_shards", "mc_build_write", "mc_build_write_begin", "mc_build_write_add", "mc_build_write_end", "mc_build_free", "mc_build_last_error",
-           "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats"]
+           "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats",
+           "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally"]
 
 _lib = None
 
@@ -131,6 +151,10 @@ def lib() -> C.CDLL:
         L.mc_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         L.mc_align_semiglobal.argtypes = [C.c_void_p] + [C.c_void_p] * 6 + [C.c_uint64] + [C.c_void_p] * 6 + [C.c_uint64, C.c_void_p]
         L.mc_align_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_classify_options_default.argtypes = [C.POINTER(McClassifyOptions)]
+        L.mc_classify_options_default.restype = None
+        L.mc_classify_candidates.argtypes = [C.c_void_p, C.POINTER(McClassifyOptions), C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.mc_classify_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -353,6 +377,46 @@ class Database:
         r = McDeviceResults()
         self._check(L.mc_candidates_from_partial_numbers(self.h, C.byref(h), lowest, C.byref(r), stream or None))
         return r
+
+    # ---- classification: one taxon per read (mc_classify_*) ----------------------------------------
+    def classify_device(self, cands_ptr: int, n: int, stride: int, *, hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0,
+                        highest: int = NUM_RANKS - 1, tally: bool = False, out_ptr: int, stream: int = 0):
+        """the ranked-LCA vote on candidate lists in device memory (cands_ptr: n x stride mc_candidate) -> n mc_assignment at out_ptr
+        (8 bytes each: assignment_dtype); asynchronous on `stream` (0 = the context's).  hitdiff as on the command line: above 1 = percent"""
+        o = classify_options(hitmin, hitdiff, lowest, highest)
+        self._check(lib().mc_classify_candidates(self.h, C.byref(o), cands_ptr or None, n, stride, CLASSIFY_TALLY if tally else 0,
+                                                 out_ptr or None, stream or None))
+
+    def classify_candidates(self, cands: np.ndarray, *, hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1,
+                            tally: bool = False) -> np.ndarray:
+        """the same on a host array cands[n, stride] (cand_dtype, e.g. what query() returns) -> assignment_dtype [n]: taxon (index + 1
+        as in lineages(), 0 = unclassified), rank (21 = unclassified), voters"""
+        cands = np.ascontiguousarray(cands, dtype=cand_dtype)
+        if cands.ndim != 2:
+            raise ValueError("classify_candidates: cands must be [n, stride]")
+        n, stride = cands.shape
+        out = np.zeros(n, dtype=assignment_dtype)
+        o = classify_options(hitmin, hitdiff, lowest, highest)
+        self._check(lib().mc_classify_candidates(self.h, C.byref(o), cands.ctypes.data if n else None, n, stride,
+                                                 CLASSIFY_HOST | (CLASSIFY_TALLY if tally else 0), out.ctypes.data if n else None, None))
+        return out
+
+    def classify(self, reads, mates=None, *, hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1,
+                 insert_max: int = 0, tally: bool = False) -> np.ndarray:
+        """query() followed by classify_candidates(): one assignment per read (pair)"""
+        cands, _, _ = self.query(reads, mates, lowest=lowest, insert_max=insert_max)
+        return self.classify_candidates(cands, hitmin=hitmin, hitdiff=hitdiff, lowest=lowest, highest=highest, tally=tally)
+
+    def tally(self, reset: bool = False):
+        """the counts of all classify calls with tally=True since the last reset -> (assigned[22] uint64: reads per result rank,
+        [21] = unclassified; taxon_counts uint64: reads per taxon, index = taxon index + 1)"""
+        L = lib()
+        num = C.c_uint64()
+        self._check(L.mc_classify_tally(self.h, None, None, 0, C.byref(num), 0))
+        assigned = np.zeros(NUM_RANKS + 1, dtype=np.uint64)
+        counts = np.zeros(num.value, dtype=np.uint64)
+        self._check(L.mc_classify_tally(self.h, assigned.ctypes.data, counts.ctypes.data, counts.size, None, int(reset)))
+        return assigned, counts
 
     def copy_results(self, dst_ptr: int, src_ptr: int, nbytes: int, to_host: bool = False, stream: int = 0, second_pipe: bool = False, from_host: bool = False):
         L = lib()

@@ -393,6 +393,7 @@ void mc_destroy(mc_ctx* ctx)
     if (ctx->buildHold) { big_cache_hold(-1); ctx->buildHold = false; }   // (a table build that was abandoned before mc_build_table_end)
     for (auto& p : ctx->parts) { if (p.dbuckets) (void)big_free(p.dbuckets); if (p.dvalues) (void)big_free(p.dvalues); if (p.ddirect) (void)big_free(p.ddirect); }
     free_align_works(ctx);
+    free_classify_state(ctx);
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);
@@ -767,6 +768,7 @@ int mc_set_lineages(mc_ctx* ctx, const uint32_t* lin, uint64_t numTargets)
     if (ctx->targetCount < numTargets) ctx->targetCount = numTargets;
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     ctx->taxkeyDev.clear();
+    ++ctx->lineageVersion;
     return MC_OK;
 }
 

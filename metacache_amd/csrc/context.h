@@ -139,6 +139,10 @@ void set_global_error(const std::string& msg);
 struct AlignWork;
 void free_align_works(mc_ctx* ctx);
 
+// classify.hip: the device copy of the lineage table, the tallies and the staging of mc_classify_* (made on first use), freed with the context
+struct ClassifyState;
+void free_classify_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -175,6 +179,9 @@ struct mc_ctx {
     std::vector<mcamd::Taxon> taxa;
     std::vector<uint32_t> lineages;        // [targets * 21], taxon index + 1
     std::map<int, uint32_t*> taxkeyDev;    // lowest_rank -> device array [targets]
+    uint64_t lineageVersion = 0;           // counts the mc_set_lineages calls: mc_classify_* copies the table to the device again when it has changed
+    std::mutex classifyMtx;
+    mcamd::ClassifyState* classify = nullptr;
 
     // workspace of mc_query_device / mc_candidates_from_hits callers (pipe0.stream == stream); every host batch slot has its own
     // Pipe, so that the H2D copy, the kernels and the D2H copy of different slots overlap on the device
