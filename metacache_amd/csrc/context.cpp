@@ -809,15 +809,48 @@ static int taxkey_for_rank(mc_ctx* ctx, int rank, const uint32_t** out)
 // ------------------------------------------------------------------------------------------------
 // the per-batch pipeline
 // ------------------------------------------------------------------------------------------------
+// the pinned words a batch's host round trips land in (Pipe::hTotal), made on the pipe's first use
+static int ensure_host_words(mc_ctx* ctx, Pipe& P) { if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128)); return MC_OK; }
+// a Workspace that carries the context's tuning (mc_set_tuning), no buffers yet
+static Workspace tuned_workspace(const mc_ctx* ctx)
+{
+    Workspace ws{};
+    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
+    return ws;
+}
+// the global window numbers of the compact store (mc_load_target_windows) for the kernels that decode them
+static void set_window_numbering(const mc_ctx* ctx, DeviceTable& tab)
+{
+    tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
+}
+// room for `entries` locations to be sorted: the lists, the sort's scratch (a second one only where a taxon key is sorted along)
+static int ensure_sort_space(mc_ctx* ctx, Pipe& P, uint64_t entries, const uint32_t* taxkey, Workspace& ws)
+{
+    int rc = MC_OK;
+    const size_t hb = (size_t)(entries + 1) * 8;
+    if ((rc = ensure(ctx, P.bHits, hb)) || (rc = ensure(ctx, P.bCscr, hb)) || (taxkey && (rc = ensure(ctx, P.bCscr2, hb)))) return rc;
+    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
+    return MC_OK;
+}
+// what every candidate call hands back: the pipe's candidates and hit counts, the sorted location lists where the call delivers them
+static void publish_results(mc_device_results* out, const Pipe& P, const Workspace& ws, bool withLists)
+{
+    out->cands = (const mc_candidate*)P.bCands.p; out->hit_counts = (const uint32_t*)P.bQstat.p;   // (QueryStat.hits: stride 4 words)
+    out->hit_offsets = withLists ? ws.hitOff : nullptr;
+    out->hits = withLists ? (const mc_location*)ws.hits : nullptr;
+    out->features = nullptr; out->win_offsets = nullptr;
+}
+
 // the sorted class of the filtered path: filtered lists the counting kernels do not take (long reads: thousands of numbers, wide window
 // ranges) are sorted -- one segmented sort over the pool -- and scanned (gw_sorted_cands_kernel); the filter kernels counted them.
 // The one place of the filtered path where the host looks at a device counter (how many such lists: the sort's segment count).
-static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, Workspace& ws, uint32_t K,
-                           const uint32_t* taxkey, uint64_t poolEntries, bool counterCopied, hipStream_t st)
+static int run_sorted_tail(mc_ctx* ctx, Pipe& P, BatchRun& r, bool counterCopied)
 {
     int rc = MC_OK;
-    const uint32_t n = b.n;
-    if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
+    Workspace& ws = r.ws;
+    const uint32_t n = r.b.n;
+    hipStream_t st = r.st;
+    if ((rc = ensure_host_words(ctx, P))) return rc;
     uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
     if (!counterCopied) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
     HIP_TRY(ctx, traced_sync(st));
@@ -831,7 +864,7 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
         }
     }
     if (!*nsorted) return MC_OK;
-    if ((rc = ensure(ctx, P.bBigPool2, poolEntries * 4))) return rc;
+    if ((rc = ensure(ctx, P.bBigPool2, r.poolEntries * 4))) return rc;
     ws.bigPool2 = (uint32_t*)P.bBigPool2.p;
     const uint32_t nseg = std::min(*nsorted, n);
     // the sorted class longest list first: the segmented sort (a block per segment) and the scan (a wave per list) take them in this order
@@ -839,7 +872,7 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
     if (launch_gw_order(kSideSorted, ws, n, nseg, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists: size query failed");
     if ((rc = ensure(ctx, P.bOrder, (size_t)3 * std::max<uint32_t>(n, 1) * 4 + ordBytes + 256))) return rc;
     size_t tmpBytes = 0;
-    if (launch_gw_segsort(nullptr, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, poolEntries, ws, n, nseg, ctx->gwBits, st) != 0)
+    if (launch_gw_segsort(nullptr, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, r.poolEntries, ws, n, nseg, ctx->gwBits, st) != 0)
         return fail(ctx, MC_ERR_HIP, "segmented sort: size query failed");
     if ((rc = ensure(ctx, P.bSortTmp, tmpBytes + 256))) return rc;
     {
@@ -849,112 +882,117 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const Sketc
             if (hipStreamCreateWithFlags(&P.sortSide.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&P.sortSide.fork, hipEventDisableTiming) != hipSuccess ||
                 hipEventCreateWithFlags(&P.sortSide.join, hipEventDisableTiming) != hipSuccess) P.sortSide = GwSortSide{};
         }
-        if (launch_gw_segsort(P.bSortTmp.p, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, poolEntries, ws, n, nseg, ctx->gwBits, st, &P.sortSide) != 0)
+        if (launch_gw_segsort(P.bSortTmp.p, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, r.poolEntries, ws, n, nseg, ctx->gwBits, st, &P.sortSide) != 0)
             return fail(ctx, MC_ERR_HIP, "segmented sort failed");
     }
-    { ScopedTimer t(ctx, "gw_sorted_cands", st); launch_big_cands(FilterStep::SortedCands, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    { ScopedTimer t(ctx, "gw_sorted_cands", st); launch_big_cands(FilterStep::SortedCands, r.b, r.sp, r.tab, ws, r.K, r.taxkey, r.cands, st); }
     return MC_OK;
 }
 
 // The filtered candidate path on the work list the probing kernels (or, on the owner side of Mode K, owner_entries_kernel) left
-// in kListFilter: filter -> counting -> [segmented sort -> scan of the sorted lists].  poolEntries: entries of ws.bigPool (slices + overflow).
+// in kListFilter: filter -> counting -> [segmented sort -> scan of the sorted lists].
+// second (8-byte store): reads beyond the first filter's reach take its second instance.
 // deferSorted: the sorted class is left to the caller (mc_query_finish runs run_sorted_tail).
-static int run_filtered_path(mc_ctx* ctx, Pipe& P, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, Workspace& ws, uint32_t K,
-                             const uint32_t* taxkey, bool compact, bool second, uint64_t poolEntries, hipStream_t st, bool deferSorted = false)
+static int run_filtered_path(mc_ctx* ctx, Pipe& P, BatchRun& r, bool second, bool deferSorted = false)
 {
-    // timers carry the kernels' own names, one kernel each: compact store gw_filter_count_kernel (or gw_filter_kernel with "gw_fuse" 0), gw_filter2,
-    // gw_compact (+ the ordering of the stream filter's reads), gw_filter_stream<fine>, gw_filter_stream (+ the second compaction),
-    // gw_count_kernel<9>, <10>, <11>; 8-byte store: big_*
-    { ScopedTimer t(ctx, compact ? (ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", st); launch_big_cands(FilterStep::Filter, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
+    // timers carry the kernels' own names, one kernel each (a bench line's dominant "kernel" must be one): compact store gw_filter_count_kernel
+    // (or gw_filter_kernel with "gw_fuse" 0), gw_filter2, gw_compact (+ the ordering of the stream filter's reads), gw_filter_stream<fine>,
+    // <mid>, gw_filter_stream (+ the second compaction), gw_count_kernel<9>, <10>, <11>; 8-byte store: big_*
     // (compact store: gw_filter_kernel itself may leave reads to the second kernel -- it counts them on the device, after the
     // host's look at the counters: always launched, returns at once with nothing to do)
-    if (compact) {                                             // (timers by kernel: a bench line's dominant "kernel" must be one)
-        { ScopedTimer t(ctx, "gw_filter2", st); launch_big_cands(FilterStep::PairFilter, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_compact", st); launch_big_cands(FilterStep::Compact, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream_fine", st); launch_big_cands(FilterStep::StreamFine, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream_mid", st); launch_big_cands(FilterStep::StreamMid, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "gw_filter_stream", st); launch_big_cands(FilterStep::Stream, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    } else if (second) { ScopedTimer t(ctx, "big_filter_2", st); launch_big_cands(FilterStep::BigFilter2, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    { ScopedTimer t(ctx, compact ? "gw_count" : "big_count", st); launch_big_cands(FilterStep::Count, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    if (compact) { ScopedTimer t(ctx, "gw_count_512", st); launch_big_cands(FilterStep::Count512, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    { ScopedTimer t(ctx, compact ? "gw_count_1024" : "big_count_2", st); launch_big_cands(FilterStep::Count1024, b, sp, tab, ws, K, taxkey, P.bCands.p, st); }
-    if (compact && !deferSorted) return run_sorted_tail(ctx, P, b, sp, tab, ws, K, taxkey, poolEntries, false, st);
+    const bool compact = r.compact, always = true, compactOnly = compact, wideSecond = !compact && second;   // when a step runs
+    const struct { FilterStep step; const char* timer; bool when; } steps[] = {
+        {FilterStep::Filter, compact ? (r.ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", always},
+        {FilterStep::PairFilter, "gw_filter2", compactOnly},
+        {FilterStep::Compact, "gw_compact", compactOnly},
+        {FilterStep::StreamFine, "gw_filter_stream_fine", compactOnly},
+        {FilterStep::StreamMid, "gw_filter_stream_mid", compactOnly},
+        {FilterStep::Stream, "gw_filter_stream", compactOnly},
+        {FilterStep::BigFilter2, "big_filter_2", wideSecond},
+        {FilterStep::Count, compact ? "gw_count" : "big_count", always},
+        {FilterStep::Count512, "gw_count_512", compactOnly},
+        {FilterStep::Count1024, compact ? "gw_count_1024" : "big_count_2", always},
+    };
+    for (const auto& s : steps)
+        if (s.when) { ScopedTimer t(ctx, s.timer, r.st); launch_big_cands(s.step, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st); }
+    if (compact && !deferSorted) return run_sorted_tail(ctx, P, r, false);
     return MC_OK;
 }
 
 // What the lane path did not finish goes through the exact wave kernels (long reads, duplicate hashes, reads the filtered path handed
 // back, -allhits, ...): sketch + probe unless done, segments for their location lists (the host sizes them: one round trip), sort + candidates.
-// sortedPool (small batches whose filtered path left its sorted class to this call): the host's look at that class's counter shares this
+// sortedIsMine (small batches whose filtered path left its sorted class to this call): the host's look at that class's counter shares this
 // call's one round trip -- the wave kernels' sketching and the scan go out first; in the rare batch that has sorted lists they run again
 // behind run_sorted_tail (query_kernel takes the reads still flagged for it: a second pass finds only what the sorted class handed back).
-static int run_wave_tail(mc_ctx* ctx, Pipe& P, const BatchView& b, const SketchParams& sp, const DeviceTable& tab, Workspace& ws, uint32_t K,
-                         const uint32_t* taxkey, bool fuse, bool skipWaveSketch, bool wantAllhits, bool wantPartial, bool wantNumbers, bool lanePath, hipStream_t st,
-                         const uint64_t* sortedPool = nullptr)
+static int run_wave_tail(mc_ctx* ctx, Pipe& P, BatchRun& r, bool sortedIsMine = false)
 {
     int rc = MC_OK;
+    Workspace& ws = r.ws;
+    const BatchView& b = r.b;
     const uint32_t n = b.n;
-    if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
+    hipStream_t st = r.st;
+    if ((rc = ensure_host_words(ctx, P))) return rc;
     auto sketch_and_scan = [&]() {
-        if (!skipWaveSketch) {
-            ScopedTimer t(ctx, "query_wave", st);
-            launch_query(b, sp, tab, fuse, wantAllhits, ws, K, P.bCands.p, st);
-        }
+        if (!r.skipWaveSketch) { ScopedTimer t(ctx, "query_wave", st); launch_query(b, r.sp, r.tab, r.fuse, r.wantAllhits, ws, r.K, r.cands, st); }
         ScopedTimer t(ctx, "scan", st);
         // (how many locations need a segment in HBM: the total goes to pinned host memory with the scan)
         launch_scan_u32(ws.hitScan, 1, n, nullptr, ws.hitOff, ws.scanTmp, st, P.hTotal);
     };
     sketch_and_scan();
     uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
-    if (sortedPool) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
+    if (sortedIsMine) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
     HIP_TRY(ctx, traced_sync(st));
-    if (sortedPool && *nsorted) {
-        if ((rc = run_sorted_tail(ctx, P, b, sp, tab, ws, K, taxkey, *sortedPool, true, st))) return rc;
+    if (sortedIsMine && *nsorted) {
+        if ((rc = run_sorted_tail(ctx, P, r, true))) return rc;
         sketch_and_scan();
         HIP_TRY(ctx, traced_sync(st));
     }
     const uint64_t totalHits = *P.hTotal;
-    const size_t hb = (size_t)(totalHits + 1) * 8;
-    if ((rc = ensure(ctx, P.bHits, hb))) return rc;
-    if ((rc = ensure(ctx, P.bCscr, hb))) return rc;
-    if (taxkey && (rc = ensure(ctx, P.bCscr2, hb))) return rc;
-    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
-    if (wantNumbers && ((rc = ensure(ctx, P.bNumbers, (size_t)(totalHits + 8) * 4)) || (rc = ensure(ctx, P.bCounts, (size_t)(n + 1) * 4)))) return rc;
-    if (wantPartial && lanePath && !wantNumbers) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, sp, tab, ws, nullptr, st); }
-    {
-        ScopedTimer t(ctx, "sort_candidates", st);
-        launch_sort_candidates(b, sp, tab, ws, taxkey, K, wantAllhits, P.bCands.p, st);
-    }
-    if (wantNumbers) {
+    if ((rc = ensure_sort_space(ctx, P, totalHits, r.taxkey, ws))) return rc;
+    if (r.wantNumbers && ((rc = ensure(ctx, P.bNumbers, (size_t)(totalHits + 8) * 4)) || (rc = ensure(ctx, P.bCounts, (size_t)(n + 1) * 4)))) return rc;
+    if (r.wantPartial && r.lanePath && !r.wantNumbers) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, r.sp, r.tab, ws, nullptr, st); }
+    { ScopedTimer t(ctx, "sort_candidates", st); launch_sort_candidates(b, r.sp, r.tab, ws, r.taxkey, r.K, r.wantAllhits, r.cands, st); }
+    if (r.wantNumbers) {
         // what the wave kernels left in ws.hits -> numbers, then the lane path's (and the chunk lanes') lists straight from the table
-        { ScopedTimer t(ctx, "pack_numbers", st); launch_pack_other_reads(b, tab, ws, (uint32_t*)P.bNumbers.p, (uint32_t*)P.bCounts.p, st); }
-        if (lanePath) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, sp, tab, ws, (uint32_t*)P.bNumbers.p, st); }
+        { ScopedTimer t(ctx, "pack_numbers", st); launch_pack_other_reads(b, r.tab, ws, (uint32_t*)P.bNumbers.p, (uint32_t*)P.bCounts.p, st); }
+        if (r.lanePath) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, r.sp, r.tab, ws, (uint32_t*)P.bNumbers.p, st); }
         P.numbersN = n; P.numbersTotal = totalHits;
     }
     return MC_OK;
 }
 
-static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, hipStream_t st);
-static int finish_on_pipe(mc_ctx* ctx, Pipe& P);
-
-int mc_query_device(mc_ctx* ctx, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
+// the rare classes of a batch whose main kernels mc_query_device(MC_DEFER_TAIL) enqueued: sorted lists, then the exact wave kernels
+static int finish_on_pipe(mc_ctx* ctx, Pipe& P)
 {
-    if (!ctx || !in || !out) return MC_ERR_INVALID;
-    flags &= ~mcamd::kQueryNoLongReads;                           // (internal: the caller of this entry point has not seen the reads)
-    if (flags & MC_SECOND_PIPE) {
-        if (!ctx->pipe1.stream) {
-            HIP_TRY(ctx, hipSetDevice(ctx->device));
-            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pipe1.stream, hipStreamNonBlocking));
-        }
-        return query_on_pipe(ctx, ctx->pipe1, in, lowestRank, flags, out, streamv ? (hipStream_t)streamv : ctx->pipe1.stream);
-    }
-    return query_on_pipe(ctx, ctx->pipe0, in, lowestRank, flags, out, streamv ? (hipStream_t)streamv : ctx->stream);
+    Pipe::Tail& tl = P.tail;
+    if (!tl.pending) return MC_OK;
+    tl.pending = false;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipEventSynchronize(tl.mainDone));
+    int rc = MC_OK;
+    tl.run.wantAllhits = false; tl.run.wantPartial = false; tl.run.wantNumbers = false; tl.run.lanePath = true;   // (only top candidates on the lane path are deferred)
+    if (tl.sortedPath && (rc = run_sorted_tail(ctx, P, tl.run, true))) return rc;
+    if ((rc = run_wave_tail(ctx, P, tl.run))) return rc;
+    HIP_TRY(ctx, hipGetLastError());
+    return MC_OK;
+}
+
+// A call takes pipe P: the device, pipe1's stream on its first use, the tail of a batch the caller deferred on P and never asked for (it
+// still owns the workspace this call is about to reuse), and the stream the call enqueues on -- the caller's, else the pipe's own
+static int enter_pipe(mc_ctx* ctx, Pipe& P, void* streamv, hipStream_t& st)
+{
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (&P == &ctx->pipe1 && !ctx->pipe1.stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pipe1.stream, hipStreamNonBlocking));
+    if (const int rc = finish_on_pipe(ctx, P)) return rc;
+    st = streamv ? (hipStream_t)streamv : P.stream;
+    return MC_OK;
 }
 
 // A pipe's buffers whose sizes follow from the batch's size (n queries, numChars characters) and the table's mean list length alone --
 // everything mc_query_device needs before its first host round trip.  mc_open_database calls this for every slot pipe WHILE the file
 // loads (reserve_slot_pipes): a hipMalloc of memory another process has just given back takes 100-200 ms per 600 MB, and eight pipes
 // growing their pools inside the first batches made the same `mcq query` run take 81 or 390 ms per 10^7 reads.
-struct PipeSizes { uint64_t maxWindows = 0, poolCap = 0, ovfCap = 0; size_t nfeat = 0; };
+struct PipeSizes { uint64_t poolCap = 0, ovfCap = 0; size_t nfeat = 0; };
 static int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool wantFeatures, bool lanePath, uint64_t locs, uint64_t keys, PipeSizes& out)
 {
     int rc = MC_OK;
@@ -992,59 +1030,11 @@ static int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool w
     if ((rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1)))) return rc;
     if ((rc = ensure(ctx, P.bStats, 64))) return rc;
     if ((rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate)))) return rc;
-    out.maxWindows = maxWindows; out.poolCap = poolCap; out.ovfCap = ovfCap; out.nfeat = nfeat;
+    out.poolCap = poolCap; out.ovfCap = ovfCap; out.nfeat = nfeat;
     return MC_OK;
 }
 
-// every slot pipe sized for a full slot of reads of the usual length (see size_pipe): called by mc_open_database from a thread of its own
-// once the table is announced; `locs` / `keys`: the part headers' counts
-}  // extern "C" (the loader's helper below has C++ linkage)
-int mcamd::reserve_slot_pipes(mc_ctx* ctx, uint64_t locs, uint64_t keys, bool waitForStores)
-{
-    if (!ctx || ctx->pipes.empty() || ctx->parts.empty()) return MC_OK;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MC_ERR_HIP;
-    t_quietErrors = true;                                        // (the loader thread owns ctx->err)
-    // The table comes first: a single-part table's location store is allocated when the index pass is through (announce_store /
-    // allocate_values), and on a device the table nearly fills the pipes must not have taken its memory by then.
-    for (; waitForStores;) {
-        if (ctx->loadSettled.load(std::memory_order_acquire)) break;
-        if (ctx->storesPlaced.load(std::memory_order_acquire) >= ctx->parts.size()) break;
-        std::this_thread::sleep_for(std::chrono::microseconds(500));
-    }
-    const SketchParams sp = ctx->querySketch;
-    const uint32_t K = ctx->cfg.max_candidates, n = ctx->coalesce ? ctx->coMaxQueries : ctx->cfg.slot_max_queries;   // (coalescer: a dispatcher's pipe takes a united batch)
-    const bool wantAll = ctx->cfg.copy_allhits != 0;
-    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && !wantAll && lane_candidates_supported(K);
-    // (a slot of short reads: 152 characters each -- a slot filled with longer reads has fewer of them and grows its buffers as before)
-    const uint64_t chars = std::min<uint64_t>(ctx->coalesce ? ctx->coMaxChars : ctx->cfg.slot_max_chars, (uint64_t)n * 152);
-    int rc = MC_OK;
-    for (Pipe* P : ctx->pipes) {
-        PipeSizes sz{};
-        if ((rc = size_pipe(ctx, *P, n, chars, false, lanePath, locs, keys, sz))) break;
-    }
-    t_quietErrors = false;
-    return rc;
-}
-// the same for the context's own two pipes (mc_query_device with and without MC_SECOND_PIPE): the part set driver sizes them for its batches
-// right after a part has loaded -- on the group loader's thread, beside the other parts' loads -- instead of inside the first batches
-int mcamd::reserve_query_pipes(mc_ctx* ctx, uint32_t n, uint64_t chars)
-{
-    if (!ctx || ctx->parts.empty() || !ctx->tableReady) return MC_OK;
-    if (hipSetDevice(ctx->device) != hipSuccess) return MC_ERR_HIP;
-    const SketchParams sp = ctx->querySketch;
-    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && lane_candidates_supported(ctx->cfg.max_candidates);
-    uint64_t locs = 0;
-    for (auto& p : ctx->parts) locs += p.locations;
-    if (!ctx->pipe1.stream && hipStreamCreateWithFlags(&ctx->pipe1.stream, hipStreamNonBlocking) != hipSuccess) return MC_ERR_HIP;
-    for (Pipe* P : {&ctx->pipe0, &ctx->pipe1}) {
-        PipeSizes sz{};
-        if (const int rc = size_pipe(ctx, *P, n, chars, false, lanePath, locs, ctx->parts[0].keysStored, sz)) return rc;
-    }
-    return MC_OK;
-}
-extern "C" {
-
-static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, hipStream_t st)
+static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
 {
     // MC_WANT_PARTIAL_HITS: the location lists as they are (unsorted), lane path allowed -- a key shard's side of Mode K; the queries the
     // lane path does not take go through the wave kernels as with MC_WANT_ALLHITS (their lists come out sorted, which is allowed)
@@ -1053,33 +1043,30 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
     const bool wantPartial = ((flags & MC_WANT_PARTIAL_HITS) != 0 || wantNumbers) && !(flags & MC_WANT_ALLHITS);
     const int wantAllhits = (flags & MC_WANT_ALLHITS) | (wantPartial ? 1 : 0);
     const bool wantFeatures = (flags & MC_WANT_FEATURES) != 0;
-    if (P.tail.pending) { int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a caller that never asked for the last batch's tail: run it, the workspace is reused now)
     if (!ctx->tableReady) return fail(ctx, MC_ERR_STATE, "no database loaded (every part needs mc_load_begin .. mc_load_end)");
     if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
     if (wantNumbers && (ctx->parts.size() != 1 || !ctx->parts[0].compact || !ctx->dGwBase))
         return fail(ctx, MC_ERR_UNSUPPORTED, "MC_WANT_PARTIAL_NUMBERS: the database has no global window numbers (compact location store)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = nullptr;
+    int rc = enter_pipe(ctx, P, streamv, st);
+    if (rc) return rc;
     const uint32_t n = in->num_queries;
     P.numbersN = 0xFFFFFFFFu;
     const SketchParams sp = ctx->querySketch;
     const uint32_t K = ctx->cfg.max_candidates;
     const uint32_t* taxkey = nullptr;
-    int rc = taxkey_for_rank(ctx, lowestRank, &taxkey);
-    if (rc) return rc;
+    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
 
     // the pipe's buffers that depend on the batch's size alone (size_pipe; mc_open_database reserves them beside the file load)
     const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && (!wantAllhits || wantPartial) && lane_candidates_supported(K);
-    const Part& T0 = ctx->parts[0];
+    const Part& T = ctx->parts[0];
     uint64_t locs = 0;
     for (auto& p : ctx->parts) locs += p.locations;
     PipeSizes sz{};
-    if ((rc = size_pipe(ctx, P, n, in->num_chars, wantFeatures, lanePath, locs, T0.keysStored, sz))) return rc;
-    const uint64_t maxWindows = sz.maxWindows, poolCap = sz.poolCap, ovfCap = sz.ovfCap;
-    const size_t nfeat = sz.nfeat;
-    (void)maxWindows;
+    if ((rc = size_pipe(ctx, P, n, in->num_chars, wantFeatures, lanePath, locs, T.keysStored, sz))) return rc;
 
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
+    BatchRun run{tuned_workspace(ctx)};                          // (filled on the way: its flags are known when the tails are reached)
+    Workspace& ws = run.ws;
     ws.winCount = (uint32_t*)P.bWinCount.p; ws.winOff = (uint32_t*)P.bWinOff.p;
     ws.features = (wantFeatures || lanePath) ? (uint32_t*)P.bFeatures.p : nullptr; ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = (uint64_t*)P.bPpay.p;
     ws.qstat = (QueryStat*)P.bQstat.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
@@ -1088,19 +1075,18 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
         ws.bigMin = ctx->bigMin;
         ws.partialLists = wantPartial ? 1u : 0u;
-        ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap; ws.bigOvfCap = (uint32_t)ovfCap;
+        ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)sz.poolCap; ws.bigOvfCap = (uint32_t)sz.ovfCap;
         ws.sliceFill = (uint32_t*)P.bSliceFill.p;
         ws.sideList = (uint32_t*)P.bSide.p;
         ws.chunkList = (flags & kQueryNoLongReads) ? nullptr : (uint2*)P.bChunkList.p;   // (null: no read is cut into chunks, the chunk launchers launch nothing)
     }
 
     BatchView b{in->seq, in->qinfo, in->max_win, in->max_win_uniform, n};
-    const Part& T = ctx->parts[0];
     const bool multiPart = ctx->parts.size() > 1;
     DeviceTable tab{T.dbuckets, T.dvalues, T.nbuckets, multiPart ? 0x00FFFFFFu : 0xFFFFFFFFu, T.maxProbe};
     if (T.compact) {
         tab.values = nullptr; tab.values32 = reinterpret_cast<const uint32_t*>(T.dvalues);
-        tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
+        set_window_numbering(ctx, tab);
     }
     tab.direct = T.ddirect;                                       // (the lane path's lookups; every other kernel goes through the buckets)
 
@@ -1114,8 +1100,9 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         }
     }
     const bool fuse = !wantAllhits && !taxkey;
+    run.b = b; run.sp = sp; run.tab = tab; run.K = K; run.taxkey = taxkey; run.cands = P.bCands.p; run.st = st; run.poolEntries = sz.poolCap + sz.ovfCap;
+    run.compact = T.compact; run.fuse = fuse; run.wantAllhits = wantAllhits != 0; run.wantPartial = wantPartial; run.wantNumbers = wantNumbers; run.lanePath = lanePath;
     bool waveWork = true;                                        // wave kernels needed (always without the lane path)
-    bool skipWaveSketch = false;                                 // ... their sketching and probing has run already
     bool sortedInTail = false;                                   // the filtered path's sorted class is run_wave_tail's to look at
     if (lanePath) {
         // short reads: one lane per query for sketching and candidates, cooperative probing in between
@@ -1137,7 +1124,7 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
             // a key shard's side of Mode K: only the features this shard owns are looked up (the others cannot be in its table)
             if (maskFeatures) {
                 ScopedTimer t(ctx, "mask_features", st);
-                launch_mask_foreign_features(ws.features, ws.winOff + n, sp.s, nfeat, ctx->cfg.key_shard_index, ctx->cfg.key_shard_count, st);
+                launch_mask_foreign_features(ws.features, ws.winOff + n, sp.s, sz.nfeat, ctx->cfg.key_shard_index, ctx->cfg.key_shard_count, st);
             }
             { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
             { ScopedTimer t(ctx, "probe_cands", st); launch_probe_cands(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
@@ -1150,7 +1137,7 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         uint32_t* hcnt = wantPartial ? none : all;
         // (MC_DEFER_TAIL: no look at the counters either -- everything is launched, the caller has another batch to enqueue)
         if (!wantPartial && n <= (1u << 20) && !(flags & MC_DEFER_TAIL)) {
-            if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
+            if ((rc = ensure_host_words(ctx, P))) return rc;
             hcnt = reinterpret_cast<uint32_t*>(P.hTotal + 1);
             launch_flag_count_host(ws, n, hcnt, st);
             HIP_TRY(ctx, traced_sync(st));
@@ -1186,58 +1173,40 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         // small batches: the sorted class's counter is looked at together with the wave tail's total (run_wave_tail: one round trip for both)
         sortedInTail = hcnt != all && !defer && T.compact && waveWork && (hcnt[kCntFilter] || waveDone);
         if (hcnt[kCntFilter] || waveDone) {
-            if ((rc = run_filtered_path(ctx, P, b, sp, tab, ws, K, taxkey, T.compact, hcnt[kCntSecond] != 0, poolCap + ovfCap, st, defer || sortedInTail))) return rc;
+            if ((rc = run_filtered_path(ctx, P, run, hcnt[kCntSecond] != 0, defer || sortedInTail))) return rc;
         }
-        skipWaveSketch = waveDone;
+        run.skipWaveSketch = waveDone;                           // (the wave kernels' sketching and probing has run already)
         if (defer) {
             Pipe::Tail& tl = P.tail;
-            if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
+            if ((rc = ensure_host_words(ctx, P))) return rc;
             if (!tl.mainDone) HIP_TRY(ctx, hipEventCreateWithFlags(&tl.mainDone, hipEventDisableTiming));
             tl.sortedPath = T.compact && (hcnt[kCntFilter] || waveDone);
             if (tl.sortedPath) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(P.hTotal + 9), ws.midCount + kCntSorted, 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(ctx, hipEventRecord(tl.mainDone, st));
-            tl.ws = ws; tl.b = b; tl.sp = sp; tl.tab = tab; tl.K = K; tl.taxkey = taxkey; tl.compact = T.compact; tl.fuse = fuse;
-            tl.skipWaveSketch = skipWaveSketch; tl.poolEntries = poolCap + ovfCap; tl.st = st;
+            tl.run = run;
             tl.pending = true;
             HIP_TRY(ctx, hipGetLastError());
             P.lastN = n;
-            out->cands = (const mc_candidate*)P.bCands.p;
-            out->hit_counts = (const uint32_t*)P.bQstat.p;
-            out->hit_offsets = nullptr; out->hits = nullptr;
-            out->features = ws.features;
-            out->win_offsets = ws.winOff;
+            publish_results(out, P, ws, false);
+            out->features = ws.features; out->win_offsets = ws.winOff;
             return MC_OK;
         }
     } else {
         HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ws.qflag, 1, n, st));     // every query: needs sketch + probe
     }
-    const uint64_t sortedPoolEntries = poolCap + ovfCap;
-    if (waveWork && (rc = run_wave_tail(ctx, P, b, sp, tab, ws, K, taxkey, fuse, skipWaveSketch, wantAllhits != 0, wantPartial, wantNumbers, lanePath, st,
-                                        sortedInTail ? &sortedPoolEntries : nullptr))) return rc;
+    if (waveWork && (rc = run_wave_tail(ctx, P, run, sortedInTail))) return rc;
     HIP_TRY(ctx, hipGetLastError());
     P.lastN = n;
-    out->cands = (const mc_candidate*)P.bCands.p;
-    out->hit_counts = (const uint32_t*)P.bQstat.p;       // QueryStat.hits: stride 4 words
-    out->hit_offsets = wantAllhits ? ws.hitOff : nullptr;
-    out->hits = wantAllhits ? (const mc_location*)ws.hits : nullptr;
-    out->features = ws.features;
-    out->win_offsets = ws.winOff;
+    publish_results(out, P, ws, wantAllhits != 0);
+    out->features = ws.features; out->win_offsets = ws.winOff;
     return MC_OK;
 }
 
-// the rare classes of a batch whose main kernels mc_query_device(MC_DEFER_TAIL) enqueued: sorted lists, then the exact wave kernels
-static int finish_on_pipe(mc_ctx* ctx, Pipe& P)
+int mc_query_device(mc_ctx* ctx, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
 {
-    Pipe::Tail& tl = P.tail;
-    if (!tl.pending) return MC_OK;
-    tl.pending = false;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(tl.mainDone));
-    int rc = MC_OK;
-    if (tl.sortedPath && (rc = run_sorted_tail(ctx, P, tl.b, tl.sp, tl.tab, tl.ws, tl.K, tl.taxkey, tl.poolEntries, true, tl.st))) return rc;
-    if ((rc = run_wave_tail(ctx, P, tl.b, tl.sp, tl.tab, tl.ws, tl.K, tl.taxkey, tl.fuse, tl.skipWaveSketch, false, false, false, true, tl.st))) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return MC_OK;
+    if (!ctx || !in || !out) return MC_ERR_INVALID;
+    flags &= ~mcamd::kQueryNoLongReads;                           // (internal: the caller of this entry point has not seen the reads)
+    return query_on_pipe(ctx, (flags & MC_SECOND_PIPE) ? ctx->pipe1 : ctx->pipe0, in, lowestRank, flags, out, streamv);
 }
 
 int mc_query_finish(mc_ctx* ctx, int flags)
@@ -1252,29 +1221,25 @@ int mc_candidates_from_hits(mc_ctx* ctx, const mc_device_hits* in, int lowestRan
 {
     if (!ctx || !in || !out || !in->hit_offsets) return MC_ERR_INVALID;
     if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     Pipe& P = ctx->pipe0;
-    if (P.tail.pending) { const int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a deferred tail still owns the workspace this call is about to reuse)
-    hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
+    hipStream_t st = nullptr;
+    int rc = enter_pipe(ctx, P, streamv, st);
+    if (rc) return rc;
     const uint32_t n = in->num_queries;
     const uint32_t K = ctx->cfg.max_candidates;
     const uint32_t* taxkey = nullptr;
-    int rc = taxkey_for_rank(ctx, lowestRank, &taxkey);
-    if (rc) return rc;
+    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
     uint64_t total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, in->hit_offsets + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));
-    const size_t hb = (size_t)(total + 1) * 8;
-    if ((rc = ensure(ctx, P.bHits, hb)) || (rc = ensure(ctx, P.bCscr, hb)) || (taxkey && (rc = ensure(ctx, P.bCscr2, hb)))) return rc;
+    Workspace ws = tuned_workspace(ctx);
+    if ((rc = ensure_sort_space(ctx, P, total, taxkey, ws))) return rc;
     if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) ||
         (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))))
         return rc;
     // the lists are sorted in place: work on a copy inside the context
     if (total) HIP_TRY(ctx, hipMemcpyAsync(P.bHits.p, in->hits, total * 8, hipMemcpyDeviceToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(P.bHitOff.p, in->hit_offsets, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, st));
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
-    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
     ws.hitOff = (uint64_t*)P.bHitOff.p; ws.qstat = (QueryStat*)P.bQstat.p;
     BatchView b{nullptr, nullptr, in->max_win, in->max_win_uniform, n};
     DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
@@ -1284,11 +1249,7 @@ int mc_candidates_from_hits(mc_ctx* ctx, const mc_device_hits* in, int lowestRan
     }
     HIP_TRY(ctx, hipGetLastError());
     P.lastN = 0;
-    out->cands = (const mc_candidate*)P.bCands.p;
-    out->hit_counts = (const uint32_t*)P.bQstat.p;
-    out->hit_offsets = ws.hitOff;
-    out->hits = (const mc_location*)ws.hits;
-    out->features = nullptr; out->win_offsets = nullptr;
+    publish_results(out, P, ws, true);
     return MC_OK;
 }
 
@@ -1297,17 +1258,16 @@ int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* i
 {
     if (!ctx || !in || !out || !in->counts || (!in->hits && in->total_hits) || in->num_sources < 1) return MC_ERR_INVALID;
     if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     Pipe& P = ctx->pipe0;
-    if (P.tail.pending) { const int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a deferred tail still owns the workspace this call is about to reuse)
-    hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
+    hipStream_t st = nullptr;
+    int rc = enter_pipe(ctx, P, streamv, st);
+    if (rc) return rc;
     const uint32_t n = in->num_queries, S = in->num_sources;
     const uint32_t K = ctx->cfg.max_candidates;
     const uint32_t* taxkey = nullptr;
-    int rc = taxkey_for_rank(ctx, lowestRank, &taxkey);
-    if (rc) return rc;
-    const size_t hb = (size_t)(in->total_hits + 1) * 8;
-    if ((rc = ensure(ctx, P.bHits, hb)) || (rc = ensure(ctx, P.bCscr, hb)) || (taxkey && (rc = ensure(ctx, P.bCscr2, hb)))) return rc;
+    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
+    Workspace ws = tuned_workspace(ctx);
+    if ((rc = ensure_sort_space(ctx, P, in->total_hits, taxkey, ws))) return rc;
     if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) ||
         (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))) ||
         (rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1))) ||
@@ -1321,9 +1281,6 @@ int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* i
     uint64_t* srcStart = (uint64_t*)P.bPpay.p;
     launch_union_partial(in->counts, S, n, reinterpret_cast<const uint64_t*>(in->hits), (uint32_t*)P.bScanIn.p, srcStart, (uint64_t*)P.bHitOff.p,
                          (uint64_t*)P.bHits.p, P.bScan.p, st);
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
-    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
     ws.hitOff = (uint64_t*)P.bHitOff.p; ws.qstat = (QueryStat*)P.bQstat.p;
     BatchView b{nullptr, nullptr, in->max_win, in->max_win_uniform, n};
     // Long united lists (RefSeq scale: 1 300 locations per read) take the filtered path of the replicated mode instead of a sort: the union
@@ -1350,11 +1307,7 @@ int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* i
     }
     HIP_TRY(ctx, hipGetLastError());
     P.lastN = 0;
-    out->cands = (const mc_candidate*)P.bCands.p;
-    out->hit_counts = (const uint32_t*)P.bQstat.p;
-    out->hit_offsets = ws.hitOff;
-    out->hits = (const mc_location*)ws.hits;
-    out->features = nullptr; out->win_offsets = nullptr;
+    publish_results(out, P, ws, true);
     return MC_OK;
 }
 
@@ -1367,11 +1320,11 @@ int mc_partial_numbers(mc_ctx* ctx, const mc_device_results* res, uint32_t n, co
     if (!res->hit_offsets) return fail(ctx, MC_ERR_STATE, "mc_partial_numbers: the results hold no location lists (MC_WANT_PARTIAL_HITS)");
     if (ctx->parts.size() != 1 || !ctx->parts[0].compact || !ctx->dGwBase)
         return fail(ctx, MC_ERR_UNSUPPORTED, "mc_partial_numbers: the database has no global window numbers (compact location store)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     // (the pipe whose batch these results are: a caller with two batches in flight -- keyset.cpp's lanes -- runs the shards' lookups on either)
     Pipe& P = (ctx->pipe1.bHitOff.p && res->hit_offsets == (const uint64_t*)ctx->pipe1.bHitOff.p) ? ctx->pipe1 : ctx->pipe0;
-    if (P.tail.pending) { const int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a deferred tail still owns the workspace this call is about to reuse)
-    hipStream_t st = streamv ? (hipStream_t)streamv : (&P == &ctx->pipe1 && ctx->pipe1.stream) ? ctx->pipe1.stream : ctx->stream;
+    hipStream_t st = nullptr;
+    int rc = enter_pipe(ctx, P, streamv, st);
+    if (rc) return rc;
     for (uint32_t i = 0; i < numCuts; ++i) {
         if (cutQueries[i] > n) return fail(ctx, MC_ERR_INVALID, "mc_partial_numbers: cut beyond the batch");
         HIP_TRY(ctx, hipMemcpyAsync(&cutOffsets[i], res->hit_offsets + cutQueries[i], 8, hipMemcpyDeviceToHost, st));
@@ -1379,13 +1332,12 @@ int mc_partial_numbers(mc_ctx* ctx, const mc_device_results* res, uint32_t n, co
     uint64_t total = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&total, res->hit_offsets + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));                    // the one host round trip of the exchange: its split sizes
-    int rc;
     if (P.numbersN == n && P.numbersTotal == total && res->hit_offsets == (const uint64_t*)P.bHitOff.p) {
         // mc_query_device(MC_WANT_PARTIAL_NUMBERS) left the numbers and the counts where they belong
     } else {
         if ((rc = ensure(ctx, P.bNumbers, (size_t)(total + 8) * 4)) || (rc = ensure(ctx, P.bCounts, (size_t)(n + 1) * 4))) return rc;
         DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-        tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
+        set_window_numbering(ctx, tab);
         {
             ScopedTimer t(ctx, "pack_numbers", st);
             launch_pack_numbers(reinterpret_cast<const uint64_t*>(res->hits), res->hit_offsets, total, n, tab, (uint32_t*)P.bNumbers.p, (uint32_t*)P.bCounts.p, st);
@@ -1416,14 +1368,12 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     if ((uint64_t)n * S > 0xFFFFFFF0ull) return fail(ctx, MC_ERR_UNSUPPORTED, "mc_candidates_from_partial_numbers: batch too large");
     const uint64_t totalIn = in->source_offsets[S];
     if (totalIn && !in->numbers) return MC_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if ((flags & MC_SECOND_PIPE) && !ctx->pipe1.stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pipe1.stream, hipStreamNonBlocking));
     Pipe& P = (flags & MC_SECOND_PIPE) ? ctx->pipe1 : ctx->pipe0;
-    if (P.tail.pending) { const int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a deferred tail still owns the workspace this call is about to reuse)
-    hipStream_t st = streamv ? (hipStream_t)streamv : (flags & MC_SECOND_PIPE) ? ctx->pipe1.stream : ctx->stream;
-    const uint32_t* taxkey = nullptr;
-    int rc = taxkey_for_rank(ctx, lowestRank, &taxkey);
+    hipStream_t st = nullptr;
+    int rc = enter_pipe(ctx, P, streamv, st);
     if (rc) return rc;
+    const uint32_t* taxkey = nullptr;
+    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
     const uint64_t avg = totalIn / std::max<uint32_t>(n, 1);
     const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(std::max<uint64_t>((uint64_t)n * 448, totalIn / 2),
                                                                                   (uint64_t)big_filter_grid(n, true, ctx->filterBpc) * 4 * std::min<uint64_t>(131072, std::max<uint64_t>(4096, avg))));
@@ -1436,8 +1386,8 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
         (rc = ensure(ctx, P.bSide, (size_t)kSideRows * std::max<uint32_t>(n, 1) * 4)) ||
         (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))))
         return rc;
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
+    BatchRun run{tuned_workspace(ctx)};
+    Workspace& ws = run.ws;
     ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = (uint64_t*)P.bPpay.p;
     uint64_t* srcStart = ws.ppay + (size_t)n * S + 2;                 // [S][n + 1] exclusive scans of the sources' counts
     ws.qstat = (QueryStat*)P.bQstat.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
@@ -1450,7 +1400,7 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     // the receive buffer stands in for the table's location store
     DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
     tab.values32 = in->numbers;
-    tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
+    set_window_numbering(ctx, tab);
     KeyshardBases bases{};
     for (uint32_t s = 0; s < S; ++s) bases.b[s] = in->source_offsets[s];
     HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
@@ -1459,26 +1409,23 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
         for (uint32_t s = 0; s < S; ++s) launch_scan_u32(in->counts + (size_t)s * n, 1, n, nullptr, srcStart + (size_t)s * (n + 1), ws.scanTmp, st);
         launch_owner_entries(b, tab, ws, in->counts, srcStart, bases, S, st);
     }
-    const SketchParams one{16, 1, 16, 1};
-    if ((rc = run_filtered_path(ctx, P, b, one, tab, ws, K, taxkey, true, true, poolCap + ovfCap, st))) return rc;
+    run.b = b; run.sp = SketchParams{16, 1, 16, 1}; run.tab = tab; run.K = K; run.taxkey = taxkey; run.cands = P.bCands.p; run.st = st;
+    run.poolEntries = poolCap + ovfCap; run.compact = true;
+    if ((rc = run_filtered_path(ctx, P, run, true))) return rc;
     // what is left (short lists, reads the filtered path handed back): decoded to (target, window) lists and sorted
     launch_scan_u32(ws.hitScan, 1, n, nullptr, ws.hitOff, ws.scanTmp, st);
-    if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128));
+    if ((rc = ensure_host_words(ctx, P))) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(P.hTotal, ws.hitOff + n, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(P.hTotal + 10, ws.midCount + kCntFilter, 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));
     ctx->ownerStats[0] += n; ctx->ownerStats[1] += *reinterpret_cast<const uint32_t*>(P.hTotal + 10); ctx->ownerStats[2] += totalIn; ctx->ownerStats[3] += *P.hTotal;
-    const size_t hb = (size_t)(*P.hTotal + 1) * 8;
-    if ((rc = ensure(ctx, P.bHits, hb)) || (rc = ensure(ctx, P.bCscr, hb)) || (taxkey && (rc = ensure(ctx, P.bCscr2, hb)))) return rc;
-    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
+    if ((rc = ensure_sort_space(ctx, P, *P.hTotal, taxkey, ws))) return rc;
     { ScopedTimer t(ctx, "decode_union", st); launch_decode_union(b, tab, ws, in->counts, srcStart, bases, S, st); }
     DeviceTable none{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
     { ScopedTimer t(ctx, "cands_from_hits", st); launch_cands_from_hits(b, none, ws, taxkey, K, P.bCands.p, st); }
     HIP_TRY(ctx, hipGetLastError());
     P.lastN = 0;
-    out->cands = (const mc_candidate*)P.bCands.p;
-    out->hit_counts = (const uint32_t*)P.bQstat.p;
-    out->hit_offsets = nullptr; out->hits = nullptr; out->features = nullptr; out->win_offsets = nullptr;
+    publish_results(out, P, ws, false);
     return MC_OK;
 }
 
@@ -1582,13 +1529,12 @@ int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, 
 int mc_last_batch_stats(mc_ctx* ctx, uint64_t stats[8])
 {
     if (!ctx) return MC_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
     std::memset(stats, 0, 64);
     Pipe& P = ctx->pipe0;
-    if (P.tail.pending) { const int rcf = finish_on_pipe(ctx, P); if (rcf) return rcf; }   // (a deferred tail still owns the workspace this call is about to reuse)
+    hipStream_t st = nullptr;
+    if (const int rc = enter_pipe(ctx, P, nullptr, st)) return rc;
     if (!P.bStats.p || !P.bQstat.p) return MC_OK;
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
+    Workspace ws = tuned_workspace(ctx);
     ws.qstat = (QueryStat*)P.bQstat.p; ws.winOff = (uint32_t*)P.bWinOff.p; ws.stats = (uint64_t*)P.bStats.p;
     if (P.bMid.p) { ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords); }
     launch_batch_stats(ws, P.lastN, ctx->stream);
@@ -1766,8 +1712,6 @@ static void co_take(mc_ctx* ctx, std::vector<uint32_t>& mine, int& lowest)
     }
     ctx->coBatches++; ctx->coSlots += mine.size();
 }
-static void co_run(mc_ctx* ctx, mcamd::CoDispatcher* D, const std::vector<uint32_t>& mine, int lowest);
-
 static void co_dispatch(mc_ctx* ctx, mcamd::CoDispatcher*)
 {
     (void)hipSetDevice(ctx->device);
@@ -1944,3 +1888,49 @@ int mc_batch_clear(mc_ctx* ctx, uint32_t slot)
 }
 
 }  // extern "C"
+
+// every slot pipe sized for a full slot of reads of the usual length (see size_pipe): called by mc_open_database from a thread of its own
+// once the table is announced; `locs` / `keys`: the part headers' counts
+int mcamd::reserve_slot_pipes(mc_ctx* ctx, uint64_t locs, uint64_t keys, bool waitForStores)
+{
+    if (!ctx || ctx->pipes.empty() || ctx->parts.empty()) return MC_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess) return MC_ERR_HIP;
+    t_quietErrors = true;                                        // (the loader thread owns ctx->err)
+    // The table comes first: a single-part table's location store is allocated when the index pass is through (announce_store /
+    // allocate_values), and on a device the table nearly fills the pipes must not have taken its memory by then.
+    for (; waitForStores;) {
+        if (ctx->loadSettled.load(std::memory_order_acquire)) break;
+        if (ctx->storesPlaced.load(std::memory_order_acquire) >= ctx->parts.size()) break;
+        std::this_thread::sleep_for(std::chrono::microseconds(500));
+    }
+    const SketchParams sp = ctx->querySketch;
+    const uint32_t K = ctx->cfg.max_candidates, n = ctx->coalesce ? ctx->coMaxQueries : ctx->cfg.slot_max_queries;   // (coalescer: a dispatcher's pipe takes a united batch)
+    const bool wantAll = ctx->cfg.copy_allhits != 0;
+    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && !wantAll && lane_candidates_supported(K);
+    // (a slot of short reads: 152 characters each -- a slot filled with longer reads has fewer of them and grows its buffers as before)
+    const uint64_t chars = std::min<uint64_t>(ctx->coalesce ? ctx->coMaxChars : ctx->cfg.slot_max_chars, (uint64_t)n * 152);
+    int rc = MC_OK;
+    for (Pipe* P : ctx->pipes) {
+        PipeSizes sz{};
+        if ((rc = size_pipe(ctx, *P, n, chars, false, lanePath, locs, keys, sz))) break;
+    }
+    t_quietErrors = false;
+    return rc;
+}
+// the same for the context's own two pipes (mc_query_device with and without MC_SECOND_PIPE): the part set driver sizes them for its batches
+// right after a part has loaded -- on the group loader's thread, beside the other parts' loads -- instead of inside the first batches
+int mcamd::reserve_query_pipes(mc_ctx* ctx, uint32_t n, uint64_t chars)
+{
+    if (!ctx || ctx->parts.empty() || !ctx->tableReady) return MC_OK;
+    const SketchParams sp = ctx->querySketch;
+    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && lane_candidates_supported(ctx->cfg.max_candidates);
+    uint64_t locs = 0;
+    for (auto& p : ctx->parts) locs += p.locations;
+    for (Pipe* P : {&ctx->pipe0, &ctx->pipe1}) {
+        PipeSizes sz{};
+        hipStream_t st = nullptr;
+        if (const int rc = enter_pipe(ctx, *P, nullptr, st)) return rc;
+        if (const int rc = size_pipe(ctx, *P, n, chars, false, lanePath, locs, ctx->parts[0].keysStored, sz)) return rc;
+    }
+    return MC_OK;
+}

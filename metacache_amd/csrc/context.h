@@ -20,6 +20,15 @@ struct DevBuf {                 // grow-only device allocation
     size_t cap = 0;
 };
 
+struct BatchRun {               // the state of ONE batch on a pipe: what run_sorted_tail / run_filtered_path / run_wave_tail (context.cpp) work on
+    Workspace ws{}; BatchView b{}; SketchParams sp{}; DeviceTable tab{};
+    uint32_t K = 0; const uint32_t* taxkey = nullptr;
+    void* cands = nullptr;          // the pipe's candidate buffer
+    hipStream_t st = nullptr;
+    uint64_t poolEntries = 0;       // entries of ws.bigPool (slices + overflow)
+    bool compact = false, fuse = false, skipWaveSketch = false, wantAllhits = false, wantPartial = false, wantNumbers = false, lanePath = false;
+};
+
 struct Pipe {                   // the device workspace of ONE batch in flight + the stream its work is enqueued on
     GwSortSide sortSide;            // second stream + fork / join events of the sorted path (created on first use)
     hipStream_t stream = nullptr;
@@ -33,13 +42,9 @@ struct Pipe {                   // the device workspace of ONE batch in flight +
     // MC_DEFER_TAIL: the batch's main kernels are enqueued, the rare classes (sorted lists, what is left for the exact wave kernels) wait
     // for mc_query_finish -- the host looks at their counters THEN, while the device is busy with the other pipe's batch
     struct Tail {
-        bool pending = false;
-        Workspace ws{}; BatchView b{}; SketchParams sp{}; DeviceTable tab{};
-        uint32_t K = 0; const uint32_t* taxkey = nullptr;
-        bool compact = false, sortedPath = false, fuse = false, skipWaveSketch = false;
-        uint64_t poolEntries = 0;
-        hipStream_t st = nullptr;
+        bool pending = false, sortedPath = false;
         hipEvent_t mainDone = nullptr;   // recorded behind the main kernels and the copy of the sorted-class counter
+        BatchRun run;                    // the batch as mc_query_device left it
     } tail;
 };
 
