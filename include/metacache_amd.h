@@ -495,12 +495,66 @@ int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* opt, const mc
 int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t* taxon_counts, uint64_t capacity,
                       uint64_t* num_counts, int reset);
 
+/* ---- target coverage: the two-pass classification of -cov-percentile ------------------------------
+ * The reference (map_queries_to_targets_default, classification.cpp:747-838) keeps every read's candidates, collects per target the
+ * windows that qualifying candidates cover (matches_per_target::insert, matches_per_target.hpp:100-127), removes the targets at the
+ * low end of the coverage distribution (filter_targets_by_coverage, classification.cpp:591-634) and classifies every read again from
+ * the candidates that are left (update_candidates, :660-671).  Here the covered windows of ALL targets are one bitmap in the context:
+ * target t owns ceil(windows(t) / 32) 32-bit words of it.  Needs the targets' window counts (mc_open_database and the builder's tables
+ * announce them; mc_load_target_windows otherwise) and the lineage table; MC_ERR_STATE without either, or without a device.
+ * Announcing other window counts (mc_load_target_windows, mc_load_location_range) or other lineages (mc_set_lineages) DROPS the
+ * accumulated coverage, its statistics and the keep mask; no coverage call may be in flight then.  (The calls that lay the bitmap out
+ * again or replace the mask wait for the device and hold one mutex with the launches of mc_coverage_add / mc_coverage_drop, so a
+ * host thread that marks or drops meanwhile launches on the old or on the new state, never on freed memory; what it marked is lost.)
+ *   A read's list is cands[i * stride .. i * stride + stride) up to the first entry with hits == 0.  An entry QUALIFIES when
+ *   hits >= hits_min and tax(c) != 0, tax(c) as for mc_classify_candidates above (lineage slot lowest_rank itself for rank 0, else the
+ *   first non-zero slot from lowest_rank up; a tgt beyond the lineage table has none).  An entry that does not qualify is skipped and
+ *   the walk goes on.  A qualifying entry marks the windows beg .. min(end, windows(tgt) - 1) of its target.  Entries with
+ *   tgt >= the number of announced targets, with beg > end, or with windows at or beyond windows(tgt) mark only their in-range part (if
+ *   any) and add one each to the out-of-range statistic.
+ * Without MC_COVERAGE_HOST the arrays are DEVICE pointers (16-byte aligned) and the call is asynchronous on 'stream' (a hipStream_t;
+ * NULL = the context's own): enqueued behind the call that made the candidates it needs no synchronisation in between, on either pipe.
+ * Calls on different streams may mark at the same time.  (mc_set_tuning "coverage_load_first" 0: the marking kernel sends every mask out
+ * as an atomic instead of loading the word first -- the same bitmap, kept for measurements)
+ * MC_ERR_INVALID (checked first): NULL ctx, NULL arrays with num_queries > 0, stride == 0, lowest_rank outside 0 .. MC_NUM_RANKS - 1,
+ * unknown flags.  num_queries == 0: MC_OK. */
+#define MC_COVERAGE_HOST 1           /* cands (and out) are HOST arrays, staged in pieces as MC_CLASSIFY_HOST does; the call returns when done */
+int mc_coverage_add(mc_ctx* ctx, const mc_candidate* cands, uint32_t num_queries, uint32_t stride, uint32_t hits_min,
+                    int32_t lowest_rank, int flags, void* stream);
+/* covered[t] = marked windows of target t, windows[t] = its announced window count (the denominators of classification.cpp:606-611):
+ * the first min(capacity, *num_targets) of each are copied; either pointer, num_targets and stats may be NULL.  stats[0..3] =
+ * qualifying entries that marked windows, out-of-range entries, bits set in the bitmap, mc_coverage_add calls -- since the last reset.
+ * Waits for the context's own streams; a caller that marked on streams of its own synchronises them first.  reset != 0 clears the
+ * bitmap and the statistics after they have been read (the keep mask stays). */
+int mc_coverage_counts(mc_ctx* ctx, uint32_t* covered, uint32_t* windows, uint64_t capacity, uint64_t* num_targets,
+                       uint64_t stats[4], int reset);
+/* filter_targets_by_coverage (classification.cpp:591-634) on the host, no context: the targets are visited in 'order' (num_order ids;
+ * NULL = ascending target id, all num_targets of them); those with covered == 0 are skipped and not kept; covP = (float)covered /
+ * (float)windows, summed in float in visiting order; a STABLE sort ascending by covP; then, from the low end,
+ * part += covP; if (part > percentile * sum) stop; else the target is dropped.  keep[t] = 1 exactly for visited targets that were not
+ * dropped (keep has num_targets bytes).  MC_ERR_INVALID: percentile not finite or outside [0, 1] (the command line's rule "a value
+ * above 1 is a percentage", options.cpp:1313, is the caller's), NULL arrays with num_targets > 0, an id >= num_targets or repeated.
+ * The reference's own result additionally depends on the iteration order of its std::unordered_map (the visiting order, and with it
+ * the rounding of the float sum) and on std::sort's order of equal values: that is why 'order' is a parameter, and why a caller that
+ * must drop exactly the reference's targets (mcq) keeps this one step in the reference's containers. */
+int mc_coverage_keep(const uint32_t* covered, const uint32_t* windows, uint64_t num_targets, const uint32_t* order,
+                     uint64_t num_order, float percentile, uint8_t* keep);
+/* the targets whose candidates mc_coverage_drop keeps: keep[t] != 0 for t < num_targets (copied to the device); NULL = no mask.
+ * No mc_coverage_drop may be in flight. */
+int mc_coverage_set_keep(mc_ctx* ctx, const uint8_t* keep, uint64_t num_targets);
+/* update_candidates (classification.cpp:660-671): out row i = the entries of in row i (up to its first hits == 0) whose tgt is kept,
+ * in their order, then zeros; a tgt beyond the mask is not kept.  out may be 'in' itself; any other overlap is MC_ERR_INVALID, as are
+ * NULL ctx, NULL arrays with num_queries > 0, stride == 0 and unknown flags (MC_COVERAGE_HOST: host arrays).  MC_ERR_STATE when no
+ * mask is set.  Device arrays are 16-byte aligned; asynchronous on 'stream' as mc_coverage_add. */
+int mc_coverage_drop(mc_ctx* ctx, const mc_candidate* in, uint32_t num_queries, uint32_t stride, int flags, mc_candidate* out,
+                     void* stream);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with
  * the tuning switch "gw_fuse" 0), "gw_filter2", "gw_compact" (+ the ordering of the stream filter's reads), "gw_filter_stream_fine" (the sixteen-wave instance), "gw_filter_stream" (+ the second gw_compact), "gw_count" (gw_count_kernel<9>), "gw_count_512" (<10>), "gw_count_1024" (<11>); 8-byte store:
  * "big_filter", "big_filter_2", "big_count", "big_count_2" --, "gw_sort", "gw_sorted_cands", "query_wave", "scan", "sort_candidates";
- * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits).  Returns accumulated milliseconds and launch counts since the last reset. */
+ * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts).  Returns accumulated milliseconds and launch counts since the last reset. */
 int mc_timing_enable(mc_ctx* ctx, int on);
 int mc_timing_reset(mc_ctx* ctx);
 int mc_timing_get(mc_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);

@@ -92,6 +92,23 @@ public:
     unsigned part_count() const noexcept { return parts_; }
     mc_ctx* handle() const noexcept { return ctx_; }
 
+    // -cov-percentile between its two passes (filter_targets_by_coverage, classification.cpp:591-634): the covered-window counts of what
+    // the batches' cover() calls have marked (mc_coverage_counts, which is reset), the targets kept at `percentile` (a factor in
+    // [0, 1]; mc_coverage_keep visiting the targets by ascending id) and the mask for classify_kept (mc_coverage_set_keep).
+    // Returns the number of targets kept.
+    std::size_t keep_by_coverage(float percentile) const
+    {
+        std::uint64_t n = 0;
+        if (mc_coverage_counts(ctx_, nullptr, nullptr, 0, &n, nullptr, 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        std::vector<std::uint32_t> covered(n), windows(n);
+        std::vector<std::uint8_t> keep(n);
+        if (mc_coverage_counts(ctx_, covered.data(), windows.data(), n, nullptr, nullptr, 1) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        if (mc_coverage_keep(covered.data(), windows.data(), n, nullptr, 0, percentile, keep.data()) != MC_OK)
+            throw std::runtime_error("mc_coverage_keep: percentile outside [0, 1]");
+        if (mc_coverage_set_keep(ctx_, keep.data(), n) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        return std::size_t(std::count(keep.begin(), keep.end(), std::uint8_t(1)));
+    }
+
     // database::query_gpu_async(queryBatch, hostId, querySketching, lowestRank)  database.hpp:386-397
     void query_gpu_async(query_batch& batch, unsigned hostId, taxon_rank lowestRank) const;
 
@@ -148,13 +165,35 @@ public:
             s.first = assigned_.data(); s.last = s.first + assigned_.size();
             return s;
         }
-        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); }   // query_batch.cuh:255-259
+        // -cov-percentile, first pass (after wait_for_results): the windows that this batch's qualifying candidates cover are marked in
+        // the context's bitmap (matches_per_target::insert, matches_per_target.hpp:100-127; mc_coverage_add on the slot's host arrays)
+        void cover(std::uint32_t hitsMin, int lowestRank)
+        {
+            if (mc_coverage_add(ctx_, res_.cands, res_.num_queries, res_.max_candidates, hitsMin, lowestRank, MC_COVERAGE_HOST, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+        }
+        // second pass, after database::keep_by_coverage: classify() from the candidates of the targets that were kept
+        // (update_candidates, classification.cpp:660-671; mc_coverage_drop into a buffer of this object, then the vote)
+        span<mc_assignment> classify_kept(const mc_classify_options& opt, bool tally = false)
+        {
+            kept_.resize(std::size_t(res_.num_queries) * res_.max_candidates);
+            assigned_.resize(res_.num_queries);
+            if (mc_coverage_drop(ctx_, res_.cands, res_.num_queries, res_.max_candidates, MC_COVERAGE_HOST, kept_.data(), nullptr) != MC_OK ||
+                mc_classify_candidates(ctx_, &opt, kept_.data(), res_.num_queries, res_.max_candidates,
+                                       MC_CLASSIFY_HOST | (tally ? MC_CLASSIFY_TALLY : 0), assigned_.data(), nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            span<mc_assignment> s;
+            s.first = assigned_.data(); s.last = s.first + assigned_.size();
+            return s;
+        }
+        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
         mc_ctx* ctx_ = nullptr; std::uint32_t slot_ = 0;
         mc_results res_{};
         std::vector<match_candidate> tops_;
         std::vector<mc_assignment> assigned_;
+        std::vector<mc_candidate> kept_;
     };
 
     query_batch(const database& db, unsigned numHostThreads) : ctx_(db.ctx_), hosts_(numHostThreads)

@@ -20,6 +20,7 @@ loc_dtype = np.dtype([("win", "<u4"), ("tgt", "<u4")])
 qstat_dtype = np.dtype([("hits", "<u4"), ("nfeat", "<u4"), ("nfound", "<u4"), ("nsteps", "<u4")])
 assignment_dtype = np.dtype({"names": ["taxon", "rank", "voters"], "formats": ["<u4", "u1", "u1"], "offsets": [0, 4, 5], "itemsize": 8})   # mc_assignment, info split into its bytes
 CLASSIFY_HOST, CLASSIFY_TALLY = 1, 2
+COVERAGE_HOST = 1
 
 
 class McConfig(C.Structure):
@@ -74,6 +75,31 @@ def hitdiff_factor(hitdiff: float) -> float:
     return float(v)
 
 
+def percentile_factor(percentile: float) -> float:
+    """-cov-percentile as the command line reads it (options.cpp:1313): kept as a float, a value above 1 is a percentage -- times
+    0.01 in double, rounded back to float"""
+    v = np.float32(percentile)
+    if v > np.float32(1):
+        v = np.float32(np.float64(v) * 0.01)
+    return float(v)
+
+
+def coverage_keep(covered, windows, percentile: float, order=None) -> np.ndarray:
+    """mc_coverage_keep (filter_targets_by_coverage): covered / windows per target, percentile as on the command line (above 1 =
+    percent), order = the target ids in visiting order (None: ascending) -> keep[targets] uint8"""
+    covered = np.ascontiguousarray(covered, dtype=np.uint32)
+    windows = np.ascontiguousarray(windows, dtype=np.uint32)
+    if covered.shape != windows.shape or covered.ndim != 1:
+        raise ValueError("coverage_keep: covered and windows must be one-dimensional and of one length")
+    keep = np.zeros(len(covered), dtype=np.uint8)
+    o = None if order is None else np.ascontiguousarray(order, dtype=np.uint32)
+    rc = lib().mc_coverage_keep(covered.ctypes.data, windows.ctypes.data, len(covered), None if o is None else o.ctypes.data,
+                                0 if o is None else len(o), percentile_factor(percentile), keep.ctypes.data)
+    if rc != MC_OK:
+        raise McError(f"mc_coverage_keep -> {rc}: percentile outside [0, 1] or not finite, or an id of `order` repeated or beyond the targets")
+    return keep
+
+
 def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1) -> McClassifyOptions:
     return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
 
@@ -93,7 +119,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_build_begin", "mc_build_add_target", "mc_build_add_target_src", "mc_build_add_target_device", "mc_build_flush", "mc_build_reserve",
            "mc_build_table_begin", "mc_build_table_add", "mc_build_table_end", "mc_build_set_parent", "mc_build_target_windows", "mc_build_remove_ambiguous", "mc_build_counts", "mc_build_add_existing_target", "mc_build_add_locations", "mc_build_finish", "mc_build_finish_shards", "mc_build_write_shards", "mc_build_write", "mc_build_write_begin", "mc_build_write_add", "mc_build_write_end", "mc_build_free", "mc_build_last_error",
            "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats",
-           "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally"]
+           "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally",
+           "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop"]
 
 _lib = None
 
@@ -155,6 +182,11 @@ def lib() -> C.CDLL:
         L.mc_classify_options_default.restype = None
         L.mc_classify_candidates.argtypes = [C.c_void_p, C.POINTER(McClassifyOptions), C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.mc_classify_tally.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
+        L.mc_coverage_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_void_p]
+        L.mc_coverage_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_int]
+        L.mc_coverage_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
+        L.mc_coverage_set_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_coverage_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -417,6 +449,70 @@ class Database:
         counts = np.zeros(num.value, dtype=np.uint64)
         self._check(L.mc_classify_tally(self.h, assigned.ctypes.data, counts.ctypes.data, counts.size, None, int(reset)))
         return assigned, counts
+
+    # ---- target coverage: the two passes of -cov-percentile (mc_coverage_*) -----------------------
+    def load_target_windows(self, windows: np.ndarray):
+        """the targets' window counts (mc_load_target_windows) for contexts that were not opened from database files; before any table load"""
+        windows = np.ascontiguousarray(windows, dtype=np.uint32)
+        self._check(lib().mc_load_target_windows(self.h, windows.ctypes.data, len(windows)))
+
+    def coverage_add_device(self, cands_ptr: int, n: int, stride: int, *, hitmin: int = 0, lowest: int = 0, stream: int = 0):
+        """marks the windows that the qualifying candidates of n rows in device memory cover; asynchronous on `stream` (0 = the context's)"""
+        self._check(lib().mc_coverage_add(self.h, cands_ptr or None, n, stride, int(hitmin), int(lowest), 0, stream or None))
+
+    def coverage_add(self, cands: np.ndarray, hitmin: int = 0, lowest: int = 0):
+        """the same for a host array cands[n, stride] (cand_dtype, e.g. what query() returns)"""
+        cands = np.ascontiguousarray(cands, dtype=cand_dtype)
+        if cands.ndim != 2:
+            raise ValueError("coverage_add: cands must be [n, stride]")
+        n, stride = cands.shape
+        self._check(lib().mc_coverage_add(self.h, cands.ctypes.data if n else None, n, stride, int(hitmin), int(lowest), COVERAGE_HOST, None))
+
+    def coverage_counts(self, reset: bool = False):
+        """-> (covered[targets] uint32, windows[targets] uint32, stats dict: marked entries, out-of-range entries, bits, add calls)"""
+        L = lib()
+        num = C.c_uint64()
+        self._check(L.mc_coverage_counts(self.h, None, None, 0, C.byref(num), None, 0))
+        covered = np.zeros(num.value, dtype=np.uint32)
+        windows = np.zeros(num.value, dtype=np.uint32)
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(L.mc_coverage_counts(self.h, covered.ctypes.data, windows.ctypes.data, num.value, None, st.ctypes.data, int(reset)))
+        return covered, windows, dict(marked=int(st[0]), out_of_range=int(st[1]), bits=int(st[2]), calls=int(st[3]))
+
+    def coverage_set_keep(self, keep):
+        """the targets whose candidates coverage_drop keeps (uint8 per target, e.g. from coverage_keep); None = no mask"""
+        if keep is None:
+            self._check(lib().mc_coverage_set_keep(self.h, None, 0))
+            return
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        self._check(lib().mc_coverage_set_keep(self.h, keep.ctypes.data, len(keep)))
+
+    def coverage_drop_device(self, in_ptr: int, n: int, stride: int, out_ptr: int, stream: int = 0):
+        """rows in device memory without the candidates of dropped targets (out_ptr may be in_ptr); asynchronous on `stream`"""
+        self._check(lib().mc_coverage_drop(self.h, in_ptr or None, n, stride, 0, out_ptr or None, stream or None))
+
+    def coverage_drop(self, cands: np.ndarray) -> np.ndarray:
+        """the same for a host array cands[n, stride] -> a new array"""
+        cands = np.ascontiguousarray(cands, dtype=cand_dtype)
+        if cands.ndim != 2:
+            raise ValueError("coverage_drop: cands must be [n, stride]")
+        n, stride = cands.shape
+        out = np.zeros_like(cands)
+        self._check(lib().mc_coverage_drop(self.h, cands.ctypes.data if n else None, n, stride, COVERAGE_HOST, out.ctypes.data if n else None, None))
+        return out
+
+    def classify_by_coverage(self, reads, mates=None, *, percentile: float, hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0,
+                             highest: int = NUM_RANKS - 1, insert_max: int = 0, order=None) -> np.ndarray:
+        """CLEARS the context's accumulated coverage, before and after, and replaces its keep mask: not for callers that gather coverage
+        over several batches (they call the steps themselves).  -cov-percentile for one set of reads: query, coverage_add,
+        coverage_counts, coverage_keep (targets visited in `order`, None = ascending id), coverage_drop and the vote -> assignment_dtype [n]"""
+        cands, _, _ = self.query(reads, mates, lowest=lowest, insert_max=insert_max)
+        self.coverage_counts(reset=True)
+        self.coverage_add(cands, hitmin=hitmin, lowest=lowest)
+        covered, windows, _ = self.coverage_counts(reset=True)
+        self.coverage_set_keep(coverage_keep(covered, windows, percentile, order))
+        left = self.coverage_drop(cands)
+        return self.classify_candidates(left, hitmin=hitmin, hitdiff=hitdiff, lowest=lowest, highest=highest)
 
     def copy_results(self, dst_ptr: int, src_ptr: int, nbytes: int, to_host: bool = False, stream: int = 0, second_pipe: bool = False, from_host: bool = False):
         L = lib()

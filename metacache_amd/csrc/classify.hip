@@ -18,20 +18,6 @@
 #include <cmath>
 #include <cstring>
 
-namespace mcamd {
-
-struct ClassifyState {                   // what the context keeps on the device for mc_classify_*
-    uint64_t version = ~0ull;            // ctx->lineageVersion the device copy was made from
-    uint32_t* dLin = nullptr;            // [MC_NUM_RANKS][numTargets], rank-major
-    uint32_t numTargets = 0;
-    unsigned long long* dTally = nullptr;   // [MC_NUM_RANKS + 1] reads per result rank | [numCounts] reads per taxon (index = taxon index + 1)
-    uint64_t numCounts = 0;              // 1 + the largest entry of the lineage table
-    std::mutex stageMtx;                 // MC_CLASSIFY_HOST callers take turns at the staging buffers
-    DevBuf stageIn, stageOut;
-};
-
-}  // namespace mcamd
-
 using namespace mcamd;
 
 namespace {
@@ -144,9 +130,11 @@ __global__ __launch_bounds__(kBlock) void taxon_vote_kernel(VoteArgs a)
     }
 }
 
+}  // namespace
+
 // the device copy of the lineage table and the tallies that are sized by it: made on first use, made again after mc_set_lineages
 // (the tallies then start from zero: their taxon indices belonged to the old table)
-int ensure_state(mc_ctx* ctx, ClassifyState** out)
+int mcamd::ensure_classify_state(mc_ctx* ctx, ClassifyState** out)
 {
     std::lock_guard<std::mutex> lock(ctx->classifyMtx);
     if (!ctx->classify) ctx->classify = new ClassifyState;
@@ -177,6 +165,8 @@ int ensure_state(mc_ctx* ctx, ClassifyState** out)
     S.version = ctx->lineageVersion;
     return MC_OK;
 }
+
+namespace {
 
 int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
 {
@@ -249,7 +239,7 @@ int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* o, const mc_c
     if (!ctx->stream) return fail(ctx, MC_ERR_STATE, "mc_classify_candidates: the context has no device (mc_open_metadata)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ClassifyState* S = nullptr;
-    int rc = ensure_state(ctx, &S);
+    int rc = ensure_classify_state(ctx, &S);
     if (rc) return rc;
     hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
     const bool tally = (flags & MC_CLASSIFY_TALLY) != 0;
@@ -282,7 +272,7 @@ int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t
     if (!ctx->stream) return fail(ctx, MC_ERR_STATE, "mc_classify_tally: the context has no device (mc_open_metadata)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ClassifyState* S = nullptr;
-    const int rc = ensure_state(ctx, &S);
+    const int rc = ensure_classify_state(ctx, &S);
     if (rc) return rc;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->pipe1.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe1.stream));

@@ -394,6 +394,7 @@ void mc_destroy(mc_ctx* ctx)
     for (auto& p : ctx->parts) { if (p.dbuckets) (void)big_free(p.dbuckets); if (p.dvalues) (void)big_free(p.dvalues); if (p.ddirect) (void)big_free(p.ddirect); }
     free_align_works(ctx);
     free_classify_state(ctx);
+    free_coverage_state(ctx);
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);
@@ -535,6 +536,7 @@ int mc_load_target_windows(mc_ctx* ctx, const uint32_t* windows, uint64_t numTar
     for (auto& p : ctx->parts) if (p.announced) return fail(ctx, MC_ERR_STATE, "mc_load_target_windows: call it before mc_load_begin");
     if (numTargets >= 0xFFFFFFFFull) return fail(ctx, MC_ERR_INVALID, "mc_load_target_windows: too many targets");
     ctx->targetWindows.assign(windows, windows + numTargets);
+    ++ctx->windowsVersion;
     return MC_OK;
 }
 
@@ -545,6 +547,7 @@ int mc_load_location_range(mc_ctx* ctx, uint32_t maxTarget, uint32_t maxWindow)
     for (auto& p : ctx->parts) if (p.announced) return fail(ctx, MC_ERR_STATE, "mc_load_location_range: call it before mc_load_begin");
     ctx->targetWindows.clear();
     if (((uint64_t)maxTarget + 1) * ((uint64_t)maxWindow + 1 + kGwGap) < 0xFFFFFFFFull) ctx->targetWindows.assign((size_t)maxTarget + 1, maxWindow + 1);
+    ++ctx->windowsVersion;
     return MC_OK;
 }
 
@@ -1490,6 +1493,7 @@ int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value)
     else if (n == "gw_big_h") ctx->gwBigH = value <= 0 ? 0xFFFFFFFFu : (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll);   // reads beyond this many locations: the stream filter's fine-block instance (0 = none; default 32 768)
     else if (n == "gw_fuse") ctx->gwFuse = (value == 5 || value == 6) ? (int)value : (value != 0);                         // counting of short filtered lists inside the filter kernel: 1 (default) = fused, 0 = the two kernels apart
     else if (n == "align_scratch_mb") ctx->alignScratchMb = std::max<int64_t>(1, value);   // mc_align_semiglobal: device output + scratch of one sub-batch (default 512)
+    else if (n == "coverage_load_first") ctx->coverageLoadFirst = value != 0;   // mc_coverage_add: 0 = every mask goes out as an atomic (the form it was measured against)
     else return fail(ctx, MC_ERR_INVALID, "mc_set_tuning: unknown switch '" + n + "'");
     return MC_OK;
 }

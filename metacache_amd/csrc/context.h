@@ -145,8 +145,23 @@ struct AlignWork;
 void free_align_works(mc_ctx* ctx);
 
 // classify.hip: the device copy of the lineage table, the tallies and the staging of mc_classify_* (made on first use), freed with the context
-struct ClassifyState;
+struct ClassifyState {                   // what the context keeps on the device for mc_classify_* (and, the lineage planes, for mc_coverage_*)
+    uint64_t version = ~0ull;            // ctx->lineageVersion the device copy was made from
+    uint32_t* dLin = nullptr;            // [MC_NUM_RANKS][numTargets], rank-major
+    uint32_t numTargets = 0;
+    unsigned long long* dTally = nullptr;   // [MC_NUM_RANKS + 1] reads per result rank | [numCounts] reads per taxon (index = taxon index + 1)
+    uint64_t numCounts = 0;              // 1 + the largest entry of the lineage table
+    std::mutex stageMtx;                 // MC_CLASSIFY_HOST callers take turns at the staging buffers
+    DevBuf stageIn, stageOut;
+};
+// the device copy of the lineage table and the tallies that are sized by it: made on first use, made again after mc_set_lineages
+int ensure_classify_state(mc_ctx* ctx, ClassifyState** out);
 void free_classify_state(mc_ctx* ctx);
+
+// coverage.hip: the bitmap of covered windows, its word offsets per target, the keep mask and the staging of mc_coverage_* (made on first
+// use), freed with the context
+struct CoverageState;
+void free_coverage_state(mc_ctx* ctx);
 
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
@@ -187,6 +202,10 @@ struct mc_ctx {
     uint64_t lineageVersion = 0;           // counts the mc_set_lineages calls: mc_classify_* copies the table to the device again when it has changed
     std::mutex classifyMtx;
     mcamd::ClassifyState* classify = nullptr;
+    uint64_t windowsVersion = 0;           // counts the announcements of window counts (mc_load_target_windows / mc_load_location_range): mc_coverage_* lays its bitmap out again when it has changed
+    std::mutex coverageMtx;
+    mcamd::CoverageState* coverage = nullptr;
+    bool coverageLoadFirst = true;         // coverage_mark_kernel loads a word and sends the atomic only where bits are missing (mc_set_tuning "coverage_load_first")
 
     // workspace of mc_query_device / mc_candidates_from_hits callers (pipe0.stream == stream); every host batch slot has its own
     // Pipe, so that the H2D copy, the kernels and the D2H copy of different slots overlap on the device

@@ -311,6 +311,7 @@ int mc_open_metadata(const char* name, mc_ctx** out)
     std::vector<uint32_t> lin;
     make_lineages(tmp, lin);
     ctx->lineages = std::move(lin);
+    ++ctx->lineageVersion;
     *out = ctx;
     return MC_OK;
 }

@@ -1121,7 +1121,49 @@ void show_mapping_header(std::ostream& os, const Options& o)               // sh
 // filter_targets_by_coverage (classification.cpp:591-634) then walks the global map in ITS iteration order, sums float coverages in that
 // order, std::sorts them and erases targets from the low end: the order of equal coverages and the rounding of the sums come from the
 // containers.  Same containers, same insertion sequence here (the reference's -threads 1 order), so the same targets go.
-void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L, Aligner* aligner = nullptr)
+// What the containers do NOT decide -- how many windows of a target are covered -- comes from the library: the deferred candidates go
+// through mc_coverage_add batch by batch, as flat rows padded to the batch's longest list, and one mc_coverage_counts gives every
+// target's count and size.  false: the context cannot do it (no window counts, no lineages) or saw entries outside their targets (an
+// inconsistent database) -- the caller counts on the host then.
+// A candidate list never holds an entry without hits in front of one with hits (Deferred::cands comes from rows that end at the first
+// hits == 0), so the kernel's "a row ends at hits == 0" and the host loop below, which looks at every entry, see the same entries.
+// `why` says, where false comes back, what kept the device from counting: the caller reports it, the fall-back is never silent.
+static bool device_coverage(mc_ctx* ctx, const Options& o, const std::deque<Batch>& batches, std::vector<uint32_t>& covered, std::vector<uint32_t>& windows,
+                            uint64_t stats[4], std::string& why)
+{
+    uint64_t nt = 0;
+    if (!ctx) { why = "no context"; return false; }
+    if (mc_coverage_counts(ctx, nullptr, nullptr, 0, &nt, nullptr, 1) != MC_OK) { why = mc_last_error(ctx); return false; }   // (an empty bitmap to begin with)
+    std::vector<mc_candidate> rows;
+    for (const Batch& B : batches) {
+        size_t stride = 0;
+        for (const Deferred& d : B.deferred) stride = std::max(stride, d.cands.size());
+        if (stride == 0) continue;
+        rows.assign(B.deferred.size() * stride, mc_candidate{0, 0, 0, 0});
+        for (size_t i = 0; i < B.deferred.size(); ++i) {
+            const std::vector<Cand>& cs = B.deferred[i].cands;
+            for (size_t j = 0; j < cs.size(); ++j) rows[i * stride + j] = mc_candidate{cs[j].tgt, cs[j].hits, cs[j].beg, cs[j].end};
+        }
+        if (mc_coverage_add(ctx, rows.data(), (uint32_t)B.deferred.size(), (uint32_t)stride, (uint32_t)o.hitsMin, o.lowest, MC_COVERAGE_HOST, nullptr) != MC_OK) {
+            why = mc_last_error(ctx);
+            return false;
+        }
+    }
+    covered.assign(nt, 0); windows.assign(nt, 0);
+    if (mc_coverage_counts(ctx, covered.data(), windows.data(), nt, nullptr, stats, 1) != MC_OK) { why = mc_last_error(ctx); return false; }
+    if (stats[1] != 0) { why = std::to_string(stats[1]) + " candidates lie outside their targets' windows"; return false; }
+    return true;
+}
+
+// the reference's own count (classification.cpp:603-609): one set of windows per target
+static size_t host_covered_windows(const std::vector<Cover>& covers)
+{
+    std::unordered_set<uint32_t> hitWindows;
+    for (const Cover& c : covers) for (uint32_t w = c.beg; w <= c.end; ++w) hitWindows.emplace(w);
+    return hitWindows.size();
+}
+
+void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L, mc_ctx* ctx, Aligner* aligner = nullptr)
 {
     const Taxonomy& tx = L.tx;
     const size_t refBatch = o.refBatchSize ? o.refBatchSize : 4096;
@@ -1148,12 +1190,22 @@ void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<B
         std::vector<CovP> cov;
         cov.reserve(tgtMatches.size());
         float sum = 0;
+        std::vector<uint32_t> covered, windows;
+        uint64_t covStats[4] = {0, 0, 0, 0};
+        std::string why;
+        const bool fromDevice = device_coverage(ctx, o, batches, covered, windows, covStats, why);
+        if (!fromDevice) std::cerr << "mcq: -cov-percentile: covered windows counted on the host (" << why << ")\n";
+        else if (std::getenv("MCQ_PROFILE"))
+            std::cerr << "mcq profile: coverage on the device: " << covStats[3] << " mc_coverage_add calls, " << covStats[0] << " candidates marked, "
+                      << covStats[2] << " windows covered\n";
         for (const auto& m : tgtMatches) {
-            const Lineage lin = tx.target_ranks(m.first);
-            const uint32_t targetSize = tx.taxon(lin[0]) ? (uint32_t)tx.taxon(lin[0])->windows : 0u;
-            std::unordered_set<uint32_t> hitWindows;
-            for (const Cover& c : m.second) for (uint32_t w = c.beg; w <= c.end; ++w) hitWindows.emplace(w);
-            const float covP = float(hitWindows.size()) / targetSize;
+            float covP;
+            if (fromDevice && m.first < covered.size()) covP = float(covered[m.first]) / windows[m.first];
+            else {
+                const Lineage lin = tx.target_ranks(m.first);
+                const uint32_t targetSize = tx.taxon(lin[0]) ? (uint32_t)tx.taxon(lin[0])->windows : 0u;
+                covP = float(host_covered_windows(m.second)) / targetSize;
+            }
             sum += covP;
             cov.emplace_back(m.first, covP);
         }
@@ -1374,7 +1426,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
         A.noReads = true;
         if (aligning) L.wants = &A.wants;
-        classify_by_coverage(os, o, Q.batches, L, aligning ? &A : nullptr);
+        classify_by_coverage(os, o, Q.batches, L, S.ctx, aligning ? &A : nullptr);
     }
     if (merged) {                                                           // map_candidates_to_targets, classification.cpp:891-911
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, false, T};
