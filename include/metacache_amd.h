@@ -549,12 +549,59 @@ int mc_coverage_set_keep(mc_ctx* ctx, const uint8_t* keep, uint64_t num_targets)
 int mc_coverage_drop(mc_ctx* ctx, const mc_candidate* in, uint32_t num_queries, uint32_t stride, int flags, mc_candidate* out,
                      void* stream);
 
+/* ---- per-target hit lists: -hits-per-ref -----------------------------------------------------------
+ * The reference (matches_per_target::insert / sort, matches_per_target.hpp:104-136; printed by show_matches_per_targets,
+ * printing.cpp:385-420) keeps, for every target, the (query id, window range, hits) of all qualifying candidates, sorted by window
+ * range and then query id.  Here every qualifying candidate becomes one mc_target_hit in a LOG in device memory, and
+ * mc_target_hits_collect sorts the log on the device and cuts it into one slice per target.  Needs the lineage table and a device;
+ * MC_ERR_STATE without either.  A later mc_set_lineages DROPS what was accumulated and its statistics (the log keeps its size).
+ *   Which entries are recorded is the rule of mc_coverage_add, to the letter: a read's list is cands[i * stride ..) up to the first
+ *   entry with hits == 0; an entry QUALIFIES when hits >= hits_min and tax(c) != 0 (lineage slot lowest_rank itself for rank 0, else
+ *   the first non-zero slot from lowest_rank up; a tgt beyond the lineage table has none); an entry that does not qualify is skipped
+ *   and the walk goes on.  A qualifying entry becomes the record {tgt, beg, end, hits, query} with beg and end as they are (no window
+ *   table is needed) and query = query_ids[i] if query_ids is given, else first_query_id + i.
+ * mc_target_hits_reserve sizes the log to capacity_records (what it holds stays; MC_ERR_INVALID if that is more than the new size);
+ * 0 frees the log and drops what was accumulated.  It waits for the device; no add may be in flight.
+ * mc_target_hits_add without a flag: cands (16-byte aligned) and query_ids (8-byte aligned, or NULL) are DEVICE pointers and the call
+ * is asynchronous on 'stream' (a hipStream_t; NULL = the context's own): enqueued behind the call that made the candidates it needs
+ * no synchronisation in between.  It never allocates: records that find no room are NOT stored and are counted (stats[1]); without
+ * a reserved log it returns MC_ERR_STATE.  Calls on different streams may append at the same time.
+ * With MC_TARGET_HITS_HOST the arrays are HOST arrays, the call returns when done and one caller runs at a time (no device-mode add
+ * may be in flight on another stream meanwhile).  Before anything is launched it makes room for num_queries * stride more records:
+ * the log grows by doubling (a new allocation and a device-to-device copy), bounded by mc_set_tuning "target_hits_max_mb" (the log's
+ * largest size in MiB, default 8192: 3.5 x 10^8 records; the sort's second buffer at collect time is not counted).  If room cannot
+ * be made the call returns MC_ERR_NOMEM and has added NOTHING, so that the caller can keep that batch elsewhere; MC_ERR_STATE if the
+ * log has dropped records before.
+ * MC_ERR_INVALID (checked first): NULL ctx, NULL cands with num_queries > 0, stride == 0, lowest_rank outside 0 .. MC_NUM_RANKS - 1,
+ * unknown flags, misaligned device arrays.  num_queries == 0: MC_OK. */
+typedef struct { uint32_t tgt, beg, end, hits; uint64_t query; } mc_target_hit;   /* 24 bytes */
+#define MC_TARGET_HITS_HOST 1        /* cands / query_ids are HOST arrays, staged in pieces as MC_COVERAGE_HOST does */
+extern const uint32_t mc_target_hits_tile;   /* records one block sorts in LDS: the sort's pass count is ceil(log2(ceil(n / tile))) (for tests and tools) */
+int mc_target_hits_reserve(mc_ctx* ctx, uint64_t capacity_records);
+int mc_target_hits_add(mc_ctx* ctx, const mc_candidate* cands, const uint64_t* query_ids, uint64_t first_query_id,
+                       uint32_t num_queries, uint32_t stride, uint32_t hits_min, int32_t lowest_rank, int flags, void* stream);
+/* Waits for the context's stream and its second pipe's (the streams that NULL and MC_SECOND_PIPE callers enqueue on; a caller that
+ * appended on any other stream -- its own, or a batch slot's -- synchronises that one first), sorts the log on the
+ * device ascending by (tgt, beg, end, query, hits) -- compared lexicographically, query as a 64-bit number: a total order over the
+ * fields, so the result is a pure function of the SET of records, whatever call order, streams and atomics did -- and returns
+ * records[offsets[t] .. offsets[t + 1]) = target t's list; offsets[t + 1] - offsets[t] is the target's record count.
+ * *num_targets = the lineage table's target count; offsets has *num_targets + 1 entries and capacity_targets says how many TARGETS it
+ * has room for (capacity_targets + 1 entries); records has room for capacity_records.  A capacity smaller than the size is
+ * MC_ERR_INVALID.  A SIZE QUERY is any call with both arrays NULL: it fills *num_targets, *num_records and stats (each may be NULL).
+ * stats[0..3] = records stored, records dropped for lack of room, mc_target_hits_add calls, targets with at least one record --
+ * since the last reset.  With stats[1] > 0 a call that asks for an array returns MC_ERR_STATE (after the sizes and stats have been
+ * filled): a partial list must not pass for a whole one; the size query still answers, and resets.
+ * reset != 0 clears the log and the statistics after they have been read (the log keeps its size).  A call that asks for neither an
+ * array nor stats does not sort: with reset it is the cheap way to empty the log. */
+int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacity_targets, uint64_t* num_targets,
+                           mc_target_hit* records, uint64_t capacity_records, uint64_t* num_records, uint64_t stats[4], int reset);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with
  * the tuning switch "gw_fuse" 0), "gw_filter2", "gw_compact" (+ the ordering of the stream filter's reads), "gw_filter_stream_fine" (the sixteen-wave instance), "gw_filter_stream" (+ the second gw_compact), "gw_count" (gw_count_kernel<9>), "gw_count_512" (<10>), "gw_count_1024" (<11>); 8-byte store:
  * "big_filter", "big_filter_2", "big_count", "big_count_2" --, "gw_sort", "gw_sorted_cands", "query_wave", "scan", "sort_candidates";
- * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts).  Returns accumulated milliseconds and launch counts since the last reset. */
+ * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect).  Returns accumulated milliseconds and launch counts since the last reset. */
 int mc_timing_enable(mc_ctx* ctx, int on);
 int mc_timing_reset(mc_ctx* ctx);
 int mc_timing_get(mc_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);

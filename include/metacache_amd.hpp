@@ -109,6 +109,21 @@ public:
         return std::size_t(std::count(keep.begin(), keep.end(), std::uint8_t(1)));
     }
 
+    // -hits-per-ref after the last batch (matches_per_target::sort, matches_per_target.hpp:128-136): what the batches'
+    // record_target_hits() calls have logged, sorted on the device by (tgt, beg, end, query, hits) -- records[offsets[t] ..
+    // offsets[t + 1]) is target t's list (mc_target_hits_collect, which is reset: the call CONSUMES the log, hence not const)
+    struct target_hit_lists { std::vector<std::uint64_t> offsets; std::vector<mc_target_hit> records; };
+    target_hit_lists hits_per_target()
+    {
+        std::uint64_t nt = 0, nr = 0;
+        if (mc_target_hits_collect(ctx_, nullptr, 0, &nt, nullptr, 0, &nr, nullptr, 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        target_hit_lists l;
+        l.offsets.resize(nt + 1); l.records.resize(nr);
+        if (mc_target_hits_collect(ctx_, l.offsets.data(), nt, nullptr, l.records.data(), nr, nullptr, nullptr, 1) != MC_OK)
+            throw std::runtime_error(mc_last_error(ctx_));
+        return l;
+    }
+
     // database::query_gpu_async(queryBatch, hostId, querySketching, lowestRank)  database.hpp:386-397
     void query_gpu_async(query_batch& batch, unsigned hostId, taxon_rank lowestRank) const;
 
@@ -185,6 +200,15 @@ public:
             span<mc_assignment> s;
             s.first = assigned_.data(); s.last = s.first + assigned_.size();
             return s;
+        }
+        // -hits-per-ref (after wait_for_results): one record per qualifying candidate of this batch goes to the context's log
+        // (matches_per_target::insert, matches_per_target.hpp:104-110; mc_target_hits_add on the slot's host arrays); the batch's
+        // queries are numbered firstQueryId, firstQueryId + 1, ...
+        void record_target_hits(std::uint32_t hitsMin, int lowestRank, std::uint64_t firstQueryId)
+        {
+            if (mc_target_hits_add(ctx_, res_.cands, nullptr, firstQueryId, res_.num_queries, res_.max_candidates, hitsMin, lowestRank,
+                                   MC_TARGET_HITS_HOST, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
         }
         void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); }   // query_batch.cuh:255-259
     private:

@@ -21,6 +21,8 @@ qstat_dtype = np.dtype([("hits", "<u4"), ("nfeat", "<u4"), ("nfound", "<u4"), ("
 assignment_dtype = np.dtype({"names": ["taxon", "rank", "voters"], "formats": ["<u4", "u1", "u1"], "offsets": [0, 4, 5], "itemsize": 8})   # mc_assignment, info split into its bytes
 CLASSIFY_HOST, CLASSIFY_TALLY = 1, 2
 COVERAGE_HOST = 1
+TARGET_HITS_HOST = 1
+target_hit_dtype = np.dtype([("tgt", "<u4"), ("beg", "<u4"), ("end", "<u4"), ("hits", "<u4"), ("query", "<u8")])   # mc_target_hit, 24 bytes
 
 
 class McConfig(C.Structure):
@@ -100,6 +102,11 @@ def coverage_keep(covered, windows, percentile: float, order=None) -> np.ndarray
     return keep
 
 
+def target_hits_tile() -> int:
+    """records one block of the collect-side sort takes (the library's mc_target_hits_tile): n records take ceil(log2(ceil(n / tile))) merge passes"""
+    return int(C.c_uint32.in_dll(lib(), "mc_target_hits_tile").value)
+
+
 def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1) -> McClassifyOptions:
     return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
 
@@ -120,7 +127,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_build_table_begin", "mc_build_table_add", "mc_build_table_end", "mc_build_set_parent", "mc_build_target_windows", "mc_build_remove_ambiguous", "mc_build_counts", "mc_build_add_existing_target", "mc_build_add_locations", "mc_build_finish", "mc_build_finish_shards", "mc_build_write_shards", "mc_build_write", "mc_build_write_begin", "mc_build_write_add", "mc_build_write_end", "mc_build_free", "mc_build_last_error",
            "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats",
            "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally",
-           "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop"]
+           "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop",
+           "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect"]
 
 _lib = None
 
@@ -187,6 +195,9 @@ def lib() -> C.CDLL:
         L.mc_coverage_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
         L.mc_coverage_set_keep.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.mc_coverage_drop.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.mc_target_hits_reserve.argtypes = [C.c_void_p, C.c_uint64]
+        L.mc_target_hits_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_void_p]
+        L.mc_target_hits_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_int]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -513,6 +524,51 @@ class Database:
         self.coverage_set_keep(coverage_keep(covered, windows, percentile, order))
         left = self.coverage_drop(cands)
         return self.classify_candidates(left, hitmin=hitmin, hitdiff=hitdiff, lowest=lowest, highest=highest)
+
+    # ---- per-target hit lists: -hits-per-ref (mc_target_hits_*) -----------------------------------
+    def target_hits_reserve(self, capacity: int):
+        """sizes the device log to `capacity` records (what it holds stays); 0 frees it and drops what was accumulated"""
+        self._check(lib().mc_target_hits_reserve(self.h, int(capacity)))
+
+    def target_hits_add_device(self, cands_ptr: int, n: int, stride: int, *, query_ids_ptr: int = 0, first_query_id: int = 0, hitmin: int = 0,
+                               lowest: int = 0, stream: int = 0):
+        """one record per qualifying candidate of n rows in device memory (query = query_ids[i] where query_ids_ptr is given, else
+        first_query_id + i); asynchronous on `stream` (0 = the context's); never allocates: target_hits_reserve first"""
+        self._check(lib().mc_target_hits_add(self.h, cands_ptr or None, query_ids_ptr or None, int(first_query_id), n, stride, int(hitmin), int(lowest), 0,
+                                             stream or None))
+
+    def target_hits_add(self, cands: np.ndarray, query_ids=None, first_query_id: int = 0, hitmin: int = 0, lowest: int = 0):
+        """the same for a host array cands[n, stride] (cand_dtype, e.g. what query() returns); the log grows as needed, up to
+        set_tuning("target_hits_max_mb"); McError (MC_ERR_NOMEM, nothing added) beyond that"""
+        cands = np.ascontiguousarray(cands, dtype=cand_dtype)
+        if cands.ndim != 2:
+            raise ValueError("target_hits_add: cands must be [n, stride]")
+        n, stride = cands.shape
+        ids = None
+        if query_ids is not None:
+            ids = np.ascontiguousarray(query_ids, dtype=np.uint64)
+            if ids.shape != (n,):
+                raise ValueError("target_hits_add: one query id per row")
+        self._check(lib().mc_target_hits_add(self.h, cands.ctypes.data if n else None, ids.ctypes.data if ids is not None and n else None, int(first_query_id),
+                                             n, stride, int(hitmin), int(lowest), TARGET_HITS_HOST, None))
+
+    def target_hits_stats(self, reset: bool = False) -> dict:
+        """the size query of mc_target_hits_collect: targets, records and the statistics; answers when records were dropped, too"""
+        nt, nr = C.c_uint64(), C.c_uint64()
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_target_hits_collect(self.h, None, 0, C.byref(nt), None, 0, C.byref(nr), st.ctypes.data, int(reset)))
+        return dict(targets=int(nt.value), records=int(nr.value), stored=int(st[0]), dropped=int(st[1]), calls=int(st[2]), targets_hit=int(st[3]))
+
+    def target_hits_collect(self, reset: bool = False):
+        """-> (offsets[targets + 1] uint64, records (target_hit_dtype) sorted by (tgt, beg, end, query, hits), stats dict);
+        records[offsets[t]:offsets[t + 1]] is target t's list.  McError (MC_ERR_STATE) if records were dropped for lack of room."""
+        size = self.target_hits_stats()
+        offsets = np.zeros(size["targets"] + 1, dtype=np.uint64)
+        records = np.zeros(size["records"], dtype=target_hit_dtype)
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_target_hits_collect(self.h, offsets.ctypes.data, size["targets"], None, records.ctypes.data if len(records) else None, len(records),
+                                                 None, st.ctypes.data, int(reset)))
+        return offsets, records, dict(stored=int(st[0]), dropped=int(st[1]), calls=int(st[2]), targets_hit=int(st[3]))
 
     def copy_results(self, dst_ptr: int, src_ptr: int, nbytes: int, to_host: bool = False, stream: int = 0, second_pipe: bool = False, from_host: bool = False):
         L = lib()

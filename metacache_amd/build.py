@@ -18,7 +18,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmetacache_amd.so")
-SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip"]
+SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip"]
 HEADERS = ["kernels.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", os.path.join(ROOT, "include", "metacache_amd.h")]
 ARCH = "gfx950"
 BINDIR = os.path.join(PKG, "bin")
@@ -125,6 +125,21 @@ def build_slot_driver(force: bool = False, verbose: bool = False) -> str:
             print("+", " ".join(cmd), flush=True)
         subprocess.check_call(cmd)
     return SLOTDRV_LIB
+
+
+COVERSORT_LIB = os.path.join(LIBDIR, "libmccoversort.so")
+
+
+def build_cover_sort(force: bool = False, verbose: bool = False) -> str:
+    """tools/host_cover_sort.cpp -> libmccoversort.so: the single-threaded std::sort of per-target records that mc_target_hits_collect is
+    measured against (measurement tool, tools/target_hits_bench.py)"""
+    src = os.path.join(ROOT, "tools", "host_cover_sort.cpp")
+    if force or _stale(COVERSORT_LIB, [src, os.path.join(ROOT, "include", "metacache_amd.h")]):
+        cmd = ["g++", "-std=c++14", "-O2", "-fPIC", "-shared", "-I", os.path.join(ROOT, "include"), src, "-o", COVERSORT_LIB]
+        if verbose:
+            print("+", " ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return COVERSORT_LIB
 
 
 HARNESS_LIB = os.path.join(LIBDIR, "libmckharness.so")

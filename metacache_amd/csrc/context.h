@@ -163,6 +163,10 @@ void free_classify_state(mc_ctx* ctx);
 struct CoverageState;
 void free_coverage_state(mc_ctx* ctx);
 
+// target_hits.hip: the record log of mc_target_hits_*, its cursor and the staging (made on first use), freed with the context
+struct TargetHitsState;
+void free_target_hits_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -206,6 +210,10 @@ struct mc_ctx {
     std::mutex coverageMtx;
     mcamd::CoverageState* coverage = nullptr;
     bool coverageLoadFirst = true;         // coverage_mark_kernel loads a word and sends the atomic only where bits are missing (mc_set_tuning "coverage_load_first")
+
+    std::mutex targetHitsMtx;
+    mcamd::TargetHitsState* targetHits = nullptr;
+    int64_t targetHitsMaxMb = 8192;        // MC_TARGET_HITS_HOST grows the log up to this many MiB (mc_set_tuning "target_hits_max_mb")
 
     // workspace of mc_query_device / mc_candidates_from_hits callers (pipe0.stream == stream); every host batch slot has its own
     // Pipe, so that the H2D copy, the kernels and the D2H copy of different slots overlap on the device

@@ -538,6 +538,18 @@ struct Tally {
     uint64_t total() const { return classified() + unclassified(); }
 };
 
+// -hits-per-ref on the device (mc_target_hits_*): the workers hand every batch's candidate rows to the library's log instead
+// of pushing Covers; a batch the library does not take (MC_ERR_NOMEM: the log may not grow further) stays on the host as before
+constexpr bool kTargetHitsOnDevice = false;  // the default of `mcq query -hits-per-ref` (DESIGN.md 7d says what decides it); MCQ_TARGET_HITS_DEVICE overrides
+struct HitsFeed {
+    mc_ctx* ctx = nullptr;
+    std::mutex mtx;
+    std::string firstError;                  // why the first batch that stayed on the host did
+    uint32_t hostEvery = 0;                  // MCQ_TARGET_HITS_HOST_EVERY=k (tests): every k-th batch of a worker stays on the host as if its call had failed
+    uint64_t hostBatches = 0;
+    void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
+};
+
 // -align: where a batch's text gets alignment lines (behind a mapping line's taxon text, before its '\n'), for which query of the
 // batch, against which candidate; the Aligner below turns these into problems for the device and into lines
 struct AlignWant { size_t at, q; Cand c; };
@@ -553,6 +565,32 @@ struct MappingWriter {
     // over -- its lineage walk (hash lookups up the taxonomy, taxonomy.hpp:576-597) is done once per worker and taxon
     std::unordered_map<uint64_t, std::string> taxText = {};
     std::vector<AlignWant>* wants = nullptr;    // -align: the printed lines of classified reads ask for their alignment here
+    HitsFeed* feed = nullptr;                   // -hits-per-ref: the batch's candidates go to the library's log (flush_feed) instead of tally.covers
+    std::vector<mc_candidate> feedCands = {}, feedRows = {};
+    std::vector<uint32_t> feedCounts = {};
+    std::vector<uint64_t> feedIds = {};
+    uint32_t feedFlushes = 0;
+
+    // the candidates gathered since the last call as flat rows, padded to the longest list (the form the -cov-percentile feed builds), with
+    // the query ids in an array, through mc_target_hits_add; the library applies matches_per_target::insert's rule.  If the call fails
+    // nothing of the batch was recorded: its entries go to tally.covers as they always did.
+    void flush_feed()
+    {
+        if (!feed || feedIds.empty()) { feedCands.clear(); feedCounts.clear(); feedIds.clear(); return; }
+        const size_t n = feedIds.size(), rowLen = *std::max_element(feedCounts.begin(), feedCounts.end());
+        feedRows.assign(n * rowLen, mc_candidate{0, 0, 0, 0});
+        for (size_t i = 0, at = 0; i < n; at += feedCounts[i], ++i) std::copy(feedCands.begin() + at, feedCands.begin() + at + feedCounts[i], feedRows.begin() + i * rowLen);
+        const bool held = feed->hostEvery && ++feedFlushes % feed->hostEvery == 0;
+        if (held || mc_target_hits_add(feed->ctx, feedRows.data(), feedIds.data(), 0, (uint32_t)n, (uint32_t)rowLen, (uint32_t)o.hitsMin, o.lowest, MC_TARGET_HITS_HOST, nullptr) != MC_OK) {
+            feed->note(held ? "MCQ_TARGET_HITS_HOST_EVERY" : mc_last_error(feed->ctx));
+            for (size_t i = 0, at = 0; i < n; at += feedCounts[i], ++i)
+                for (size_t j = at; j < at + feedCounts[i]; ++j) {
+                    const mc_candidate& c = feedCands[j];
+                    if (lowest_ranked_ancestor(tx, c.tgt, o.lowest) && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, feedIds[i], c.beg, c.end, c.hits});
+                }
+        }
+        feedCands.clear(); feedCounts.clear(); feedIds.clear();
+    }
 
     template <class OS>
     void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits, size_t q = 0)
@@ -589,8 +627,13 @@ struct MappingWriter {
             }
         }
         if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];             // classify_and_evaluate, classification.cpp:552-554
-        if (o.hitsPerRef && !deferred)                           // matches_per_target::insert (matches_per_target.hpp:100-110)
-            for (const Cand& c : cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits});
+        if (o.hitsPerRef && !deferred) {                         // matches_per_target::insert (matches_per_target.hpp:100-110)
+            if (!feed) { for (const Cand& c : cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits}); }
+            else if (!cands.empty()) {
+                feedIds.push_back(id); feedCounts.push_back((uint32_t)cands.size());
+                for (const Cand& c : cands) feedCands.push_back(mc_candidate{c.tgt, c.hits, c.beg, c.end});
+            }
+        }
         if (o.mapView == Options::mv_none || (o.mapView == Options::mv_mapped && !best)) return;
         if (o.queryIds) out << id << o.column;
         const void* sp = memchr(header.p, ' ', header.n);
@@ -1060,6 +1103,7 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* a
                 else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0, m.q);
             }
         });
+        L.flush_feed();                                                     // (also for a batch the job failed in: what it gathered is recorded or kept, never dropped)
         if (!done) break;
         if (aligner && step.prints && !L.deferred) {                        // the batch's alignments: one device call, then the lines go into its text
             std::string err;
@@ -1234,26 +1278,40 @@ void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<B
     for (const auto& m : tgtMatches) L.tally.covers.insert(L.tally.covers.end(), m.second.begin(), m.second.end());
 }
 
-void show_hits_per_ref(std::ostream& os, const Options& o, const Taxonomy& tx, uint32_t stride, std::vector<Cover>& covers)   // show_matches_per_targets, printing.cpp:385-420
+// covers: what stayed on the host (every list where the device was not used); dev: the library's sorted records.  The two are merged
+// while they are printed (the device's record first where the four fields the lists are ordered by are equal).
+void show_hits_per_ref(std::ostream& os, const Options& o, const Taxonomy& tx, uint32_t stride, std::vector<Cover>& covers,
+                       const std::vector<mc_target_hit>& dev = {})   // show_matches_per_targets, printing.cpp:385-420
 {
-    std::sort(covers.begin(), covers.end(), [](const Cover& a, const Cover& b) {   // per target: by window range, then query id
+    auto less = [](const Cover& a, const Cover& b) {                               // per target: by window range, then query id
         if (a.tgt != b.tgt) return a.tgt < b.tgt;
         if (a.beg != b.beg) return a.beg < b.beg;
         if (a.end != b.end) return a.end < b.end;
         return a.qid < b.qid;
-    });
+    };
+    std::sort(covers.begin(), covers.end(), less);
     os << o.comment << "--- list of hits for each reference sequence ---\n"
        << o.comment << "window start position within sequence = window_index * window_stride(=" << stride << ")\n";
     os << o.comment << "TABLE_LAYOUT: " << " sequence " << o.column << " windows_in_sequence " << o.column
        << "queryid/first_window_index+additional_windows:hits,queryid/...\n";
-    for (size_t i = 0; i < covers.size();) {
-        const uint32_t tgt = covers[i].tgt;
+    size_t i = 0, j = 0;                                                           // next of covers, of dev
+    auto of = [](const mc_target_hit& h) { return Cover{h.tgt, h.query, h.beg, h.end, h.hits}; };
+    auto from_dev = [&]() { return j < dev.size() && (i >= covers.size() || !less(covers[i], of(dev[j]))); };
+    auto peek = [&](Cover& c) {
+        if (i >= covers.size() && j >= dev.size()) return false;
+        c = from_dev() ? of(dev[j]) : covers[i];
+        return true;
+    };
+    auto take = [&]() { if (from_dev()) ++j; else ++i; };
+    Cover c;
+    while (peek(c)) {
+        const uint32_t tgt = c.tgt;
         const Lineage lin = tx.target_ranks(tgt);
         show_lineage(os, o, tx, lin, 0, o.lineage ? o.highest : 0);
         os << o.column << (tx.taxon(lin[0]) ? tx.taxon(lin[0])->windows : 0) << o.column;
-        for (bool first = true; i < covers.size() && covers[i].tgt == tgt; ++i, first = false) {
+        for (bool first = true; peek(c) && c.tgt == tgt; take(), first = false) {
             if (!first) os << ',';
-            os << covers[i].qid << '/' << covers[i].beg << '+' << (covers[i].end - covers[i].beg) << ':' << covers[i].hits;
+            os << c.qid << '/' << c.beg << '+' << (c.end - c.beg) << ':' << c.hits;
         }
         os << '\n';
     }
@@ -1397,9 +1455,24 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     std::vector<Tally> tallies(S.workers);
     TargetCache targets(o.showErrors);                                      // -align: the target records of this job
     const bool aligning = o.align && !merged;
+    // -hits-per-ref: the lists are built by the library (mc_target_hits_*) where one context serves the whole run; under -cov-percentile,
+    // in the sharded command lines (part sets, key shards, -replicate) and in merge they are built on the host as before
+    HitsFeed feed;
+    std::string feedWhyNot;
+    if (o.hitsPerRef) {
+        const char* sw = std::getenv("MCQ_TARGET_HITS_DEVICE");                // 1 / 0: the library's log / the host vector, whatever the default
+        if (!(sw ? std::atoi(sw) != 0 : kTargetHitsOnDevice)) feedWhyNot = "the host sort is the default here (MCQ_TARGET_HITS_DEVICE=1 selects the library's log)";
+        else if (merged) feedWhyNot = "merge mode";
+        else if (covMode) feedWhyNot = "-cov-percentile keeps the candidates on the host";
+        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) feedWhyNot = "the run uses more than one context";
+        else if (mc_target_hits_collect(S.ctx, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 1) != MC_OK) feedWhyNot = mc_last_error(S.ctx);   // (an empty log to begin with)
+        else feed.ctx = S.ctx;
+        if (const char* e = std::getenv("MCQ_TARGET_HITS_HOST_EVERY")) feed.hostEvery = (uint32_t)std::max(0, std::atoi(e));
+    }
     auto worker = [&](unsigned w, auto&& step) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]};
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
+        if (feed.ctx) L.feed = &feed;
         if (aligning && !covMode) L.wants = &A.wants;
         work(Q, W, L, step, aligning ? &A : nullptr);
     };
@@ -1438,7 +1511,23 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
-    if (o.hitsPerRef) show_hits_per_ref(perTargetOut, o, tx, S.dbStride, T.covers);
+    if (o.hitsPerRef) {
+        std::vector<mc_target_hit> devHits;
+        if (feed.ctx) {                                                     // mc_target_hits_collect replaces the sort of all records on one host thread
+            uint64_t nt = 0, nr = 0, st[4] = {0, 0, 0, 0};
+            if (mc_target_hits_collect(feed.ctx, nullptr, 0, &nt, nullptr, 0, &nr, nullptr, 0) != MC_OK) throw std::runtime_error(mc_last_error(feed.ctx));
+            devHits.resize(nr);
+            if (mc_target_hits_collect(feed.ctx, nullptr, 0, nullptr, devHits.data(), nr, nullptr, st, 1) != MC_OK) throw std::runtime_error(mc_last_error(feed.ctx));
+            mc_target_hits_reserve(feed.ctx, 0);                            // (the log's memory goes back)
+            if (P.on) {
+                std::cerr << "mcq profile: hits per target on the device: " << st[2] << " mc_target_hits_add calls, " << st[0] << " records, " << st[3]
+                          << " targets, " << T.covers.size() << " records of " << feed.hostBatches << " batches kept on the host";
+                if (feed.hostBatches) std::cerr << " (" << feed.firstError << ")";
+                std::cerr << "\n";
+            }
+        } else if (P.on) std::cerr << "mcq: -hits-per-ref: lists built on the host (" << feedWhyNot << ")\n";
+        show_hits_per_ref(perTargetOut, o, tx, S.dbStride, T.covers, devHits);
+    }
     if (o.abundances || o.abundancePer != kNumRanks) show_abundances(perTaxonOut, o, tx, T);
     if (o.showSummary) show_summary(os, o, T, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 }
