@@ -47,8 +47,6 @@ struct AlignProblem {
 };
 struct AlignResult { int32_t fwd, rev, mfwd, mrev; uint32_t reversed, length; };
 
-int fail(mc_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
-
 // the value of the lane below (lane 0: fill).  Every lane of the wave must be active.
 __device__ __forceinline__ int wave_shr1(int v, int fill) { return __builtin_amdgcn_update_dpp(fill, v, 0x138 /* wave_shr:1 */, 0xF, 0xF, false); }
 
@@ -234,7 +232,7 @@ __global__ void __launch_bounds__(64) align_kernel(const AlignProblem* __restric
     }
 }
 
-int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
+int grow_with_headroom(mc_ctx* ctx, DevBuf& b, size_t bytes)      // an eighth more than asked for; no room is MC_ERR_NOMEM
 {
     if (bytes <= b.cap) return MC_OK;
     if (b.p) (void)hipFree(b.p);
@@ -254,9 +252,6 @@ int grow_host(mc_ctx* ctx, void*& p, size_t& cap, size_t bytes)
     cap = want;
     return MC_OK;
 }
-
-#define ALIGN_TRY(ctx, expr)                                                                                              \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 inline size_t up128(size_t x) { return (x + 127) / 128 * 128; }
 // a long-tier problem's scratch: the boundary row (one number per row of the longer of read and mate, + 1), then read 1's predecessor bits
@@ -280,9 +275,9 @@ int run_sub_batch(mc_ctx* ctx, AlignWork& w, const char* reads, const uint64_t* 
     const size_t resBytes = up128(n * sizeof(AlignResult));
     if (int rc = grow_host(ctx, w.hIn, w.hInCap, inBytes)) return rc;
     if (int rc = grow_host(ctx, w.hOut, w.hOutCap, resBytes + outBytes)) return rc;
-    if (int rc = grow(ctx, w.dChars, inBytes)) return rc;
-    if (int rc = grow(ctx, w.dRes, resBytes + outBytes)) return rc;
-    if (int rc = grow(ctx, w.dScratch, scratchBytes + 128)) return rc;
+    if (int rc = grow_with_headroom(ctx, w.dChars, inBytes)) return rc;
+    if (int rc = grow_with_headroom(ctx, w.dRes, resBytes + outBytes)) return rc;
+    if (int rc = grow_with_headroom(ctx, w.dScratch, scratchBytes + 128)) return rc;
     uint8_t* hc = static_cast<uint8_t*>(w.hIn);
     AlignProblem* hp = reinterpret_cast<AlignProblem*>(hc + probsAt);
     uint32_t* hl = reinterpret_cast<uint32_t*>(hc + listAt);       // the short tier's problems from the front, the long tier's from the back
@@ -305,18 +300,18 @@ int run_sub_batch(mc_ctx* ctx, AlignWork& w, const char* reads, const uint64_t* 
     }
     uint8_t* dc = static_cast<uint8_t*>(w.dChars.p);
     uint8_t* dr = static_cast<uint8_t*>(w.dRes.p);
-    ALIGN_TRY(ctx, hipMemcpyAsync(dc, hc, inBytes, hipMemcpyHostToDevice, w.stream));
-    ALIGN_TRY(ctx, hipEventRecord(w.e0, w.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(dc, hc, inBytes, hipMemcpyHostToDevice, w.stream));
+    HIP_TRY(ctx, hipEventRecord(w.e0, w.stream));
     const AlignProblem* dp = reinterpret_cast<const AlignProblem*>(dc + probsAt);
     const uint32_t* dl = reinterpret_cast<const uint32_t*>(dc + listAt);
     if (ns) hipLaunchKernelGGL(align_kernel<false>, dim3((uint32_t)ns), dim3(64), ldsBytes, w.stream, dp, dl, (uint32_t)ns, dc, dr + resBytes,
                                reinterpret_cast<AlignResult*>(dr), (uint8_t*)nullptr);
     if (nl) hipLaunchKernelGGL(align_kernel<true>, dim3((uint32_t)nl), dim3(64), 0, w.stream, dp, dl + (n - nl), (uint32_t)nl, dc, dr + resBytes,
                                reinterpret_cast<AlignResult*>(dr), static_cast<uint8_t*>(w.dScratch.p));
-    ALIGN_TRY(ctx, hipGetLastError());
-    ALIGN_TRY(ctx, hipEventRecord(w.e1, w.stream));
-    ALIGN_TRY(ctx, hipMemcpyAsync(w.hOut, dr, resBytes + outBytes, hipMemcpyDeviceToHost, w.stream));
-    ALIGN_TRY(ctx, hipStreamSynchronize(w.stream));
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipEventRecord(w.e1, w.stream));
+    HIP_TRY(ctx, hipMemcpyAsync(w.hOut, dr, resBytes + outBytes, hipMemcpyDeviceToHost, w.stream));
+    HIP_TRY(ctx, hipStreamSynchronize(w.stream));
     float ms = 0;
     if (hipEventElapsedTime(&ms, w.e0, w.e1) == hipSuccess) ctx->alignKernelNs += (uint64_t)((double)ms * 1e6);
     const AlignResult* hr = static_cast<const AlignResult*>(w.hOut);
@@ -376,14 +371,14 @@ extern "C" int mc_align_semiglobal(mc_ctx* ctx, const char* reads, const uint64_
     if (aligned_cap < need) return fail(ctx, MC_ERR_INVALID, "mc_align_semiglobal: the buffer for the aligned strings must hold 2 x max(1, len_q + len_s) characters per problem");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return fail(ctx, MC_ERR_HIP, "no usable HIP device (this library has no CPU fallback)"); }
-    ALIGN_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
     AlignWork* w = nullptr;
     { std::lock_guard<std::mutex> l(ctx->alignMtx); if (!ctx->alignWorks.empty()) { w = ctx->alignWorks.back(); ctx->alignWorks.pop_back(); } }
     if (!w) w = new AlignWork();
     struct Return { mc_ctx* c; AlignWork* w; ~Return() { std::lock_guard<std::mutex> l(c->alignMtx); c->alignWorks.push_back(w); } } giveBack{ctx, w};
-    if (!w->stream) ALIGN_TRY(ctx, hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
-    if (!w->e0) ALIGN_TRY(ctx, hipEventCreate(&w->e0));
-    if (!w->e1) ALIGN_TRY(ctx, hipEventCreate(&w->e1));
+    if (!w->stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&w->stream, hipStreamNonBlocking));
+    if (!w->e0) HIP_TRY(ctx, hipEventCreate(&w->e0));
+    if (!w->e1) HIP_TRY(ctx, hipEventCreate(&w->e1));
     // sub-batches: device output + the long tier's scratch + characters of one stay under the budget; one problem alone always goes
     const uint64_t budget = (uint64_t)std::max<int64_t>(1, ctx->alignScratchMb) << 20;
     for (uint64_t a = 0; a < n;) {

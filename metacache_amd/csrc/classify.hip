@@ -12,7 +12,7 @@
 // the taxa a sample piles onto claim their slots with the block's first reads -- and both reach the global counters once, at the
 // block's end.  A taxon that finds no slot goes to its global counter directly (many taxa, few reads each: no contention there).
 // Plain HIP C++; no inline assembly.
-#include "context.h"
+#include "rows_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -25,14 +25,6 @@ namespace {
 constexpr uint32_t kBlock = 256, kBins = MC_NUM_RANKS + 1, kMaxBlocks = 2048;
 constexpr int kWaveRounds = 8;           // taxa a wave adds up across its lanes before the rest add their own 1
 constexpr uint32_t kTaxonSlots = 512, kTaxonSlotBits = 9, kTaxonProbes = 2;   // a block's taxon table in LDS: slots (a power of two), slots a taxon tries
-
-int fail(mc_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
-
-#define HIP_TRY(ctx, expr)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 struct VoteArgs {
     const mc_candidate* cands;
@@ -83,10 +75,8 @@ __global__ __launch_bounds__(kBlock) void taxon_vote_kernel(VoteArgs a)
             const uint2* c = reinterpret_cast<const uint2*>(a.cands + i * a.stride);     // entry j: c[2 * j] = {tgt, hits}
             const uint2 top = c[0];
             if (top.y != 0 && top.y >= a.hitsMin && top.x < nT) {
-                // tax(cand[0]): the lineage slot `lowest` itself for sequence level, else the first one that is filled from there on
-                int r = a.lowest;
-                uint32_t t = a.lin[(uint64_t)r * nT + top.x];
-                if (a.lowest > 0) while (!t && ++r < MC_NUM_RANKS) t = a.lin[(uint64_t)r * nT + top.x];
+                int r;                                                                   // the rank of tax(cand[0]): where the LCA walk begins
+                uint32_t t = taxon_of_target(a.lin, nT, top.x, a.lowest, r);
                 if (t) {
                     const float threshold = top.y > a.hitsMin ? (float)(top.y - a.hitsMin) * a.hitsDiff : 0.0f;
                     uint32_t v = 1;
@@ -168,15 +158,6 @@ int mcamd::ensure_classify_state(mc_ctx* ctx, ClassifyState** out)
 
 namespace {
 
-int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return MC_OK;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    HIP_TRY(ctx, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return MC_OK;
-}
-
 void launch_vote(const ClassifyState& S, const mc_classify_options& o, const mc_candidate* cands, uint32_t n, uint32_t stride, bool tally,
                  mc_assignment* out, hipStream_t st)
 {
@@ -184,7 +165,7 @@ void launch_vote(const ClassifyState& S, const mc_classify_options& o, const mc_
     a.cands = cands; a.lin = S.dLin; a.out = out; a.assigned = S.dTally; a.taxonCounts = S.dTally + kBins;
     a.n = n; a.stride = stride; a.numTargets = S.numTargets;
     a.hitsMin = o.hits_min; a.hitsDiff = o.hits_diff; a.lowest = o.lowest_rank; a.highest = o.highest_rank;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, kMaxBlocks);
+    const uint32_t blocks = row_blocks(n, kBlock, kMaxBlocks);
     if (tally) hipLaunchKernelGGL(taxon_vote_kernel<true>, dim3(blocks), dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL(taxon_vote_kernel<false>, dim3(blocks), dim3(kBlock), 0, st, a);
 }
@@ -230,7 +211,7 @@ int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* o, const mc_c
     if (n > 0) {
         if (!cands || !out) return fail(ctx, MC_ERR_INVALID, "mc_classify_candidates: null array");
         const uintptr_t c0 = (uintptr_t)cands, c1 = c0 + (uintptr_t)n * stride * sizeof(mc_candidate), o0 = (uintptr_t)out, o1 = o0 + (uintptr_t)n * sizeof(mc_assignment);
-        if (o0 < c1 && c0 < o1) return fail(ctx, MC_ERR_INVALID, "mc_classify_candidates: out overlaps cands");
+        if (ranges_overlap(c0, c1, o0, o1)) return fail(ctx, MC_ERR_INVALID, "mc_classify_candidates: out overlaps cands");
         if (!(flags & MC_CLASSIFY_HOST) && ((c0 | o0) & 7u)) return fail(ctx, MC_ERR_INVALID, "mc_classify_candidates: device arrays must be 8-byte aligned");
     }
     if (n == 0) return MC_OK;
@@ -250,18 +231,13 @@ int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* o, const mc_c
     }
     // host arrays: in pieces of at most 64 MB of candidates through the staging buffers, one caller at a time
     std::lock_guard<std::mutex> lock(S->stageMtx);
-    const uint64_t perRead = (uint64_t)stride * sizeof(mc_candidate);
-    const uint32_t piece = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / perRead));
-    if ((rc = grow(ctx, S->stageIn, piece * perRead)) != MC_OK || (rc = grow(ctx, S->stageOut, (uint64_t)piece * sizeof(mc_assignment))) != MC_OK) return rc;
-    for (uint32_t done = 0; done < n; done += piece) {
-        const uint32_t m = std::min(piece, n - done);
-        HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, cands + (uint64_t)done * stride, m * perRead, hipMemcpyHostToDevice, st));
-        launch_vote(*S, *o, (const mc_candidate*)S->stageIn.p, m, stride, tally, (mc_assignment*)S->stageOut.p, st);
+    if ((rc = grow(ctx, S->stageIn, staged_piece_bytes(n, stride))) != MC_OK || (rc = grow(ctx, S->stageOut, (uint64_t)staged_piece_rows(n, stride) * sizeof(mc_assignment))) != MC_OK) return rc;
+    return for_each_staged_piece(ctx, st, S->stageIn, cands, n, stride, [&](const mc_candidate* dRows, uint32_t done, uint32_t m) {
+        launch_vote(*S, *o, dRows, m, stride, tally, (mc_assignment*)S->stageOut.p, st);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, hipMemcpyAsync(out + done, S->stageOut.p, (uint64_t)m * sizeof(mc_assignment), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return MC_OK;
+        return (int)MC_OK;
+    });
 }
 
 int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t* taxonCounts, uint64_t capacity, uint64_t* numCounts, int reset)
@@ -274,8 +250,7 @@ int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t
     ClassifyState* S = nullptr;
     const int rc = ensure_classify_state(ctx, &S);
     if (rc) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pipe1.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe1.stream));
+    if (const int drc = drain_query_streams(ctx)) return drc;
     const uint64_t take = std::min(capacity, S->numCounts);
     if (assigned) HIP_TRY(ctx, hipMemcpyAsync(assigned, S->dTally, kBins * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (take) HIP_TRY(ctx, hipMemcpyAsync(taxonCounts, S->dTally + kBins, take * 8, hipMemcpyDeviceToHost, ctx->stream));

@@ -2,6 +2,7 @@
 // pipeline, host slots, timing.  (Compiled with hipcc; the kernels live in kernels.hip.)
 #include "context.h"
 #include "devcache.h"
+#include "rows_common.h"
 
 #include <algorithm>
 #include <atomic>
@@ -13,27 +14,19 @@
 
 using namespace mcamd;
 
-namespace {
-
-thread_local std::string g_createError;
-
-#define HIP_TRY(ctx, expr)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess)                                                                       \
-            return fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));                                                                                           \
-    } while (0)
-
+static thread_local std::string g_createError;
 // a helper thread that works on a context beside its owner (reserve_slot_pipes) must not write ctx->err: its failures stay its own
 static thread_local bool t_quietErrors = false;
 static thread_local std::string* t_errSink = nullptr;         // a dispatcher thread of the slot coalescer keeps its errors for the slots it carries
-int fail(mc_ctx* ctx, int code, const std::string& msg)
+int mcamd::fail(mc_ctx* ctx, int code, const std::string& msg)
 {
     if (t_errSink) { *t_errSink = msg; return code; }
     if (t_quietErrors) return code;
     if (ctx) ctx->err = msg; else g_createError = msg;
     return code;
 }
+
+namespace {
 
 int ensure(mc_ctx* ctx, DevBuf& b, size_t bytes)
 {
@@ -95,27 +88,7 @@ static hipError_t traced_sync(hipStream_t st)
     return e;
 }
 
-// ---- timing ------------------------------------------------------------------------------
-hipEvent_t get_event(mc_ctx* ctx)
-{
-    if (!ctx->eventPool.empty()) { hipEvent_t e = ctx->eventPool.back(); ctx->eventPool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
-    return e;
-}
-
-struct ScopedTimer {
-    mc_ctx* ctx; const char* name; hipStream_t st; hipEvent_t a = nullptr, b = nullptr;
-    ScopedTimer(mc_ctx* c, const char* n, hipStream_t s) : ctx(c), name(n), st(s)
-    {
-        if (ctx->timing) { std::lock_guard<std::mutex> l(ctx->timerMtx); a = get_event(ctx); b = get_event(ctx); (void)hipEventRecord(a, st); }
-    }
-    ~ScopedTimer()
-    {
-        if (a) { std::lock_guard<std::mutex> l(ctx->timerMtx); (void)hipEventRecord(b, st); ctx->timers[name].pending.emplace_back(a, b); }
-    }
-};
-
+// ---- timing (ScopedTimer: rows_common.h) -------------------------------------------------
 void collect_timers(mc_ctx* ctx)
 {
     for (auto& kv : ctx->timers) {
@@ -1504,9 +1477,7 @@ int mc_synchronize(mc_ctx* ctx)
 {
     if (!ctx) return MC_ERR_INVALID;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pipe1.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe1.stream));
-    return MC_OK;
+    return drain_query_streams(ctx);
 }
 
 int mc_query_wait(mc_ctx* ctx, int flags)

@@ -140,6 +140,16 @@ uint64_t cut_batch_to_target_range(const mc_ctx* ctx, uint8_t* sizes, uint8_t* v
 // error text for failures that have no context yet (mc_last_error(NULL))
 void set_global_error(const std::string& msg);
 
+// context.cpp: the one way an entry point fails -- msg becomes the context's error text (without a context: the calling thread's text
+// for mc_last_error(NULL)), code is returned.  A helper thread that works on a context beside its owner keeps its texts to itself.
+int fail(mc_ctx* ctx, int code, const std::string& msg);
+
+#define HIP_TRY(ctx, expr)                                                                          \
+    do {                                                                                            \
+        hipError_t e_ = (expr);                                                                     \
+        if (e_ != hipSuccess) return ::mcamd::fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
 // align.hip: the device workspaces of mc_align_semiglobal callers (one per caller at a time), freed with the context
 struct AlignWork;
 void free_align_works(mc_ctx* ctx);

@@ -9,7 +9,7 @@
 // mask into every word its range touches.  coverage_count_kernel: one wave per target, popcounts.  coverage_drop_kernel: one lane per
 // read, the entries of kept targets move to the front of the row.
 // Plain HIP C++; no inline assembly.
-#include "context.h"
+#include "rows_common.h"
 
 #include <algorithm>
 #include <cmath>
@@ -44,14 +44,6 @@ namespace {
 
 constexpr uint32_t kBlock = 256, kMaxBlocks = 2048, kWavesPerBlock = kBlock / 64;
 
-int fail(mc_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
-
-#define HIP_TRY(ctx, expr)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct MarkArgs {
     const mc_candidate* cands;
     const uint32_t* lin;                 // rank-major lineage planes (classify.hip)
@@ -62,12 +54,6 @@ struct MarkArgs {
     uint32_t n, stride, linTargets, targets, hitsMin;
     int lowest;
 };
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_down((int)v, off);
-    return v;                            // (lane 0 holds the sum)
-}
 
 // TEST: the word is LOADED first and the atomic is issued only where it would set a bit.  The reads of a sample pile onto a few genomes,
 // so after the first moments almost every bit a candidate wants is set already and the kernel is the vote's loads plus one word.
@@ -95,10 +81,8 @@ __global__ __launch_bounds__(kBlock) void coverage_mark_kernel(MarkArgs a)
             // entry -> tables -> word is three memory latencies deep, not five
             const bool known = e.x < a.targets;
             const uint32_t W = known ? a.windows[e.x] : 0u, base = known ? a.wordBase[e.x] : 0u;
-            int r = a.lowest;
-            uint32_t t = a.lin[(uint64_t)r * nL + e.x];
-            if (a.lowest > 0) while (!t && ++r < MC_NUM_RANKS) t = a.lin[(uint64_t)r * nL + e.x];
-            if (!t) continue;
+            int r;
+            if (!taxon_of_target(a.lin, nL, e.x, a.lowest, r)) continue;
             if (!known || e.z > e.w) { ++outside; continue; }
             if (e.z >= W) { ++outside; continue; }
             uint32_t end = e.w;
@@ -115,8 +99,9 @@ __global__ __launch_bounds__(kBlock) void coverage_mark_kernel(MarkArgs a)
             }
         }
     }
-    // counted per wave, one atomic per block and counter
-    marked = wave_sum(marked); outside = wave_sum(outside);
+    // counted per wave, one atomic per block and counter.  wave_sum_u32 needs all 64 lanes: blocks are whole waves (kBlock = 256) and the
+    // lanes, whatever number of rows each has walked, have left the row loop together by here
+    marked = wave_sum_u32(marked); outside = wave_sum_u32(outside);
     if ((threadIdx.x & 63u) == 0) {
         if (marked) atomicAdd(&blockCount[0], marked);
         if (outside) atomicAdd(&blockCount[1], outside);
@@ -135,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void coverage_count_kernel(const uint32_t* 
     const uint32_t b = wordBase[t], e = wordBase[t + 1];
     uint32_t sum = 0;
     for (uint32_t w = b + lane; w < e; w += 64) sum += (uint32_t)__popc(bits[w]);
-    sum = wave_sum(sum);
+    sum = wave_sum_u32(sum);                                                              // all 64 lanes: a wave has left above as a whole or is here as a whole, the word loop behind it
     if (lane == 0) covered[t] = sum;
 }
 
@@ -195,29 +180,18 @@ int ensure_state(mc_ctx* ctx, const char* who, CoverageState** out, ClassifyStat
         HIP_TRY(ctx, hipMalloc((void**)&S.dWindows, nt * 4));
         HIP_TRY(ctx, hipMalloc((void**)&S.dCovered, nt * 4));
         HIP_TRY(ctx, hipMalloc((void**)&S.dBits, std::max<uint64_t>(words, 1) * 4));
-        HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, 2 * 8));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, kCounterPairBytes));
         HIP_TRY(ctx, hipMemcpy(S.dWordBase, S.hWordBase.data(), (nt + 1) * 4, hipMemcpyHostToDevice));
         HIP_TRY(ctx, hipMemcpy(S.dWindows, ctx->targetWindows.data(), nt * 4, hipMemcpyHostToDevice));
     }
     if (S.dKeep) { (void)hipFree(S.dKeep); S.dKeep = nullptr; S.keepTargets = 0; }
     HIP_TRY(ctx, hipMemsetAsync(S.dBits, 0, std::max<uint64_t>(S.words, 1) * 4, ctx->stream));
-    HIP_TRY(ctx, hipMemsetAsync(S.dCounters, 0, 2 * 8, ctx->stream));
+    HIP_TRY(ctx, hipMemsetAsync(S.dCounters, 0, kCounterPairBytes, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     S.addCalls = 0;
     S.winVersion = ctx->windowsVersion; S.linVersion = ctx->lineageVersion;
     return MC_OK;
 }
-
-int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return MC_OK;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    HIP_TRY(ctx, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return MC_OK;
-}
-
-uint32_t row_blocks(uint32_t n) { return (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, kMaxBlocks); }
 
 // test: the load before the atomic (the shipped form; mc_set_tuning "coverage_load_first" 0 sends every mask out as an atomic, for measurements)
 void launch_mark(const CoverageState& S, const ClassifyState& C, const mc_candidate* cands, uint32_t n, uint32_t stride, uint32_t hitsMin, int lowest,
@@ -226,11 +200,9 @@ void launch_mark(const CoverageState& S, const ClassifyState& C, const mc_candid
     MarkArgs a{};
     a.cands = cands; a.lin = C.dLin; a.wordBase = S.dWordBase; a.windows = S.dWindows; a.bits = S.dBits; a.counters = S.dCounters;
     a.n = n; a.stride = stride; a.linTargets = C.numTargets; a.targets = S.numTargets; a.hitsMin = hitsMin; a.lowest = lowest;
-    if (test) hipLaunchKernelGGL(coverage_mark_kernel<true>, dim3(row_blocks(n)), dim3(kBlock), 0, st, a);
-    else hipLaunchKernelGGL(coverage_mark_kernel<false>, dim3(row_blocks(n)), dim3(kBlock), 0, st, a);
+    if (test) hipLaunchKernelGGL(coverage_mark_kernel<true>, dim3(row_blocks(n, kBlock, kMaxBlocks)), dim3(kBlock), 0, st, a);
+    else hipLaunchKernelGGL(coverage_mark_kernel<false>, dim3(row_blocks(n, kBlock, kMaxBlocks)), dim3(kBlock), 0, st, a);
 }
-
-bool overlap(uintptr_t a0, uintptr_t a1, uintptr_t b0, uintptr_t b1) { return a0 < b1 && b0 < a1; }
 
 }  // namespace
 
@@ -275,20 +247,12 @@ int mc_coverage_add(mc_ctx* ctx, const mc_candidate* cands, uint32_t n, uint32_t
     }
     // host arrays: in pieces of at most 64 MB of candidates through the staging buffer, one caller at a time
     std::lock_guard<std::mutex> lock(S->stageMtx);
-    const uint64_t perRead = (uint64_t)stride * sizeof(mc_candidate);
-    const uint32_t piece = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / perRead));
-    if ((rc = grow(ctx, S->stageIn, piece * perRead)) != MC_OK) return rc;
-    for (uint32_t done = 0; done < n; done += piece) {
-        const uint32_t m = std::min(piece, n - done);
-        HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, cands + (uint64_t)done * stride, m * perRead, hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> state(ctx->coverageMtx);
-            launch_mark(*S, *Cl, (const mc_candidate*)S->stageIn.p, m, stride, hitsMin, lowest, test, st);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return MC_OK;
+    return for_each_staged_piece(ctx, st, S->stageIn, cands, n, stride, [&](const mc_candidate* dRows, uint32_t, uint32_t m) {
+        std::lock_guard<std::mutex> state(ctx->coverageMtx);
+        launch_mark(*S, *Cl, dRows, m, stride, hitsMin, lowest, test, st);
+        HIP_TRY(ctx, hipGetLastError());
+        return (int)MC_OK;
+    });
 }
 
 int mc_coverage_counts(mc_ctx* ctx, uint32_t* covered, uint32_t* windows, uint64_t capacity, uint64_t* numTargets, uint64_t stats[4], int reset)
@@ -297,16 +261,11 @@ int mc_coverage_counts(mc_ctx* ctx, uint32_t* covered, uint32_t* windows, uint64
     CoverageState* S = nullptr; ClassifyState* Cl = nullptr;
     const int rc = ensure_state(ctx, "mc_coverage_counts", &S, &Cl);
     if (rc) return rc;
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->pipe1.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe1.stream));
+    if (const int drc = drain_query_streams(ctx)) return drc;
     const uint32_t nt = S->numTargets;
-    hipEvent_t t0 = nullptr, t1 = nullptr;                                                // mc_timing_enable: "coverage_count_kernel" in mc_timing_get
-    if (ctx->timing && hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess) (void)hipEventRecord(t0, ctx->stream);
-    hipLaunchKernelGGL(coverage_count_kernel, dim3((nt + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream, S->dBits, S->dWordBase, nt, S->dCovered);
-    if (t0 && t1) {
-        (void)hipEventRecord(t1, ctx->stream);
-        std::lock_guard<std::mutex> l(ctx->timerMtx);
-        ctx->timers["coverage_count_kernel"].pending.emplace_back(t0, t1);
+    {
+        ScopedTimer t(ctx, "coverage_count_kernel", ctx->stream);                         // mc_timing_enable: "coverage_count_kernel" in mc_timing_get
+        hipLaunchKernelGGL(coverage_count_kernel, dim3((nt + kWavesPerBlock - 1) / kWavesPerBlock), dim3(kBlock), 0, ctx->stream, S->dBits, S->dWordBase, nt, S->dCovered);
     }
     HIP_TRY(ctx, hipGetLastError());
     std::vector<uint32_t> all(nt);
@@ -315,7 +274,7 @@ int mc_coverage_counts(mc_ctx* ctx, uint32_t* covered, uint32_t* windows, uint64
     HIP_TRY(ctx, hipMemcpyAsync(counters, S->dCounters, sizeof counters, hipMemcpyDeviceToHost, ctx->stream));
     if (reset) {
         HIP_TRY(ctx, hipMemsetAsync(S->dBits, 0, std::max<uint64_t>(S->words, 1) * 4, ctx->stream));
-        HIP_TRY(ctx, hipMemsetAsync(S->dCounters, 0, 2 * 8, ctx->stream));
+        HIP_TRY(ctx, hipMemsetAsync(S->dCounters, 0, kCounterPairBytes, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const uint64_t take = std::min<uint64_t>(capacity, nt);
@@ -392,7 +351,7 @@ int mc_coverage_drop(mc_ctx* ctx, const mc_candidate* in, uint32_t n, uint32_t s
     if (n > 0) {
         if (!in || !out) return fail(ctx, MC_ERR_INVALID, "mc_coverage_drop: null array");
         const uintptr_t bytes = (uintptr_t)n * stride * sizeof(mc_candidate), i0 = (uintptr_t)in, o0 = (uintptr_t)out;
-        if (i0 != o0 && overlap(i0, i0 + bytes, o0, o0 + bytes)) return fail(ctx, MC_ERR_INVALID, "mc_coverage_drop: out overlaps in without being it");
+        if (i0 != o0 && ranges_overlap(i0, i0 + bytes, o0, o0 + bytes)) return fail(ctx, MC_ERR_INVALID, "mc_coverage_drop: out overlaps in without being it");
         if (!(flags & MC_COVERAGE_HOST) && ((i0 | o0) & 15u)) return fail(ctx, MC_ERR_INVALID, "mc_coverage_drop: device arrays must be 16-byte aligned");
     }
     // ... then state
@@ -404,28 +363,22 @@ int mc_coverage_drop(mc_ctx* ctx, const mc_candidate* in, uint32_t n, uint32_t s
         std::lock_guard<std::mutex> state(ctx->coverageMtx);                              // (mc_coverage_set_keep frees the mask under this mutex, after the device has drained)
         if (!S->dKeep) return fail(ctx, MC_ERR_STATE, "mc_coverage_drop: no keep mask (mc_coverage_set_keep)");
         if (n == 0) return MC_OK;
-        hipLaunchKernelGGL(coverage_drop_kernel, dim3(row_blocks(n)), dim3(kBlock), 0, st, in, out, n, stride, S->dKeep, S->keepTargets);
+        hipLaunchKernelGGL(coverage_drop_kernel, dim3(row_blocks(n, kBlock, kMaxBlocks)), dim3(kBlock), 0, st, in, out, n, stride, S->dKeep, S->keepTargets);
         HIP_TRY(ctx, hipGetLastError());
         return MC_OK;
     }
     std::lock_guard<std::mutex> lock(S->stageMtx);
-    const uint64_t perRead = (uint64_t)stride * sizeof(mc_candidate);
-    const uint32_t piece = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / perRead));
-    if ((rc = grow(ctx, S->stageIn, piece * perRead)) != MC_OK) return rc;
-    for (uint32_t done = 0; done < n; done += piece) {
-        const uint32_t m = std::min(piece, n - done);
-        mc_candidate* d = (mc_candidate*)S->stageIn.p;
-        HIP_TRY(ctx, hipMemcpyAsync(d, in + (uint64_t)done * stride, m * perRead, hipMemcpyHostToDevice, st));
+    return for_each_staged_piece(ctx, st, S->stageIn, in, n, stride, [&](const mc_candidate* dRows, uint32_t done, uint32_t m) {
+        mc_candidate* d = const_cast<mc_candidate*>(dRows);                                // (the staging buffer: dropped in place)
         {
             std::lock_guard<std::mutex> state(ctx->coverageMtx);
             if (!S->dKeep) return fail(ctx, MC_ERR_STATE, "mc_coverage_drop: no keep mask (mc_coverage_set_keep)");
-            hipLaunchKernelGGL(coverage_drop_kernel, dim3(row_blocks(m)), dim3(kBlock), 0, st, d, d, m, stride, S->dKeep, S->keepTargets);
+            hipLaunchKernelGGL(coverage_drop_kernel, dim3(row_blocks(m, kBlock, kMaxBlocks)), dim3(kBlock), 0, st, d, d, m, stride, S->dKeep, S->keepTargets);
             HIP_TRY(ctx, hipGetLastError());
         }
-        HIP_TRY(ctx, hipMemcpyAsync(out + (uint64_t)done * stride, d, m * perRead, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return MC_OK;
+        HIP_TRY(ctx, hipMemcpyAsync(out + (uint64_t)done * stride, d, (uint64_t)m * stride * sizeof(mc_candidate), hipMemcpyDeviceToHost, st));
+        return (int)MC_OK;
+    });
 }
 
 }  // extern "C"

@@ -18,7 +18,7 @@
 // The number of passes decides where the block sort writes, so the result always ends in the log itself.
 // target_hits_bounds_kernel: one lane per target, a lower_bound over the sorted log.
 // Plain HIP C++; no inline assembly.
-#include "context.h"
+#include "rows_common.h"
 #include "devcache.h"
 
 #include <algorithm>
@@ -52,14 +52,6 @@ constexpr uint64_t kPad = ~0ull;                                     // (a recor
 static_assert(sizeof(mc_target_hit) == 24, "mc_target_hit is three 64-bit words");
 static_assert((kTile & (kTile - 1)) == 0 && kTile % (2 * kBlock) == 0, "the bitonic network takes a power of two, every thread whole pairs");
 
-int fail(mc_ctx* ctx, int code, const std::string& msg) { ctx->err = msg; return code; }
-
-#define HIP_TRY(ctx, expr)                                                                          \
-    do {                                                                                            \
-        hipError_t e_ = (expr);                                                                     \
-        if (e_ != hipSuccess) return fail((ctx), MC_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct AppendArgs {
     const mc_candidate* cands;
     const uint64_t* queryIds;            // NULL: firstQueryId + i
@@ -71,14 +63,29 @@ struct AppendArgs {
     int lowest;
 };
 
-// the rule of mc_coverage_add: hits >= hits_min and a taxon on rank `lowest` (rank 0) or on the first filled rank from there up
+// the rule of mc_coverage_add: hits >= hits_min and a taxon (taxon_of_target)
 __device__ __forceinline__ bool qualifies(const AppendArgs& a, const uint4 e)
 {
     if (e.y < a.hitsMin || e.x >= a.linTargets) return false;
-    int r = a.lowest;
-    uint32_t t = a.lin[(uint64_t)r * a.linTargets + e.x];
-    if (a.lowest > 0) while (!t && ++r < MC_NUM_RANKS) t = a.lin[(uint64_t)r * a.linTargets + e.x];
-    return t != 0;
+    int r;
+    return taxon_of_target(a.lin, a.linTargets, e.x, a.lowest, r) != 0;
+}
+
+// The wave's sums of target_hits_append_kernel in their __shfl form: device_common.h's DPP forms (wave_incl_scan_u32, wave_sum_u32) need
+// fewer registers here and no ds_bpermute, but the kernel has not been timed with them.
+__device__ __forceinline__ uint32_t wave_incl_scan_shfl(uint32_t v, uint32_t lane)      // inclusive prefix sum over the lanes
+{
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t u = (uint32_t)__shfl_up((int)v, off);
+        if (lane >= (uint32_t)off) v += u;
+    }
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_sum_shfl(uint32_t v)                             // lane 0 holds the sum
+{
+    for (int off = 32; off > 0; off >>= 1) v += (uint32_t)__shfl_down((int)v, off);
+    return v;
 }
 
 __global__ __launch_bounds__(kBlock) void target_hits_append_kernel(AppendArgs a)
@@ -103,13 +110,9 @@ __global__ __launch_bounds__(kBlock) void target_hits_append_kernel(AppendArgs a
                 ++count;
                 if (j < 64u) mask |= 1ull << j;
             }
-        // inclusive prefix sum over the wave's lanes
-        uint32_t incl = count;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = (uint32_t)__shfl_up((int)incl, off);
-            if (lane >= (uint32_t)off) incl += v;
-        }
+        // inclusive prefix sum over the wave's lanes (all 64 are here: blocks are whole waves, kBlock = 256, this loop makes the same trips
+        // for every lane of a block, and the lanes that walked a row have joined the others again)
+        const uint32_t incl = wave_incl_scan_shfl(count, lane);
         const uint32_t total = (uint32_t)__shfl((int)incl, 63);
         unsigned long long first = 0;
         if (lane == 63u && total != 0) first = atomicAdd(&a.counters[0], (unsigned long long)total);    // ONE atomic per wave
@@ -131,8 +134,8 @@ __global__ __launch_bounds__(kBlock) void target_hits_append_kernel(AppendArgs a
             }
         }
     }
-    // counted per wave, one atomic per block
-    for (int off = 32; off > 0; off >>= 1) dropped += (uint32_t)__shfl_down((int)dropped, off);
+    // counted per wave, one atomic per block (all 64 lanes: the row loop is behind every lane of the block)
+    dropped = wave_sum_shfl(dropped);
     if (lane == 0 && dropped) atomicAdd(&blockDropped, dropped);
     __syncthreads();
     if (threadIdx.x == 0 && blockDropped) atomicAdd(&a.counters[1], (unsigned long long)blockDropped);
@@ -282,25 +285,16 @@ int ensure_state(mc_ctx* ctx, const char* who, TargetHitsState** out)
     TargetHitsState& S = *ctx->targetHits;
     *out = &S;
     if (!S.dCounters) {
-        HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, 2 * 8));
-        HIP_TRY(ctx, hipMemset(S.dCounters, 0, 2 * 8));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, kCounterPairBytes));
+        HIP_TRY(ctx, hipMemset(S.dCounters, 0, kCounterPairBytes));
         S.linVersion = ctx->lineageVersion;
     }
     if (S.linVersion != ctx->lineageVersion) {                                            // other lineages: what was recorded under the old ones goes
         HIP_TRY(ctx, hipDeviceSynchronize());
-        HIP_TRY(ctx, hipMemset(S.dCounters, 0, 2 * 8));
+        HIP_TRY(ctx, hipMemset(S.dCounters, 0, kCounterPairBytes));
         S.addCalls = 0; S.sorted = false; S.sortedN = 0;
         S.linVersion = ctx->lineageVersion;
     }
-    return MC_OK;
-}
-
-int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
-{
-    if (bytes <= b.cap) return MC_OK;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
-    HIP_TRY(ctx, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
     return MC_OK;
 }
 
@@ -330,24 +324,8 @@ void launch_append(const TargetHitsState& S, const ClassifyState& C, const mc_ca
     AppendArgs a{};
     a.cands = cands; a.queryIds = ids; a.lin = C.dLin; a.log = S.dLog; a.counters = S.dCounters; a.cap = S.cap; a.firstQueryId = firstId;
     a.n = n; a.stride = stride; a.linTargets = C.numTargets; a.hitsMin = hitsMin; a.lowest = lowest;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(((uint64_t)n + kBlock - 1) / kBlock, kMaxBlocks);
-    hipLaunchKernelGGL(target_hits_append_kernel, dim3(blocks), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(target_hits_append_kernel, dim3(row_blocks(n, kBlock, kMaxBlocks)), dim3(kBlock), 0, st, a);
 }
-
-struct Timed {                           // mc_timing_enable: a kernel sequence between two events on the context's stream
-    mc_ctx* ctx; const char* name; hipEvent_t t0 = nullptr, t1 = nullptr;
-    Timed(mc_ctx* c, const char* n) : ctx(c), name(n)
-    {
-        if (ctx->timing && hipEventCreate(&t0) == hipSuccess && hipEventCreate(&t1) == hipSuccess) (void)hipEventRecord(t0, ctx->stream);
-    }
-    void stop()
-    {
-        if (!t0 || !t1) return;
-        (void)hipEventRecord(t1, ctx->stream);
-        std::lock_guard<std::mutex> l(ctx->timerMtx);
-        ctx->timers[name].pending.emplace_back(t0, t1);
-    }
-};
 
 // the log's first n records in order, in the log itself; `tmp` has room for n records
 void launch_sort(mc_target_hit* log, mc_target_hit* tmp, uint64_t n, hipStream_t st)
@@ -399,7 +377,7 @@ int mc_target_hits_reserve(mc_ctx* ctx, uint64_t capacity)
     const uint64_t stored = std::min<uint64_t>(counters[0], S->cap);
     if (capacity == 0) {
         free_device(*S);
-        HIP_TRY(ctx, hipMemset(S->dCounters, 0, 2 * 8));
+        HIP_TRY(ctx, hipMemset(S->dCounters, 0, kCounterPairBytes));
         S->addCalls = 0;
         return MC_OK;
     }
@@ -437,9 +415,8 @@ int mc_target_hits_add(mc_ctx* ctx, const mc_candidate* cands, const uint64_t* q
     }
     // host arrays: room for every entry first (all or nothing), then in pieces of at most 64 MB of candidates through the staging buffers
     std::lock_guard<std::mutex> lock(S->stageMtx);
-    const uint64_t perRead = (uint64_t)stride * sizeof(mc_candidate);
-    const uint32_t piece = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n, (64ull << 20) / perRead));
-    if ((rc = grow(ctx, S->stageIn, piece * perRead)) != MC_OK) return rc;
+    const uint32_t piece = staged_piece_rows(n, stride);
+    if ((rc = grow(ctx, S->stageIn, staged_piece_bytes(n, stride))) != MC_OK) return rc;      // (here already: both buffers before the log is touched)
     if (queryIds && (rc = grow(ctx, S->stageIds, (uint64_t)piece * 8)) != MC_OK) return rc;
     {
         std::lock_guard<std::mutex> state(ctx->targetHitsMtx);
@@ -458,18 +435,13 @@ int mc_target_hits_add(mc_ctx* ctx, const mc_candidate* cands, const uint64_t* q
         S->sorted = false;
         ++S->addCalls;
     }
-    for (uint32_t done = 0; done < n; done += piece) {
-        const uint32_t m = std::min(piece, n - done);
-        HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, cands + (uint64_t)done * stride, m * perRead, hipMemcpyHostToDevice, st));
+    return for_each_staged_piece(ctx, st, S->stageIn, cands, n, stride, [&](const mc_candidate* dRows, uint32_t done, uint32_t m) {
         if (queryIds) HIP_TRY(ctx, hipMemcpyAsync(S->stageIds.p, queryIds + done, (uint64_t)m * 8, hipMemcpyHostToDevice, st));
-        {
-            std::lock_guard<std::mutex> state(ctx->targetHitsMtx);
-            launch_append(*S, *Cl, (const mc_candidate*)S->stageIn.p, queryIds ? (const uint64_t*)S->stageIds.p : nullptr, firstQueryId + done, m, stride, hitsMin, lowest, st);
-            HIP_TRY(ctx, hipGetLastError());
-        }
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-    }
-    return MC_OK;
+        std::lock_guard<std::mutex> state(ctx->targetHitsMtx);
+        launch_append(*S, *Cl, dRows, queryIds ? (const uint64_t*)S->stageIds.p : nullptr, firstQueryId + done, m, stride, hitsMin, lowest, st);
+        HIP_TRY(ctx, hipGetLastError());
+        return (int)MC_OK;
+    });
 }
 
 int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacityTargets, uint64_t* numTargets, mc_target_hit* records, uint64_t capacityRecords,
@@ -483,8 +455,7 @@ int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacityTarg
     if ((rc = ensure_classify_state(ctx, &Cl)) != MC_OK) return rc;
     std::lock_guard<std::mutex> lock(ctx->targetHitsMtx);
     hipStream_t st = ctx->stream;
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (ctx->pipe1.stream) HIP_TRY(ctx, hipStreamSynchronize(ctx->pipe1.stream));
+    if ((rc = drain_query_streams(ctx)) != MC_OK) return rc;
     unsigned long long counters[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpy(counters, S->dCounters, sizeof counters, hipMemcpyDeviceToHost));
     const uint64_t n = std::min<uint64_t>(counters[0], S->cap), nt = Cl->numTargets;
@@ -502,9 +473,7 @@ int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacityTarg
                 (void)hipGetLastError();
                 return fail(ctx, MC_ERR_NOMEM, "mc_target_hits_collect: the device has no room for the sort's second buffer (" + std::to_string(n) + " records)");
             }
-            Timed t(ctx, "target_hits_sort");
-            launch_sort(S->dLog, tmp, n, st);
-            t.stop();
+            { ScopedTimer t(ctx, "target_hits_sort", st); launch_sort(S->dLog, tmp, n, st); }
             const hipError_t e = hipGetLastError();
             const hipError_t e2 = hipStreamSynchronize(st);
             if (tmp) (void)big_free(tmp);
@@ -512,12 +481,8 @@ int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacityTarg
             HIP_TRY(ctx, e2);
         }
         S->sorted = true; S->sortedN = n;
-        {
-            Timed t(ctx, "target_hits_bounds");
-            hipLaunchKernelGGL(target_hits_bounds_kernel, dim3((uint32_t)((nt + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, S->dLog, n, (uint32_t)nt, S->dOffsets);
-            t.stop();
-            HIP_TRY(ctx, hipGetLastError());
-        }
+        { ScopedTimer t(ctx, "target_hits_bounds", st); hipLaunchKernelGGL(target_hits_bounds_kernel, dim3((uint32_t)((nt + 1 + kBlock - 1) / kBlock)), dim3(kBlock), 0, st, S->dLog, n, (uint32_t)nt, S->dOffsets); }
+        HIP_TRY(ctx, hipGetLastError());
         off.resize(nt + 1);
         HIP_TRY(ctx, hipMemcpyAsync(off.data(), S->dOffsets, (nt + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -537,7 +502,7 @@ int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacityTarg
         if (records && n) HIP_TRY(ctx, hipMemcpy(records, S->dLog, n * sizeof(mc_target_hit), hipMemcpyDeviceToHost));
     }
     if (reset) {
-        HIP_TRY(ctx, hipMemset(S->dCounters, 0, 2 * 8));
+        HIP_TRY(ctx, hipMemset(S->dCounters, 0, kCounterPairBytes));
         S->addCalls = 0; S->sorted = false; S->sortedN = 0;
     }
     return MC_OK;

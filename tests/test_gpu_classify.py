@@ -314,6 +314,42 @@ def test_two_streams_tally_at_the_same_time_and_reset_clears():
         db.close()
 
 
+def test_host_arrays_beyond_one_staged_piece_equal_the_device_path():
+    """MC_CLASSIFY_HOST stages 64 MB pieces: 2^20 rows of stride 4; one row more starts a second piece, whose assignments go to
+    out + 2^20.  The last row's taxon is one that no other row can be given."""
+    import torch
+    NT, stride = 5000, 4
+    piece = (64 << 20) // (stride * 16)
+    n = piece + 1
+    rng = np.random.default_rng(4242)
+    lin = random_lineages(rng, NT)
+    own = NT - 1
+    lin[own, 0] = own + 1                                                    # the sequence-level taxon of `own`: only a row whose top candidate is `own` can get it
+    rows = random_rows(rng, n, stride, NT)
+    rows["tgt"][:, 0][rows["tgt"][:, 0] == own] = 0
+    rows[n - 1] = np.zeros(stride, dtype=api.cand_dtype)
+    rows[n - 1, 0] = (own, 50, 0, 3)
+    opt = dict(hitmin=5, hitdiff=0.5, lowest=0, highest=19)
+    dev = torch.device("cuda", 0)
+    db = api.Database.open(os.path.join(GOLDEN, "toy32"))
+    try:
+        db.set_lineages(lin)
+        dcands = torch.from_numpy(rows.view(np.uint32).reshape(n, stride * 4).view(np.int32)).to(dev)
+        out = torch.empty((n, 2), dtype=torch.int32, device=dev)
+        torch.cuda.synchronize()
+        device_vote(db, torch, dcands, n, stride, out, **opt)
+        db.synchronize()
+        want = as_triples(out.cpu().numpy().view(api.assignment_dtype).reshape(n))
+        got = as_triples(db.classify_candidates(rows, **opt))
+        bad = np.flatnonzero((got != want).any(axis=1))
+        assert bad.size == 0, (bad.size, int(bad[0]), got[bad[0]], want[bad[0]])
+        at = [n - 2, n - 1, 2 ** 20 - 1]
+        assert np.array_equal(got[at], classify_ref.vote_all(lin, rows[at], 5, api.hitdiff_factor(0.5), 0, 19))
+        assert got[n - 1].tolist() == [own + 1, 0, 1] and (got[: n - 1, 0] != own + 1).all()
+    finally:
+        db.close()
+
+
 # ---- composition with the query ----------------------------------------------------------------------------------------------------
 def _device_batch(db, reads, dev):
     import torch

@@ -381,6 +381,31 @@ def test_drop(table):
     assert table.db.coverage_drop(np.zeros((0, 3), dtype=api.cand_dtype)).shape == (0, 3)
 
 
+def test_drop_of_host_arrays_beyond_one_staged_piece(table):
+    """MC_COVERAGE_HOST stages 64 MB pieces: 2^20 rows of stride 4; one row more starts a second piece, which goes to out + 2^20 rows"""
+    torch = table.torch
+    rng = np.random.default_rng(33)
+    stride = 4
+    n = (64 << 20) // (stride * 16) + 1
+    nt = len(table.windows)
+    c = random_rows(rng, n, stride, table.windows, len(table.lin))
+    mask = (rng.random(nt) < 0.5).astype(np.uint8)
+    kept = int(np.flatnonzero(mask)[0])
+    c[n - 1] = rows_of([[(kept, 9, 1, 2), (int(np.flatnonzero(mask == 0)[0]), 8, 3, 4), (kept, 7, 5, 6)]], stride)[0]       # the second piece: its middle entry goes
+    table.db.coverage_set_keep(mask)
+    want = coverage_ref.drop(c, mask)
+    assert want["hits"][n - 1].tolist() == [9, 7, 0, 0] and 0.2 < (want["hits"] > 0).sum() / (c["hits"] > 0).sum() < 0.8
+    got = table.db.coverage_drop(c)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (bad.size, int(bad[0]), got[bad[0]], want[bad[0]])
+    d_in = table.to_device(c)
+    d_out = torch.full_like(d_in, -1)
+    torch.cuda.synchronize()
+    table.db.coverage_drop_device(d_in.data_ptr(), n, stride, d_out.data_ptr())
+    table.db.synchronize()
+    assert np.array_equal(table.to_host(d_out, n, stride), got)
+
+
 # ---- end to end on the toy database ----------------------------------------------------------------------------------------------------
 def read_fasta(path):
     reads, cur = [], None

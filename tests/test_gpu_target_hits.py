@@ -274,6 +274,38 @@ def test_host_mode_beyond_target_hits_max_mb_adds_nothing(table):
         table.db.set_tuning("target_hits_max_mb", 8192)
 
 
+@pytest.mark.parametrize("with_ids", [True, False])
+def test_host_mode_beyond_one_staged_piece_numbers_the_queries_of_the_second_piece(table, with_ids):
+    """MC_TARGET_HITS_HOST stages 64 MB pieces: 2^20 rows of stride 4; one row more starts a second piece, which reads query_ids + 2^20
+    or counts on from first_query_id + 2^20.  All rows are empty but a handful on both sides of the border (the last row is the second
+    piece), so the model only has to look at those; every filled row has a `beg` of its own to find its records by."""
+    stride = 4
+    piece = (64 << 20) // (stride * 16)
+    n = piece + 1
+    rng = np.random.default_rng(15)
+    g = good_targets(table.lin)
+    bad = int(np.flatnonzero(ref.tax_all(table.lin, np.arange(len(table.lin)), 0) == 0)[0])
+    filled = [0, 77, piece - 3, piece - 2, piece - 1, n - 1]
+    cands = np.zeros((n, stride), dtype=api.cand_dtype)
+    for k, r in enumerate(filled):
+        beg = 1000 + k
+        cands[r] = rows_of([[(int(g[k]), 9, beg, beg + 1), (bad, 9, beg, beg), (int(g[-1 - k]), 8, beg, beg + 2), (int(g[k]), 7, beg, beg + 3)][: 1 + (k + 3) % stride]], stride)[0]
+    first = BIG * 3 + 11
+    ids = rng.integers(0, 2 ** 64, size=n, dtype=np.uint64) if with_ids else None
+    query_of = (lambda r: int(ids[r])) if with_ids else (lambda r: first + r)
+    rec = ref.records_of(table.lin, cands[filled], 0, 0, np.array([query_of(r) for r in filled], dtype=np.uint64))
+    assert len(filled) < len(rec) < len(filled) * stride
+    table.empty(0)                                                         # (the call reserves n * stride records: 100 MB)
+    try:
+        table.db.target_hits_add(cands, ids, first_query_id=first)
+        off, got = table.check(rec)
+        for k, r in enumerate(filled):
+            mine = got[got["beg"] == 1000 + k]
+            assert len(mine) > 0 and (mine["query"] == np.uint64(query_of(r))).all(), (r, mine)
+    finally:
+        table.empty(0)
+
+
 # ---- the sort ------------------------------------------------------------------------------------------------------------------------------
 def passes_of(n, tile):
     tiles, p = -(-n // tile), 0
