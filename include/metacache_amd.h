@@ -422,6 +422,12 @@ int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, 
  * "gw_big_h" (reads beyond this many locations take the fine-block instance of the stream filter; default 32 768, 0 = none),
  * "lane_fusion" (sketching + lookups of the lane path in one kernel: -1 = on tables beyond 1 GiB (default), 0 / 1 = never / always),
  * "direct_index" (-1 by table size, 0 / 1; on a loaded table the index is built or dropped at once: mc_table_layout),
+ * "filter_lookup" (the lane path's direct-index lookups inside the filter kernel, the lane kernel only sketches: -1 (default) = on tables
+ *   with the compact store whose direct index the size rule built (bucket table of 8 GiB or more), for calls that launch every kernel
+ *   without a host look at the work-list counters (MC_DEFER_TAIL or more than 2^20 reads), ask for top candidates only and give ONE window
+ *   range of at most 3 for all reads (max_win NULL: single reads of up to two windows -- the batches it was measured faster on; batches
+ *   with a range per read were measured slower with it, read pairs not at all);
+ *   0 = never; 1 = wherever a direct index exists, whatever the batch size -- tests and A/B runs),
  * "list_align" (before the table is loaded: the compact store's lists on 128-byte lines of their own, mc_table_layout).
  * Every value of every switch gives the same results (tests/test_gpu_variants.py and the variant loops of test_gpu_scale.py /
  * test_gpu_reference_midscale.py run them against the goldens, the oracle and the reference). */

@@ -870,16 +870,26 @@ static int run_sorted_tail(mc_ctx* ctx, Pipe& P, BatchRun& r, bool counterCopied
 // in kListFilter: filter -> counting -> [segmented sort -> scan of the sorted lists].
 // second (8-byte store): reads beyond the first filter's reach take its second instance.
 // deferSorted: the sorted class is left to the caller (mc_query_finish runs run_sorted_tail).
-static int run_filtered_path(mc_ctx* ctx, Pipe& P, BatchRun& r, bool second, bool deferSorted = false)
+// The path's first step alone: the filter (compact store, "filter_lookup": followed by gw_filter_count_kernel<LOOKUP> inside the SAME pair of
+// timer events -- the timer's count stays one per batch).  The caller launches what waits for the LOOKUP instance's work lists (the mid / hash
+// kernels) between this and run_filtered_path(.., filterDone = true).
+static void run_filter_step(mc_ctx* ctx, BatchRun& r)
+{
+    ScopedTimer t(ctx, r.compact ? (r.ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", r.st);
+    launch_big_cands(FilterStep::Filter, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
+    if (r.compact && r.ws.filterLookup) launch_big_cands(FilterStep::FilterLookup, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
+}
+
+static int run_filtered_path(mc_ctx* ctx, Pipe& P, BatchRun& r, bool second, bool deferSorted = false, bool filterDone = false)
 {
     // timers carry the kernels' own names, one kernel each (a bench line's dominant "kernel" must be one): compact store gw_filter_count_kernel
     // (or gw_filter_kernel with "gw_fuse" 0), gw_filter2, gw_compact (+ the ordering of the stream filter's reads), gw_filter_stream<fine>,
     // <mid>, gw_filter_stream (+ the second compaction), gw_count_kernel<9>, <10>, <11>; 8-byte store: big_*
     // (compact store: gw_filter_kernel itself may leave reads to the second kernel -- it counts them on the device, after the
     // host's look at the counters: always launched, returns at once with nothing to do)
+    if (!filterDone) run_filter_step(ctx, r);
     const bool compact = r.compact, always = true, compactOnly = compact, wideSecond = !compact && second;   // when a step runs
     const struct { FilterStep step; const char* timer; bool when; } steps[] = {
-        {FilterStep::Filter, compact ? (r.ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", always},
         {FilterStep::PairFilter, "gw_filter2", compactOnly},
         {FilterStep::Compact, "gw_compact", compactOnly},
         {FilterStep::StreamFine, "gw_filter_stream_fine", compactOnly},
@@ -1091,7 +1101,24 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         const bool maskFeatures = wantPartial && !wantFeatures && ctx->cfg.key_shard_count > 1;
         const bool quadTable = ctx->quadLookup >= 0 ? ctx->quadLookup != 0 : (uint64_t)tab.nbuckets * 64ull > (1ull << 30);
         const bool fuseSketch = !maskFeatures && (ctx->fuseLane >= 0 ? ctx->fuseLane != 0 : quadTable);
-        if (fuseSketch) {
+        // "filter_lookup": the lookups of reads of up to 64 features inside the filter kernel (gw_filter_count_kernel<LOOKUP>, behind the wave
+        // kernel's rejoin); the lane kernel only sketches, the mid / hash kernels wait for the filter's work lists.  Every kernel is launched
+        // without a look at the counters.  -1: tables whose direct index the size rule built (bucket table of 8 GiB or more), on batches that
+        // skip the host's look anyway (MC_DEFER_TAIL or more than 2^20 reads); 1: wherever a direct index exists (tests, A/B runs); 0: never.
+        const bool noHostLook = (flags & MC_DEFER_TAIL) != 0 || n > (1u << 20);
+        // (auto only for the batches it was measured on and won: one window range for all reads, of at most 3 windows -- single reads of up to
+        // two windows.  Batches with a window range per read (long reads, mixed lengths) were measured 1.5 ms per step SLOWER with it, read pairs
+        // (range 4) have not been measured: both keep the old order.  docs/LAB_NOTEBOOK_r07.md section 5)
+        const bool shortSingles = in->max_win == nullptr && in->max_win_uniform <= 3u;
+        const bool filterLookup = T.compact && tab.direct && !wantPartial && !wantAllhits && !maskFeatures && ctx->gwFuse == 1 &&
+                                  (ctx->filterLookup > 0 || (ctx->filterLookup < 0 && noHostLook && shortSingles && (uint64_t)T.nbuckets * sizeof(TableBucket) >= (8ull << 30)));
+        ws.filterLookup = filterLookup ? 1u : 0u;
+        if (filterLookup) {
+            { ScopedTimer t(ctx, "sketch_lane", st); launch_sketch_lane(b, sp, ws, st); }
+            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
+            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
+            { ScopedTimer t(ctx, "probe_cands", st); launch_probe_cands(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }   // (reads of more than 64 features)
+        } else if (fuseSketch) {
             { ScopedTimer t(ctx, "sketch_probe", st); launch_sketch_probe_lane(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
             { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
             { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
@@ -1113,7 +1140,7 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         none[kCntWaveSketch] = none[kCntWaveCands] = 1;
         uint32_t* hcnt = wantPartial ? none : all;
         // (MC_DEFER_TAIL: no look at the counters either -- everything is launched, the caller has another batch to enqueue)
-        if (!wantPartial && n <= (1u << 20) && !(flags & MC_DEFER_TAIL)) {
+        if (!wantPartial && n <= (1u << 20) && !(flags & MC_DEFER_TAIL) && !filterLookup) {
             if ((rc = ensure_host_words(ctx, P))) return rc;
             hcnt = reinterpret_cast<uint32_t*>(P.hTotal + 1);
             launch_flag_count_host(ws, n, hcnt, st);
@@ -1127,7 +1154,7 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
             if (hcnt[kCntHash512]) { ScopedTimer t(ctx, "hash_cands_512", st); launch_hash_cands(kListHash512, b, tab, ws, K, taxkey, P.bCands.p, st); }
             if (hcnt[kCntHash1024]) { ScopedTimer t(ctx, "hash_cands_1024", st); launch_hash_cands(kListHash1024, b, tab, ws, K, taxkey, P.bCands.p, st); }
         };
-        mid_and_hash();
+        if (!filterLookup) mid_and_hash();
         bool waveDone = false;
         if (T.compact && !wantPartial && hcnt[kCntWaveSketch]) {
             // compact store: the wave kernel's sketching and probing first, so that its reads can join the filtered path
@@ -1150,7 +1177,8 @@ static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lo
         // small batches: the sorted class's counter is looked at together with the wave tail's total (run_wave_tail: one round trip for both)
         sortedInTail = hcnt != all && !defer && T.compact && waveWork && (hcnt[kCntFilter] || waveDone);
         if (hcnt[kCntFilter] || waveDone) {
-            if ((rc = run_filtered_path(ctx, P, run, hcnt[kCntSecond] != 0, defer || sortedInTail))) return rc;
+            if (filterLookup) { run_filter_step(ctx, run); mid_and_hash(); }     // (the mid / hash kernels' lists are the LOOKUP instance's)
+            if ((rc = run_filtered_path(ctx, P, run, hcnt[kCntSecond] != 0, defer || sortedInTail, filterLookup))) return rc;
         }
         run.skipWaveSketch = waveDone;                           // (the wave kernels' sketching and probing has run already)
         if (defer) {
@@ -1462,6 +1490,7 @@ int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value)
         }
     }
     else if (n == "list_align") ctx->listAlignWant = value < 0 ? -1 : (value != 0);   // before the table is loaded: lists of the compact store on lines of their own
+    else if (n == "filter_lookup") ctx->filterLookup = value < 0 ? -1 : (value != 0);   // the lane path's direct-index lookups inside the filter kernel (-1: size-built index, batches without the host's look at the counters)
     else if (n == "lane_fusion") ctx->fuseLane = value < 0 ? -1 : (value != 0);   // sketch + probe of the lane path in one kernel (-1: where the lookups are quad-cooperative)
     else if (n == "gw_mid_h") ctx->gwMidH = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 32768));   // reads up to this many locations: the stream filter's small-filter instance (0 = none; default 8 192)
     else if (n == "gw_big_h") ctx->gwBigH = value <= 0 ? 0xFFFFFFFFu : (uint32_t)std::min<int64_t>(value, 0xFFFFFFFFll);   // reads beyond this many locations: the stream filter's fine-block instance (0 = none; default 32 768)

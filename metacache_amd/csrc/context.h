@@ -250,6 +250,8 @@ struct mc_ctx {
                                            // lowers it to 1 / (parts it still has to place on the device) -- mcamd::open_hints
     int directWant = -1;                   // direct-address index beside the buckets: -1 = for tables whose buckets take 8 GiB and more, where 34 GB + head-room are free;
                                            // 0 / 1 (mc_set_tuning "direct_index" before the table is loaded, MC_DIRECT_INDEX)
+    int filterLookup = -1;                 // the lane path's direct-index lookups inside gw_filter_count_kernel<LOOKUP>: -1 = tables whose index the size rule built, on batches
+                                           // launched without the host's look at the counters; 0 / 1 = never / wherever an index exists (mc_set_tuning "filter_lookup")
     int fuseLane = -1;                     // sketching + probing of the lane path in ONE kernel: -1 = where the lookups are quad-cooperative (tables beyond 1 GiB: the
                                            // probing waits for HBM and the sketching runs under it: 5.27 -> 5.08 ms per 5 x 10^6 reads at full scale), 0 / 1 = never / always
                                            // (MC_LANE_FUSION, mc_set_tuning "lane_fusion"); small tables: 5 % slower on configs[1] (ALU phase at the probe kernel's occupancy)

@@ -1180,9 +1180,17 @@ constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: th
 // per SIMD, 13.3 -> 12.0 ms per 5 x 10^6 reads (WPE = 6; the kernel waits for its LDS round trips and its lists 45 % of its wave cycles:
 // a sixth wave fills them).  (A software-pipelined form -- the next read's loads issued as phase B frees the registers -- needed
 // 127 registers = four waves per SIMD and was slower, 14.95 against 13.1 ms per 5 x 10^6 reads; removed in round 5, docs/LAB_NOTEBOOK_r04.md.)
-template <uint32_t WAVES, uint32_t TLOG2, bool TAX, uint32_t WPE = MC_GW_FILTER_WPE>
+//
+// LOOKUP (round 7, "filter_lookup"): the kernel walks the READS the lane kernel sketched (kFlagProbe, at most 64 features) instead of the
+// records of kListFilter and does the direct-index lookups itself, one lane per feature -- the lane that loaded the hand-over entry of a
+// found feature now loads the index entry of feature `lane`, two reads ahead: the read's features (i + 2), their index entries (i + 1),
+// the entries of read i in registers.  The random 8-byte requests move from the lookup kernel, which runs at the request rate, into this
+// one, whose memory side is half idle.  The read's statistics, its hand-over entries (found features only, singletons first; the slots
+// up to nf cleared) and its class are written as probe_cands_one does; reads of another class go to their work lists, reads of this class
+// that the kernel does not finish get a record of kListFilter / kListFiltered (appended: one atomic each, they are few).
+template <uint32_t WAVES, uint32_t TLOG2, bool TAX, uint32_t WPE = MC_GW_FILTER_WPE, bool LOOKUP = false>
 __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchView b, DeviceTable tab, Workspace ws, uint32_t K, const uint32_t* __restrict__ taxkey,
-                                                                                 mc_candidate_dev* __restrict__ cands)
+                                                                                 mc_candidate_dev* __restrict__ cands, const uint32_t s)
 {
     using Bloom = GwBloom<TLOG2, TLOG2>;
     constexpr uint32_t kKeep = WPE >= 6 ? 384 : 512;               // numbers kept in LDS: the counting takes them when at most 256 are distinct
@@ -1199,36 +1207,118 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     uint32_t* bits = bitS[wave];
     uint64_t* T = kSeven ? reinterpret_cast<uint64_t*>(bits) : roundS[kSeven ? 0 : wave];
     uint32_t* kept = keptS[wave];
-    const uint32_t total = ws.midCount[kCntFilter];
-    const uint4* __restrict__ work = ws.midList + list_at(kListFilter, b.n);
+    const uint32_t total = LOOKUP ? b.n : ws.midCount[kCntFilter];
+    uint4* const work = ws.midList + list_at(kListFilter, b.n);
     uint4* __restrict__ outRec = ws.midList + list_at(kListFiltered, b.n);
     const uint32_t nWaves = gridDim.x * WAVES;
     const uint32_t w0 = blockIdx.x * WAVES + wave;
-    auto load_rec = [&](uint32_t w) -> uint4 { return w < total ? work[w] : make_uint4(0, 0, 0, 0); };
+    auto load_rec = [&](uint32_t w) -> uint4 { return (!LOOKUP && w < total) ? work[w] : make_uint4(0, 0, 0, 0); };
     const uint64_t sliceCap = ws.bigPoolCap / nWaves;
     uint32_t* const slice = reinterpret_cast<uint32_t*>(ws.bigPool) + (uint64_t)w0 * sliceCap;
-    uint64_t sliceUsed = 0;
+    uint64_t sliceUsed = (LOOKUP && ws.sliceFill) ? ws.sliceFill[w0] : 0u;   // (LOOKUP: behind what the launch over kListFilter left in the slice)
     uint32_t deferred = 0;
     uint4 rec = load_rec(w0), recNext = load_rec(w0 + nWaves);
     uint32_t esz = 0; uint64_t epay = 0;
     auto load_entries = [&](const uint4& r) {
+        if constexpr (LOOKUP) return;
         const uint32_t ne = (r.z >> 12) <= kGwSmallH ? min(r.z & 0xFFFu, 64u) : 0u;
         esz = lane < ne ? ws.psize[r.y + lane] : 0u;
         epay = lane < ne ? ws.ppay[r.y + lane] : 0ull;
     };
     load_entries(rec);
+    // LOOKUP: {first feature slot, features} of reads i, i + 1, i + 2 (m0, m1, m2; kLkSkip: not this kernel's read), the index entries of
+    // read i + 1 (lkEnt: they are read i's when the loop takes them), the features of read i + 2 (lkFeat), how many features a read has (lkNfeat)
+    // (a form that loaded the reads' offsets and flags 64 reads at a time, one per lane, and handed them out by v_readlane held two more
+    // registers: 20 instead of 14 spilled, +0.3 ms per 5 x 10^6 reads; docs/LAB_NOTEBOOK_r07.md)
+    constexpr uint32_t kLkSkip = 0xFFFFFFFFu;
+    auto load_meta = [&](uint32_t q) -> uint2 {
+        if (!LOOKUP || q >= b.n) return make_uint2(kLkSkip, 0u);
+        const uint32_t o0 = ws.winOff[q], nf = (ws.winOff[q + 1] - o0) * s;
+        return (ws.qflag[q] == kFlagProbe && nf <= 64u) ? make_uint2(o0 * s, nf) : make_uint2(kLkSkip, 0u);
+    };
+    auto load_feat = [&](const uint2& m) -> uint32_t { return (m.x != kLkSkip && lane < m.y) ? ws.features[m.x + lane] : 0xFFFFFFFFu; };
+    uint2 m0 = load_meta(w0), m1 = load_meta(w0 + nWaves), m2 = load_meta(w0 + 2 * nWaves);
+    uint32_t lkFeat = 0xFFFFFFFFu, lkNfeat = 0; uint64_t lkEnt = 0;
+    if constexpr (LOOKUP) {
+        const uint32_t f0 = load_feat(m0);
+        lkFeat = load_feat(m1);
+        lkNfeat = (uint32_t)__popcll(__ballot(f0 != 0xFFFFFFFFu));
+        lkEnt = f0 != 0xFFFFFFFFu ? tab.direct[f0] : 0ull;
+    }
     const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
     GwPend P;
     for (uint32_t w = w0; w < total; w += nWaves) {
-        const uint32_t q = rec.x, nent = rec.z & 0xFFFu, H = rec.z >> 12, maxWin = rec.w;
-        const uint32_t sz = esz & 0xFFFFu; const uint64_t pay = epay;
-        rec = recNext;
-        recNext = load_rec(w + 2 * nWaves);
-        load_entries(rec);
+        uint32_t q, nent, H, maxWin, sz, fbase = 0; uint64_t pay;
+        uint32_t rix = 0xFFFFFFFFu;                                // LOOKUP: the read's record in kListFilter, made when something is left to the later kernels
+        if constexpr (!LOOKUP) {
+            q = rec.x; nent = rec.z & 0xFFFu; H = rec.z >> 12; maxWin = rec.w;
+            sz = esz & 0xFFFFu; pay = epay;
+            rec = recNext;
+            recNext = load_rec(w + 2 * nWaves);
+            load_entries(rec);
+        } else {
+            const uint2 cur = m0; const uint64_t e = lkEnt; const uint32_t nfeat = lkNfeat;
+            lkNfeat = (uint32_t)__popcll(__ballot(lkFeat != 0xFFFFFFFFu));
+            lkEnt = lkFeat != 0xFFFFFFFFu ? tab.direct[lkFeat] : 0ull;
+            lkFeat = load_feat(m2);
+            m0 = m1; m1 = m2; m2 = load_meta(w + 3 * nWaves);
+            if (cur.x == kLkSkip) continue;
+            q = w; fbase = cur.x;
+            sz = (uint32_t)e & 0xFFFFu; pay = direct_payload(e);
+            const uint64_t fm = __ballot(sz != 0u), sm = __ballot(sz == 1u);
+            nent = (uint32_t)__popcll(fm);
+            const uint32_t n1 = (uint32_t)__popcll(sm), lsz = sz > 1u ? sz : 0u;
+            const uint32_t lincl = wave_incl_scan_u32(lsz, lane);
+            H = n1 + rdlane(lincl, 63);
+            maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+            if (lane == 0) { QueryStat qs; qs.hits = H; qs.nfeat = nfeat; qs.nfound = nent; qs.nsteps = nfeat; ws.qstat[q] = qs; }
+            if (H == 0) {                                          // nothing found: empty candidates, as the lane kernel leaves them
+                if (lane < K) { mc_candidate_dev ev; ev.tgt = 0xFFFFFFFFu; ev.hits = 0; ev.beg = 0; ev.end = 0; cands[(size_t)q * K + lane] = ev; }
+                if (lane == 0) { ws.hitScan[q] = 0u; ws.qflag[q] = kFlagDone; }
+                continue;
+            }
+            {   // the hand-over entries (size | list offset << 16, payload): found features only, singletons first; the slots up to nf cleared
+                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+                const uint32_t sbelow = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+                if (sz != 0u) {
+                    const uint32_t slot = sz == 1u ? sbelow : n1 + (below - sbelow);
+                    const uint32_t off = sz == 1u ? slot : n1 + lincl - lsz;
+                    ws.psize[fbase + slot] = sz | ((off & 0xFFFu) << 16);
+                    ws.ppay[fbase + slot] = pay;
+                } else if (lane < cur.y) ws.psize[fbase + nent + (lane - below)] = 0u;
+            }
+            // the read's class (probe_cands_one); lists up to kLaneHits, which a lane of the lookup kernel finishes itself, are mid_cands_kernel<4>'s
+            const bool hashOK = nent <= kHashEnt && maxWin <= kHashWin;
+            const bool bigOK = H > ws.bigMin && H > 64u && nent <= 0xFFFu && maxWin <= tab.gwGap && H <= kMaxHitsPerQuery;
+            const uint32_t cls = bigOK ? kClassFilter : H <= 64 ? kListMid64 : H <= 128 ? (hashOK ? kListHash256 : kListMid128) : H <= kMidMax ? (hashOK ? kListHash256 : kListMid256)
+                               : (H <= kHashMax && hashOK) ? (H <= kHashMax / 2 ? kListHash512 : kListHash1024) : kClassWave;
+            if (lane == 0) {
+                ws.hitScan[q] = (H <= kMaxHitsPerQuery && H > kLdsCap && !(cls >= kListHash512 && cls != kClassWave)) ? H : 0u;
+                ws.qflag[q] = cls != kClassWave ? kFlagMid : kFlagCands;
+                if (cls != kClassWave && cls != kClassFilter) {
+                    const uint32_t at = atomicAdd(&ws.midCount[class_counter(cls)], 1u);
+                    ws.midList[list_at(class_list(cls), b.n) + at] = make_uint4(q, fbase, nent | (H << 12), maxWin);
+                }
+            }
+            if (cls != kClassFilter) continue;
+        }
+        // the read's place in kListFilter / kListFiltered
+        auto slot_of = [&]() -> uint32_t {
+            if constexpr (!LOOKUP) return w;
+            else {
+                if (rix == 0xFFFFFFFFu) {
+                    uint32_t at = 0;
+                    if (lane == 0) { at = atomicAdd(&ws.midCount[kCntFilter], 1u); work[at] = make_uint4(q, fbase, nent | (H << 12), maxWin); }
+                    rix = rdlane(at, 0);
+                }
+                return rix;
+            }
+        };
         const uint32_t myR = sz > 1 ? (sz + 15u) >> 4 : 0u;
         const uint32_t incl = wave_incl_scan_u32(myR, lane), Rc = rdlane(incl, 63);
         if (H > kGwSmallH || nent > 64u || Rc > kGwRounds || maxWin > tab.gwGap || sliceCap - sliceUsed < kGwRounds * 16u + 64u) {
-            if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwDefer, maxWin);
+            const uint32_t at = slot_of();
+            if (lane == 0) outRec[at] = make_uint4(q, 0u, kGwDefer, maxWin);
             ++deferred;
             continue;
         }
@@ -1274,15 +1364,19 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             n2 = S.n2;
         }
         if (here && n2 <= kKeep) {
-            if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwCounted | n2, maxWin);
+            if constexpr (!LOOKUP) { if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwCounted | n2, maxWin); }   // (LOOKUP: a read finished here has no record)
             wave_lds_sync();
-            const bool counted = gw_count_read<9, TAX, true, true>(q, [&]() -> uint2 { const uint4 r6 = work[w]; return make_uint2(r6.y, r6.z & 0xFFFu); }, n2, maxWin,
+            const bool counted = gw_count_read<9, TAX, true, true>(q, [&]() -> uint2 {
+                                            if constexpr (LOOKUP) { wave_mem_sync(); return make_uint2(fbase, nent); }   // (the entries are this wave's own stores)
+                                            else { const uint4 r6 = work[w]; return make_uint2(r6.y, r6.z & 0xFFFu); }
+                                        }, n2, maxWin,
                                         [&](uint32_t r) -> uint32_t { return r * 64 + lane < n2 ? kept[r * 64 + lane] : kGwNone; },
                                         reinterpret_cast<uint2*>(bits), kSeven ? kept : reinterpret_cast<uint32_t*>(T), kSeven ? reinterpret_cast<uint64_t*>(kept) : T,
                                         lane, grp, sub4, K, taxkey, tab, ws, cands, P);
             if (!counted && kSeven) {
                 // (the kept numbers' place went to the counting: the read is filtered again by gw_filter2_kernel, 1 read in 60)
-                if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwDefer, maxWin);
+                const uint32_t at = slot_of();
+                if (lane == 0) outRec[at] = make_uint4(q, 0u, kGwDefer, maxWin);
                 ++deferred;
                 wave_lds_sync();
             } else if (!counted) {
@@ -1291,7 +1385,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
                 // per 5 x 10^6 reads).  (Room: the slice holds kGwRounds x 16 + 64 numbers more, checked above.)
 #pragma unroll
                 for (uint32_t r = 0; r < kKeep / 64; ++r) if (r * 64 + lane < n2) slice[sliceUsed + r * 64 + lane] = kept[r * 64 + lane];
-                if (lane == 0) outRec[w] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), n2, maxWin);
+                const uint32_t at = slot_of();
+                if (lane == 0) outRec[at] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), n2, maxWin);
                 sliceUsed += n2;
                 wave_lds_sync();
             }
@@ -1305,9 +1400,10 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         }
         const uint32_t room = (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - sliceUsed);
         const bool fallback = n2 > room;
+        const uint32_t at = slot_of();
         if (lane == 0) {
-            if (fallback) { ws.hitScan[q] = H; ws.qflag[q] = kFlagCands; outRec[w] = make_uint4(q, 0u, kGwFallback, maxWin); }
-            else outRec[w] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), n2, maxWin);
+            if (fallback) { ws.hitScan[q] = H; ws.qflag[q] = kFlagCands; outRec[at] = make_uint4(q, 0u, kGwFallback, maxWin); }
+            else outRec[at] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), n2, maxWin);
         }
         if (!fallback) sliceUsed += n2;
         wave_lds_sync();
@@ -1556,12 +1652,16 @@ void launch_gw_cands(FilterStep step, const BatchView& b, const SketchParams& sp
         // SIX waves per SIMD with 384 instead of 512 kept numbers in LDS (26 KB per block, 80 registers, three spilled): 13.3 -> 12.0 ms per
         // 5 x 10^6 reads; SEVEN with the round table in the filter bits' place until the loads are out and the counting's distinct slots in the
         // kept numbers' (22 KB, 72 registers, five spilled): 11.65 ms, the step 17.9 -> 16.4 ms.  "gw_fuse" 6 / 5: the six- / five-wave instances)
-        else if (ws.gwFuse == 6 && taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 6>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-        else if (ws.gwFuse == 6) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 6>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-        else if (ws.gwFuse == 5 && taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 4>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-        else if (ws.gwFuse == 5) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 4>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-        else if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
-        else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c);
+        else if (ws.gwFuse == 6 && taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 6>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else if (ws.gwFuse == 6) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 6>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else if (ws.gwFuse == 5 && taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 4>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else if (ws.gwFuse == 5) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 4>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+    } else if (step == FilterStep::FilterLookup) {
+        // the seven-wave instance walking the reads, the direct-index lookups inside ("filter_lookup"; behind the launch over kListFilter)
+        if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7, true>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7, true>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
     } else if (step == FilterStep::PairFilter) {
         // reads of up to 2 x kGwRounds rounds (read pairs): two register batches
         // ("gw_fuse" 5 also brings back the pair filter of rounds 3-5: both filter halves of 2^15 bits, 38 KB per block, four waves per SIMD)

@@ -171,6 +171,7 @@ struct Workspace {           // device buffers sized by the host for this batch
     uint32_t  gwMidH = 0;         // reads up to this many locations take the stream filter's small-filter instance (2^16 + 2^13 bits: six waves per SIMD; 0: none)
     uint32_t  gwBigH = 32768;     // reads beyond this many locations take the stream filter's fine-block instance (gw_kernels.hip kGwBigH; 0xFFFFFFFF: none)
     int32_t   filterBpc = 0, countBpc = 0, gwFuse = 1;   // gwFuse: gw_filter_count_kernel (1) or gw_filter_kernel + gw_count_kernel (0)
+    uint32_t  filterLookup = 0;   // 1: the lane kernels' reads of up to 64 features are looked up by gw_filter_count_kernel<LOOKUP> (probe_cands_kernel leaves them alone)
 };
 
 // ---- the lane path's work lists: who hands which reads to whom ------------------------------------------------------------------------
@@ -279,6 +280,7 @@ void launch_hash_cands(WorkList list, const BatchView& b, const DeviceTable& tab
 // Count and Count1024, the compact store (gw_kernels.hip) all others
 enum class FilterStep {
     Filter,           // big_filter_kernel / gw_filter_count_kernel (gw_filter_kernel with "gw_fuse" 0)
+    FilterLookup,     // compact, "filter_lookup": gw_filter_count_kernel<LOOKUP> over the reads the lane kernel sketched
     BigFilter2,       // 8-byte: big_filter_kernel's second instance (reads with more than kBigEnt entries)
     PairFilter,       // compact: gw_filter2_kernel (read pairs: two register batches)
     Compact,          // compact: gw_compact_kernel, the stream filter's reads (+ launch_gw_order)

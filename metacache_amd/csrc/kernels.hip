@@ -1903,7 +1903,8 @@ __global__ __launch_bounds__(kLaneBlock) void probe_cands_kernel(BatchView b, ui
 {
     __shared__ uint64_t lst[kLaneBlock * kLaneRow];
     const uint32_t q = blockIdx.x * kLaneBlock + threadIdx.x;
-    const bool valid = q < b.n && ws.qflag[q] == kFlagProbe;
+    // ("filter_lookup": reads of up to 64 features are gw_filter_count_kernel<LOOKUP>'s)
+    const bool valid = q < b.n && ws.qflag[q] == kFlagProbe && (!ws.filterLookup || (ws.winOff[q + 1] - ws.winOff[q]) * s > 64u);
     probe_cands_one<QUAD, DIRECT>(b, s, tab, ws, K, taxkey, cands, q, lst + threadIdx.x * kLaneRow, valid);
 }
 
