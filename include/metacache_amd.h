@@ -176,6 +176,23 @@ int mc_db_taxon(const mc_ctx* ctx, uint64_t index, int64_t* id, int64_t* parent,
 int mc_db_taxon_source(const mc_ctx* ctx, uint64_t index, const char** filename, uint64_t* file_index, uint64_t* windows);
 int mc_db_lineages(const mc_ctx* ctx, const uint32_t** lin, uint64_t* num_targets);
 
+/* lineage table of EVERY taxon (taxonLineages_[taxon], taxonomy.hpp:1315-1322 = make_ranks of any taxon, :576-597): what
+ * mc_evaluate_assignments compares two arbitrary taxa by.  Row x - 1 describes the taxon whose lineage entry is x (taxon index + 1).
+ *   lin[(x-1) * MC_NUM_RANKS + r] = the ancestor-or-self of rank r as index + 1, 0 = none: the taxon itself in its own rank's slot if it
+ *     has a rank, then the parent chain; a later (higher) ancestor of the same rank overwrites an earlier one; the walk ends at an
+ *     unknown id or a self-parent.
+ *   rank[x-1] = the taxon's rank, MC_NUM_RANKS = none (a larger value is read as none).  rank == NULL derives it from the rows: the slot
+ *     that names the taxon itself, none if there is no such slot.
+ *   covered[x-1] != 0: the taxon is a target or lies on the FULL parent chain, ranked or not, of at least one target
+ *     (taxonomy_cache::covers, taxonomy.hpp:1355-1366, which walks make_lineage, not make_ranks).  covered may be NULL; then
+ *     MC_EVALUATE_COVERAGE is MC_ERR_STATE.
+ * mc_open_database and mc_open_metadata fill the table from the .meta taxonomy block (the targets' rows are the rows of mc_db_lineages).
+ * mc_db_taxon_table hands the host copy out (rank and covered may be NULL; *covered = NULL where the table has none) and works on a
+ * metadata-only context.  Setting a table DROPS the evaluation tallies; no evaluation may be in flight.
+ * MC_ERR_INVALID: an entry above num_taxa, NULL lin with num_taxa > 0, more than 2^32 - 2 taxa. */
+int mc_set_taxon_table(mc_ctx* ctx, const uint32_t* lin, const uint8_t* rank, const uint8_t* covered, uint64_t num_taxa);
+int mc_db_taxon_table(const mc_ctx* ctx, const uint32_t** lin, const uint8_t** rank, const uint8_t** covered, uint64_t* num_taxa);
+
 /* host batch slots: query_batch::add_paired_read (query_batch.cuh:85-186), database::query_gpu_async
  * (database.hpp:386-397), host_data.wait_for_results / allhits(i) / top_candidates(i) / clear
  * (query_batch.cuh:212-259); caller code database_query.hpp:87-124 */
@@ -501,6 +518,50 @@ int mc_classify_candidates(mc_ctx* ctx, const mc_classify_options* opt, const mc
 int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t* taxon_counts, uint64_t capacity,
                       uint64_t* num_counts, int reset);
 
+/* ---- evaluation against a ground truth: -precision / -taxon-coverage ---------------------------------
+ * The last block of the reference's query summary (classification.cpp:237-295 update_coverage_statistics / evaluate_classification,
+ * classification_statistics.hpp:87-107 assign_known_correct, printed by printing.cpp:537-592) on the device: given what each read was
+ * assigned and what it really is, how many reads were classified correctly and wrongly on every rank, and how many hits fell on taxa
+ * the database does not cover.  Needs the taxon table (mc_set_taxon_table; rank[], lin[][] and covered[] below are its arrays, a rank of
+ * MC_NUM_RANKS = 21 is "none").  Per read i, with a = assigned[i].taxon and t = truth[i] (taxon index + 1, 0 = none / unknown):
+ *   1. an entry greater than the table's num_taxa is treated as 0 and counted once in out_of_table.
+ *   2. ar = a ? rank[a-1] : 21.  The TABLE's rank: assigned[i].info is not read, so assignment arrays of any producer work.
+ *   3. kr = t ? rank[t-1] : 21.  A truth without a rank counts as unknown (mcq's ground truth hands over the next ranked ancestor,
+ *      classification.cpp:109-137; resolving read headers stays the caller's).
+ *   4. cr = 21; if a and t: the first slot r = 0 .. 20 with lin[a-1][r] != 0 && lin[a-1][r] == lin[t-1][r] gives
+ *      cr = rank[that taxon - 1]  (ranked_lca, taxonomy.hpp:1291-1301, then ->rank()).
+ *   5. assign_known_correct: cr = max(cr, ar, kr); assigned[ar]++; known[kr]++; if kr != 21: correct[cr]++, and if cr > kr && cr > ar:
+ *      wrong[cr-1]++ ("counted wrong").
+ *   6. verdicts[i] = {kr, cr, counted wrong ? 1 : 0, 0} where verdicts is given.
+ *   7. with MC_EVALUATE_COVERAGE and t != 0: for every slot with x = lin[t-1][r] != 0, rr = rank[x-1] and on = (a != 0 && rr >= ar);
+ *      coverage[rr] counts a true_pos (covered[x-1], on), false_neg (covered, not on), false_pos (not covered, on) or true_neg
+ *      (update_coverage_statistics, classification.cpp:237-263).
+ * Without MC_EVALUATE_HOST the arrays are DEVICE pointers (assigned 8-byte, truth and verdicts 4-byte aligned) and the call is
+ * asynchronous on 'stream' (NULL = the context's own): enqueued behind mc_classify_candidates it needs no synchronisation in between.
+ * Calls on different streams may tally at the same time; the counters are exact 64-bit sums and order-free.  With MC_EVALUATE_HOST the
+ * arrays are staged in pieces through buffers of the context, one caller at a time (mc_set_tuning "evaluate_stage_rows": reads per
+ * piece, 0 = default), and the call returns when done; one that fails on the device after its first piece has counted the pieces
+ * before it.  The table goes to the device with the first call and again after a later mc_set_taxon_table.
+ * MC_ERR_INVALID (checked first): NULL ctx, NULL assigned or truth with num_queries > 0, neither verdicts nor MC_EVALUATE_TALLY,
+ * MC_EVALUATE_COVERAGE without MC_EVALUATE_TALLY, unknown flags, misaligned device arrays, verdicts overlapping an input.
+ * num_queries == 0: MC_OK.  MC_ERR_STATE: no taxon table, MC_EVALUATE_COVERAGE without covered[], a context without a device. */
+typedef struct { uint8_t known, correct, flags, reserved; } mc_verdict;     /* kr, cr, bit 0 of flags = counted wrong */
+#define MC_EVALUATE_HOST     1       /* the arrays are HOST arrays, the call returns when done */
+#define MC_EVALUATE_TALLY    2       /* add this call's reads to the context's evaluation tallies (mc_evaluate_tally) */
+#define MC_EVALUATE_COVERAGE 4       /* with MC_EVALUATE_TALLY: also the confusion counters of -taxon-coverage (rule 7) */
+int mc_evaluate_assignments(mc_ctx* ctx, const mc_assignment* assigned, const uint32_t* truth, uint32_t num_queries,
+                            int flags, mc_verdict* verdicts, void* stream);
+/* the tallies of all MC_EVALUATE_TALLY calls since the last reset (or the last mc_set_taxon_table): the per-rank bins as the rule above
+ * fills them -- the cumulative figures of the summary (classification_statistics.hpp:135-227) are sums over them --, reads = reads
+ * evaluated, out_of_table = entries of rule 1.  Waits for the context's own streams as mc_classify_tally does; reset != 0 clears the
+ * counters after they have been read.  These counters are the evaluation's own: mc_classify_tally's are not touched. */
+typedef struct {
+    uint64_t assigned[MC_NUM_RANKS + 1], known[MC_NUM_RANKS + 1], correct[MC_NUM_RANKS + 1], wrong[MC_NUM_RANKS + 1];
+    uint64_t coverage[MC_NUM_RANKS + 1][4];      /* true_pos, false_pos, true_neg, false_neg */
+    uint64_t reads, out_of_table;
+} mc_evaluation;
+int mc_evaluate_tally(mc_ctx* ctx, mc_evaluation* out, int reset);
+
 /* ---- target coverage: the two-pass classification of -cov-percentile ------------------------------
  * The reference (map_queries_to_targets_default, classification.cpp:747-838) keeps every read's candidates, collects per target the
  * windows that qualifying candidates cover (matches_per_target::insert, matches_per_target.hpp:100-127), removes the targets at the
@@ -607,7 +668,7 @@ int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacity_tar
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with
  * the tuning switch "gw_fuse" 0), "gw_filter2", "gw_compact" (+ the ordering of the stream filter's reads), "gw_filter_stream_fine" (the sixteen-wave instance), "gw_filter_stream" (+ the second gw_compact), "gw_count" (gw_count_kernel<9>), "gw_count_512" (<10>), "gw_count_1024" (<11>); 8-byte store:
  * "big_filter", "big_filter_2", "big_count", "big_count_2" --, "gw_sort", "gw_sorted_cands", "query_wave", "scan", "sort_candidates";
- * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect).  Returns accumulated milliseconds and launch counts since the last reset. */
+ * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect); "taxon_evaluate" (taxon_evaluate_kernel, mc_evaluate_assignments).  Returns accumulated milliseconds and launch counts since the last reset. */
 int mc_timing_enable(mc_ctx* ctx, int on);
 int mc_timing_reset(mc_ctx* ctx);
 int mc_timing_get(mc_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);

@@ -64,6 +64,59 @@ candidate_generation_rules make_candidate_generation_rules(const Query& query, c
     return rules;
 }
 
+// classification_statistics (classification_statistics.hpp:135-227) over the per-rank bins of mc_evaluate_tally: the reference's accessor
+// names and arithmetic.  assigned / known / correct (r) are sums from sequence up to r, wrong(r) from r up to root.
+class classification_statistics {
+public:
+    using rank = taxon_rank;
+    using count_t = std::uint64_t;
+    struct confusion_statistics {                                                 // stat_confusion.hpp: one rank's four counters
+        count_t tp = 0, fp = 0, tn = 0, fn = 0;
+        count_t true_pos() const noexcept { return tp; }
+        count_t false_pos() const noexcept { return fp; }
+        count_t true_neg() const noexcept { return tn; }
+        count_t false_neg() const noexcept { return fn; }
+        count_t total() const noexcept { return tp + fp + tn + fn; }
+    };
+    classification_statistics() : e_{} {}
+    explicit classification_statistics(const mc_evaluation& e) : e_(e) {}
+    const mc_evaluation& bins() const noexcept { return e_; }
+
+    count_t assigned() const noexcept { return upto(e_.assigned, rank::root); }
+    count_t assigned(rank r) const noexcept { return upto(e_.assigned, r); }
+    count_t unassigned() const noexcept { return e_.assigned[MC_NUM_RANKS]; }
+    count_t total() const noexcept { return assigned() + unassigned(); }
+    count_t known() const noexcept { return upto(e_.known, rank::root); }
+    count_t known(rank r) const noexcept { return upto(e_.known, r); }
+    count_t unknown() const noexcept { return e_.known[MC_NUM_RANKS]; }
+    count_t correct() const noexcept { return upto(e_.correct, rank::root); }
+    count_t correct(rank r) const noexcept { return upto(e_.correct, r); }
+    count_t wrong() const noexcept { return wrong(rank::Sequence); }
+    count_t wrong(rank rr) const noexcept { count_t s = 0; for (int r = int(rr); r < MC_NUM_RANKS; ++r) s += e_.wrong[r]; return s; }
+    confusion_statistics coverage(rank r) const noexcept
+    {
+        const std::uint64_t* c = e_.coverage[int(r)];
+        confusion_statistics s; s.tp = c[0]; s.fp = c[1]; s.tn = c[2]; s.fn = c[3];
+        return s;
+    }
+
+    double known_rate(rank r) const noexcept { return total() > 0 ? known(r) / double(total()) : 0; }
+    double known_rate() const noexcept { return total() > 0 ? known() / double(total()) : 0; }
+    double unknown_rate() const noexcept { return total() > 0 ? unknown() / double(total()) : 0; }
+    double classification_rate(rank r) const noexcept { return total() > 0 ? assigned(r) / double(total()) : 0; }
+    double unclassified_rate() const noexcept { return total() > 0 ? unassigned() / double(total()) : 0; }
+    double sensitivity(rank r) const noexcept { return known(r) > 0 ? correct(r) / double(known(r)) : 0; }
+    double precision(rank r) const noexcept
+    {
+        const double tot = double(correct(r)) + double(wrong(r));                 // (in general neither assigned(r) nor known(r))
+        return tot > 0 ? correct(r) / tot : 0;
+    }
+
+private:
+    static count_t upto(const std::uint64_t* a, rank rr) noexcept { count_t s = 0; for (int r = 0; r <= int(rr) && r < MC_NUM_RANKS; ++r) s += a[r]; return s; }
+    mc_evaluation e_;
+};
+
 class query_batch;
 
 class database {
@@ -124,6 +177,15 @@ public:
         return l;
     }
 
+    // -precision / -taxon-coverage after the last batch: what the batches' evaluate() calls have counted (mc_evaluate_tally; reset: the
+    // counters start from zero again)
+    classification_statistics evaluation(bool reset = false) const
+    {
+        mc_evaluation e;
+        if (mc_evaluate_tally(ctx_, &e, reset ? 1 : 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        return classification_statistics(e);
+    }
+
     // database::query_gpu_async(queryBatch, hostId, querySketching, lowestRank)  database.hpp:386-397
     void query_gpu_async(query_batch& batch, unsigned hostId, taxon_rank lowestRank) const;
 
@@ -180,6 +242,21 @@ public:
             s.first = assigned_.data(); s.last = s.first + assigned_.size();
             return s;
         }
+        // -precision / -taxon-coverage (after classify()): this batch's assignments against what the queries really are -- truth[i] =
+        // taxon index + 1 of query i's true taxon, 0 = unknown -- counted into the context's evaluation tallies
+        // (evaluate_classification, classification.cpp:272-295; mc_evaluate_assignments on the slot's host arrays; database::evaluation
+        // reads them); coverage: also the confusion counters of -taxon-coverage.  The verdicts are valid until the next evaluate() or clear().
+        span<mc_verdict> evaluate(span<const std::uint32_t> truth, bool coverage = false)
+        {
+            if (truth.size() != assigned_.size()) throw std::runtime_error("evaluate: one truth per query of the batch that classify() has judged");
+            verdicts_.resize(assigned_.size());
+            if (mc_evaluate_assignments(ctx_, assigned_.data(), truth.begin(), std::uint32_t(assigned_.size()),
+                                        MC_EVALUATE_HOST | MC_EVALUATE_TALLY | (coverage ? MC_EVALUATE_COVERAGE : 0), verdicts_.data(), nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            span<mc_verdict> s;
+            s.first = verdicts_.data(); s.last = s.first + verdicts_.size();
+            return s;
+        }
         // -cov-percentile, first pass (after wait_for_results): the windows that this batch's qualifying candidates cover are marked in
         // the context's bitmap (matches_per_target::insert, matches_per_target.hpp:100-127; mc_coverage_add on the slot's host arrays)
         void cover(std::uint32_t hitsMin, int lowestRank)
@@ -210,7 +287,7 @@ public:
                                    MC_TARGET_HITS_HOST, nullptr) != MC_OK)
                 throw std::runtime_error(mc_last_error(ctx_));
         }
-        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); }   // query_batch.cuh:255-259
+        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
         mc_ctx* ctx_ = nullptr; std::uint32_t slot_ = 0;
@@ -218,6 +295,7 @@ public:
         std::vector<match_candidate> tops_;
         std::vector<mc_assignment> assigned_;
         std::vector<mc_candidate> kept_;
+        std::vector<mc_verdict> verdicts_;
     };
 
     query_batch(const database& db, unsigned numHostThreads) : ctx_(db.ctx_), hosts_(numHostThreads)

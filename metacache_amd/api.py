@@ -22,6 +22,10 @@ assignment_dtype = np.dtype({"names": ["taxon", "rank", "voters"], "formats": ["
 CLASSIFY_HOST, CLASSIFY_TALLY = 1, 2
 COVERAGE_HOST = 1
 TARGET_HITS_HOST = 1
+EVALUATE_HOST, EVALUATE_TALLY, EVALUATE_COVERAGE = 1, 2, 4
+verdict_dtype = np.dtype([("known", "u1"), ("correct", "u1"), ("flags", "u1"), ("reserved", "u1")])   # mc_verdict: kr, cr, bit 0 = counted wrong
+RANK_NAMES = ["sequence", "form", "variety", "subspecies", "species", "subgenus", "genus", "subtribe", "tribe", "subfamily", "family",
+              "suborder", "order", "subclass", "class", "subphylum", "phylum", "subkingdom", "kingdom", "domain", "root"]
 target_hit_dtype = np.dtype([("tgt", "<u4"), ("beg", "<u4"), ("end", "<u4"), ("hits", "<u4"), ("query", "<u8")])   # mc_target_hit, 24 bytes
 
 
@@ -111,6 +115,89 @@ def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, hig
     return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
 
 
+class McEvaluation(C.Structure):
+    _fields_ = [("assigned", C.c_uint64 * (NUM_RANKS + 1)), ("known", C.c_uint64 * (NUM_RANKS + 1)), ("correct", C.c_uint64 * (NUM_RANKS + 1)),
+                ("wrong", C.c_uint64 * (NUM_RANKS + 1)), ("coverage", (C.c_uint64 * 4) * (NUM_RANKS + 1)), ("reads", C.c_uint64),
+                ("out_of_table", C.c_uint64)]
+
+
+class Confusion:
+    """confusion_statistics of one rank (classification_statistics.hpp): the four counters of -taxon-coverage"""
+
+    def __init__(self, row):
+        self._tp, self._fp, self._tn, self._fn = (int(x) for x in row)
+
+    def true_pos(self): return self._tp
+    def false_pos(self): return self._fp
+    def true_neg(self): return self._tn
+    def false_neg(self): return self._fn
+    def total(self): return self._tp + self._fp + self._tn + self._fn
+
+
+class Evaluation:
+    """The reference's classification_statistics (classification_statistics.hpp:135-227) over the per-rank bins of mc_evaluate_tally:
+    bins[0..3] = assigned, known, correct, wrong ([22] each, [21] = none), coverage[22, 4] = true_pos, false_pos, true_neg, false_neg.
+    A rank argument is the rank's number (0 = sequence .. 20 = root); without one the figure is over all ranks."""
+    SUMMARY_RANKS = (0, 3, 4, 6, 10, 12, 14, 16, 18, 19, 20)      # what show_taxon_statistics prints (printing.cpp:505-513)
+
+    def __init__(self, assigned, known, correct, wrong, coverage=None, reads=0, out_of_table=0):
+        self.bins = np.array([assigned, known, correct, wrong], dtype=np.uint64).reshape(4, NUM_RANKS + 1)
+        self.confusion = (np.zeros((NUM_RANKS + 1, 4), dtype=np.uint64) if coverage is None
+                          else np.array(coverage, dtype=np.uint64).reshape(NUM_RANKS + 1, 4))
+        self.reads, self.out_of_table = int(reads), int(out_of_table)
+
+    def _upto(self, k, r):
+        return int(self.bins[k, :(NUM_RANKS if r is None else r + 1)].sum())
+
+    def assigned(self, r=None): return self._upto(0, r)
+    def known(self, r=None): return self._upto(1, r)
+    def correct(self, r=None): return self._upto(2, r)
+    def wrong(self, r=None): return int(self.bins[3, (0 if r is None else r):NUM_RANKS].sum())
+    def unassigned(self): return int(self.bins[0, NUM_RANKS])
+    def unknown(self): return int(self.bins[1, NUM_RANKS])
+    def total(self): return self.assigned() + self.unassigned()
+    def _rate(self, x): return x / float(self.total()) if self.total() > 0 else 0.0
+    def known_rate(self, r=None): return self._rate(self.known(r))
+    def unknown_rate(self): return self._rate(self.unknown())
+    def classification_rate(self, r): return self._rate(self.assigned(r))
+    def unclassified_rate(self): return self._rate(self.unassigned())
+    def sensitivity(self, r): return self.correct(r) / float(self.known(r)) if self.known(r) > 0 else 0.0
+
+    def precision(self, r):
+        tot = float(self.correct(r) + self.wrong(r))              # (in general neither assigned(r) nor known(r))
+        return self.correct(r) / tot if tot > 0 else 0.0
+
+    def coverage(self, r): return Confusion(self.confusion[r])
+
+    def summary_lines(self, comment="# "):
+        """show_taxon_statistics (printing.cpp:500-592) from 'unclassified:' to the end, numbers as the reference's stream prints them
+        (%g: six significant digits)"""
+        if self.assigned() < 1:
+            return ["None of the input sequences could be classified."]
+        ranks = [r for r in self.SUMMARY_RANKS if self.assigned(r) > 0]
+        name = lambda r: RANK_NAMES[r].ljust(11)
+        out = []
+        if self.unassigned() > 0:
+            out.append(f"{comment}unclassified: {100 * self.unclassified_rate():g}% ({self.unassigned()})")
+        out.append(f"{comment}classified:")
+        out += [f"{comment}  {name(r)}{100 * self.classification_rate(r):g}% ({self.assigned(r)})" for r in ranks]
+        if self.known() > 0:
+            if self.unknown() > 0:
+                out.append(f"{comment}ground truth unknown: {100 * self.unknown_rate():g}% ({self.unknown()})")
+            out.append(f"{comment}ground truth known:")
+            out += [f"{comment}  {name(r)}{100 * self.known_rate(r):g}% ({self.known(r)})" for r in ranks]
+            out.append(f"{comment}correctly classified:")
+            out += [f"{comment}  {name(r)}{self.correct(r)}" for r in ranks]
+            out.append(f"{comment}precision (correctly classified / classified) if ground truth known:")
+            out += [f"{comment}  {name(r)}{100 * self.precision(r):g}%" for r in ranks]
+            out.append(f"{comment}sensitivity (correctly classified / all) if ground truth known:")
+            out += [f"{comment}  {name(r)}{100 * self.sensitivity(r):g}%" for r in ranks]
+            if self.coverage(19).total() > 0:
+                out.append(f"{comment}false positives (hit on taxa not covered in DB):")
+                out += [f"{comment}  {name(r)}{self.coverage(r).false_pos()}" for r in ranks]
+        return out
+
+
 class McDeviceResults(C.Structure):
     _fields_ = [("cands", C.c_void_p), ("hit_counts", C.c_void_p), ("hit_offsets", C.c_void_p), ("hits", C.c_void_p),
                 ("features", C.c_void_p), ("win_offsets", C.c_void_p)]
@@ -128,7 +215,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_build_set_query_config", "mc_align_semiglobal", "mc_align_stats",
            "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally",
            "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop",
-           "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect"]
+           "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect",
+           "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally"]
 
 _lib = None
 
@@ -198,6 +286,10 @@ def lib() -> C.CDLL:
         L.mc_target_hits_reserve.argtypes = [C.c_void_p, C.c_uint64]
         L.mc_target_hits_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int, C.c_void_p]
         L.mc_target_hits_collect.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p, C.c_int]
+        L.mc_set_taxon_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_db_taxon_table.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.mc_evaluate_assignments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
+        L.mc_evaluate_tally.argtypes = [C.c_void_p, C.POINTER(McEvaluation), C.c_int]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -460,6 +552,54 @@ class Database:
         counts = np.zeros(num.value, dtype=np.uint64)
         self._check(L.mc_classify_tally(self.h, assigned.ctypes.data, counts.ctypes.data, counts.size, None, int(reset)))
         return assigned, counts
+
+    # ---- evaluation against a ground truth: -precision / -taxon-coverage (mc_evaluate_*) ------------
+    def set_taxon_table(self, lin: np.ndarray, rank=None, covered=None):
+        """lin[taxa, 21] uint32: every taxon's ranked lineage as taxon index + 1 (0 = none); rank[taxa] uint8 (21 = none; None: derived
+        from the rows); covered[taxa] uint8 (None: no -taxon-coverage counters) -- for contexts that were not opened from database files"""
+        lin = np.ascontiguousarray(lin, dtype=np.uint32)
+        if lin.ndim != 2 or lin.shape[1] != NUM_RANKS:
+            raise ValueError("set_taxon_table: lin must be [taxa, 21]")
+        rank = None if rank is None else np.ascontiguousarray(rank, dtype=np.uint8)
+        covered = None if covered is None else np.ascontiguousarray(covered, dtype=np.uint8)
+        if any(x is not None and x.shape != (lin.shape[0],) for x in (rank, covered)):
+            raise ValueError("set_taxon_table: rank and covered have one entry per taxon")
+        self._check(lib().mc_set_taxon_table(self.h, lin.ctypes.data, None if rank is None else rank.ctypes.data,
+                                             None if covered is None else covered.ctypes.data, lin.shape[0]))
+
+    def taxon_table(self):
+        """-> (lin[taxa, 21] uint32, rank[taxa] uint8, covered[taxa] uint8 or None): copies of the context's taxon table"""
+        pl, pr, pc, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(lib().mc_db_taxon_table(self.h, C.byref(pl), C.byref(pr), C.byref(pc), C.byref(n)))
+        lin = _view(pl.value, n.value * NUM_RANKS, np.dtype("<u4")).reshape(n.value, NUM_RANKS).copy()
+        return lin, _view(pr.value, n.value, np.dtype("u1")).copy(), (_view(pc.value, n.value, np.dtype("u1")).copy() if pc.value else None)
+
+    def evaluate_device(self, assigned_ptr: int, truth_ptr: int, n: int, *, tally: bool = True, coverage: bool = False, verdicts_ptr: int = 0,
+                        stream: int = 0):
+        """judges n assignments in device memory (mc_assignment, 8 bytes each) by the truths at truth_ptr (uint32: taxon index + 1,
+        0 = unknown) -> n mc_verdict at verdicts_ptr (4 bytes each, 0 = none wanted) and / or the context's evaluation tallies;
+        asynchronous on `stream` (0 = the context's)"""
+        flags = (EVALUATE_TALLY if tally else 0) | (EVALUATE_COVERAGE if coverage else 0)
+        self._check(lib().mc_evaluate_assignments(self.h, assigned_ptr or None, truth_ptr or None, n, flags, verdicts_ptr or None, stream or None))
+
+    def evaluate(self, assigned: np.ndarray, truth: np.ndarray, *, tally: bool = True, coverage: bool = False) -> np.ndarray:
+        """the same on host arrays: assigned[n] (assignment_dtype, e.g. what classify() returns), truth[n] uint32 -> verdict_dtype [n]"""
+        assigned = np.ascontiguousarray(assigned, dtype=assignment_dtype)
+        truth = np.ascontiguousarray(truth, dtype=np.uint32)
+        if assigned.ndim != 1 or truth.shape != assigned.shape:
+            raise ValueError("evaluate: assigned and truth must be one-dimensional and of one length")
+        n = len(truth)
+        out = np.zeros(n, dtype=verdict_dtype)
+        flags = EVALUATE_HOST | (EVALUATE_TALLY if tally else 0) | (EVALUATE_COVERAGE if coverage else 0)
+        self._check(lib().mc_evaluate_assignments(self.h, assigned.ctypes.data if n else None, truth.ctypes.data if n else None, n, flags,
+                                                  out.ctypes.data, None))
+        return out
+
+    def evaluation(self, reset: bool = False) -> Evaluation:
+        """the tallies of all evaluate calls with tally=True since the last reset (mc_evaluate_tally)"""
+        e = McEvaluation()
+        self._check(lib().mc_evaluate_tally(self.h, C.byref(e), int(reset)))
+        return Evaluation(list(e.assigned), list(e.known), list(e.correct), list(e.wrong), [list(row) for row in e.coverage], e.reads, e.out_of_table)
 
     # ---- target coverage: the two passes of -cov-percentile (mc_coverage_*) -----------------------
     def load_target_windows(self, windows: np.ndarray):

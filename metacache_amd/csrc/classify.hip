@@ -38,23 +38,6 @@ struct VoteArgs {
     int lowest, highest;
 };
 
-// adds, for every distinct key among the wave's active lanes, the number of lanes that hold it: `rounds` keys are counted across the
-// wave (one add each, by the first lane that holds the key), the lanes left after that add 1 each.  All lanes of the wave call this.
-template <class Add>
-__device__ __forceinline__ void wave_add_by_key(uint32_t key, bool active, int rounds, Add add)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    unsigned long long todo = __ballot(active);
-    for (int r = 0; r < rounds && todo; ++r) {
-        const int leader = __ffsll(todo) - 1;
-        const uint32_t k = (uint32_t)__shfl((int)key, leader);
-        const unsigned long long same = __ballot(active && key == k);
-        if (lane == (uint32_t)leader) add(k, (uint32_t)__popcll(same));
-        todo &= ~same;
-    }
-    if ((todo >> lane) & 1ull) add(key, 1u);
-}
-
 template <bool TALLY>
 __global__ __launch_bounds__(kBlock) void taxon_vote_kernel(VoteArgs a)
 {

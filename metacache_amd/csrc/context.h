@@ -177,6 +177,11 @@ void free_coverage_state(mc_ctx* ctx);
 struct TargetHitsState;
 void free_target_hits_state(mc_ctx* ctx);
 
+// evaluate.hip: the device copy of the taxon table (padded rows), the evaluation tallies and the staging of mc_evaluate_* (made on first
+// use), freed with the context
+struct EvaluateState;
+void free_evaluate_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -220,6 +225,15 @@ struct mc_ctx {
     std::mutex coverageMtx;
     mcamd::CoverageState* coverage = nullptr;
     bool coverageLoadFirst = true;         // coverage_mark_kernel loads a word and sends the atomic only where bits are missing (mc_set_tuning "coverage_load_first")
+
+    // mc_set_taxon_table: the ranked lineage, rank and covered flag of EVERY taxon (host copy: mc_db_taxon_table), what mc_evaluate_* compares by
+    std::vector<uint32_t> taxonLin;        // [taxa * 21], taxon index + 1
+    std::vector<uint8_t> taxonRank, taxonCovered;   // [taxa]; taxonCovered is empty where the table came without one
+    bool taxonTableSet = false, taxonCoveredSet = false;
+    uint64_t taxonTableVersion = 0;        // counts the mc_set_taxon_table calls: mc_evaluate_* copies the table to the device again when it has changed
+    std::mutex evaluateMtx;
+    mcamd::EvaluateState* evaluate = nullptr;
+    uint32_t evaluateStageRows = 0;        // MC_EVALUATE_HOST: reads per staged piece (mc_set_tuning "evaluate_stage_rows"; 0 = what 64 MB of pairs hold)
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

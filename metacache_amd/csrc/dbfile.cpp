@@ -70,29 +70,73 @@ int read_meta(const std::string& name, Meta& m, std::string& err)
     return MC_OK;
 }
 
-// ranked lineage of every target as taxon index + 1 (taxonomy.hpp:576-597, :919-1030)
-void make_lineages(const Meta& m, std::vector<uint32_t>& lin)
+using ById = std::unordered_map<int64_t, uint32_t>;
+
+ById index_by_id(const std::vector<Taxon>& taxa)
 {
-    std::unordered_map<int64_t, uint32_t> byId;
-    byId.reserve(m.taxa.size() * 2);
-    for (uint32_t i = 0; i < m.taxa.size(); ++i) byId.emplace(m.taxa[i].id, i);
+    ById byId;
+    byId.reserve(taxa.size() * 2);
+    for (uint32_t i = 0; i < taxa.size(); ++i) byId.emplace(taxa[i].id, i);
+    return byId;
+}
+
+// the ONE walk behind the lineage tables (make_ranks and make_lineage, taxonomy.hpp:576-597): visit(index) for the taxon itself, then for
+// every ancestor -- parents live among the non-target taxa --, until an unknown id or a self-parent (or, in a file whose parents run in a
+// circle, after as many steps as there are taxa)
+template <class Fn>
+void walk_up(const std::vector<Taxon>& taxa, const ById& byId, uint32_t self, Fn&& visit)
+{
+    visit(self);
+    int64_t id = taxa[self].parent;
+    for (size_t steps = 0; id > 0 && steps < taxa.size(); ++steps) {
+        auto p = byId.find(id);
+        if (p == byId.end()) break;
+        visit(p->second);
+        if (taxa[p->second].parent == id) break;
+        id = taxa[p->second].parent;
+    }
+}
+
+// make_ranks: every ranked taxon of the walk in its rank's slot as index + 1; a later (higher) one of the same rank overwrites
+void ranked_row(const std::vector<Taxon>& taxa, const ById& byId, uint32_t self, uint32_t* L)
+{
+    walk_up(taxa, byId, self, [&](uint32_t i) { if (taxa[i].rank < MC_NUM_RANKS) L[taxa[i].rank] = i + 1; });
+}
+
+// ranked lineage of every target as taxon index + 1 (taxonomy.hpp:576-597, :919-1030)
+void make_lineages(const Meta& m, const ById& byId, std::vector<uint32_t>& lin)
+{
     lin.assign(m.targetCount * MC_NUM_RANKS, 0);
     for (uint64_t t = 0; t < m.targetCount; ++t) {
         auto it = byId.find(-(int64_t)t - 1);
-        if (it == byId.end()) continue;
-        uint32_t* L = &lin[t * MC_NUM_RANKS];
-        const Taxon& tx = m.taxa[it->second];
-        if (tx.rank < MC_NUM_RANKS) L[tx.rank] = it->second + 1;
-        int64_t id = tx.parent;
-        while (id > 0) {                                   // parents live among the non-target taxa
-            auto p = byId.find(id);
-            if (p == byId.end()) break;
-            const Taxon& px = m.taxa[p->second];
-            if (px.rank < MC_NUM_RANKS) L[px.rank] = p->second + 1;
-            if (px.parent == id) break;
-            id = px.parent;
-        }
+        if (it != byId.end()) ranked_row(m.taxa, byId, it->second, &lin[t * MC_NUM_RANKS]);
     }
+}
+
+// ... and of EVERY taxon (taxonLineages_, taxonomy.hpp:1315-1322), with its rank and whether a target lies at or below it on a full
+// parent chain (taxonomy_cache::covers, :1355-1366): the table of mc_set_taxon_table
+void make_taxon_table(const std::vector<Taxon>& taxa, const ById& byId, std::vector<uint32_t>& lin, std::vector<uint8_t>& rank, std::vector<uint8_t>& covered)
+{
+    lin.assign(taxa.size() * MC_NUM_RANKS, 0);
+    rank.assign(taxa.size(), (uint8_t)MC_NUM_RANKS);
+    covered.assign(taxa.size(), 0);
+    for (uint32_t i = 0; i < taxa.size(); ++i) {
+        ranked_row(taxa, byId, i, &lin[(size_t)i * MC_NUM_RANKS]);
+        rank[i] = (uint8_t)std::min<uint32_t>(taxa[i].rank, MC_NUM_RANKS);
+        if (taxa[i].id < 0) walk_up(taxa, byId, i, [&](uint32_t a) { covered[a] = 1; });
+    }
+}
+
+// what both ways of opening a database derive from the taxonomy block: the targets' lineages and the table of all taxa
+int set_tables_from_taxa(mc_ctx* ctx, std::vector<uint32_t>& lin)
+{
+    Meta tmp{}; tmp.targetCount = ctx->targetCount; tmp.taxa = ctx->taxa;
+    const ById byId = index_by_id(tmp.taxa);
+    make_lineages(tmp, byId, lin);
+    std::vector<uint32_t> tlin;
+    std::vector<uint8_t> rank, covered;
+    make_taxon_table(tmp.taxa, byId, tlin, rank, covered);
+    return mc_set_taxon_table(ctx, tlin.data(), rank.data(), covered.data(), tmp.taxa.size());
 }
 
 struct PartHeader { uint64_t nkeys = 0, nvalues = 0, batch = 0; };
@@ -278,10 +322,8 @@ int mc_open_database(const char* name, const mc_config* cfgIn, mc_ctx** out)
         return rc;
     }
     const double tr2 = now_s();
-    Meta tmp{}; tmp.targetCount = ctx->targetCount; tmp.taxa = ctx->taxa;
     std::vector<uint32_t> lin;
-    make_lineages(tmp, lin);
-    if ((rc = mc_set_lineages(ctx, lin.data(), ctx->targetCount))) { set_global_error(ctx->err); mc_destroy(ctx); return rc; }
+    if ((rc = set_tables_from_taxa(ctx, lin)) || (rc = mc_set_lineages(ctx, lin.data(), ctx->targetCount))) { set_global_error(ctx->err); mc_destroy(ctx); return rc; }
     if (trace) std::fprintf(stderr, "mc_open_database %s part %d: metadata %.3f s, mc_create %.3f s, table allocation %.3f s, files %.3f s, lineages %.3f s\n", name, cfg.single_part, tr1 - tr0,
                             trCreate, trBegin, trLoad, now_s() - tr2);
     *out = ctx;
@@ -307,12 +349,44 @@ int mc_open_metadata(const char* name, mc_ctx** out)
     ctx->maxLocs = m.maxLocs;
     ctx->parts.resize(std::max<uint32_t>(m.numParts, 1));
     ctx->taxa = std::move(m.taxa);
-    Meta tmp{}; tmp.targetCount = ctx->targetCount; tmp.taxa = ctx->taxa;
     std::vector<uint32_t> lin;
-    make_lineages(tmp, lin);
+    if ((rc = set_tables_from_taxa(ctx, lin))) { set_global_error(ctx->err); delete ctx; return rc; }
     ctx->lineages = std::move(lin);
     ++ctx->lineageVersion;
     *out = ctx;
+    return MC_OK;
+}
+
+// host side only (a metadata-only context takes a table as well); the device copy follows with the next mc_evaluate_* call (evaluate.hip)
+int mc_set_taxon_table(mc_ctx* ctx, const uint32_t* lin, const uint8_t* rank, const uint8_t* covered, uint64_t numTaxa)
+{
+    if (!ctx) return MC_ERR_INVALID;
+    if (numTaxa > 0 && !lin) return fail(ctx, MC_ERR_INVALID, "mc_set_taxon_table: no lineage rows");
+    if (numTaxa > 0xFFFFFFFEull) return fail(ctx, MC_ERR_INVALID, "mc_set_taxon_table: more than 2^32 - 2 taxa");
+    for (uint64_t i = 0; i < numTaxa * MC_NUM_RANKS; ++i)
+        if (lin[i] > numTaxa) return fail(ctx, MC_ERR_INVALID, "mc_set_taxon_table: an entry names a taxon beyond the table");
+    std::vector<uint8_t> rk((size_t)numTaxa, (uint8_t)MC_NUM_RANKS);
+    for (uint64_t x = 0; x < numTaxa; ++x) {
+        if (rank) { rk[x] = std::min<uint8_t>(rank[x], MC_NUM_RANKS); continue; }
+        for (uint32_t r = 0; r < MC_NUM_RANKS; ++r)
+            if (lin[x * MC_NUM_RANKS + r] == x + 1) { rk[x] = (uint8_t)r; break; }
+    }
+    ctx->taxonLin.assign(lin, lin + numTaxa * MC_NUM_RANKS);
+    ctx->taxonRank = std::move(rk);
+    if (covered) ctx->taxonCovered.assign(covered, covered + numTaxa); else ctx->taxonCovered.clear();
+    ctx->taxonCoveredSet = covered != nullptr;
+    ctx->taxonTableSet = true;
+    ++ctx->taxonTableVersion;
+    return MC_OK;
+}
+
+int mc_db_taxon_table(const mc_ctx* ctx, const uint32_t** lin, const uint8_t** rank, const uint8_t** covered, uint64_t* numTaxa)
+{
+    if (!ctx || !lin || !numTaxa) return MC_ERR_INVALID;
+    *lin = ctx->taxonLin.data();
+    if (rank) *rank = ctx->taxonRank.data();
+    if (covered) *covered = ctx->taxonCoveredSet ? ctx->taxonCovered.data() : nullptr;
+    *numTaxa = ctx->taxonRank.size();
     return MC_OK;
 }
 

@@ -550,6 +550,17 @@ struct HitsFeed {
     void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
 };
 
+// -precision / -taxon-coverage on the device (mc_evaluate_*) with MCQ_EVALUATE_DEVICE=1: the workers hand every batch's
+// (assigned taxon, truth) pairs to the library instead of counting them; a batch the library does not take is counted on the host as before
+struct EvalFeed {
+    mc_ctx* ctx = nullptr;
+    std::mutex mtx;
+    std::string firstError;                  // why the first batch that stayed on the host did
+    uint64_t calls = 0, reads = 0, hostBatches = 0;
+    void took(uint64_t n) { std::lock_guard<std::mutex> l(mtx); ++calls; reads += n; }
+    void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
+};
+
 // -align: where a batch's text gets alignment lines (behind a mapping line's taxon text, before its '\n'), for which query of the
 // batch, against which candidate; the Aligner below turns these into problems for the device and into lines
 struct AlignWant { size_t at, q; Cand c; };
@@ -570,6 +581,54 @@ struct MappingWriter {
     std::vector<uint32_t> feedCounts = {};
     std::vector<uint64_t> feedIds = {};
     uint32_t feedFlushes = 0;
+
+    EvalFeed* eval = nullptr;                   // -precision: the batch's (assigned, truth) pairs go to the library (flush_eval) instead of tally.known / correct / wrong
+    std::vector<mc_assignment> evalAssigned = {};
+    std::vector<uint32_t> evalTruth = {};
+
+    // evaluate_classification + update_coverage_statistics (classification.cpp:237-295) for one read on the host
+    void count_truth(uint32_t best, uint32_t truth)
+    {
+        const int bestRank = best ? tx.taxon(best)->rank : kNumRanks;
+        const int knownRank = truth ? tx.taxon(truth)->rank : kNumRanks;
+        int correctRank = kNumRanks;                         // rank of the ranked LCA of mapping and truth
+        if (best && truth) {
+            const Lineage la = tx.ranks_of(best), lb = tx.ranks_of(truth);
+            for (int r = 0; r < kNumRanks; ++r) if (la[r] && la[r] == lb[r]) { correctRank = tx.taxon(la[r])->rank; break; }
+        }
+        // assign_known_correct (classification_statistics.hpp:86-106)
+        if (correctRank < bestRank) correctRank = bestRank;
+        if (correctRank < knownRank) correctRank = knownRank;
+        ++tally.known[knownRank];
+        if (knownRank != kNumRanks) {
+            ++tally.correct[correctRank];
+            if (correctRank > knownRank && correctRank > bestRank) ++tally.wrong[correctRank - 1];
+        }
+        if (o.taxonCoverage && truth) {                       // update_coverage_statistics, classification.cpp:242-265
+            for (uint32_t t : tx.ranks_of(truth)) {
+                if (!t) continue;
+                const int r = tx.taxon(t)->rank;
+                const bool classifiedOnRank = best && r >= bestRank;
+                if (!tx.covers(t) && classifiedOnRank) ++tally.covFalsePos[r];
+                if (r == 19) ++tally.covDomain;
+            }
+        }
+    }
+
+    // the pairs gathered since the last call through mc_evaluate_assignments; if the call fails the batch's reads are counted here as they
+    // always were.  A batch is one staged piece (a few thousand reads against the library's 4 * 10^6), so a call that failed has counted
+    // nothing of it there; a failure after the first of several pieces would count those pieces twice.
+    void flush_eval()
+    {
+        if (!eval || evalTruth.empty()) return;
+        const int flags = MC_EVALUATE_HOST | MC_EVALUATE_TALLY | (o.taxonCoverage ? MC_EVALUATE_COVERAGE : 0);
+        if (mc_evaluate_assignments(eval->ctx, evalAssigned.data(), evalTruth.data(), (uint32_t)evalTruth.size(), flags, nullptr, nullptr) == MC_OK) eval->took(evalTruth.size());
+        else {
+            eval->note(mc_last_error(eval->ctx));
+            for (size_t i = 0; i < evalTruth.size(); ++i) count_truth(evalAssigned[i].taxon, evalTruth[i]);
+        }
+        evalAssigned.clear(); evalTruth.clear();
+    }
 
     // the candidates gathered since the last call as flat rows, padded to the longest list (the form the -cov-percentile feed builds), with
     // the query ids in an array, through mc_target_hits_add; the library applies matches_per_target::insert's rule.  If the call fails
@@ -602,29 +661,8 @@ struct MappingWriter {
         uint32_t truth = 0;
         if (o.determineGroundTruth) truth = ground_truth(tx, std::string(header.p, header.n));
         if (o.precision) {                                       // evaluate_classification, classification.cpp:272-295
-            const int knownRank = truth ? tx.taxon(truth)->rank : kNumRanks;
-            int correctRank = kNumRanks;                         // rank of the ranked LCA of mapping and truth
-            if (best && truth) {
-                const Lineage la = tx.ranks_of(best), lb = tx.ranks_of(truth);
-                for (int r = 0; r < kNumRanks; ++r) if (la[r] && la[r] == lb[r]) { correctRank = tx.taxon(la[r])->rank; break; }
-            }
-            // assign_known_correct (classification_statistics.hpp:86-106)
-            if (correctRank < bestRank) correctRank = bestRank;
-            if (correctRank < knownRank) correctRank = knownRank;
-            ++tally.known[knownRank];
-            if (knownRank != kNumRanks) {
-                ++tally.correct[correctRank];
-                if (correctRank > knownRank && correctRank > bestRank) ++tally.wrong[correctRank - 1];
-            }
-            if (o.taxonCoverage && truth) {                       // update_coverage_statistics, classification.cpp:242-265
-                for (uint32_t t : tx.ranks_of(truth)) {
-                    if (!t) continue;
-                    const int r = tx.taxon(t)->rank;
-                    const bool classifiedOnRank = best && r >= bestRank;
-                    if (!tx.covers(t) && classifiedOnRank) ++tally.covFalsePos[r];
-                    if (r == 19) ++tally.covDomain;
-                }
-            }
+            if (eval) { evalAssigned.push_back(mc_assignment{best, (uint32_t)bestRank}); evalTruth.push_back(truth); }
+            else count_truth(best, truth);
         }
         if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];             // classify_and_evaluate, classification.cpp:552-554
         if (o.hitsPerRef && !deferred) {                         // matches_per_target::insert (matches_per_target.hpp:100-110)
@@ -1103,6 +1141,7 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* a
                 else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0, m.q);
             }
         });
+        L.flush_eval();
         L.flush_feed();                                                     // (also for a batch the job failed in: what it gathered is recorded or kept, never dropped)
         if (!done) break;
         if (aligner && step.prints && !L.deferred) {                        // the batch's alignments: one device call, then the lines go into its text
@@ -1469,8 +1508,23 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         else feed.ctx = S.ctx;
         if (const char* e = std::getenv("MCQ_TARGET_HITS_HOST_EVERY")) feed.hostEvery = (uint32_t)std::max(0, std::atoi(e));
     }
+    // -precision / -taxon-coverage: counted by the library (mc_evaluate_*) where MCQ_EVALUATE_DEVICE=1 asks for it and one context serves
+    // the whole run; under -cov-percentile, in the sharded command lines and in merge the host loop stays
+    EvalFeed evalFeed;
+    std::string evalWhyNot;
+    const char* evalSwitch = std::getenv("MCQ_EVALUATE_DEVICE");
+    const bool evalWanted = o.precision && evalSwitch && std::atoi(evalSwitch) != 0;
+    if (evalWanted) {
+        mc_evaluation e0;
+        if (merged) evalWhyNot = "merge mode";
+        else if (covMode) evalWhyNot = "-cov-percentile classifies on the host after the coverage filter";
+        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) evalWhyNot = "the run uses more than one context";
+        else if (mc_evaluate_tally(S.ctx, &e0, 1) != MC_OK) evalWhyNot = mc_last_error(S.ctx);      // (counters at zero to begin with)
+        else evalFeed.ctx = S.ctx;
+    }
     auto worker = [&](unsigned w, auto&& step) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]};
+        if (evalFeed.ctx) L.eval = &evalFeed;
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
         if (feed.ctx) L.feed = &feed;
         if (aligning && !covMode) L.wants = &A.wants;
@@ -1494,6 +1548,15 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
 
     Tally T;
     for (const Tally& t : tallies) T += t;
+    if (evalFeed.ctx) {                                                     // what the library counted, beside what stayed on the host
+        mc_evaluation E;
+        if (mc_evaluate_tally(evalFeed.ctx, &E, 1) != MC_OK) throw std::runtime_error(mc_last_error(evalFeed.ctx));
+        for (int r = 0; r <= kNumRanks; ++r) {
+            T.known[r] += E.known[r]; T.correct[r] += E.correct[r]; T.wrong[r] += E.wrong[r];
+            T.covFalsePos[r] += E.coverage[r][1];
+        }
+        for (int c = 0; c < 4; ++c) T.covDomain += E.coverage[19][c];
+    }
     if (covMode) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, true, T};
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
@@ -1511,6 +1574,12 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    if (P.on && evalFeed.ctx) {
+        std::cerr << "mcq profile: evaluation on the device: " << evalFeed.calls << " mc_evaluate_assignments calls, " << evalFeed.reads << " reads, "
+                  << evalFeed.hostBatches << " batches counted on the host";
+        if (evalFeed.hostBatches) std::cerr << " (" << evalFeed.firstError << ")";
+        std::cerr << "\n";
+    } else if (P.on && evalWanted) std::cerr << "mcq: -precision: evaluated on the host (" << evalWhyNot << ")\n";
     if (o.hitsPerRef) {
         std::vector<mc_target_hit> devHits;
         if (feed.ctx) {                                                     // mc_target_hits_collect replaces the sort of all records on one host thread

@@ -1,6 +1,7 @@
-// metacache_amd/csrc/rows_common.h -- what the consumers of candidate rows (classify.hip, coverage.hip, target_hits.hip) share with each
-// other and with context.cpp: the staging of host arrays, the drain before a readback, the kernel timer, and -- on the device -- the
-// taxon-of-a-target rule.  The wave reductions they use are device_common.h's.  Internal.
+// metacache_amd/csrc/rows_common.h -- what the consumers of candidate rows (classify.hip, coverage.hip, target_hits.hip) and of their
+// assignments (evaluate.hip) share with each other and with context.cpp: the staging of host arrays, the drain before a readback, the
+// kernel timer, and -- on the device -- the taxon-of-a-target rule and the per-key wave sum of the tallies.  The wave reductions they use are
+// device_common.h's.  Internal.
 #pragma once
 
 #include "context.h"
@@ -98,6 +99,23 @@ __device__ __forceinline__ uint32_t taxon_of_target(const uint32_t* lin, uint32_
     if (lowest > 0) while (!t && ++r < MC_NUM_RANKS) t = lin[(uint64_t)r * linTargets + tgt];
     rank = r;
     return t;
+}
+
+// adds, for every distinct key among the wave's active lanes, the number of lanes that hold it: `rounds` keys are counted across the
+// wave (one add each, by the first lane that holds the key), the lanes left after that add 1 each.  All lanes of the wave call this.
+template <class Add>
+__device__ __forceinline__ void wave_add_by_key(uint32_t key, bool active, int rounds, Add add)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long todo = __ballot(active);
+    for (int r = 0; r < rounds && todo; ++r) {
+        const int leader = __ffsll(todo) - 1;
+        const uint32_t k = (uint32_t)__shfl((int)key, leader);
+        const unsigned long long same = __ballot(active && key == k);
+        if (lane == (uint32_t)leader) add(k, (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+    if ((todo >> lane) & 1ull) add(key, 1u);
 }
 
 #endif  // __HIPCC__
