@@ -663,12 +663,74 @@ int mc_target_hits_add(mc_ctx* ctx, const mc_candidate* cands, const uint64_t* q
 int mc_target_hits_collect(mc_ctx* ctx, uint64_t* offsets, uint64_t capacity_targets, uint64_t* num_targets,
                            mc_target_hit* records, uint64_t capacity_records, uint64_t* num_records, uint64_t stats[4], int reset);
 
+/* ---- mapping lines: the per-read output of `metacache query` ----------------------------------------
+ * The reference prints one line per read (show_query_mapping, classification.cpp:432-523; show_candidates and show_candidate_ranges,
+ * printing.cpp:283-380).  Here the lines of a whole batch are rendered on the device, behind the query and the vote.  Every text of a
+ * line that depends on the taxonomy or on the output options (-taxids, -taxids-only, -omit-ranks, -lineage, -separate-cols, -separator,
+ * -lowest, -highest) depends on the taxon or on the target alone, so the library needs neither: it needs three TABLES OF STRINGS and a
+ * handful of flags.  Line i, with `column` the column separator:
+ *     [id column] name column [truth column] [tophits column] [locations column] result '\n'
+ *   id        (MC_FORMAT_QUERY_IDS) query_ids[i] if query_ids is given, else first_query_id + i (modulo 2^64), as a decimal number.
+ *   name      names[name_off[i] .. name_off[i + 1]): the bytes as they are (the caller cuts the header at its first blank).
+ *   truth     (MC_FORMAT_TRUTH) the MC_TEXT_RESULT entry of truth[i].
+ *   tophits   (MC_FORMAT_TOPHITS) the read's candidates cands[i * stride ..) up to the first with hits == 0, joined by ','; each is
+ *             text ':' hits with text = the MC_TEXT_CANDIDATE entry of its tgt.  A candidate whose text is empty -- or whose tgt lies
+ *             beyond the table -- prints nothing, neither the ':' nor the hits, but its comma stays (show_candidates for a target
+ *             without a taxon).
+ *   locations (MC_FORMAT_LOCATIONS) per candidate of the same walk '[' win_stride * beg ',' win_stride * end + win_len "] ", in 64 bits.
+ *   result    the MC_TEXT_RESULT entry of assigned[i].taxon (entry 0: the unclassified text).  Where the MC_TEXT_TARGET_RESULT table is
+ *             set, an assignment with taxon != 0 and rank 0 (bits 0-7 of info: a sequence-level result) prints that table's entry of
+ *             the read's FIRST candidate's tgt instead.
+ *   A result index (taxon, truth, or that tgt) beyond its table prints entry 0 of MC_TEXT_RESULT and is counted once in
+ *   mc_format_stats.  With MC_FORMAT_MAPPED_ONLY a read with assigned[i].taxon == 0 has no line at all (line_off[i + 1] == line_off[i]).
+ * mc_format_set_text: `count` strings, string k = bytes[offsets[k] .. offsets[k + 1]), offsets[0] == 0 and not decreasing; copied.  The
+ * table goes to the device with the first mc_format_mappings and again after a later set; no format call may be in flight while a
+ * table is replaced.  Needs no device (an mc_open_metadata context takes the tables, and checks arguments).  MC_ERR_INVALID: NULL ctx
+ * or offsets, an unknown table, MC_TEXT_RESULT with count == 0, offsets that do not begin at 0 or decrease.
+ * mc_format_mappings: line i = out[line_off[i] .. line_off[i + 1]); line_off[n] = the bytes all lines need.  If that exceeds
+ * out_capacity NO BYTE OF out IS WRITTEN and line_off is still complete, so that the caller can size a buffer and call again.
+ *   Without MC_FORMAT_HOST all arrays are DEVICE pointers (out and cands 16-byte, assigned and the u64 arrays 8-byte, truth 4-byte
+ *   aligned) and the call is asynchronous on 'stream' (a hipStream_t; NULL = the context's own): enqueued behind mc_query_device ->
+ *   mc_classify_candidates it needs no synchronisation in between.  The overflow verdict is then line_off[n] > out_capacity, for the
+ *   caller to read; the call returns MC_OK.  line_off has room for num_queries + 1 + MC_FORMAT_SCRATCH entries: the tail is the
+ *   workspace of the scan, so the call keeps no per-call state in the context and calls on different streams may run at the same time.
+ *   With MC_FORMAT_HOST the arrays are HOST arrays (line_off: num_queries + 1 entries), staged in pieces through buffers of the context
+ *   as MC_CLASSIFY_HOST does (mc_set_tuning "format_stage_rows": reads per piece, 0 = default), one caller at a time; the call returns
+ *   when out is filled, or MC_ERR_NOMEM (line_off complete, out untouched) when the lines do not fit.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, options or line_off, NULL cands, assigned or name_off with
+ * num_queries > 0, NULL out with out_capacity > 0, stride == 0, column_len > 16, unknown flags, MC_FORMAT_TRUTH without truth,
+ * misaligned device arrays, out overlapping an input or line_off.  MC_ERR_STATE: no MC_TEXT_RESULT table, MC_FORMAT_TOPHITS without
+ * the MC_TEXT_CANDIDATE table, a context without a device (mc_open_metadata).  num_queries == 0: MC_OK and line_off[0] = 0 (a DEVICE line_off
+ * is written on the stream, so that form needs the device even then).
+ * mc_format_stats: stats[0..4] = mc_format_mappings calls that had reads, reads handed over, lines written, bytes written, result indices beyond
+ * their table -- the last three counted by the calls whose lines fitted.  Waits for the context's own streams. */
+#define MC_TEXT_RESULT        0      /* indexed by mc_assignment.taxon (and truth); entry 0 = the unclassified text */
+#define MC_TEXT_TARGET_RESULT 1      /* indexed by target, optional: the result text of sequence-level assignments */
+#define MC_TEXT_CANDIDATE     2      /* indexed by target: the text in front of ":hits" */
+int mc_format_set_text(mc_ctx* ctx, int which, const char* bytes, const uint64_t* offsets, uint64_t count);
+typedef struct {
+    char     column[16];             /* the column separator (-separator) ... */
+    uint32_t column_len;             /* ... and its length, 0 .. 16 */
+    uint32_t win_stride, win_len;    /* the database's window stride and window length: the locations column */
+} mc_format_options;
+#define MC_FORMAT_HOST        1      /* the arrays are HOST arrays, the call returns when out is filled */
+#define MC_FORMAT_QUERY_IDS   2      /* -queryids */
+#define MC_FORMAT_TRUTH       4      /* -ground-truth */
+#define MC_FORMAT_TOPHITS     8      /* -tophits */
+#define MC_FORMAT_LOCATIONS   16     /* -locations */
+#define MC_FORMAT_MAPPED_ONLY 32     /* -mapped-only */
+#define MC_FORMAT_SCRATCH     2048   /* entries of workspace behind a DEVICE line_off */
+int mc_format_mappings(mc_ctx* ctx, const mc_format_options* opt, const mc_candidate* cands, uint32_t stride, const mc_assignment* assigned,
+                       const uint32_t* truth, const uint64_t* query_ids, uint64_t first_query_id, const char* names, const uint64_t* name_off,
+                       uint32_t num_queries, int flags, char* out, uint64_t out_capacity, uint64_t* line_off, void* stream);
+int mc_format_stats(mc_ctx* ctx, uint64_t stats[5]);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with
  * the tuning switch "gw_fuse" 0), "gw_filter2", "gw_compact" (+ the ordering of the stream filter's reads), "gw_filter_stream_fine" (the sixteen-wave instance), "gw_filter_stream" (+ the second gw_compact), "gw_count" (gw_count_kernel<9>), "gw_count_512" (<10>), "gw_count_1024" (<11>); 8-byte store:
  * "big_filter", "big_filter_2", "big_count", "big_count_2" --, "gw_sort", "gw_sorted_cands", "query_wave", "scan", "sort_candidates";
- * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect); "taxon_evaluate" (taxon_evaluate_kernel, mc_evaluate_assignments).  Returns accumulated milliseconds and launch counts since the last reset. */
+ * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect); "taxon_evaluate" (taxon_evaluate_kernel, mc_evaluate_assignments); "format_lengths" (format_lengths_kernel + format_scan_kernel) and "format_write" (format_write_kernel, mc_format_mappings).  Returns accumulated milliseconds and launch counts since the last reset. */
 int mc_timing_enable(mc_ctx* ctx, int on);
 int mc_timing_reset(mc_ctx* ctx);
 int mc_timing_get(mc_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);

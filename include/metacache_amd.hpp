@@ -177,6 +177,16 @@ public:
         return l;
     }
 
+    // one of the three string tables of the mapping lines (mc_format_set_text): MC_TEXT_RESULT (per taxon index + 1, entry 0 = the
+    // unclassified text), MC_TEXT_TARGET_RESULT and MC_TEXT_CANDIDATE (per target); no format_mappings() may be in flight
+    void set_mapping_text(int which, const std::vector<std::string>& strings) const
+    {
+        std::string bytes;
+        std::vector<std::uint64_t> off(1, 0);
+        for (const std::string& t : strings) { bytes += t; off.push_back(bytes.size()); }
+        if (mc_format_set_text(ctx_, which, bytes.data(), off.data(), strings.size()) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+    }
+
     // -precision / -taxon-coverage after the last batch: what the batches' evaluate() calls have counted (mc_evaluate_tally; reset: the
     // counters start from zero again)
     classification_statistics evaluation(bool reset = false) const
@@ -257,6 +267,30 @@ public:
             s.first = verdicts_.data(); s.last = s.first + verdicts_.size();
             return s;
         }
+        // the batch's mapping lines (after classify()): what show_query_mapping prints per query (classification.cpp:432-523,
+        // printing.cpp:283-380), rendered on the device from the slot's host arrays (mc_format_mappings; the string tables:
+        // database::set_mapping_text).  names[nameOff[i] .. nameOff[i + 1]) is query i's name; the queries are numbered firstQueryId,
+        // firstQueryId + 1, ...; flags: MC_FORMAT_QUERY_IDS, _TRUTH (truth: one taxon index + 1 per query), _TOPHITS, _LOCATIONS,
+        // _MAPPED_ONLY.  Line i is text[offsets[i] .. offsets[i + 1]).  Valid until the next format_mappings() or clear().
+        struct mapping_lines { const std::string& text; const std::vector<std::uint64_t>& offsets; };
+        mapping_lines format_mappings(const mc_format_options& opt, int flags, const char* names, span<const std::uint64_t> nameOff,
+                                      std::uint64_t firstQueryId, span<const std::uint32_t> truth = span<const std::uint32_t>())
+        {
+            const std::uint32_t n = res_.num_queries;
+            if (assigned_.size() != n || nameOff.size() != std::size_t(n) + 1 || ((flags & MC_FORMAT_TRUTH) && truth.size() != n))
+                throw std::runtime_error("format_mappings: one assignment (classify()), one name and -- with MC_FORMAT_TRUTH -- one truth per query of the batch");
+            lineOff_.resize(std::size_t(n) + 1);
+            if (lines_.size() < std::size_t(n) * 128 + 16) lines_.resize(std::size_t(n) * 128 + 16);
+            auto render = [&]() {
+                return mc_format_mappings(ctx_, &opt, res_.cands, res_.max_candidates, assigned_.data(), (flags & MC_FORMAT_TRUTH) ? truth.begin() : nullptr,
+                                          nullptr, firstQueryId, names, nameOff.begin(), n, flags | MC_FORMAT_HOST, &lines_[0], lines_.size(), lineOff_.data(), nullptr);
+            };
+            int rc = render();
+            if (rc == MC_ERR_NOMEM) { lines_.resize(lineOff_[n]); rc = render(); }      // (line_off came back complete: now the lines fit)
+            if (rc != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+            lines_.resize(lineOff_[n]);
+            return mapping_lines{lines_, lineOff_};
+        }
         // -cov-percentile, first pass (after wait_for_results): the windows that this batch's qualifying candidates cover are marked in
         // the context's bitmap (matches_per_target::insert, matches_per_target.hpp:100-127; mc_coverage_add on the slot's host arrays)
         void cover(std::uint32_t hitsMin, int lowestRank)
@@ -287,7 +321,7 @@ public:
                                    MC_TARGET_HITS_HOST, nullptr) != MC_OK)
                 throw std::runtime_error(mc_last_error(ctx_));
         }
-        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); }   // query_batch.cuh:255-259
+        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); lineOff_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
         mc_ctx* ctx_ = nullptr; std::uint32_t slot_ = 0;
@@ -296,6 +330,8 @@ public:
         std::vector<mc_assignment> assigned_;
         std::vector<mc_candidate> kept_;
         std::vector<mc_verdict> verdicts_;
+        std::string lines_;
+        std::vector<std::uint64_t> lineOff_;
     };
 
     query_batch(const database& db, unsigned numHostThreads) : ctx_(db.ctx_), hosts_(numHostThreads)

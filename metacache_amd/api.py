@@ -23,6 +23,9 @@ CLASSIFY_HOST, CLASSIFY_TALLY = 1, 2
 COVERAGE_HOST = 1
 TARGET_HITS_HOST = 1
 EVALUATE_HOST, EVALUATE_TALLY, EVALUATE_COVERAGE = 1, 2, 4
+FORMAT_HOST, FORMAT_QUERY_IDS, FORMAT_TRUTH, FORMAT_TOPHITS, FORMAT_LOCATIONS, FORMAT_MAPPED_ONLY = 1, 2, 4, 8, 16, 32
+FORMAT_SCRATCH = 2048                    # MC_FORMAT_SCRATCH: entries of workspace behind a device line_off
+TEXT_RESULT, TEXT_TARGET_RESULT, TEXT_CANDIDATE = 0, 1, 2
 verdict_dtype = np.dtype([("known", "u1"), ("correct", "u1"), ("flags", "u1"), ("reserved", "u1")])   # mc_verdict: kr, cr, bit 0 = counted wrong
 RANK_NAMES = ["sequence", "form", "variety", "subspecies", "species", "subgenus", "genus", "subtribe", "tribe", "subfamily", "family",
               "suborder", "order", "subclass", "class", "subphylum", "phylum", "subkingdom", "kingdom", "domain", "root"]
@@ -113,6 +116,89 @@ def target_hits_tile() -> int:
 
 def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1) -> McClassifyOptions:
     return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
+
+
+class McFormatOptions(C.Structure):
+    _fields_ = [("column", C.c_char * 16), ("column_len", C.c_uint32), ("win_stride", C.c_uint32), ("win_len", C.c_uint32)]
+
+
+def format_options(column: bytes = b"\t|\t", win_stride: int = 0, win_len: int = 0) -> McFormatOptions:
+    """mc_format_options: the column separator (at most 16 bytes; a longer one is handed over as it is for the library to refuse) and
+    the database's window stride and length"""
+    o = McFormatOptions()
+    C.memmove(C.addressof(o), bytes(column[:16]), min(len(column), 16))
+    o.column_len, o.win_stride, o.win_len = len(column), int(win_stride), int(win_len)
+    return o
+
+
+def format_flags(*, query_ids=False, truth=False, tophits=False, locations=False, mapped_only=False) -> int:
+    return ((FORMAT_QUERY_IDS if query_ids else 0) | (FORMAT_TRUTH if truth else 0) | (FORMAT_TOPHITS if tophits else 0) |
+            (FORMAT_LOCATIONS if locations else 0) | (FORMAT_MAPPED_ONLY if mapped_only else 0))
+
+
+def pack_strings(strings):
+    """list of bytes -> (bytes, offsets uint64 [len + 1]): the form of mc_format_set_text and of the names of mc_format_mappings"""
+    off = np.zeros(len(strings) + 1, dtype=np.uint64)
+    if len(strings):
+        off[1:] = np.cumsum([len(x) for x in strings], dtype=np.uint64)
+    return b"".join(strings), off
+
+
+def mapping_texts(taxa, taxon_lin, target_lin, *, lowest: int = 0, highest: int = NUM_RANKS - 2, taxids: bool = False, taxids_only: bool = False,
+                  omit_ranks: bool = False, lineage: bool = False, separate_cols: bool = False, separator: str = "\t|\t", none: str = "--"):
+    """The three string tables of mc_format_set_text for one set of output options, built as the command line prints
+    (print_taxon, show_lineage, show_taxon, show_candidates; printing.cpp:160-310).  taxa: (id, parent, rank, name) per taxon as
+    Database.taxa() gives them; taxon_lin[taxa, 21] and target_lin[targets, 21]: Database.taxon_table()[0] and Database.lineages()
+    (taxon index + 1, 0 = none); lowest / highest: the ranks of -lowest / -highest (the command line's defaults: sequence .. domain).
+    Needs no device: all three come from an mc_open_metadata context.
+    -> {TEXT_RESULT: [bytes per taxon index + 1, entry 0 = unclassified], TEXT_TARGET_RESULT: [bytes per target],
+        TEXT_CANDIDATE: [bytes per target]}"""
+    show_id, show_name, show_rank = taxids or taxids_only, not taxids_only, not omit_ranks
+    if lowest > highest:
+        lowest = highest
+    collapse, tax_sep, rank_suffix, id_prefix, id_suffix = True, ",", ":", "(", ")"
+    if separate_cols:
+        collapse, tax_sep, rank_suffix, id_prefix, id_suffix = False, separator, separator, separator, ""
+
+    def print_taxon(name, tid, rank):
+        s = ""
+        if show_rank:
+            s += (none if rank == NUM_RANKS else RANK_NAMES[rank]) + rank_suffix
+        if show_name:
+            s += name + (id_prefix + str(tid) + id_suffix if show_id else "")
+        elif show_id:
+            s += str(tid)
+        return s
+
+    def show_lineage(lin, lo, hi):
+        parts = []
+        for r in range(lo, hi + 1):
+            x = int(lin[r])
+            parts.append(print_taxon(taxa[x - 1][3], taxa[x - 1][0], taxa[x - 1][2]) if x else print_taxon(none, 0, r))
+        return tax_sep.join(parts)
+
+    def show_taxon(best, lin):
+        if not best or taxa[best - 1][2] > highest:
+            if collapse:
+                return "0" if (show_id and not show_name and not show_rank) else none
+            rmax = highest if lineage else lowest
+            return tax_sep.join(print_taxon(none, 0, NUM_RANKS) for _ in range(lowest, rmax + 1))
+        rmin = max(lowest, taxa[best - 1][2])
+        return show_lineage(lin, rmin, highest if lineage else rmin)
+
+    def candidate(row):
+        if lowest == 0:
+            x = int(row[0])
+            return taxa[x - 1][3] if x else ""
+        x = next((int(v) for v in row[lowest:] if v), 0)
+        return str(taxa[x - 1][0]) if x else ""
+
+    zeros = np.zeros(NUM_RANKS, dtype=np.uint32)
+    result = [show_taxon(0, zeros)] + [show_taxon(x + 1, taxon_lin[x]) for x in range(len(taxa))]
+    target_result = [show_taxon(int(row[0]), row) for row in target_lin]
+    cand = [candidate(row) for row in target_lin]
+    enc = lambda l: [x.encode() for x in l]
+    return {TEXT_RESULT: enc(result), TEXT_TARGET_RESULT: enc(target_result), TEXT_CANDIDATE: enc(cand)}
 
 
 class McEvaluation(C.Structure):
@@ -216,7 +302,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_classify_options_default", "mc_classify_candidates", "mc_classify_tally",
            "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop",
            "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect",
-           "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally"]
+           "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally",
+           "mc_format_set_text", "mc_format_mappings", "mc_format_stats"]
 
 _lib = None
 
@@ -290,6 +377,10 @@ def lib() -> C.CDLL:
         L.mc_db_taxon_table.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.mc_evaluate_assignments.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p]
         L.mc_evaluate_tally.argtypes = [C.c_void_p, C.POINTER(McEvaluation), C.c_int]
+        L.mc_format_set_text.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_format_mappings.argtypes = [C.c_void_p, C.POINTER(McFormatOptions), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mc_format_stats.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -600,6 +691,54 @@ class Database:
         e = McEvaluation()
         self._check(lib().mc_evaluate_tally(self.h, C.byref(e), int(reset)))
         return Evaluation(list(e.assigned), list(e.known), list(e.correct), list(e.wrong), [list(row) for row in e.coverage], e.reads, e.out_of_table)
+
+    # ---- mapping lines: the per-read output of the command line (mc_format_*) ------------------------
+    def format_set_text(self, which: int, strings):
+        """one of the three string tables (TEXT_RESULT, TEXT_TARGET_RESULT, TEXT_CANDIDATE): a list of bytes, e.g. from mapping_texts()"""
+        data, off = pack_strings([bytes(x) for x in strings])
+        buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        self._check(lib().mc_format_set_text(self.h, which, buf.ctypes.data, off.ctypes.data, len(off) - 1))
+
+    def format_device(self, opt: McFormatOptions, cands_ptr: int, stride: int, assigned_ptr: int, names_ptr: int, name_off_ptr: int, n: int, *,
+                      flags: int = 0, truth_ptr: int = 0, query_ids_ptr: int = 0, first_query_id: int = 0, out_ptr: int, out_capacity: int,
+                      line_off_ptr: int, stream: int = 0):
+        """renders n mapping lines from arrays in device memory into out_ptr (16-byte aligned); line_off_ptr: n + 1 + FORMAT_SCRATCH
+        uint64, entry n = the bytes all lines need (more than out_capacity: nothing was written); asynchronous on `stream`"""
+        self._check(lib().mc_format_mappings(self.h, C.byref(opt), cands_ptr or None, stride, assigned_ptr or None, truth_ptr or None,
+                                             query_ids_ptr or None, first_query_id, names_ptr or None, name_off_ptr or None, n, flags,
+                                             out_ptr or None, out_capacity, line_off_ptr or None, stream or None))
+
+    def format_mappings(self, opt: McFormatOptions, cands: np.ndarray, assigned: np.ndarray, names, *, flags: int = 0, truth=None,
+                        query_ids=None, first_query_id: int = 0):
+        """the same on host arrays: cands[n, stride] (cand_dtype), assigned[n] (assignment_dtype), names: n bytes objects
+        -> (bytes: all lines, line_off uint64 [n + 1])"""
+        cands = np.ascontiguousarray(cands, dtype=cand_dtype)
+        assigned = np.ascontiguousarray(assigned, dtype=assignment_dtype)
+        if cands.ndim != 2 or assigned.shape != (cands.shape[0],) or len(names) != cands.shape[0]:
+            raise ValueError("format_mappings: cands must be [n, stride], assigned and names of length n")
+        n, stride = cands.shape
+        nbytes, noff = pack_strings([bytes(x) for x in names])
+        nbuf = np.frombuffer(nbytes, dtype=np.uint8) if nbytes else np.zeros(1, dtype=np.uint8)
+        tr = None if truth is None else np.ascontiguousarray(truth, dtype=np.uint32)
+        ids = None if query_ids is None else np.ascontiguousarray(query_ids, dtype=np.uint64)
+        line_off = np.zeros(n + 1, dtype=np.uint64)
+        args = lambda out, cap: (self.h, C.byref(opt), cands.ctypes.data if n else None, stride, assigned.ctypes.data if n else None,
+                                 None if tr is None else tr.ctypes.data, None if ids is None else ids.ctypes.data, first_query_id,
+                                 nbuf.ctypes.data, noff.ctypes.data, n, flags | FORMAT_HOST, out, cap, line_off.ctypes.data, None)
+        rc = lib().mc_format_mappings(*args(None, 0))                       # the size first: line_off is complete either way
+        if rc != -3:
+            self._check(rc)
+        total = int(line_off[n])
+        out = np.zeros(max(total, 1), dtype=np.uint8)
+        if total:
+            self._check(lib().mc_format_mappings(*args(out.ctypes.data, total)))
+        return out[:total].tobytes(), line_off
+
+    def format_stats(self):
+        """-> [mc_format_mappings calls, reads, lines written, bytes written, result indices beyond their table]"""
+        st = np.zeros(5, dtype=np.uint64)
+        self._check(lib().mc_format_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
 
     # ---- target coverage: the two passes of -cov-percentile (mc_coverage_*) -----------------------
     def load_target_windows(self, windows: np.ndarray):

@@ -182,6 +182,11 @@ void free_target_hits_state(mc_ctx* ctx);
 struct EvaluateState;
 void free_evaluate_state(mc_ctx* ctx);
 
+// format.hip: the string tables of mc_format_* (host copies and their device copies), its counters and the staging of MC_FORMAT_HOST,
+// freed with the context
+struct FormatState;
+void free_format_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -234,6 +239,10 @@ struct mc_ctx {
     std::mutex evaluateMtx;
     mcamd::EvaluateState* evaluate = nullptr;
     uint32_t evaluateStageRows = 0;        // MC_EVALUATE_HOST: reads per staged piece (mc_set_tuning "evaluate_stage_rows"; 0 = what 64 MB of pairs hold)
+
+    std::mutex formatMtx;
+    mcamd::FormatState* format = nullptr;  // made by the first mc_format_set_text
+    uint32_t formatStageRows = 0;          // MC_FORMAT_HOST: reads per staged piece (mc_set_tuning "format_stage_rows"; 0 = what 64 MB of candidates hold)
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

@@ -346,6 +346,38 @@ uint32_t lowest_ranked_ancestor(const Taxonomy& tx, uint32_t tgt, int lowest)
     return 0;
 }
 
+// The three string tables of mc_format_set_text for this job's output options, from the functions the host loop prints with: the result
+// text of every taxon (entry 0: unclassified), the result text of every target (sequence-level results print the TARGET's lineage) and
+// the text a candidate of every target has in front of ":hits" (show_candidates).  false + why: the library did not take a table.
+static bool set_format_tables(mc_ctx* ctx, const Options& o, const Taxonomy& tx, std::string& why)
+{
+    FastOut t;
+    std::vector<uint64_t> off;
+    auto begin = [&]() { t.s.clear(); off.assign(1, 0); };
+    auto set = [&](int which) {
+        if (mc_format_set_text(ctx, which, t.s.data(), off.data(), off.size() - 1) == MC_OK) return true;
+        why = mc_last_error(ctx);
+        return false;
+    };
+    begin();
+    for (uint32_t x = 0; x <= tx.taxa.size(); ++x) { show_taxon(t, o, tx, x, false, 0); off.push_back(t.s.size()); }
+    if (!set(MC_TEXT_RESULT)) return false;
+    begin();
+    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) { show_taxon(t, o, tx, tx.targetLineages[tgt * kNumRanks], true, (uint32_t)tgt); off.push_back(t.s.size()); }
+    if (!set(MC_TEXT_TARGET_RESULT)) return false;
+    begin();
+    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) {
+        const Taxon* x = tx.taxon(lowest_ranked_ancestor(tx, (uint32_t)tgt, o.lowest));
+        if (x && o.lowest == 0) t << x->name;
+        else if (x) {
+            const Taxon* a = x->rank < o.lowest ? tx.taxon(tx.target_ranks((uint32_t)tgt)[o.lowest]) : x;
+            if (a) t << a->id; else t << x->name;
+        }
+        off.push_back(t.s.size());
+    }
+    return set(MC_TEXT_CANDIDATE);
+}
+
 // one query's device candidate list (K entries, the used ones first) as Cands
 void device_candidates(const mc_candidate* c, uint32_t K, const Taxonomy& tx, int lowest, std::vector<Cand>& out)
 {
@@ -561,6 +593,21 @@ struct EvalFeed {
     void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
 };
 
+// the mapping lines on the device (mc_format_*) with MCQ_FORMAT_DEVICE=1: a worker lays a batch's candidates out as flat rows,
+// has the library vote (mc_classify_candidates) and render the lines (mc_format_mappings), and takes its tallies from the assignments;
+// a batch whose call fails is classified and formatted on the host as a whole, as before
+struct FormatFeed {
+    mc_ctx* ctx = nullptr;
+    mc_format_options opt{};
+    mc_classify_options vote{};
+    int flags = 0;                           // MC_FORMAT_HOST | what the output options ask for
+    std::mutex mtx;
+    std::string firstError;                  // why the first batch that stayed on the host did
+    uint64_t calls = 0, reads = 0, lines = 0, hostBatches = 0;
+    void took(uint64_t n, uint64_t l) { std::lock_guard<std::mutex> g(mtx); ++calls; reads += n; lines += l; }
+    void note(const std::string& why) { std::lock_guard<std::mutex> g(mtx); if (hostBatches++ == 0) firstError = why; }
+};
+
 // -align: where a batch's text gets alignment lines (behind a mapping line's taxon text, before its '\n'), for which query of the
 // batch, against which candidate; the Aligner below turns these into problems for the device and into lines
 struct AlignWant { size_t at, q; Cand c; };
@@ -585,6 +632,13 @@ struct MappingWriter {
     EvalFeed* eval = nullptr;                   // -precision: the batch's (assigned, truth) pairs go to the library (flush_eval) instead of tally.known / correct / wrong
     std::vector<mc_assignment> evalAssigned = {};
     std::vector<uint32_t> evalTruth = {};
+
+    FormatFeed* fmt = nullptr;                  // MCQ_FORMAT_DEVICE: the batch's lines come from the library (device_lines) instead of operator()
+    std::vector<mc_candidate> fmtRows = {};
+    std::vector<mc_assignment> fmtAssigned = {};
+    std::vector<uint32_t> fmtTruth = {};
+    std::vector<uint64_t> fmtIds = {}, fmtNameOff = {}, fmtLineOff = {};
+    std::string fmtNames = {}, fmtBytes = {};
 
     // evaluate_classification + update_coverage_statistics (classification.cpp:237-295) for one read on the host
     void count_truth(uint32_t best, uint32_t truth)
@@ -649,6 +703,68 @@ struct MappingWriter {
                 }
         }
         feedCands.clear(); feedCounts.clear(); feedIds.clear();
+    }
+
+    // One batch through the library: what operator() does read by read -- vote, tallies, line -- for all its reads at once.  false: a call
+    // failed (fmt says why) and NOTHING of the batch was counted or written, so that the caller's host loop does the whole batch.
+    template <class OS, class Queries>
+    bool device_lines(OS& out, const Queries& queries, const mc_results& r)
+    {
+        const uint32_t K = r.max_candidates;
+        fmtRows.clear(); fmtIds.clear(); fmtTruth.clear(); fmtNames.clear(); fmtNameOff.assign(1, 0);
+        for (uint32_t i = 0; i < r.num_queries; ++i) {
+            const auto& m = queries[i];
+            if (m.empty) continue;                                   // processQuery, classification.cpp:780
+            fmtRows.insert(fmtRows.end(), r.cands + (size_t)i * K, r.cands + (size_t)(i + 1) * K);
+            fmtIds.push_back(m.id);
+            const void* sp = memchr(m.header.p, ' ', m.header.n);
+            fmtNames.append(m.header.p, sp ? (size_t)((const char*)sp - m.header.p) : m.header.n);
+            fmtNameOff.push_back(fmtNames.size());
+            if (o.determineGroundTruth) fmtTruth.push_back(ground_truth(tx, std::string(m.header.p, m.header.n)));
+        }
+        const size_t n = fmtIds.size();
+        if (n == 0) return true;
+        fmtAssigned.resize(n);
+        if (mc_classify_candidates(fmt->ctx, &fmt->vote, fmtRows.data(), (uint32_t)n, K, MC_CLASSIFY_HOST, fmtAssigned.data(), nullptr) != MC_OK) {
+            fmt->note(mc_last_error(fmt->ctx));
+            return false;
+        }
+        fmtLineOff.resize(n + 1);
+        if (fmtBytes.size() < n * 128) fmtBytes.resize(n * 128);
+        auto render = [&]() {
+            return mc_format_mappings(fmt->ctx, &fmt->opt, fmtRows.data(), K, fmtAssigned.data(), (fmt->flags & MC_FORMAT_TRUTH) ? fmtTruth.data() : nullptr,
+                                      fmtIds.data(), 0, fmtNames.data(), fmtNameOff.data(), (uint32_t)n, fmt->flags, &fmtBytes[0], fmtBytes.size(), fmtLineOff.data(), nullptr);
+        };
+        int rc = render();
+        if (rc == MC_ERR_NOMEM) { fmtBytes.resize(fmtLineOff[n] + fmtLineOff[n] / 4); rc = render(); }      // (line_off came back complete: now they fit)
+        if (rc != MC_OK) { fmt->note(mc_last_error(fmt->ctx)); return false; }
+        uint64_t lines = 0;
+        for (size_t j = 0; j < n; ++j) {
+            const uint32_t best = fmtAssigned[j].taxon;
+            ++tally.assigned[fmtAssigned[j].info & 0xFFu];
+            lines += fmtLineOff[j + 1] > fmtLineOff[j];
+            const uint32_t truth = o.determineGroundTruth ? fmtTruth[j] : 0;
+            if (o.precision) {
+                if (eval) { evalAssigned.push_back(fmtAssigned[j]); evalTruth.push_back(truth); }
+                else count_truth(best, truth);
+            }
+            if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];
+            if (o.hitsPerRef) {                                      // matches_per_target::insert (matches_per_target.hpp:100-110)
+                const mc_candidate* row = &fmtRows[j * K];
+                uint32_t used = 0;
+                while (used < K && row[used].hits != 0) ++used;
+                if (!feed) {
+                    for (uint32_t c = 0; c < used; ++c)
+                        if (lowest_ranked_ancestor(tx, row[c].tgt, o.lowest) && row[c].hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{row[c].tgt, fmtIds[j], row[c].beg, row[c].end, row[c].hits});
+                } else if (used) {
+                    feedIds.push_back(fmtIds[j]); feedCounts.push_back(used);
+                    feedCands.insert(feedCands.end(), row, row + used);
+                }
+            }
+        }
+        out.write(fmtBytes.data(), (std::streamsize)fmtLineOff[n]);
+        fmt->took(n, lines);
+        return true;
     }
 
     template <class OS>
@@ -1129,6 +1245,7 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* a
         // (a moved-from string keeps its 15-character SSO capacity, never 0)
         if (step.prints) { out.s.clear(); if (out.s.capacity() < 64) W.take_buffer(out.s); out << B->prefix; }
         const bool done = step(*B, [&](const std::vector<Query>& queries, const mc_results& r) {
+            if (L.fmt && L.device_lines(out, queries, r)) return;           // (false: the batch is classified and formatted here, as a whole)
             for (uint32_t i = 0; i < r.num_queries; ++i) {
                 const Query& m = queries[i];
                 if (m.empty) continue;                                      // processQuery, classification.cpp:780
@@ -1522,8 +1639,38 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         else if (mc_evaluate_tally(S.ctx, &e0, 1) != MC_OK) evalWhyNot = mc_last_error(S.ctx);      // (counters at zero to begin with)
         else evalFeed.ctx = S.ctx;
     }
+    // the mapping lines: rendered by the library (mc_format_*) where MCQ_FORMAT_DEVICE=1 asks for it and one context serves the whole run;
+    // what the library does not print (-allhits, the alignment lines), what classifies later or elsewhere (-cov-percentile, -maxcand 0's
+    // host candidates, the sharded command lines, merge) keeps the host loop
+    FormatFeed fmtFeed;
+    std::string fmtWhyNot;
+    const char* fmtSwitch = std::getenv("MCQ_FORMAT_DEVICE");
+    const bool fmtWanted = fmtSwitch && std::atoi(fmtSwitch) != 0;
+    if (fmtWanted) {
+        if (merged) fmtWhyNot = "merge mode";
+        else if (o.mapView == Options::mv_none) fmtWhyNot = "no mapping lines are printed";
+        else if (o.allhits) fmtWhyNot = "-allhits: the library does not print location lists";
+        else if (aligning) fmtWhyNot = "-align: the alignment lines are put into the host's lines";
+        else if (covMode) fmtWhyNot = "-cov-percentile classifies on the host after the coverage filter";
+        else if (o.maxCand < 1) fmtWhyNot = "-maxcand 0: lists longer than the device's are made on the host";
+        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) fmtWhyNot = "the run uses more than one context";
+        else if (o.column.size() > sizeof fmtFeed.opt.column) fmtWhyNot = "a column separator of more than 16 bytes";
+        else {
+            std::string why;
+            if (!set_format_tables(S.ctx, o, tx, why)) fmtWhyNot = why;
+            else {
+                fmtFeed.ctx = S.ctx;
+                std::memcpy(fmtFeed.opt.column, o.column.data(), o.column.size());
+                fmtFeed.opt.column_len = (uint32_t)o.column.size(); fmtFeed.opt.win_stride = S.dbStride; fmtFeed.opt.win_len = S.dbWinlen;
+                fmtFeed.vote = mc_classify_options{(uint32_t)o.hitsMin, o.hitsDiff, o.lowest, o.highest};
+                fmtFeed.flags = MC_FORMAT_HOST | (o.queryIds ? MC_FORMAT_QUERY_IDS : 0) | (o.showGroundTruth ? MC_FORMAT_TRUTH : 0) | (o.tophits ? MC_FORMAT_TOPHITS : 0) |
+                                (o.locations ? MC_FORMAT_LOCATIONS : 0) | (o.mapView == Options::mv_mapped ? MC_FORMAT_MAPPED_ONLY : 0);
+            }
+        }
+    }
     auto worker = [&](unsigned w, auto&& step) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]};
+        if (fmtFeed.ctx) L.fmt = &fmtFeed;
         if (evalFeed.ctx) L.eval = &evalFeed;
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
         if (feed.ctx) L.feed = &feed;
@@ -1574,6 +1721,12 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    if (P.on && fmtFeed.ctx) {
+        std::cerr << "mcq profile: mapping lines on the device: " << fmtFeed.calls << " mc_format_mappings calls, " << fmtFeed.reads << " reads, " << fmtFeed.lines
+                  << " lines, " << fmtFeed.hostBatches << " batches formatted on the host";
+        if (fmtFeed.hostBatches) std::cerr << " (" << fmtFeed.firstError << ")";
+        std::cerr << "\n";
+    } else if (P.on && fmtWanted) std::cerr << "mcq: mapping lines formatted on the host (" << fmtWhyNot << ")\n";
     if (P.on && evalFeed.ctx) {
         std::cerr << "mcq profile: evaluation on the device: " << evalFeed.calls << " mc_evaluate_assignments calls, " << evalFeed.reads << " reads, "
                   << evalFeed.hostBatches << " batches counted on the host";

@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--no-ref", action="store_true")
     ap.add_argument("--build", action="store_true", help="also time `build` from FASTA files (mcq and the reference)")
+    ap.add_argument("--format-switch", action="store_true", help="only `-tophits -queryids` with and without MCQ_FORMAT_DEVICE=1 (DESIGN.md 7f): "
+                    "three runs each, taking turns; the two outputs must be the same bytes")
     args = ap.parse_args()
     build.build_library()
     G, GL = 16, 5_000_000
@@ -94,6 +96,27 @@ def main():
     ref = os.path.join(ROOT, "oracle", "_ref", "metacache_u16")
     o = os.path.join(tmp, "o.txt")
     run([mcq, "query", db, fa_small, "-no-map", "-out", o])                               # page cache + first-touch warm-up
+    if args.format_switch:
+        o2 = os.path.join(tmp, "o2.txt")
+        env = dict(os.environ, MCQ_PROFILE="1")
+        env.pop("MCQ_FORMAT_DEVICE", None)
+        runs = {"mcq_nomap": [], "mcq_tophits_ids": [], "mcq_tophits_ids_format_device": []}
+        for _ in range(3):
+            for name, extra, out, sw in (("mcq_nomap", ["-no-map"], o, None), ("mcq_tophits_ids", ["-tophits", "-queryids"], o, None),
+                                         ("mcq_tophits_ids_format_device", ["-tophits", "-queryids"], o2, "1")):
+                run([mcq, "query", db, fa] + extra + ["-out", out], env=dict(env, MCQ_FORMAT_DEVICE=sw) if sw else env)
+                runs[name].append(speed_of(out)[1])
+        for name, ms in runs.items():
+            res[name] = {"query_ms": sorted(ms)[1], "query_ms_all": ms, "Mreads_per_min": round(args.reads / (sorted(ms)[1] / 1e3) * 60 / 1e6, 1)}
+        host = [l for l in open(o) if not l.startswith("#")]
+        devl = [l for l in open(o2) if not l.startswith("#")]
+        res["identical_mapping_lines_host_vs_format_device"] = {"host": len(host), "device": len(devl), "differing": sum(x != y for x, y in zip(host, devl)) + abs(len(host) - len(devl))}
+        print(json.dumps(res, indent=1))
+        if args.out:
+            os.makedirs(os.path.dirname(args.out) or ".", exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     for name, extra in (("mcq_nomap", ["-no-map"]), ("mcq_map", []), ("mcq_tophits_ids", ["-tophits", "-queryids"])):
         wall = run([mcq, "query", db, fa] + extra + ["-out", o])
         q, ms = speed_of(o)
