@@ -1,0 +1,295 @@
+// mcq_device_steps.h -- `mcq query`: handing a batch's work to the library instead of doing it in the host loop.
+// A hand-off -- coverage, hits, evaluate, format: the four sections below -- is one DeviceStep per job with three steps for run_job: open (the
+// switch, the reasons to stay on the host, the opening library call), finish (the library's results into the Tally / its sorted records)
+// and report (the stderr lines); and one client per worker, which owns the buffers a batch is gathered in and their flush.  A call that
+// fails leaves its whole batch to the host loop, so that nothing is counted twice, and the step keeps the reason of the first such batch.
+// Part of mcq_main.cpp's one translation unit: included there behind what it uses (Options, FastOut, show_taxon, Cand, ground_truth,
+// lowest_ranked_ancestor, device_candidates, Session, Cover, Tally, Batch, Profile).
+#ifndef MCQ_DEVICE_STEPS_H_
+#define MCQ_DEVICE_STEPS_H_
+
+struct DeviceStep {
+    mc_ctx* ctx = nullptr;                   // the context the batches go to (null: the host loop does the work)
+    std::string off;                         // asked for and not on the device: why
+    std::mutex mtx; std::string firstError;  // firstError: why the first batch that stayed on the host did
+    uint64_t calls = 0, reads = 0, hostBatches = 0;
+    void took(uint64_t n) { std::lock_guard<std::mutex> l(mtx); ++calls; reads += n; }
+    void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
+    // under MCQ_PROFILE: what the library did (`device`, up to the number of batches it left to the host), or that the host did it all and why
+    void report(const Profile& P, const std::string& device, const char* left, const char* host) const
+    {
+        if (P.on && ctx) std::cerr << "mcq profile: " << device << hostBatches << left << (hostBatches ? " (" + firstError + ")" : std::string()) << "\n";
+        else if (P.on && !off.empty()) std::cerr << "mcq: " << host << " (" << off << ")\n";
+    }
+};
+
+// The reasons to stay on the host that the hand-offs share, in the order they are looked at ("": none).  A hand-off words what -cov-percentile
+// means to it, and its own reasons stand between the shared ones: ownFirst in front of -cov-percentile, ownSecond in front of the contexts.
+static std::string shared_host_reason(const Session& S, bool merged, bool covMode, const char* covWording, const char* ownFirst = nullptr, const char* ownSecond = nullptr)
+{
+    if (merged) return "merge mode";
+    if (ownFirst) return ownFirst;
+    if (covMode) return covWording;
+    if (ownSecond) return ownSecond;
+    return S.keyset || S.partset || S.replication > 1 || !S.ctx ? "the run uses more than one context" : "";   // (the sharded command lines, -replicate)
+}
+
+// matches_per_target::insert's rule (matches_per_target.hpp:100-110): a record for every candidate whose target has a taxon on rank `lowest`
+// or the closest one above it, and whose hits reach -hitmin.  For a candidate from the device Cand::tax IS that taxon -- device_candidates
+// and host_candidates set it to lowest_ranked_ancestor(tx, tgt, lowest), nothing changes it -- so `Cand::tax != 0` and
+// `lowest_ranked_ancestor(tx, tgt, lowest) != 0` are the same predicate there: lists of Cands pass the first, flat rows the second.
+// (Merge mode's candidates have a taxon and no target, and exist as Cands only.)
+inline bool records_match(uint32_t tax, uint32_t hits, const Options& o) { return tax && hits >= (uint32_t)o.hitsMin; }
+inline mc_candidate as_candidate(const Cand& c) { return mc_candidate{c.tgt, c.hits, c.beg, c.end}; }
+
+// n candidate lists (len(i) entries: at(i, j)) as flat rows padded to the longest list, as mc_coverage_add and mc_target_hits_add take them; -> a row's length
+template <class Len, class At>
+size_t padded_rows(size_t n, Len&& len, At&& at, std::vector<mc_candidate>& rows)
+{
+    size_t rowLen = 0;
+    for (size_t i = 0; i < n; ++i) rowLen = std::max<size_t>(rowLen, len(i));
+    rows.assign(n * rowLen, mc_candidate{0, 0, 0, 0});
+    for (size_t i = 0; i < n; ++i) for (size_t j = 0, m = len(i); j < m; ++j) rows[i * rowLen + j] = at(i, j);
+    return rowLen;
+}
+
+// ---- coverage (mc_coverage_*): how many windows of a target -cov-percentile's deferred candidates cover -----------------
+// The lists (Batch::deferred) go through mc_coverage_add batch by batch, one mc_coverage_counts gives every target's count and size.  Off: the
+// context cannot do it (no window counts, no lineages) or saw entries outside their targets (an inconsistent database) -- the caller counts on
+// the host then, and report() says so: the fall-back is never silent.  A candidate list never holds an entry without hits in front of one with
+// hits (its rows end at the first hits == 0), so the kernel's "a row ends at hits == 0" and the host's loop over every entry see the same entries.
+struct CoverageStep : DeviceStep {
+    std::vector<uint32_t> covered, windows;  // per target
+    uint64_t stats[4] = {0, 0, 0, 0};
+    void open(mc_ctx* c, const Options& o, const std::deque<Batch>& batches)
+    {
+        uint64_t nt = 0; std::vector<mc_candidate> rows;
+        if (!c) { off = "no context"; return; }
+        if (mc_coverage_counts(c, nullptr, nullptr, 0, &nt, nullptr, 1) != MC_OK) { off = mc_last_error(c); return; }   // (an empty bitmap to begin with)
+        for (const Batch& B : batches) {
+            const auto& reads = B.deferred;
+            const size_t rowLen = padded_rows(reads.size(), [&](size_t i) { return reads[i].cands.size(); }, [&](size_t i, size_t j) { return as_candidate(reads[i].cands[j]); }, rows);
+            if (rowLen && mc_coverage_add(c, rows.data(), (uint32_t)reads.size(), (uint32_t)rowLen, (uint32_t)o.hitsMin, o.lowest, MC_COVERAGE_HOST, nullptr) != MC_OK) { off = mc_last_error(c); return; }
+        }
+        covered.assign(nt, 0); windows.assign(nt, 0);
+        if (mc_coverage_counts(c, covered.data(), windows.data(), nt, nullptr, stats, 1) != MC_OK) off = mc_last_error(c);
+        else if (stats[1] != 0) off = std::to_string(stats[1]) + " candidates lie outside their targets' windows";
+        else ctx = c;
+    }
+    void report(const Profile& P) const
+    {
+        if (!ctx) std::cerr << "mcq: -cov-percentile: covered windows counted on the host (" << off << ")\n";
+        else if (P.on) std::cerr << "mcq profile: coverage on the device: " << stats[3] << " mc_coverage_add calls, " << stats[0] << " candidates marked, " << stats[2] << " windows covered\n";
+    }
+};
+
+// ---- hits (mc_target_hits_*): -hits-per-ref's records in the library's log ---------------------------------------------
+// The lists are built by the library where one context serves the whole run; under -cov-percentile, in the sharded command lines and in
+// merge they are built on the host.  A batch the library does not take (MC_ERR_NOMEM: the log may not grow further) stays on the host too.
+constexpr bool kTargetHitsOnDevice = false;  // the default of `mcq query -hits-per-ref` (DESIGN.md 7d says what decides it); MCQ_TARGET_HITS_DEVICE overrides
+struct HitsStep : DeviceStep {
+    uint32_t hostEvery = 0;                  // MCQ_TARGET_HITS_HOST_EVERY=k (tests): every k-th batch of a worker stays on the host as if its call had failed
+    uint64_t stats[4] = {0, 0, 0, 0};
+    std::vector<mc_target_hit> records;      // the library's sorted records, after finish()
+    void open(const Session& S, const Options& o, bool merged, bool covMode)
+    {
+        if (!o.hitsPerRef) return;
+        const char* sw = std::getenv("MCQ_TARGET_HITS_DEVICE");                // 1 / 0: the library's log / the host vector, whatever the default
+        if (!(sw ? std::atoi(sw) != 0 : kTargetHitsOnDevice)) off = "the host sort is the default here (MCQ_TARGET_HITS_DEVICE=1 selects the library's log)";
+        else off = shared_host_reason(S, merged, covMode, "-cov-percentile keeps the candidates on the host");
+        if (off.empty() && mc_target_hits_collect(S.ctx, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 1) != MC_OK) off = mc_last_error(S.ctx);   // (an empty log to begin with)
+        if (off.empty()) ctx = S.ctx;
+        if (const char* e = std::getenv("MCQ_TARGET_HITS_HOST_EVERY")) hostEvery = (uint32_t)std::max(0, std::atoi(e));
+    }
+    void finish()                            // mc_target_hits_collect replaces the sort of all records on one host thread
+    {
+        if (!ctx) return;
+        uint64_t nt = 0, nr = 0;
+        if (mc_target_hits_collect(ctx, nullptr, 0, &nt, nullptr, 0, &nr, nullptr, 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx));
+        records.resize(nr);
+        if (mc_target_hits_collect(ctx, nullptr, 0, nullptr, records.data(), nr, nullptr, stats, 1) != MC_OK) throw std::runtime_error(mc_last_error(ctx));
+        mc_target_hits_reserve(ctx, 0);                                         // (the log's memory goes back)
+    }
+    void report(const Profile& P, size_t hostRecords) const
+    {
+        DeviceStep::report(P, "hits per target on the device: " + std::to_string(stats[2]) + " mc_target_hits_add calls, " + std::to_string(stats[0]) + " records, " + std::to_string(stats[3]) + " targets, " + std::to_string(hostRecords) + " records of ",
+                           " batches kept on the host", "-hits-per-ref: lists built on the host");
+    }
+};
+struct HitsClient {                          // a worker's candidates since its last flush: list after list, with their query ids
+    HitsStep* step = nullptr;                // (null: the records go to Tally::covers one by one)
+    std::vector<mc_candidate> cands, rows; std::vector<uint64_t> ids;
+    std::vector<size_t> ends; uint32_t flushes = 0;   // list i: cands[ends[i - 1] .. ends[i])
+    void add(uint64_t id, const std::vector<Cand>& list)
+    {
+        for (const Cand& c : list) cands.push_back(as_candidate(c));
+        if (!list.empty()) { ids.push_back(id); ends.push_back(cands.size()); }
+    }
+    // through mc_target_hits_add (the library applies records_match's rule); if the call fails nothing of the batch was recorded: its entries go to `covers`
+    void flush(const Options& o, const Taxonomy& tx, std::vector<Cover>& covers)
+    {
+        const size_t n = ids.size();
+        if (step && n) {
+            auto begin = [&](size_t i) { return i ? ends[i - 1] : 0; };
+            const size_t rowLen = padded_rows(n, [&](size_t i) { return ends[i] - begin(i); }, [&](size_t i, size_t j) { return cands[begin(i) + j]; }, rows);
+            const bool held = step->hostEvery && ++flushes % step->hostEvery == 0;
+            if (held || mc_target_hits_add(step->ctx, rows.data(), ids.data(), 0, (uint32_t)n, (uint32_t)rowLen, (uint32_t)o.hitsMin, o.lowest, MC_TARGET_HITS_HOST, nullptr) != MC_OK) {
+                step->note(held ? "MCQ_TARGET_HITS_HOST_EVERY" : mc_last_error(step->ctx));
+                for (size_t i = 0, j = 0; i < n; ++i) for (; j < ends[i]; ++j)
+                    if (records_match(lowest_ranked_ancestor(tx, cands[j].tgt, o.lowest), cands[j].hits, o)) covers.push_back(Cover{cands[j].tgt, ids[i], cands[j].beg, cands[j].end, cands[j].hits});
+            }
+        }
+        cands.clear(); ends.clear(); ids.clear();
+    }
+};
+
+// ---- evaluate (mc_evaluate_*): -precision / -taxon-coverage counted by the library -------------------------------------
+// The workers hand every batch's (assigned taxon, truth) pairs over instead of counting them, where MCQ_EVALUATE_DEVICE=1 asks for it and one
+// context serves the whole run; under -cov-percentile, in the sharded command lines and in merge the host loop stays.
+struct EvalStep : DeviceStep {
+    void open(const Session& S, const Options& o, bool merged, bool covMode)
+    {
+        const char* sw = std::getenv("MCQ_EVALUATE_DEVICE");
+        if (!o.precision || !sw || std::atoi(sw) == 0) return;
+        mc_evaluation e0;
+        off = shared_host_reason(S, merged, covMode, "-cov-percentile classifies on the host after the coverage filter");
+        if (off.empty() && mc_evaluate_tally(S.ctx, &e0, 1) != MC_OK) off = mc_last_error(S.ctx);      // (counters at zero to begin with)
+        if (off.empty()) ctx = S.ctx;
+    }
+    void finish(Tally& T)                    // what the library counted, beside what stayed on the host
+    {
+        if (!ctx) return;
+        mc_evaluation E;
+        if (mc_evaluate_tally(ctx, &E, 1) != MC_OK) throw std::runtime_error(mc_last_error(ctx));
+        for (int r = 0; r <= kNumRanks; ++r) { T.known[r] += E.known[r]; T.correct[r] += E.correct[r]; T.wrong[r] += E.wrong[r]; T.covFalsePos[r] += E.coverage[r][1]; }
+        for (int c = 0; c < 4; ++c) T.covDomain += E.coverage[19][c];
+    }
+    void report(const Profile& P) const
+    {
+        DeviceStep::report(P, "evaluation on the device: " + std::to_string(calls) + " mc_evaluate_assignments calls, " + std::to_string(reads) + " reads, ", " batches counted on the host", "-precision: evaluated on the host");
+    }
+};
+struct EvalClient {                          // a worker's pairs since its last flush
+    EvalStep* step = nullptr;                // (null: the reads are counted on the host one by one)
+    std::vector<mc_assignment> assigned; std::vector<uint32_t> truth;
+    void add(mc_assignment a, uint32_t t) { assigned.push_back(a); truth.push_back(t); }
+    // through mc_evaluate_assignments; if the call fails the batch's reads are counted by onHost(taxon, truth) as they always were.  A batch is one staged piece (a few
+    // thousand reads against the library's 4 * 10^6), so a call that failed has counted nothing of it there; a failure after the first of several pieces would count those twice.
+    template <class OnHost>
+    void flush(const Options& o, OnHost&& onHost)
+    {
+        if (!step || truth.empty()) return;
+        const int flags = MC_EVALUATE_HOST | MC_EVALUATE_TALLY | (o.taxonCoverage ? MC_EVALUATE_COVERAGE : 0);
+        if (mc_evaluate_assignments(step->ctx, assigned.data(), truth.data(), (uint32_t)truth.size(), flags, nullptr, nullptr) == MC_OK) step->took(truth.size());
+        else { step->note(mc_last_error(step->ctx)); for (size_t i = 0; i < truth.size(); ++i) onHost(assigned[i].taxon, truth[i]); }
+        assigned.clear(); truth.clear();
+    }
+};
+
+// ---- format (mc_format_*): the mapping lines rendered by the library --------------------------------------------------
+// With MCQ_FORMAT_DEVICE=1 a worker lays a batch's candidates out as flat rows, has the library vote (mc_classify_candidates) and render the
+// lines (mc_format_mappings), and takes its tallies from the assignments.  What the library does not print (-allhits, the alignment lines), what
+// classifies later or elsewhere (-cov-percentile, -maxcand 0's host candidates, the sharded command lines, merge) keeps the host loop.
+// The three string tables of mc_format_set_text for this job's output options, from the functions the host loop prints with: the result
+// text of every taxon (entry 0: unclassified), the result text of every target (sequence-level results print the TARGET's lineage) and
+// the text a candidate of every target has in front of ":hits" (show_candidates).  false + why: the library did not take a table.
+static bool set_format_tables(mc_ctx* ctx, const Options& o, const Taxonomy& tx, std::string& why)
+{
+    FastOut t;
+    std::vector<uint64_t> off;
+    auto begin = [&]() { t.s.clear(); off.assign(1, 0); };
+    auto set = [&](int which) { const bool ok = mc_format_set_text(ctx, which, t.s.data(), off.data(), off.size() - 1) == MC_OK; if (!ok) why = mc_last_error(ctx); return ok; };
+    begin();
+    for (uint32_t x = 0; x <= tx.taxa.size(); ++x) { show_taxon(t, o, tx, x, false, 0); off.push_back(t.s.size()); }
+    if (!set(MC_TEXT_RESULT)) return false;
+    begin();
+    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) { show_taxon(t, o, tx, tx.targetLineages[tgt * kNumRanks], true, (uint32_t)tgt); off.push_back(t.s.size()); }
+    if (!set(MC_TEXT_TARGET_RESULT)) return false;
+    begin();
+    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) {
+        const Taxon* x = tx.taxon(lowest_ranked_ancestor(tx, (uint32_t)tgt, o.lowest));
+        if (x && o.lowest == 0) t << x->name;
+        else if (x) {
+            const Taxon* a = x->rank < o.lowest ? tx.taxon(tx.target_ranks((uint32_t)tgt)[o.lowest]) : x;
+            if (a) t << a->id; else t << x->name;
+        }
+        off.push_back(t.s.size());
+    }
+    return set(MC_TEXT_CANDIDATE);
+}
+struct FormatStep : DeviceStep {
+    mc_format_options opt{}; mc_classify_options vote{};
+    uint64_t lines = 0; int flags = 0;       // flags: MC_FORMAT_HOST | what the output options ask for
+    void took(uint64_t n, uint64_t l) { std::lock_guard<std::mutex> g(mtx); ++calls; reads += n; lines += l; }
+    void open(const Session& S, const Options& o, bool merged, bool covMode, bool aligning)
+    {
+        const char* sw = std::getenv("MCQ_FORMAT_DEVICE");
+        if (!sw || std::atoi(sw) == 0) return;
+        const char* first = o.mapView == Options::mv_none ? "no mapping lines are printed" : o.allhits ? "-allhits: the library does not print location lists"
+                          : aligning ? "-align: the alignment lines are put into the host's lines" : nullptr;
+        const char* second = o.maxCand < 1 ? "-maxcand 0: lists longer than the device's are made on the host" : nullptr;
+        off = shared_host_reason(S, merged, covMode, "-cov-percentile classifies on the host after the coverage filter", first, second);
+        if (off.empty() && o.column.size() > sizeof opt.column) off = "a column separator of more than 16 bytes";
+        if (!off.empty() || !set_format_tables(S.ctx, o, S.tx, off)) return;
+        ctx = S.ctx;
+        std::memcpy(opt.column, o.column.data(), o.column.size());
+        opt.column_len = (uint32_t)o.column.size(); opt.win_stride = S.dbStride; opt.win_len = S.dbWinlen;
+        vote = mc_classify_options{(uint32_t)o.hitsMin, o.hitsDiff, o.lowest, o.highest};
+        flags = MC_FORMAT_HOST | (o.queryIds ? MC_FORMAT_QUERY_IDS : 0) | (o.showGroundTruth ? MC_FORMAT_TRUTH : 0) | (o.tophits ? MC_FORMAT_TOPHITS : 0) |
+                (o.locations ? MC_FORMAT_LOCATIONS : 0) | (o.mapView == Options::mv_mapped ? MC_FORMAT_MAPPED_ONLY : 0);
+    }
+    void report(const Profile& P) const
+    {
+        DeviceStep::report(P, "mapping lines on the device: " + std::to_string(calls) + " mc_format_mappings calls, " + std::to_string(reads) + " reads, " + std::to_string(lines) + " lines, ",
+                           " batches formatted on the host", "mapping lines formatted on the host");
+    }
+};
+struct FormatClient {                        // a worker's batch as the library takes it, and what comes back
+    FormatStep* step = nullptr;              // (null: the host loop classifies and prints read by read)
+    std::vector<mc_candidate> rows; std::vector<mc_assignment> assigned; std::vector<uint32_t> truth;
+    std::vector<uint64_t> ids, nameOff, lineOff; std::string names, bytes;
+    std::vector<Cand> cands;                 // (one read's, for -hits-per-ref)
+    // One batch through the library: what the writer L (MappingWriter) does read by read -- vote, tallies, line -- for all its reads at once.
+    // false: a call failed (the step says why) and NOTHING of the batch was counted or written, so that the caller's host loop does the whole batch.
+    template <class OS, class Queries, class Writer>
+    bool lines(OS& out, const Queries& queries, const mc_results& r, Writer& L)
+    {
+        const Options& o = L.o;
+        const uint32_t K = r.max_candidates;
+        rows.clear(); ids.clear(); truth.clear(); names.clear(); nameOff.assign(1, 0);
+        for (uint32_t i = 0; i < r.num_queries; ++i) {
+            const auto& m = queries[i];
+            if (m.empty) continue;                                   // processQuery, classification.cpp:780
+            rows.insert(rows.end(), r.cands + (size_t)i * K, r.cands + (size_t)(i + 1) * K);
+            ids.push_back(m.id);
+            const void* sp = memchr(m.header.p, ' ', m.header.n);
+            names.append(m.header.p, sp ? (size_t)((const char*)sp - m.header.p) : m.header.n);
+            nameOff.push_back(names.size());
+            if (o.determineGroundTruth) truth.push_back(ground_truth(L.tx, std::string(m.header.p, m.header.n)));
+        }
+        const size_t n = ids.size();
+        if (n == 0) return true;
+        assigned.resize(n);
+        if (mc_classify_candidates(step->ctx, &step->vote, rows.data(), (uint32_t)n, K, MC_CLASSIFY_HOST, assigned.data(), nullptr) != MC_OK) { step->note(mc_last_error(step->ctx)); return false; }
+        lineOff.resize(n + 1);
+        if (bytes.size() < n * 128) bytes.resize(n * 128);
+        auto render = [&]() {
+            return mc_format_mappings(step->ctx, &step->opt, rows.data(), K, assigned.data(), (step->flags & MC_FORMAT_TRUTH) ? truth.data() : nullptr,
+                                      ids.data(), 0, names.data(), nameOff.data(), (uint32_t)n, step->flags, &bytes[0], bytes.size(), lineOff.data(), nullptr);
+        };
+        int rc = render();
+        if (rc == MC_ERR_NOMEM) { bytes.resize(lineOff[n] + lineOff[n] / 4); rc = render(); }      // (line_off came back complete: now they fit)
+        if (rc != MC_OK) { step->note(mc_last_error(step->ctx)); return false; }
+        uint64_t printed = 0;
+        for (size_t j = 0; j < n; ++j) {
+            printed += lineOff[j + 1] > lineOff[j];
+            if (o.hitsPerRef) device_candidates(&rows[j * K], K, L.tx, o.lowest, cands);
+            L.count_read(ids[j], assigned[j], o.determineGroundTruth ? truth[j] : 0, cands);
+        }
+        out.write(bytes.data(), (std::streamsize)lineOff[n]);
+        step->took(n, printed);
+        return true;
+    }
+};
+
+#endif  // MCQ_DEVICE_STEPS_H_

@@ -346,38 +346,6 @@ uint32_t lowest_ranked_ancestor(const Taxonomy& tx, uint32_t tgt, int lowest)
     return 0;
 }
 
-// The three string tables of mc_format_set_text for this job's output options, from the functions the host loop prints with: the result
-// text of every taxon (entry 0: unclassified), the result text of every target (sequence-level results print the TARGET's lineage) and
-// the text a candidate of every target has in front of ":hits" (show_candidates).  false + why: the library did not take a table.
-static bool set_format_tables(mc_ctx* ctx, const Options& o, const Taxonomy& tx, std::string& why)
-{
-    FastOut t;
-    std::vector<uint64_t> off;
-    auto begin = [&]() { t.s.clear(); off.assign(1, 0); };
-    auto set = [&](int which) {
-        if (mc_format_set_text(ctx, which, t.s.data(), off.data(), off.size() - 1) == MC_OK) return true;
-        why = mc_last_error(ctx);
-        return false;
-    };
-    begin();
-    for (uint32_t x = 0; x <= tx.taxa.size(); ++x) { show_taxon(t, o, tx, x, false, 0); off.push_back(t.s.size()); }
-    if (!set(MC_TEXT_RESULT)) return false;
-    begin();
-    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) { show_taxon(t, o, tx, tx.targetLineages[tgt * kNumRanks], true, (uint32_t)tgt); off.push_back(t.s.size()); }
-    if (!set(MC_TEXT_TARGET_RESULT)) return false;
-    begin();
-    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) {
-        const Taxon* x = tx.taxon(lowest_ranked_ancestor(tx, (uint32_t)tgt, o.lowest));
-        if (x && o.lowest == 0) t << x->name;
-        else if (x) {
-            const Taxon* a = x->rank < o.lowest ? tx.taxon(tx.target_ranks((uint32_t)tgt)[o.lowest]) : x;
-            if (a) t << a->id; else t << x->name;
-        }
-        off.push_back(t.s.size());
-    }
-    return set(MC_TEXT_CANDIDATE);
-}
-
 // one query's device candidate list (K entries, the used ones first) as Cands
 void device_candidates(const mc_candidate* c, uint32_t K, const Taxonomy& tx, int lowest, std::vector<Cand>& out)
 {
@@ -570,43 +538,18 @@ struct Tally {
     uint64_t total() const { return classified() + unclassified(); }
 };
 
-// -hits-per-ref on the device (mc_target_hits_*): the workers hand every batch's candidate rows to the library's log instead
-// of pushing Covers; a batch the library does not take (MC_ERR_NOMEM: the log may not grow further) stays on the host as before
-constexpr bool kTargetHitsOnDevice = false;  // the default of `mcq query -hits-per-ref` (DESIGN.md 7d says what decides it); MCQ_TARGET_HITS_DEVICE overrides
-struct HitsFeed {
-    mc_ctx* ctx = nullptr;
-    std::mutex mtx;
-    std::string firstError;                  // why the first batch that stayed on the host did
-    uint32_t hostEvery = 0;                  // MCQ_TARGET_HITS_HOST_EVERY=k (tests): every k-th batch of a worker stays on the host as if its call had failed
-    uint64_t hostBatches = 0;
-    void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
+struct Deferred { uint64_t id; View header; std::vector<Cand> cands; size_t q; };   // (q: the query's place in its batch, BatchQueue::read)
+struct Batch {
+    size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast;
+    std::vector<Deferred> deferred;                                         // -cov-percentile: its reads' candidates
+    std::vector<mc_candidate> carried;                                      // part groups: its reads' candidate lists from the groups so far
+};
+struct Profile {                                                            // MCQ_PROFILE: phase times on stderr (development aid)
+    const bool on = std::getenv("MCQ_PROFILE") != nullptr;
+    std::atomic<uint64_t> parse{0}, submit{0}, wait{0}, classify{0};
 };
 
-// -precision / -taxon-coverage on the device (mc_evaluate_*) with MCQ_EVALUATE_DEVICE=1: the workers hand every batch's
-// (assigned taxon, truth) pairs to the library instead of counting them; a batch the library does not take is counted on the host as before
-struct EvalFeed {
-    mc_ctx* ctx = nullptr;
-    std::mutex mtx;
-    std::string firstError;                  // why the first batch that stayed on the host did
-    uint64_t calls = 0, reads = 0, hostBatches = 0;
-    void took(uint64_t n) { std::lock_guard<std::mutex> l(mtx); ++calls; reads += n; }
-    void note(const std::string& why) { std::lock_guard<std::mutex> l(mtx); if (hostBatches++ == 0) firstError = why; }
-};
-
-// the mapping lines on the device (mc_format_*) with MCQ_FORMAT_DEVICE=1: a worker lays a batch's candidates out as flat rows,
-// has the library vote (mc_classify_candidates) and render the lines (mc_format_mappings), and takes its tallies from the assignments;
-// a batch whose call fails is classified and formatted on the host as a whole, as before
-struct FormatFeed {
-    mc_ctx* ctx = nullptr;
-    mc_format_options opt{};
-    mc_classify_options vote{};
-    int flags = 0;                           // MC_FORMAT_HOST | what the output options ask for
-    std::mutex mtx;
-    std::string firstError;                  // why the first batch that stayed on the host did
-    uint64_t calls = 0, reads = 0, lines = 0, hostBatches = 0;
-    void took(uint64_t n, uint64_t l) { std::lock_guard<std::mutex> g(mtx); ++calls; reads += n; lines += l; }
-    void note(const std::string& why) { std::lock_guard<std::mutex> g(mtx); if (hostBatches++ == 0) firstError = why; }
-};
+#include "mcq_device_steps.h"
 
 // -align: where a batch's text gets alignment lines (behind a mapping line's taxon text, before its '\n'), for which query of the
 // batch, against which candidate; the Aligner below turns these into problems for the device and into lines
@@ -623,22 +566,9 @@ struct MappingWriter {
     // over -- its lineage walk (hash lookups up the taxonomy, taxonomy.hpp:576-597) is done once per worker and taxon
     std::unordered_map<uint64_t, std::string> taxText = {};
     std::vector<AlignWant>* wants = nullptr;    // -align: the printed lines of classified reads ask for their alignment here
-    HitsFeed* feed = nullptr;                   // -hits-per-ref: the batch's candidates go to the library's log (flush_feed) instead of tally.covers
-    std::vector<mc_candidate> feedCands = {}, feedRows = {};
-    std::vector<uint32_t> feedCounts = {};
-    std::vector<uint64_t> feedIds = {};
-    uint32_t feedFlushes = 0;
-
-    EvalFeed* eval = nullptr;                   // -precision: the batch's (assigned, truth) pairs go to the library (flush_eval) instead of tally.known / correct / wrong
-    std::vector<mc_assignment> evalAssigned = {};
-    std::vector<uint32_t> evalTruth = {};
-
-    FormatFeed* fmt = nullptr;                  // MCQ_FORMAT_DEVICE: the batch's lines come from the library (device_lines) instead of operator()
-    std::vector<mc_candidate> fmtRows = {};
-    std::vector<mc_assignment> fmtAssigned = {};
-    std::vector<uint32_t> fmtTruth = {};
-    std::vector<uint64_t> fmtIds = {}, fmtNameOff = {}, fmtLineOff = {};
-    std::string fmtNames = {}, fmtBytes = {};
+    HitsClient hits = {};                       // -hits-per-ref: the batch's candidates go to the library's log instead of tally.covers
+    EvalClient eval = {};                       // -precision: the batch's (assigned, truth) pairs go to the library instead of tally.known / correct / wrong
+    FormatClient fmt = {};                      // MCQ_FORMAT_DEVICE: the batch's lines come from the library (FormatClient::lines) instead of operator()
 
     // evaluate_classification + update_coverage_statistics (classification.cpp:237-295) for one read on the host
     void count_truth(uint32_t best, uint32_t truth)
@@ -669,102 +599,19 @@ struct MappingWriter {
         }
     }
 
-    // the pairs gathered since the last call through mc_evaluate_assignments; if the call fails the batch's reads are counted here as they
-    // always were.  A batch is one staged piece (a few thousand reads against the library's 4 * 10^6), so a call that failed has counted
-    // nothing of it there; a failure after the first of several pieces would count those pieces twice.
-    void flush_eval()
-    {
-        if (!eval || evalTruth.empty()) return;
-        const int flags = MC_EVALUATE_HOST | MC_EVALUATE_TALLY | (o.taxonCoverage ? MC_EVALUATE_COVERAGE : 0);
-        if (mc_evaluate_assignments(eval->ctx, evalAssigned.data(), evalTruth.data(), (uint32_t)evalTruth.size(), flags, nullptr, nullptr) == MC_OK) eval->took(evalTruth.size());
-        else {
-            eval->note(mc_last_error(eval->ctx));
-            for (size_t i = 0; i < evalTruth.size(); ++i) count_truth(evalAssigned[i].taxon, evalTruth[i]);
-        }
-        evalAssigned.clear(); evalTruth.clear();
-    }
+    // the end of a batch: what its reads gathered for the library goes there, the pairs first, then the candidates
+    void flush() { eval.flush(o, [&](uint32_t best, uint32_t truth) { count_truth(best, truth); }); hits.flush(o, tx, tally.covers); }
 
-    // the candidates gathered since the last call as flat rows, padded to the longest list (the form the -cov-percentile feed builds), with
-    // the query ids in an array, through mc_target_hits_add; the library applies matches_per_target::insert's rule.  If the call fails
-    // nothing of the batch was recorded: its entries go to tally.covers as they always did.
-    void flush_feed()
+    // One read's statistics from its assignment (taxon, rank) and its candidates, counted here or gathered for the library
+    void count_read(uint64_t id, mc_assignment a, uint32_t truth, const std::vector<Cand>& cands)
     {
-        if (!feed || feedIds.empty()) { feedCands.clear(); feedCounts.clear(); feedIds.clear(); return; }
-        const size_t n = feedIds.size(), rowLen = *std::max_element(feedCounts.begin(), feedCounts.end());
-        feedRows.assign(n * rowLen, mc_candidate{0, 0, 0, 0});
-        for (size_t i = 0, at = 0; i < n; at += feedCounts[i], ++i) std::copy(feedCands.begin() + at, feedCands.begin() + at + feedCounts[i], feedRows.begin() + i * rowLen);
-        const bool held = feed->hostEvery && ++feedFlushes % feed->hostEvery == 0;
-        if (held || mc_target_hits_add(feed->ctx, feedRows.data(), feedIds.data(), 0, (uint32_t)n, (uint32_t)rowLen, (uint32_t)o.hitsMin, o.lowest, MC_TARGET_HITS_HOST, nullptr) != MC_OK) {
-            feed->note(held ? "MCQ_TARGET_HITS_HOST_EVERY" : mc_last_error(feed->ctx));
-            for (size_t i = 0, at = 0; i < n; at += feedCounts[i], ++i)
-                for (size_t j = at; j < at + feedCounts[i]; ++j) {
-                    const mc_candidate& c = feedCands[j];
-                    if (lowest_ranked_ancestor(tx, c.tgt, o.lowest) && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, feedIds[i], c.beg, c.end, c.hits});
-                }
+        ++tally.assigned[a.info & 0xFFu];
+        if (o.precision) { if (eval.step) eval.add(a, truth); else count_truth(a.taxon, truth); }    // evaluate_classification, classification.cpp:272-295
+        if ((o.abundances || o.abundancePer != kNumRanks) && a.taxon) ++tally.counts[a.taxon];       // classify_and_evaluate, classification.cpp:552-554
+        if (o.hitsPerRef && !deferred) {                         // matches_per_target::insert (records_match)
+            if (hits.step) hits.add(id, cands);
+            else for (const Cand& c : cands) if (records_match(c.tax, c.hits, o)) tally.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits});
         }
-        feedCands.clear(); feedCounts.clear(); feedIds.clear();
-    }
-
-    // One batch through the library: what operator() does read by read -- vote, tallies, line -- for all its reads at once.  false: a call
-    // failed (fmt says why) and NOTHING of the batch was counted or written, so that the caller's host loop does the whole batch.
-    template <class OS, class Queries>
-    bool device_lines(OS& out, const Queries& queries, const mc_results& r)
-    {
-        const uint32_t K = r.max_candidates;
-        fmtRows.clear(); fmtIds.clear(); fmtTruth.clear(); fmtNames.clear(); fmtNameOff.assign(1, 0);
-        for (uint32_t i = 0; i < r.num_queries; ++i) {
-            const auto& m = queries[i];
-            if (m.empty) continue;                                   // processQuery, classification.cpp:780
-            fmtRows.insert(fmtRows.end(), r.cands + (size_t)i * K, r.cands + (size_t)(i + 1) * K);
-            fmtIds.push_back(m.id);
-            const void* sp = memchr(m.header.p, ' ', m.header.n);
-            fmtNames.append(m.header.p, sp ? (size_t)((const char*)sp - m.header.p) : m.header.n);
-            fmtNameOff.push_back(fmtNames.size());
-            if (o.determineGroundTruth) fmtTruth.push_back(ground_truth(tx, std::string(m.header.p, m.header.n)));
-        }
-        const size_t n = fmtIds.size();
-        if (n == 0) return true;
-        fmtAssigned.resize(n);
-        if (mc_classify_candidates(fmt->ctx, &fmt->vote, fmtRows.data(), (uint32_t)n, K, MC_CLASSIFY_HOST, fmtAssigned.data(), nullptr) != MC_OK) {
-            fmt->note(mc_last_error(fmt->ctx));
-            return false;
-        }
-        fmtLineOff.resize(n + 1);
-        if (fmtBytes.size() < n * 128) fmtBytes.resize(n * 128);
-        auto render = [&]() {
-            return mc_format_mappings(fmt->ctx, &fmt->opt, fmtRows.data(), K, fmtAssigned.data(), (fmt->flags & MC_FORMAT_TRUTH) ? fmtTruth.data() : nullptr,
-                                      fmtIds.data(), 0, fmtNames.data(), fmtNameOff.data(), (uint32_t)n, fmt->flags, &fmtBytes[0], fmtBytes.size(), fmtLineOff.data(), nullptr);
-        };
-        int rc = render();
-        if (rc == MC_ERR_NOMEM) { fmtBytes.resize(fmtLineOff[n] + fmtLineOff[n] / 4); rc = render(); }      // (line_off came back complete: now they fit)
-        if (rc != MC_OK) { fmt->note(mc_last_error(fmt->ctx)); return false; }
-        uint64_t lines = 0;
-        for (size_t j = 0; j < n; ++j) {
-            const uint32_t best = fmtAssigned[j].taxon;
-            ++tally.assigned[fmtAssigned[j].info & 0xFFu];
-            lines += fmtLineOff[j + 1] > fmtLineOff[j];
-            const uint32_t truth = o.determineGroundTruth ? fmtTruth[j] : 0;
-            if (o.precision) {
-                if (eval) { evalAssigned.push_back(fmtAssigned[j]); evalTruth.push_back(truth); }
-                else count_truth(best, truth);
-            }
-            if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];
-            if (o.hitsPerRef) {                                      // matches_per_target::insert (matches_per_target.hpp:100-110)
-                const mc_candidate* row = &fmtRows[j * K];
-                uint32_t used = 0;
-                while (used < K && row[used].hits != 0) ++used;
-                if (!feed) {
-                    for (uint32_t c = 0; c < used; ++c)
-                        if (lowest_ranked_ancestor(tx, row[c].tgt, o.lowest) && row[c].hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{row[c].tgt, fmtIds[j], row[c].beg, row[c].end, row[c].hits});
-                } else if (used) {
-                    feedIds.push_back(fmtIds[j]); feedCounts.push_back(used);
-                    feedCands.insert(feedCands.end(), row, row + used);
-                }
-            }
-        }
-        out.write(fmtBytes.data(), (std::streamsize)fmtLineOff[n]);
-        fmt->took(n, lines);
-        return true;
     }
 
     template <class OS>
@@ -773,21 +620,9 @@ struct MappingWriter {
         bool isTarget; uint32_t tgt;
         const uint32_t best = classify(o, tx, cands, isTarget, tgt);
         const int bestRank = best ? tx.taxon(best)->rank : kNumRanks;
-        ++tally.assigned[bestRank];
         uint32_t truth = 0;
         if (o.determineGroundTruth) truth = ground_truth(tx, std::string(header.p, header.n));
-        if (o.precision) {                                       // evaluate_classification, classification.cpp:272-295
-            if (eval) { evalAssigned.push_back(mc_assignment{best, (uint32_t)bestRank}); evalTruth.push_back(truth); }
-            else count_truth(best, truth);
-        }
-        if ((o.abundances || o.abundancePer != kNumRanks) && best) ++tally.counts[best];             // classify_and_evaluate, classification.cpp:552-554
-        if (o.hitsPerRef && !deferred) {                         // matches_per_target::insert (matches_per_target.hpp:100-110)
-            if (!feed) { for (const Cand& c : cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) tally.covers.push_back(Cover{c.tgt, id, c.beg, c.end, c.hits}); }
-            else if (!cands.empty()) {
-                feedIds.push_back(id); feedCounts.push_back((uint32_t)cands.size());
-                for (const Cand& c : cands) feedCands.push_back(mc_candidate{c.tgt, c.hits, c.beg, c.end});
-            }
-        }
+        count_read(id, mc_assignment{best, (uint32_t)bestRank}, truth, cands);
         if (o.mapView == Options::mv_none || (o.mapView == Options::mv_mapped && !best)) return;
         if (o.queryIds) out << id << o.column;
         const void* sp = memchr(header.p, ' ', header.n);
@@ -828,12 +663,6 @@ void run_workers(unsigned n, Fn&& fn)
 // ---- the batches: runs of consecutive queries of one file (pair of files), ids continuing across files -----------------------------
 // Batches are produced while the workers already run: plain files are indexed chunk by chunk (SeqFile::stream_*), and a batch goes out
 // as soon as its records are known -- the first one after a few megabytes instead of after the whole file.
-struct Deferred { uint64_t id; View header; std::vector<Cand> cands; size_t q; };   // (q: the query's place in its batch, BatchQueue::read)
-struct Batch {
-    size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast;
-    std::vector<Deferred> deferred;                                         // -cov-percentile: its reads' candidates
-    std::vector<mc_candidate> carried;                                      // part groups: its reads' candidate lists from the groups so far
-};
 struct Records { View h1, s1, h2, s2; std::string scratch1, scratch2; };    // one query's records (scratch: multi-line sequences)
 
 struct BatchQueue {
@@ -1135,10 +964,6 @@ struct OrderedOut {
 // ---- the device steps: a batch's queries in, their candidate lists out (emit(queries, results) once or more) ----------------------
 struct Query { uint64_t id; View header; bool empty; uint64_t len; size_t q; };   // (q: its place in the batch, BatchQueue::read)
 
-struct Profile {                                                            // MCQ_PROFILE: phase times on stderr (development aid)
-    const bool on = std::getenv("MCQ_PROFILE") != nullptr;
-    std::atomic<uint64_t> parse{0}, submit{0}, wait{0}, classify{0};
-};
 uint64_t now_ns() { return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // maxWindowsInRange (candidate_structs.hpp:143-145)
@@ -1245,7 +1070,7 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* a
         // (a moved-from string keeps its 15-character SSO capacity, never 0)
         if (step.prints) { out.s.clear(); if (out.s.capacity() < 64) W.take_buffer(out.s); out << B->prefix; }
         const bool done = step(*B, [&](const std::vector<Query>& queries, const mc_results& r) {
-            if (L.fmt && L.device_lines(out, queries, r)) return;           // (false: the batch is classified and formatted here, as a whole)
+            if (L.fmt.step && L.fmt.lines(out, queries, r, L)) return;              // (false: the batch is classified and formatted here, as a whole)
             for (uint32_t i = 0; i < r.num_queries; ++i) {
                 const Query& m = queries[i];
                 if (m.empty) continue;                                      // processQuery, classification.cpp:780
@@ -1258,8 +1083,7 @@ void work(BatchQueue& Q, OrderedOut& W, MappingWriter& L, Step& step, Aligner* a
                 else L(out, m.id, m.header, cands, o.allhits ? hits : nullptr, o.allhits ? nhits : 0, m.q);
             }
         });
-        L.flush_eval();
-        L.flush_feed();                                                     // (also for a batch the job failed in: what it gathered is recorded or kept, never dropped)
+        L.flush();                                                          // (also for a batch the job failed in: what it gathered is recorded or kept, never dropped)
         if (!done) break;
         if (aligner && step.prints && !L.deferred) {                        // the batch's alignments: one device call, then the lines go into its text
             std::string err;
@@ -1321,39 +1145,8 @@ void show_mapping_header(std::ostream& os, const Options& o)               // sh
 // filter_targets_by_coverage (classification.cpp:591-634) then walks the global map in ITS iteration order, sums float coverages in that
 // order, std::sorts them and erases targets from the low end: the order of equal coverages and the rounding of the sums come from the
 // containers.  Same containers, same insertion sequence here (the reference's -threads 1 order), so the same targets go.
-// What the containers do NOT decide -- how many windows of a target are covered -- comes from the library: the deferred candidates go
-// through mc_coverage_add batch by batch, as flat rows padded to the batch's longest list, and one mc_coverage_counts gives every
-// target's count and size.  false: the context cannot do it (no window counts, no lineages) or saw entries outside their targets (an
-// inconsistent database) -- the caller counts on the host then.
-// A candidate list never holds an entry without hits in front of one with hits (Deferred::cands comes from rows that end at the first
-// hits == 0), so the kernel's "a row ends at hits == 0" and the host loop below, which looks at every entry, see the same entries.
-// `why` says, where false comes back, what kept the device from counting: the caller reports it, the fall-back is never silent.
-static bool device_coverage(mc_ctx* ctx, const Options& o, const std::deque<Batch>& batches, std::vector<uint32_t>& covered, std::vector<uint32_t>& windows,
-                            uint64_t stats[4], std::string& why)
-{
-    uint64_t nt = 0;
-    if (!ctx) { why = "no context"; return false; }
-    if (mc_coverage_counts(ctx, nullptr, nullptr, 0, &nt, nullptr, 1) != MC_OK) { why = mc_last_error(ctx); return false; }   // (an empty bitmap to begin with)
-    std::vector<mc_candidate> rows;
-    for (const Batch& B : batches) {
-        size_t stride = 0;
-        for (const Deferred& d : B.deferred) stride = std::max(stride, d.cands.size());
-        if (stride == 0) continue;
-        rows.assign(B.deferred.size() * stride, mc_candidate{0, 0, 0, 0});
-        for (size_t i = 0; i < B.deferred.size(); ++i) {
-            const std::vector<Cand>& cs = B.deferred[i].cands;
-            for (size_t j = 0; j < cs.size(); ++j) rows[i * stride + j] = mc_candidate{cs[j].tgt, cs[j].hits, cs[j].beg, cs[j].end};
-        }
-        if (mc_coverage_add(ctx, rows.data(), (uint32_t)B.deferred.size(), (uint32_t)stride, (uint32_t)o.hitsMin, o.lowest, MC_COVERAGE_HOST, nullptr) != MC_OK) {
-            why = mc_last_error(ctx);
-            return false;
-        }
-    }
-    covered.assign(nt, 0); windows.assign(nt, 0);
-    if (mc_coverage_counts(ctx, covered.data(), windows.data(), nt, nullptr, stats, 1) != MC_OK) { why = mc_last_error(ctx); return false; }
-    if (stats[1] != 0) { why = std::to_string(stats[1]) + " candidates lie outside their targets' windows"; return false; }
-    return true;
-}
+// What the containers do NOT decide -- how many windows of a target are covered -- comes from the library (CoverageStep): a batch's
+// deferred candidate lists go there as flat rows, and where the library cannot count, the reference's own count below is used.
 
 // the reference's own count (classification.cpp:603-609): one set of windows per target
 static size_t host_covered_windows(const std::vector<Cover>& covers)
@@ -1363,7 +1156,7 @@ static size_t host_covered_windows(const std::vector<Cover>& covers)
     return hitWindows.size();
 }
 
-void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L, mc_ctx* ctx, Aligner* aligner = nullptr)
+void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<Batch>& batches, MappingWriter& L, mc_ctx* ctx, const Profile& P, Aligner* aligner = nullptr)
 {
     const Taxonomy& tx = L.tx;
     const size_t refBatch = o.refBatchSize ? o.refBatchSize : 4096;
@@ -1379,7 +1172,7 @@ void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<B
         for (const Batch& B : batches) {
             if (B.f1 != curFile || B.qBeg == 0) { if (inBatch) flush(); curFile = B.f1; }
             for (const Deferred& d : B.deferred) {
-                for (const Cand& c : d.cands) if (c.tax && c.hits >= (uint32_t)o.hitsMin) batchMap[c.tgt].push_back(Cover{c.tgt, d.id, c.beg, c.end, c.hits});
+                for (const Cand& c : d.cands) if (records_match(c.tax, c.hits, o)) batchMap[c.tgt].push_back(Cover{c.tgt, d.id, c.beg, c.end, c.hits});
                 if (++inBatch == refBatch) flush();
             }
         }
@@ -1390,17 +1183,12 @@ void classify_by_coverage(std::ostream& os, const Options& o, const std::deque<B
         std::vector<CovP> cov;
         cov.reserve(tgtMatches.size());
         float sum = 0;
-        std::vector<uint32_t> covered, windows;
-        uint64_t covStats[4] = {0, 0, 0, 0};
-        std::string why;
-        const bool fromDevice = device_coverage(ctx, o, batches, covered, windows, covStats, why);
-        if (!fromDevice) std::cerr << "mcq: -cov-percentile: covered windows counted on the host (" << why << ")\n";
-        else if (std::getenv("MCQ_PROFILE"))
-            std::cerr << "mcq profile: coverage on the device: " << covStats[3] << " mc_coverage_add calls, " << covStats[0] << " candidates marked, "
-                      << covStats[2] << " windows covered\n";
+        CoverageStep dev;
+        dev.open(ctx, o, batches);
+        dev.report(P);
         for (const auto& m : tgtMatches) {
             float covP;
-            if (fromDevice && m.first < covered.size()) covP = float(covered[m.first]) / windows[m.first];
+            if (dev.ctx && m.first < dev.covered.size()) covP = float(dev.covered[m.first]) / dev.windows[m.first];
             else {
                 const Lineage lin = tx.target_ranks(m.first);
                 const uint32_t targetSize = tx.taxon(lin[0]) ? (uint32_t)tx.taxon(lin[0])->windows : 0u;
@@ -1611,69 +1399,16 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     std::vector<Tally> tallies(S.workers);
     TargetCache targets(o.showErrors);                                      // -align: the target records of this job
     const bool aligning = o.align && !merged;
-    // -hits-per-ref: the lists are built by the library (mc_target_hits_*) where one context serves the whole run; under -cov-percentile,
-    // in the sharded command lines (part sets, key shards, -replicate) and in merge they are built on the host as before
-    HitsFeed feed;
-    std::string feedWhyNot;
-    if (o.hitsPerRef) {
-        const char* sw = std::getenv("MCQ_TARGET_HITS_DEVICE");                // 1 / 0: the library's log / the host vector, whatever the default
-        if (!(sw ? std::atoi(sw) != 0 : kTargetHitsOnDevice)) feedWhyNot = "the host sort is the default here (MCQ_TARGET_HITS_DEVICE=1 selects the library's log)";
-        else if (merged) feedWhyNot = "merge mode";
-        else if (covMode) feedWhyNot = "-cov-percentile keeps the candidates on the host";
-        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) feedWhyNot = "the run uses more than one context";
-        else if (mc_target_hits_collect(S.ctx, nullptr, 0, nullptr, nullptr, 0, nullptr, nullptr, 1) != MC_OK) feedWhyNot = mc_last_error(S.ctx);   // (an empty log to begin with)
-        else feed.ctx = S.ctx;
-        if (const char* e = std::getenv("MCQ_TARGET_HITS_HOST_EVERY")) feed.hostEvery = (uint32_t)std::max(0, std::atoi(e));
-    }
-    // -precision / -taxon-coverage: counted by the library (mc_evaluate_*) where MCQ_EVALUATE_DEVICE=1 asks for it and one context serves
-    // the whole run; under -cov-percentile, in the sharded command lines and in merge the host loop stays
-    EvalFeed evalFeed;
-    std::string evalWhyNot;
-    const char* evalSwitch = std::getenv("MCQ_EVALUATE_DEVICE");
-    const bool evalWanted = o.precision && evalSwitch && std::atoi(evalSwitch) != 0;
-    if (evalWanted) {
-        mc_evaluation e0;
-        if (merged) evalWhyNot = "merge mode";
-        else if (covMode) evalWhyNot = "-cov-percentile classifies on the host after the coverage filter";
-        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) evalWhyNot = "the run uses more than one context";
-        else if (mc_evaluate_tally(S.ctx, &e0, 1) != MC_OK) evalWhyNot = mc_last_error(S.ctx);      // (counters at zero to begin with)
-        else evalFeed.ctx = S.ctx;
-    }
-    // the mapping lines: rendered by the library (mc_format_*) where MCQ_FORMAT_DEVICE=1 asks for it and one context serves the whole run;
-    // what the library does not print (-allhits, the alignment lines), what classifies later or elsewhere (-cov-percentile, -maxcand 0's
-    // host candidates, the sharded command lines, merge) keeps the host loop
-    FormatFeed fmtFeed;
-    std::string fmtWhyNot;
-    const char* fmtSwitch = std::getenv("MCQ_FORMAT_DEVICE");
-    const bool fmtWanted = fmtSwitch && std::atoi(fmtSwitch) != 0;
-    if (fmtWanted) {
-        if (merged) fmtWhyNot = "merge mode";
-        else if (o.mapView == Options::mv_none) fmtWhyNot = "no mapping lines are printed";
-        else if (o.allhits) fmtWhyNot = "-allhits: the library does not print location lists";
-        else if (aligning) fmtWhyNot = "-align: the alignment lines are put into the host's lines";
-        else if (covMode) fmtWhyNot = "-cov-percentile classifies on the host after the coverage filter";
-        else if (o.maxCand < 1) fmtWhyNot = "-maxcand 0: lists longer than the device's are made on the host";
-        else if (S.keyset || S.partset || S.replication > 1 || !S.ctx) fmtWhyNot = "the run uses more than one context";
-        else if (o.column.size() > sizeof fmtFeed.opt.column) fmtWhyNot = "a column separator of more than 16 bytes";
-        else {
-            std::string why;
-            if (!set_format_tables(S.ctx, o, tx, why)) fmtWhyNot = why;
-            else {
-                fmtFeed.ctx = S.ctx;
-                std::memcpy(fmtFeed.opt.column, o.column.data(), o.column.size());
-                fmtFeed.opt.column_len = (uint32_t)o.column.size(); fmtFeed.opt.win_stride = S.dbStride; fmtFeed.opt.win_len = S.dbWinlen;
-                fmtFeed.vote = mc_classify_options{(uint32_t)o.hitsMin, o.hitsDiff, o.lowest, o.highest};
-                fmtFeed.flags = MC_FORMAT_HOST | (o.queryIds ? MC_FORMAT_QUERY_IDS : 0) | (o.showGroundTruth ? MC_FORMAT_TRUTH : 0) | (o.tophits ? MC_FORMAT_TOPHITS : 0) |
-                                (o.locations ? MC_FORMAT_LOCATIONS : 0) | (o.mapView == Options::mv_mapped ? MC_FORMAT_MAPPED_ONLY : 0);
-            }
-        }
-    }
+    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep;              // the hand-offs to the library (mcq_device_steps.h)
+    hitsStep.open(S, o, merged != nullptr, covMode);
+    evalStep.open(S, o, merged != nullptr, covMode);
+    fmtStep.open(S, o, merged != nullptr, covMode, aligning);
     auto worker = [&](unsigned w, auto&& step) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, covMode, tallies[w]};
-        if (fmtFeed.ctx) L.fmt = &fmtFeed;
-        if (evalFeed.ctx) L.eval = &evalFeed;
+        if (hitsStep.ctx) L.hits.step = &hitsStep;
+        if (evalStep.ctx) L.eval.step = &evalStep;
+        if (fmtStep.ctx) L.fmt.step = &fmtStep;
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
-        if (feed.ctx) L.feed = &feed;
         if (aligning && !covMode) L.wants = &A.wants;
         work(Q, W, L, step, aligning ? &A : nullptr);
     };
@@ -1695,21 +1430,14 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
 
     Tally T;
     for (const Tally& t : tallies) T += t;
-    if (evalFeed.ctx) {                                                     // what the library counted, beside what stayed on the host
-        mc_evaluation E;
-        if (mc_evaluate_tally(evalFeed.ctx, &E, 1) != MC_OK) throw std::runtime_error(mc_last_error(evalFeed.ctx));
-        for (int r = 0; r <= kNumRanks; ++r) {
-            T.known[r] += E.known[r]; T.correct[r] += E.correct[r]; T.wrong[r] += E.wrong[r];
-            T.covFalsePos[r] += E.coverage[r][1];
-        }
-        for (int c = 0; c < 4; ++c) T.covDomain += E.coverage[19][c];
-    }
+    evalStep.finish(T);
+    hitsStep.finish();
     if (covMode) {
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, true, T};
         Aligner A{S.ctx, o, tx, targets, Q, S.dbStride, S.dbWinlen};
         A.noReads = true;
         if (aligning) L.wants = &A.wants;
-        classify_by_coverage(os, o, Q.batches, L, S.ctx, aligning ? &A : nullptr);
+        classify_by_coverage(os, o, Q.batches, L, S.ctx, P, aligning ? &A : nullptr);
     }
     if (merged) {                                                           // map_candidates_to_targets, classification.cpp:891-911
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, false, T};
@@ -1721,35 +1449,10 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
-    if (P.on && fmtFeed.ctx) {
-        std::cerr << "mcq profile: mapping lines on the device: " << fmtFeed.calls << " mc_format_mappings calls, " << fmtFeed.reads << " reads, " << fmtFeed.lines
-                  << " lines, " << fmtFeed.hostBatches << " batches formatted on the host";
-        if (fmtFeed.hostBatches) std::cerr << " (" << fmtFeed.firstError << ")";
-        std::cerr << "\n";
-    } else if (P.on && fmtWanted) std::cerr << "mcq: mapping lines formatted on the host (" << fmtWhyNot << ")\n";
-    if (P.on && evalFeed.ctx) {
-        std::cerr << "mcq profile: evaluation on the device: " << evalFeed.calls << " mc_evaluate_assignments calls, " << evalFeed.reads << " reads, "
-                  << evalFeed.hostBatches << " batches counted on the host";
-        if (evalFeed.hostBatches) std::cerr << " (" << evalFeed.firstError << ")";
-        std::cerr << "\n";
-    } else if (P.on && evalWanted) std::cerr << "mcq: -precision: evaluated on the host (" << evalWhyNot << ")\n";
-    if (o.hitsPerRef) {
-        std::vector<mc_target_hit> devHits;
-        if (feed.ctx) {                                                     // mc_target_hits_collect replaces the sort of all records on one host thread
-            uint64_t nt = 0, nr = 0, st[4] = {0, 0, 0, 0};
-            if (mc_target_hits_collect(feed.ctx, nullptr, 0, &nt, nullptr, 0, &nr, nullptr, 0) != MC_OK) throw std::runtime_error(mc_last_error(feed.ctx));
-            devHits.resize(nr);
-            if (mc_target_hits_collect(feed.ctx, nullptr, 0, nullptr, devHits.data(), nr, nullptr, st, 1) != MC_OK) throw std::runtime_error(mc_last_error(feed.ctx));
-            mc_target_hits_reserve(feed.ctx, 0);                            // (the log's memory goes back)
-            if (P.on) {
-                std::cerr << "mcq profile: hits per target on the device: " << st[2] << " mc_target_hits_add calls, " << st[0] << " records, " << st[3]
-                          << " targets, " << T.covers.size() << " records of " << feed.hostBatches << " batches kept on the host";
-                if (feed.hostBatches) std::cerr << " (" << feed.firstError << ")";
-                std::cerr << "\n";
-            }
-        } else if (P.on) std::cerr << "mcq: -hits-per-ref: lists built on the host (" << feedWhyNot << ")\n";
-        show_hits_per_ref(perTargetOut, o, tx, S.dbStride, T.covers, devHits);
-    }
+    fmtStep.report(P);
+    evalStep.report(P);
+    hitsStep.report(P, T.covers.size());
+    if (o.hitsPerRef) show_hits_per_ref(perTargetOut, o, tx, S.dbStride, T.covers, hitsStep.records);
     if (o.abundances || o.abundancePer != kNumRanks) show_abundances(perTaxonOut, o, tx, T);
     if (o.showSummary) show_summary(os, o, T, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 }
