@@ -725,6 +725,35 @@ int mc_format_mappings(mc_ctx* ctx, const mc_format_options* opt, const mc_candi
                        uint32_t num_queries, int flags, char* out, uint64_t out_capacity, uint64_t* line_off, void* stream);
 int mc_format_stats(mc_ctx* ctx, uint64_t stats[5]);
 
+/* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
+ * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the
+ * database -- how many features, how many locations, the distribution of the list sizes, which locations a feature has -- and here the
+ * table in HBM is the only copy of that content, so three calls read it back.  They are also the way to state that a loaded table
+ * holds exactly what its file (or the arrays given to mc_load_batch) says, whatever the layout of the store.
+ * All three work on the bucket table of a context with ONE part, never on the direct-address index; all arrays are HOST arrays; the
+ * calls run on the context's own stream and return when their work is done.  NO QUERY MAY BE IN FLIGHT on the context's first pipe
+ * (mc_query_device without MC_SECOND_PIPE, mc_candidates_from_*) meanwhile.  `flags` is reserved and must be 0.
+ * mc_table_histogram: hist[s] = stored features whose list has s locations, s = 0 .. 255 (hist[0] is always 0: a feature that the
+ *   load-time rules emptied is not stored); *dead (may be NULL) = features handed to the loader (the number announced to mc_load_begin,
+ *   once all of them are in) that remove_overpopulated emptied = handed over - stored.  Features, locations, the largest size and the
+ *   moments of the statistics line follow from hist in exact integers.
+ * mc_table_features: every stored feature in ASCENDING feature order with its list size; *num = their number, the first
+ *   min(capacity, *num) are copied.  keys / sizes may be NULL with capacity 0 (the size query, which does not sort).
+ * mc_table_lookup: the lists of n features, in the order given -- any order, duplicates allowed, a feature that is not stored has an
+ *   empty list: list i = locs[offsets[i] .. offsets[i + 1]) in the order of the database file (after max_locations_per_feature: its
+ *   first locations), offsets has n + 1 entries.  If offsets[n] > capacity: MC_ERR_NOMEM, NO entry of locs is written, offsets is
+ *   complete (the convention of mc_format_mappings), so that the caller can size locs and call again.  n == 0: MC_OK, offsets[0] = 0.
+ * Errors, the arguments before any device call: MC_ERR_INVALID: NULL ctx, hist, num or offsets, NULL keys with n > 0 (mc_table_features:
+ *   NULL keys or sizes with capacity > 0), NULL locs with capacity > 0, flags != 0.  MC_ERR_STATE: a context without a device
+ *   (mc_open_metadata), a table that is not finished (mc_load_end not yet called).  MC_ERR_UNSUPPORTED: more than one part in the context
+ *   (a list of the union is not a list of a file: open the parts one by one, mc_config.single_part), a key shard, a target-range shard,
+ *   a stored size above 255.  MC_ERR_NOMEM also: the device cannot hold the temporaries (mc_table_features: 16 bytes per stored feature
+ *   + the sort's own; mc_table_lookup: 24 bytes per key and 8 per location of a piece); the error text names the bytes asked for.
+ * mc_timing_get names: "table_hist", "table_enumerate" (the write pass + the sort), "table_lookup" (sizes + offsets), "table_gather". */
+int mc_table_histogram(mc_ctx* ctx, uint64_t hist[256], uint64_t* dead);
+int mc_table_features(mc_ctx* ctx, uint32_t* keys, uint32_t* sizes, uint64_t capacity, uint64_t* num, int flags);
+int mc_table_lookup(mc_ctx* ctx, const uint32_t* keys, uint64_t n, uint64_t* offsets, mc_location* locs, uint64_t capacity, int flags);
+
 /* per-kernel timing with HIP events on the launching stream (for bench.py's roofline block).
  * names: "plan", "sketch_lane", "chunk_sketch", "chunk_probe", "probe_cands", "mid_cands_64", "mid_cands_128", "mid_cands_256",
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with

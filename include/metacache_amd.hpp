@@ -17,6 +17,7 @@
 #include "metacache_amd.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
@@ -117,6 +118,44 @@ private:
     mc_evaluation e_;
 };
 
+// The statistics line of `info <db> statistics` (print_content_properties, printing.cpp:662-696) from the histogram of list sizes that
+// database::table_histogram returns.  features, locations and the power sums are exact integers; the moments follow the reference's
+// arithmetic on doubles made from them (stat_moments.hpp:685-707, :836-854); buckets is what the reference's hash table of
+// features + dead keys reserves at the database's default load factor, in single precision (hash_multimap.hpp:552-554).  Several
+// parts: add() each part's histogram, and sum the parts' buckets.  Above about 5 * 10^8 features the reference's own running double
+// sums are no longer exact: its printed six digits are what this matches, not its last bit.
+struct table_statistics {
+    std::uint64_t features = 0, locations = 0, sum2 = 0, sum3 = 0, max = 0, dead = 0;
+    table_statistics() = default;
+    explicit table_statistics(const std::uint64_t hist[256], std::uint64_t deadFeatures = 0) { add(hist, deadFeatures); }
+    void add(const std::uint64_t hist[256], std::uint64_t deadFeatures = 0)
+    {
+        for (std::uint64_t s = 1; s < 256; ++s) {
+            if (!hist[s]) continue;
+            features += hist[s]; locations += s * hist[s]; sum2 += s * s * hist[s]; sum3 += s * s * s * hist[s];
+            max = std::max(max, s);
+        }
+        dead += deadFeatures;
+    }
+    double mean() const noexcept { return features ? double(locations) / double(features) : 0.0; }
+    double variance() const noexcept
+    {
+        if (features < 2) return 0.0;
+        const double n = double(features), s1 = double(locations);
+        return (double(sum2) - s1 * s1 / n) / (n - 1.0);
+    }
+    double stddev() const noexcept { return std::sqrt(variance()); }
+    double skewness() const noexcept
+    {
+        const double cm2 = variance();
+        if (features < 2 || !(cm2 > 0.0)) return 0.0;
+        const double n = double(features), n2 = n * n, s1 = double(locations), s2 = double(sum2);
+        const double cm3 = (n2 * double(sum3) - 3.0 * n * (s1 * s2) + 2.0 * (s1 * s1 * s1)) / (n * n2);
+        return cm3 / std::pow(cm2, 1.5);
+    }
+    std::uint64_t buckets(float loadFactor = 0.8f) const noexcept { return std::uint64_t(1.0f + float(features + dead) / loadFactor); }
+};
+
 class query_batch;
 
 class database {
@@ -194,6 +233,43 @@ public:
         mc_evaluation e;
         if (mc_evaluate_tally(ctx_, &e, reset ? 1 : 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
         return classification_statistics(e);
+    }
+
+    // what the table in HBM holds (mc_table_*; one part per context -- read(name, part) -- and no query in flight meanwhile):
+    // the histogram of list sizes with the number of features the load-time rules emptied (table_statistics makes the statistics line),
+    struct size_histogram { std::uint64_t hist[256]; std::uint64_t dead; };
+    size_histogram table_histogram() const
+    {
+        size_histogram h{};
+        if (mc_table_histogram(ctx_, h.hist, &h.dead) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        return h;
+    }
+    // every stored feature in ascending order with the length of its location list (print_feature_counts, host_hashmap.hpp:433-445),
+    struct feature_sizes { std::vector<std::uint32_t> features, sizes; };
+    feature_sizes table_features() const
+    {
+        std::uint64_t n = 0;
+        if (mc_table_features(ctx_, nullptr, nullptr, 0, &n, 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        feature_sizes f;
+        f.features.resize(n); f.sizes.resize(n);
+        if (n && mc_table_features(ctx_, f.features.data(), f.sizes.data(), n, &n, 0) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+        return f;
+    }
+    // and the location lists of some features, in the order of the database file (print_feature_map, host_hashmap.hpp:413-429): list i
+    // = locations[offsets[i] .. offsets[i + 1]); a feature the table does not hold has an empty list
+    struct feature_lists { std::vector<std::uint64_t> offsets; std::vector<location> locations; };
+    feature_lists table_lookup(span<const std::uint32_t> features) const
+    {
+        static_assert(sizeof(location) == sizeof(mc_location), "location mirrors mc_location");
+        feature_lists l;
+        l.offsets.resize(features.size() + 1);
+        int rc = mc_table_lookup(ctx_, features.begin(), features.size(), l.offsets.data(), nullptr, 0, 0);
+        if (rc != MC_OK && rc != MC_ERR_NOMEM) throw std::runtime_error(mc_last_error(ctx_));   // (MC_ERR_NOMEM: offsets came back complete)
+        l.locations.resize(l.offsets[features.size()]);
+        if (!l.locations.empty() && mc_table_lookup(ctx_, features.begin(), features.size(), l.offsets.data(),
+                                                    reinterpret_cast<mc_location*>(l.locations.data()), l.locations.size(), 0) != MC_OK)
+            throw std::runtime_error(mc_last_error(ctx_));
+        return l;
     }
 
     // database::query_gpu_async(queryBatch, hostId, querySketching, lowestRank)  database.hpp:386-397

@@ -13,6 +13,7 @@ import numpy as np
 from . import build as _build
 
 MC_OK, MC_BATCH_FULL = 0, 1
+MC_ERR_NOMEM = -3
 NUM_RANKS = 21
 
 cand_dtype = np.dtype([("tgt", "<u4"), ("hits", "<u4"), ("beg", "<u4"), ("end", "<u4")])
@@ -303,7 +304,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_coverage_add", "mc_coverage_counts", "mc_coverage_keep", "mc_coverage_set_keep", "mc_coverage_drop",
            "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect",
            "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally",
-           "mc_format_set_text", "mc_format_mappings", "mc_format_stats"]
+           "mc_format_set_text", "mc_format_mappings", "mc_format_stats",
+           "mc_table_histogram", "mc_table_features", "mc_table_lookup"]
 
 _lib = None
 
@@ -381,6 +383,9 @@ def lib() -> C.CDLL:
         L.mc_format_mappings.argtypes = [C.c_void_p, C.POINTER(McFormatOptions), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mc_format_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_table_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.mc_table_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
+        L.mc_table_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -394,6 +399,36 @@ def lib() -> C.CDLL:
 
 class McError(RuntimeError):
     pass
+
+
+def table_statistics(hist, dead: int = 0, load_factor: float = 0.8) -> dict:
+    """The statistics of `metacache info <db> statistics` (print_content_properties, printing.cpp:662-696) from the histogram of list
+    sizes (Database.table_histogram; hist[s] = features with s locations): features, locations, max, mean, stddev, skewness, buckets.
+    n = features, S1 = locations, S2 and S3 = the sums of the squared and cubed sizes are exact integers; the moments then follow the
+    reference's arithmetic on doubles made from them (stat_moments.hpp:685-707, :836-854):
+        cm2 = (S2 - S1 * S1 / n) / (n - 1), stddev = sqrt(cm2), cm3 = (n^2 * S3 - 3 * n * (S1 * S2) + 2 * (S1 * S1 * S1)) / (n * n^2),
+        skewness = cm3 / pow(cm2, 1.5); both 0 for n < 2.
+    buckets = what the reference's hash table of features + dead keys reserves (hash_multimap.hpp:552-554 with the database's default
+    load factor 0.8): uint64(1.0f + float(features + dead) / 0.8f) in single precision.  Several parts: sum the histograms, and the
+    parts' bucket counts.
+    Above about 5 * 10^8 features the reference's own running double sums are no longer exact (S3 passes 2^53): its printed six digits are
+    what this matches, not its last bit."""
+    h = [int(x) for x in hist]
+    n = sum(h)
+    s1 = sum(s * c for s, c in enumerate(h))
+    s2 = sum(s * s * c for s, c in enumerate(h))
+    s3 = sum(s * s * s * c for s, c in enumerate(h))
+    top = max((s for s, c in enumerate(h) if c), default=0)
+    stddev = skewness = 0.0
+    if n >= 2:
+        dn, d1, d2, d3 = float(n), float(s1), float(s2), float(s3)
+        cm2 = (d2 - d1 * d1 / dn) / (dn - 1.0)
+        n2 = dn * dn
+        cm3 = (n2 * d3 - 3.0 * dn * (d1 * d2) + 2.0 * (d1 * d1 * d1)) / (dn * n2)
+        stddev = float(np.sqrt(cm2))
+        skewness = float(cm3 / np.power(cm2, 1.5)) if cm2 > 0 else 0.0
+    buckets = int(np.uint64(np.float32(1.0) + np.float32(n + int(dead)) / np.float32(load_factor)))
+    return dict(features=n, locations=s1, max=top, mean=(float(s1) / float(n)) if n else 0.0, stddev=stddev, skewness=skewness, buckets=buckets)
 
 
 def default_config(**kw) -> McConfig:
@@ -868,6 +903,44 @@ class Database:
         a = (C.c_uint64 * 4)()
         self._check(lib().mc_table_layout(self.h, a))
         return {"location_bytes": int(a[0]) & 0xFF, "direct_index": bool(int(a[0]) >> 32), "window_gap": int(a[1]) & 0xFFFFFFFF, "list_align": int(a[1]) >> 32, "buckets": int(a[2]), "list_locations": int(a[3])}
+
+    # ---- table content: what the table in HBM holds (mc_table_*) --------------------------------
+    def table_histogram(self):
+        """-> (hist[256] uint64: stored features per list size, dead: features the load-time rules emptied); table_statistics(hist)
+        makes the statistics line of `info <db> statistics` from it"""
+        hist = np.zeros(256, dtype=np.uint64)
+        dead = C.c_uint64()
+        self._check(lib().mc_table_histogram(self.h, hist.ctypes.data, C.byref(dead)))
+        return hist, int(dead.value)
+
+    def table_features(self):
+        """-> (keys uint32, sizes uint32): every stored feature in ascending order with the length of its location list"""
+        L = lib()
+        num = C.c_uint64()
+        self._check(L.mc_table_features(self.h, None, None, 0, C.byref(num), 0))
+        keys = np.zeros(num.value, dtype=np.uint32)
+        sizes = np.zeros(num.value, dtype=np.uint32)
+        if num.value:
+            self._check(L.mc_table_features(self.h, keys.ctypes.data, sizes.ctypes.data, num.value, C.byref(num), 0))
+        return keys, sizes
+
+    def table_lookup(self, keys):
+        """-> (offsets[n + 1] uint64, locs (loc_dtype)): locs[offsets[i]:offsets[i + 1]] = the locations of feature keys[i] in the order of
+        the database file; any order of keys, duplicates allowed, a feature the table does not hold has an empty list"""
+        L = lib()
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        if keys.ndim != 1:
+            raise ValueError("table_lookup: keys must be one-dimensional")
+        n = len(keys)
+        offsets = np.zeros(n + 1, dtype=np.uint64)
+        rc = L.mc_table_lookup(self.h, keys.ctypes.data if n else None, n, offsets.ctypes.data, None, 0, 0)
+        if rc != MC_ERR_NOMEM:                                     # (MC_ERR_NOMEM with the offsets complete is the size query's answer)
+            self._check(rc)
+        total = int(offsets[n])
+        locs = np.zeros(total, dtype=loc_dtype)
+        if total:
+            self._check(L.mc_table_lookup(self.h, keys.ctypes.data, n, offsets.ctypes.data, locs.ctypes.data, total, 0))
+        return offsets, locs
 
     def target_range(self) -> tuple:
         """[lo, hi): the targets whose locations this context holds (mc_target_range)"""

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmetacache_amd.so")
-SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip", "evaluate.hip", "format.hip"]
+SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip", "evaluate.hip", "format.hip", "table_info.hip"]
 HEADERS = ["kernels.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", "rows_common.h", os.path.join(ROOT, "include", "metacache_amd.h")]
 ARCH = "gfx950"
 BINDIR = os.path.join(PKG, "bin")
@@ -162,7 +162,7 @@ def build_cli(force: bool = False, verbose: bool = False) -> str:
     """mcq: plain host C++14 linked against the C ABI only (rpath to the in-tree library)."""
     os.makedirs(BINDIR, exist_ok=True)
     src = os.path.join(CSRC, "mcq_main.cpp")
-    if force or _stale(MCQ, [src, os.path.join(CSRC, "mcq_common.h"), os.path.join(CSRC, "mcq_build.h"), os.path.join(CSRC, "mcq_device_steps.h"),
+    if force or _stale(MCQ, [src, os.path.join(CSRC, "mcq_common.h"), os.path.join(CSRC, "mcq_build.h"), os.path.join(CSRC, "mcq_device_steps.h"), os.path.join(CSRC, "mcq_table_info.h"),
                            LIB, os.path.join(ROOT, "include", "metacache_amd.h")]):
         cmd = ["g++", "-std=c++14", "-O2", "-I", os.path.join(ROOT, "include"), src, "-o", MCQ,
                "-L", LIBDIR, "-lmetacache_amd", "-lz", "-Wl,-rpath,$ORIGIN/../lib", "-pthread"]

@@ -1618,7 +1618,10 @@ int merge_main(const std::vector<std::string>& args)
     return 0;
 }
 
-// ---- info mode (mode_info.cpp), the parts that read metadata only: database properties, targets, lineage table, rank statistics ----
+#include "mcq_table_info.h"
+
+// ---- info mode (mode_info.cpp): database properties, targets, lineage table, rank statistics from the metadata alone; the topics that
+// describe the table's content (statistics, featurecounts, featuremap) from the table on the device, behind MCQ_INFO_DEVICE=1 ----
 int info_main(const std::vector<std::string>& args)
 {
     auto static_properties = [](uint32_t tb, uint64_t k, uint64_t sk, uint64_t w, uint64_t stride, uint64_t maxLocs) {   // printing.cpp:625-657
@@ -1656,7 +1659,8 @@ int info_main(const std::vector<std::string>& args)
     std::string name = args[0];
     { auto pos = name.find(".meta"); if (pos != std::string::npos) name.erase(pos); else { pos = name.find(".cache"); if (pos != std::string::npos) name.erase(pos); } }
     const std::string what = args.size() > 1 ? args[1] : "";
-    if (what == "statistics" || what == "stat" || what == "locations" || what == "loc" || what == "featuremap" || what == "features" || what == "featurecounts")
+    const char* infoDevice = std::getenv("MCQ_INFO_DEVICE");
+    if (info_table_topic(what) && !(infoDevice && std::atoi(infoDevice) != 0))
         throw std::runtime_error("'info " + what + "' describes the reference's host hash table; not available here");
     std::cerr << "Reading database '" << name << "' ... Reading database metadata ...\nCompleted database reading.\ndone." << std::endl;
     mc_ctx* ctx = nullptr;
@@ -1674,9 +1678,19 @@ int info_main(const std::vector<std::string>& args)
         if (tx.taxa[i].rank == 0 && tx.taxa[i].id < 0) tx.targetByName.emplace(tx.taxa[i].name, (uint32_t)i + 1);
     }
     mc_db_lineages(ctx, &tx.targetLineages, &tx.numTargets);
+    uint32_t tb = 4;
+    { std::ifstream is(name + ".meta", std::ios::binary); char hdr[10] = {}; is.read(hdr, 10); if (is.gcount() == 10) tb = (uint8_t)hdr[9]; }
+    if (info_table_topic(what)) {                                                // show_database_statistics / show_feature_map / show_feature_counts
+        static_properties(tb, info[0], info[1], info[2], info[3], info[4]);
+        uint64_t ranked = 0, inTree = 0;
+        for (const Taxon& t : tx.taxa) {
+            const bool target = t.rank == 0 && t.id < 0;
+            if (target && t.parent != 0) ++ranked;
+            if (!target) ++inTree;
+        }
+        return info_table_content(name, what, info[6], info[5], ranked, inTree);
+    }
     if (what.empty()) {                                                          // show_database_config
-        uint32_t tb = 4;
-        { std::ifstream is(name + ".meta", std::ios::binary); char hdr[10] = {}; is.read(hdr, 10); if (is.gcount() == 10) tb = (uint8_t)hdr[9]; }
         static_properties(tb, info[0], info[1], info[2], info[3], info[4]);
         query_config();
         std::cout << "database parts       " << info[6] << "\n------------------------------------------------\n";
