@@ -888,6 +888,72 @@ namespace {
 // directory entry requested when the winners are known, gwBase words before the next read's counting, the candidates written after
 // it -- so that the loads run behind the next read's LDS phases (a read with places left for single hits finishes at once: step D
 // needs the picked targets).  One of these per wave.
+// The hand-over entries of ONE read of gw_filter_count_kernel<LOOKUP> (round 8: written only for reads that somebody will visit again --
+// a read the kernel finishes has none).  Lane i holds the index entry of the read's feature i (sz 0: not found / no feature; fm, sm: the
+// lanes with sz != 0 / sz == 1, lincl: inclusive scan of the sizes > 1).  The layout is the lookup kernels': found features only,
+// singletons first, size | (list offset & 0xFFF) << 16, payload; the slots up to nf cleared.
+__device__ __forceinline__ void lk_store_entries(const Workspace& ws, const uint32_t fbase, const uint32_t nf, const uint32_t lane, const uint32_t sz, const uint64_t pay,
+                                                 const uint64_t fm, const uint64_t sm, const uint32_t lincl)
+{
+    const uint32_t nent = (uint32_t)__popcll(fm), n1 = (uint32_t)__popcll(sm), lsz = sz > 1u ? sz : 0u;
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+    const uint32_t sbelow = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
+    if (sz != 0u) {
+        const uint32_t slot = sz == 1u ? sbelow : n1 + (below - sbelow);
+        const uint32_t off = sz == 1u ? slot : n1 + lincl - lsz;
+        ws.psize[fbase + slot] = sz | ((off & 0xFFFu) << 16);
+        ws.ppay[fbase + slot] = pay;
+    } else if (lane < nf) ws.psize[fbase + nent + (lane - below)] = 0u;
+}
+__device__ __forceinline__ void lk_store_entries(const Workspace& ws, const uint32_t fbase, const uint32_t nf, const uint32_t lane, const uint32_t sz, const uint64_t pay)
+{
+    lk_store_entries(ws, fbase, nf, lane, sz, pay, __ballot(sz != 0u), __ballot(sz == 1u), wave_incl_scan_u32(sz > 1u ? sz : 0u, lane));
+}
+// The index entries of read q's features (at most 64), one per lane, from the read's number alone: nothing of the read has to stay in
+// registers for the few reads that need them again (two dependent loads; the lines of a read just processed are mostly still in the L2).
+__device__ __forceinline__ void lk_load_entries(const Workspace& ws, const DeviceTable& tab, const uint32_t s, const uint32_t q, const uint32_t lane,
+                                                uint32_t& fbase, uint32_t& nf, uint32_t& sz, uint64_t& pay)
+{
+    const uint32_t o0 = ws.winOff[q];
+    fbase = o0 * s; nf = (ws.winOff[q + 1] - o0) * s;
+    const uint32_t f = lane < nf ? ws.features[fbase + lane] : 0xFFFFFFFFu;
+    const uint64_t e = f != 0xFFFFFFFFu ? tab.direct[f] : 0ull;
+    sz = (uint32_t)e & 0xFFFFu; pay = direct_payload(e);
+}
+
+// Where gw_count_read and GwPend find a read's hand-over entries:
+//   where()  {first entry slot in ws.psize / ws.ppay, entries} of the read that is being counted
+//   load()   step D: this lane's entry of that read (size, payload; size 0: none)
+//   leave()  read q (the read being counted, or the one before it: GwPend) goes on to the exact wave kernel, which reads its entries
+// GwEntRecord: the lookup kernels wrote the entries, the read's record of kListFilter says where.
+struct GwEntRecord {
+    const uint4* rec;
+    __device__ __forceinline__ uint2 where() const { const uint4 r6 = *rec; return make_uint2(r6.y, r6.z & 0xFFFu); }
+    __device__ __forceinline__ void load(const Workspace& ws, const DeviceTable&, uint32_t, uint32_t fbase, uint32_t nent, uint32_t lane, uint32_t& sz, uint64_t& pay) const
+    {
+        sz = lane < nent ? (ws.psize[fbase + lane] & 0xFFFFu) : 0u;
+        pay = lane < nent ? ws.ppay[fbase + lane] : 0ull;
+    }
+    __device__ __forceinline__ void leave(const Workspace&, const DeviceTable&, uint32_t, uint32_t) const {}
+};
+// GwEntLookup (gw_filter_count_kernel<LOOKUP>): no entries in memory until a read leaves; both are derived from the read's number.
+// Step D takes the entries at their features' lanes (not compacted: it only wants every location once).
+struct GwEntLookup {
+    uint32_t fbase, nent, s;
+    __device__ __forceinline__ uint2 where() const { return make_uint2(fbase, nent); }
+    __device__ __forceinline__ void load(const Workspace& ws, const DeviceTable& tab, uint32_t q, uint32_t, uint32_t, uint32_t lane, uint32_t& sz, uint64_t& pay) const
+    {
+        uint32_t fb, nf;
+        lk_load_entries(ws, tab, s, q, lane, fb, nf, sz, pay);
+    }
+    __device__ __forceinline__ void leave(const Workspace& ws, const DeviceTable& tab, uint32_t q, uint32_t lane) const
+    {
+        uint32_t fb, nf, sz; uint64_t pay;
+        lk_load_entries(ws, tab, s, q, lane, fb, nf, sz, pay);
+        lk_store_entries(ws, fb, nf, lane, sz, pay);
+    }
+};
+
 struct GwPend {
     bool pend = false;
     uint32_t q = 0, wv = kGwNone, wh = 0, wd = 0, dir = 0, b0 = 0, b1 = 0, b2 = 0;
@@ -895,8 +961,8 @@ struct GwPend {
     {
         if (pend && wv != kGwNone) { b0 = tab.gwBase[dir]; b1 = tab.gwBase[dir + 1]; b2 = tab.gwBase[min(dir + 2, tab.gwTargets)]; }
     }
-    template <bool TAX>
-    __device__ __forceinline__ void finish(const uint32_t lane, const uint32_t K, const DeviceTable& tab, const Workspace& ws, mc_candidate_dev* __restrict__ cands)   // stage 2
+    template <bool TAX, class Ent>
+    __device__ __forceinline__ void finish(const uint32_t lane, const uint32_t K, const DeviceTable& tab, const Workspace& ws, mc_candidate_dev* __restrict__ cands, const Ent& ent)   // stage 2
     {
         if (!pend) return;
         uint32_t t = 0xFFFFFFFFu, lo = 0, hi = 0;
@@ -907,6 +973,7 @@ struct GwPend {
         }
         uint32_t plo[kLaneK], phi[kLaneK];
         const bool again = gw_winners_out<TAX>(lane, K, wv, wh, wd, t, lo, hi, cands + (size_t)q * K, plo, phi);
+        if (again) ent.leave(ws, tab, q, lane);                    // (the read BEFORE the one the caller is at)
         if (lane == 0) {
             if (again) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
             else ws.qflag[q] = kFlagDone;
@@ -921,9 +988,9 @@ struct GwPend {
 // DEFER: the winners' target lookup waits in P for the caller's next read (see GwPend; the caller finishes the last one).
 // LONG (first instance's table only): the list may hold up to 2^LOG2S numbers as long as no more than half of them are DISTINCT (a filtered
 // list of 400 numbers has about 100 distinct ones); a list with more goes to the exact wave kernel.
-// entf(): where step D finds the read's entries -- {first entry slot in ws.psize / ws.ppay, entries} (the record of kListFilter)
-template <uint32_t LOG2S, bool TAX, bool DEFER, bool LONG = false, class GetV, class EntF>
-__device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, const uint32_t n2, const uint32_t maxWin, GetV&& getv,
+// ent: where the read's hand-over entries are (GwEntRecord / GwEntLookup)
+template <uint32_t LOG2S, bool TAX, bool DEFER, bool LONG = false, class GetV, class Ent>
+__device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, const uint32_t n2, const uint32_t maxWin, GetV&& getv,
                                               uint2* slots, uint32_t* ck, uint64_t* T, const uint32_t lane, const uint32_t grp, const uint32_t sub4,
                                               const uint32_t K, const uint32_t* __restrict__ taxkey, const DeviceTable& tab, const Workspace& ws,
                                               mc_candidate_dev* __restrict__ cands, GwPend& P)
@@ -972,7 +1039,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, con
     wave_lds_sync();
     if constexpr (LONG) {
         if (C > kList) {                                           // more distinct numbers than the table is made for (the neighbour lookups need free slots):
-            if constexpr (DEFER) P.template finish<TAX>(lane, K, tab, ws, cands);   // the caller sends the list on (false)
+            if constexpr (DEFER) P.template finish<TAX>(lane, K, tab, ws, cands, ent);   // the caller sends the list on (false)
             wave_lds_sync();
             return false;
         }
@@ -990,7 +1057,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, con
     }
     strong = __builtin_amdgcn_readfirstlane(strong);
     if constexpr (DEFER) {
-        P.template finish<TAX>(lane, K, tab, ws, cands);           // the previous read's candidates
+        P.template finish<TAX>(lane, K, tab, ws, cands, ent);      // the previous read's candidates
         if (strong >= K) {                                         // this read's: later
             P.pend = true; P.q = q; P.wv = wv; P.wh = wh; P.wd = wd;
             P.dir = wv != kGwNone ? tab.gwDir[wv >> tab.gwDirShift] : 0u;
@@ -1005,22 +1072,24 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, con
     }
     bool done = true;
     if (again) {                                                   // two winners of one target: the exact wave kernel
+        ent.leave(ws, tab, q, lane);
         if (lane == 0) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
         done = false;
     } else if (strong < K) {
-        const uint2 r6 = entf();
+        const uint2 r6 = ent.where();
         const uint32_t fbase = r6.x, nent = r6.y;
         if (TAX || nent > kBigEnt) {
             // places left for single-hit taxa: the order among those depends on every target's taxon -> the exact wave kernel
             // (so do reads with more than 64 found features: the sweep below reads one entry per lane)
+            ent.leave(ws, tab, q, lane);
             if (lane == 0) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
             done = false;
         } else if constexpr (!TAX) {
             // ---- D. the smallest numbers of targets that were not picked with >= 2 hits -- every such target's best range is a
             //      single location, and the first of them in (target, window) order are what the CPU's list keeps
             wave_lds_sync();
-            const uint32_t sz = lane < nent ? (ws.psize[fbase + lane] & 0xFFFFu) : 0u;
-            const uint64_t pay = lane < nent ? ws.ppay[fbase + lane] : 0ull;
+            uint32_t sz; uint64_t pay;
+            ent.load(ws, tab, q, fbase, nent, lane, sz, pay);
             const uint32_t myR = sz > 1 ? (sz + 15u) >> 4 : 0u;
             const uint32_t incl = wave_incl_scan_u32(myR, lane), Rc = rdlane(incl, 63), start = incl - myR;
             // every lane keeps the kLaneK smallest numbers it sees (several may be one target's: the rounds below strike whole
@@ -1084,6 +1153,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, EntF&& entf, con
                 if (lane == 0) out[rnd] = e;
             }
             if (unsure) {
+                ent.leave(ws, tab, q, lane);
                 if (lane == 0) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
                 done = false;
             }
@@ -1158,13 +1228,13 @@ __global__ __launch_bounds__(WAVES * 64, LOG2S == 9 ? MC_GW_COUNT_WPE : LOG2S ==
 #pragma unroll
         for (uint32_t r = 0; r < kPre; ++r) cur[r] = pre[r];
         if (todo) { const uint32_t jn = (uint32_t)__ffsll((unsigned long long)todo) - 1; fetch(rdlane(myRec.y, jn), rdlane(myRec.z, jn)); }
-        gw_count_read<LOG2S, TAX, kDefer>(q, [&]() -> uint2 { const uint4 r6 = work6[w]; return make_uint2(r6.y, r6.z & 0xFFFu); }, n2, maxWin, [&](uint32_t r) -> uint32_t {
+        gw_count_read<LOG2S, TAX, kDefer>(q, GwEntRecord{work6 + w}, n2, maxWin, [&](uint32_t r) -> uint32_t {
             if constexpr (LOG2S <= 10) return cur[r < kPre ? r : 0];
             else return r * 64 + lane < n2 ? src[r * 64 + lane] : kGwNone;
         }, slots, ck, T, lane, grp, sub4, K, taxkey, tab, ws, cands, P);
       }
     }
-    if constexpr (kDefer) { P.bases(tab); P.template finish<TAX>(lane, K, tab, ws, cands); }
+    if constexpr (kDefer) { P.bases(tab); P.template finish<TAX>(lane, K, tab, ws, cands, GwEntRecord{work6}); }
 }
 
 constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: the read was counted inside the filter kernel (| kept numbers)
@@ -1185,9 +1255,11 @@ constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: th
 // records of kListFilter and does the direct-index lookups itself, one lane per feature -- the lane that loaded the hand-over entry of a
 // found feature now loads the index entry of feature `lane`, two reads ahead: the read's features (i + 2), their index entries (i + 1),
 // the entries of read i in registers.  The random 8-byte requests move from the lookup kernel, which runs at the request rate, into this
-// one, whose memory side is half idle.  The read's statistics, its hand-over entries (found features only, singletons first; the slots
-// up to nf cleared) and its class are written as probe_cands_one does; reads of another class go to their work lists, reads of this class
-// that the kernel does not finish get a record of kListFilter / kListFiltered (appended: one atomic each, they are few).
+// one, whose memory side is half idle.  The read's statistics and its class are written as probe_cands_one does; reads of another class go
+// to their work lists, reads of this class that the kernel does not finish get a record of kListFilter / kListFiltered (appended: one
+// atomic each, they are few).  The hand-over entries (found features only, singletons first; the slots up to nf cleared) are written
+// for those two kinds of reads ONLY (round 8: lk_store_entries) -- a read the kernel finishes, 59 in 60 at RefSeq scale,
+// is never visited again (what the stores' share of the kernel's write requests was: docs/LAB_NOTEBOOK_r08.md).
 template <uint32_t WAVES, uint32_t TLOG2, bool TAX, uint32_t WPE = MC_GW_FILTER_WPE, bool LOOKUP = false>
 __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchView b, DeviceTable tab, Workspace ws, uint32_t K, const uint32_t* __restrict__ taxkey,
                                                                                  mc_candidate_dev* __restrict__ cands, const uint32_t s)
@@ -1248,7 +1320,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
     GwPend P;
     for (uint32_t w = w0; w < total; w += nWaves) {
-        uint32_t q, nent, H, maxWin, sz, fbase = 0; uint64_t pay;
+        uint32_t q, nent, H, maxWin, sz, fbase = 0, nfs = 0; uint64_t pay;
         uint32_t rix = 0xFFFFFFFFu;                                // LOOKUP: the read's record in kListFilter, made when something is left to the later kernels
         if constexpr (!LOOKUP) {
             q = rec.x; nent = rec.z & 0xFFFu; H = rec.z >> 12; maxWin = rec.w;
@@ -1263,7 +1335,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             lkFeat = load_feat(m2);
             m0 = m1; m1 = m2; m2 = load_meta(w + 3 * nWaves);
             if (cur.x == kLkSkip) continue;
-            q = w; fbase = cur.x;
+            q = w; fbase = cur.x; nfs = cur.y;
             sz = (uint32_t)e & 0xFFFFu; pay = direct_payload(e);
             const uint64_t fm = __ballot(sz != 0u), sm = __ballot(sz == 1u);
             nent = (uint32_t)__popcll(fm);
@@ -1276,16 +1348,6 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
                 if (lane < K) { mc_candidate_dev ev; ev.tgt = 0xFFFFFFFFu; ev.hits = 0; ev.beg = 0; ev.end = 0; cands[(size_t)q * K + lane] = ev; }
                 if (lane == 0) { ws.hitScan[q] = 0u; ws.qflag[q] = kFlagDone; }
                 continue;
-            }
-            {   // the hand-over entries (size | list offset << 16, payload): found features only, singletons first; the slots up to nf cleared
-                const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
-                const uint32_t sbelow = __builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sm, 0u));
-                if (sz != 0u) {
-                    const uint32_t slot = sz == 1u ? sbelow : n1 + (below - sbelow);
-                    const uint32_t off = sz == 1u ? slot : n1 + lincl - lsz;
-                    ws.psize[fbase + slot] = sz | ((off & 0xFFFu) << 16);
-                    ws.ppay[fbase + slot] = pay;
-                } else if (lane < cur.y) ws.psize[fbase + nent + (lane - below)] = 0u;
             }
             // the read's class (probe_cands_one); lists up to kLaneHits, which a lane of the lookup kernel finishes itself, are mid_cands_kernel<4>'s
             const bool hashOK = nent <= kHashEnt && maxWin <= kHashWin;
@@ -1300,8 +1362,11 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
                     ws.midList[list_at(class_list(cls), b.n) + at] = make_uint4(q, fbase, nent | (H << 12), maxWin);
                 }
             }
-            if (cls != kClassFilter) continue;
+            // the hand-over entries: for the reads that go to another kernel -- here the other classes', below the few of this class that
+            // the kernel does not finish (a read it finishes has none: nobody visits it again)
+            if (cls != kClassFilter) { lk_store_entries(ws, fbase, nfs, lane, sz, pay, fm, sm, lincl); continue; }
         }
+        auto entries_out = [&]() { if constexpr (LOOKUP) GwEntLookup{fbase, nent, s}.leave(ws, tab, q, lane); };   // (from the read's number: sz / pay are gone by then)
         // the read's place in kListFilter / kListFiltered
         auto slot_of = [&]() -> uint32_t {
             if constexpr (!LOOKUP) return w;
@@ -1317,6 +1382,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         const uint32_t myR = sz > 1 ? (sz + 15u) >> 4 : 0u;
         const uint32_t incl = wave_incl_scan_u32(myR, lane), Rc = rdlane(incl, 63);
         if (H > kGwSmallH || nent > 64u || Rc > kGwRounds || maxWin > tab.gwGap || sliceCap - sliceUsed < kGwRounds * 16u + 64u) {
+            if constexpr (LOOKUP) lk_store_entries(ws, fbase, nfs, lane, sz, pay);   // (still in registers here)
             const uint32_t at = slot_of();
             if (lane == 0) outRec[at] = make_uint4(q, 0u, kGwDefer, maxWin);
             ++deferred;
@@ -1366,15 +1432,18 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         if (here && n2 <= kKeep) {
             if constexpr (!LOOKUP) { if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwCounted | n2, maxWin); }   // (LOOKUP: a read finished here has no record)
             wave_lds_sync();
-            const bool counted = gw_count_read<9, TAX, true, true>(q, [&]() -> uint2 {
-                                            if constexpr (LOOKUP) { wave_mem_sync(); return make_uint2(fbase, nent); }   // (the entries are this wave's own stores)
-                                            else { const uint4 r6 = work[w]; return make_uint2(r6.y, r6.z & 0xFFFu); }
-                                        }, n2, maxWin,
+            auto count = [&](const auto& ent) {
+                return gw_count_read<9, TAX, true, true>(q, ent, n2, maxWin,
                                         [&](uint32_t r) -> uint32_t { return r * 64 + lane < n2 ? kept[r * 64 + lane] : kGwNone; },
                                         reinterpret_cast<uint2*>(bits), kSeven ? kept : reinterpret_cast<uint32_t*>(T), kSeven ? reinterpret_cast<uint64_t*>(kept) : T,
                                         lane, grp, sub4, K, taxkey, tab, ws, cands, P);
+            };
+            bool counted;
+            if constexpr (LOOKUP) counted = count(GwEntLookup{fbase, nent, s});
+            else counted = count(GwEntRecord{work + w});
             if (!counted && kSeven) {
                 // (the kept numbers' place went to the counting: the read is filtered again by gw_filter2_kernel, 1 read in 60)
+                entries_out();
                 const uint32_t at = slot_of();
                 if (lane == 0) outRec[at] = make_uint4(q, 0u, kGwDefer, maxWin);
                 ++deferred;
@@ -1385,6 +1454,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
                 // per 5 x 10^6 reads).  (Room: the slice holds kGwRounds x 16 + 64 numbers more, checked above.)
 #pragma unroll
                 for (uint32_t r = 0; r < kKeep / 64; ++r) if (r * 64 + lane < n2) slice[sliceUsed + r * 64 + lane] = kept[r * 64 + lane];
+                entries_out();
                 const uint32_t at = slot_of();
                 if (lane == 0) outRec[at] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), n2, maxWin);
                 sliceUsed += n2;
@@ -1400,6 +1470,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         }
         const uint32_t room = (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - sliceUsed);
         const bool fallback = n2 > room;
+        entries_out();                                             // (gw_count_kernel's step D, or the exact wave kernel)
         const uint32_t at = slot_of();
         if (lane == 0) {
             if (fallback) { ws.hitScan[q] = H; ws.qflag[q] = kFlagCands; outRec[at] = make_uint4(q, 0u, kGwFallback, maxWin); }
@@ -1408,7 +1479,9 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         if (!fallback) sliceUsed += n2;
         wave_lds_sync();
     }
-    P.bases(tab); P.template finish<TAX>(lane, K, tab, ws, cands);
+    P.bases(tab);
+    if constexpr (LOOKUP) P.template finish<TAX>(lane, K, tab, ws, cands, GwEntLookup{0u, 0u, s});
+    else P.template finish<TAX>(lane, K, tab, ws, cands, GwEntRecord{work});
     if (lane == 0) {
         if (ws.sliceFill) ws.sliceFill[w0] = (uint32_t)sliceUsed;
         if (deferred) atomicAdd(&ws.midCount[kCntSecond], deferred);
