@@ -725,6 +725,50 @@ int mc_format_mappings(mc_ctx* ctx, const mc_format_options* opt, const mc_candi
                        uint32_t num_queries, int flags, char* out, uint64_t out_capacity, uint64_t* line_off, void* stream);
 int mc_format_stats(mc_ctx* ctx, uint64_t stats[5]);
 
+/* ---- the all-hits column (-allhits): a read's whole location list, run-length encoded ----------------
+ * show_matches (printing.cpp:315-365).  Read i's list is hits[hit_off[i] .. hit_off[i + 1]).  A RUN is a maximal stretch of consecutive
+ * entries with equal tgt and equal win (nothing assumes a sorted list; the lists of mc_query_device(MC_WANT_ALLHITS) are).  Runs print in
+ * list order with nothing between them, an empty list gives an empty piece; the trailing ',' stays.  With text = entry tgt of the table
+ * of mc_format_matches_set_text, C = the run's length in decimal (as the reference's int for lengths below 2^31):
+ *   MC_MATCHES_WINDOWS (-lowest sequence):  text '/' W ':' C ','   W = win as the signed 32-bit number int(win) (win >= 2^31 prints negative);
+ *                                           a run whose entry is empty, or whose tgt lies beyond the table, prints NOTHING.
+ *   otherwise (a lowest rank above it):     text ':' C ','         an empty entry still prints ":C,"; a tgt beyond the table prints nothing.
+ *   A tgt beyond the table is counted once per run in mc_format_matches_stats, in both forms.
+ * mc_format_matches_set_text: the table, indexed by target; the rules of mc_format_set_text (count == 0 is allowed, a string has less
+ *   than 16 MiB; needs no device); copied, and sent to the device again after a later set -- no format call may be in flight meanwhile.
+ * mc_format_matches: piece i = out[piece_off[i] .. piece_off[i + 1]); piece_off[n] = the bytes all pieces need.  If that exceeds
+ *   out_capacity NO BYTE OF out IS WRITTEN and piece_off is still complete (the contract of mc_format_mappings).
+ *   Without MC_FORMAT_HOST all arrays are DEVICE pointers (out 16-byte, hits, hit_off and piece_off 8-byte aligned) and the call is
+ *   asynchronous on 'stream' (NULL = the context's own): behind mc_query_device(MC_WANT_ALLHITS) -- hits / hit_offsets of its
+ *   mc_device_results -- it needs no synchronisation.  piece_off has room for num_queries + 1 + MC_FORMAT_SCRATCH entries (the scan's
+ *   workspace: no per-call state in the context, calls on different streams may run at the same time); returns MC_OK, the overflow
+ *   verdict is piece_off[n] > out_capacity.
+ *   With MC_FORMAT_HOST the arrays are HOST arrays (piece_off: num_queries + 1 entries), staged through buffers of the context in pieces
+ *   of whole reads with at most mc_set_tuning "format_stage_hits" locations (0 = default: 4 Mi) -- a read whose list alone is longer
+ *   goes alone --, one caller at a time; returns when out is filled, or MC_ERR_NOMEM (piece_off complete, out untouched).
+ *   MC_ERR_INVALID (checked first, before any device call): NULL ctx or piece_off, NULL hit_off with num_queries > 0, NULL out with
+ *   out_capacity > 0, unknown flags, misaligned device arrays, a host hit_off that decreases, out overlapping an input or piece_off.
+ *   MC_ERR_STATE: no table, a context without a device (mc_open_metadata).  num_queries == 0: MC_OK and piece_off[0] = 0 (a DEVICE
+ *   piece_off is written on the stream, so that form needs the device even then).
+ * mc_format_mappings_with: mc_format_mappings with ONE MORE COLUMN between the truth column and the tophits column (where the reference
+ *   prints -allhits): the bytes extra[extra_off[i] .. extra_off[i + 1]) followed by the column separator.  With MC_FORMAT_MAPPED_ONLY a
+ *   read without a line skips its piece.  extra == NULL: exactly mc_format_mappings.  extra / extra_off are device or host arrays as the
+ *   others are (extra_off: num_queries + 1 entries, 8-byte aligned on the device, not decreasing); `extra` may be the `out` of
+ *   mc_format_matches and extra_off its piece_off, enqueued on the same stream with no synchronisation in between.  The same flags,
+ *   errors and statistics as mc_format_mappings; MC_ERR_INVALID also for extra without extra_off and for out overlapping either.
+ * mc_format_matches_stats: stats[0..4] = mc_format_matches calls that had reads, reads handed over, runs printed, bytes written, runs whose
+ *   tgt lay beyond the table -- the last three counted by the calls whose pieces fitted.  Waits for the context's own streams.
+ * mc_timing_get names: "matches_lengths" (matches_kernel<false> + format_scan_kernel), "matches_write" (matches_kernel<true>). */
+#define MC_MATCHES_WINDOWS    2      /* the window form: text '/' window ':' length ',' */
+int mc_format_matches_set_text(mc_ctx* ctx, const char* bytes, const uint64_t* offsets, uint64_t count);
+int mc_format_matches(mc_ctx* ctx, const mc_location* hits, const uint64_t* hit_off, uint32_t num_queries, int flags, char* out, uint64_t out_capacity,
+                      uint64_t* piece_off, void* stream);
+int mc_format_mappings_with(mc_ctx* ctx, const mc_format_options* opt, const mc_candidate* cands, uint32_t stride, const mc_assignment* assigned,
+                            const uint32_t* truth, const uint64_t* query_ids, uint64_t first_query_id, const char* names, const uint64_t* name_off,
+                            uint32_t num_queries, int flags, char* out, uint64_t out_capacity, uint64_t* line_off, void* stream,
+                            const char* extra, const uint64_t* extra_off);
+int mc_format_matches_stats(mc_ctx* ctx, uint64_t stats[5]);
+
 /* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
  * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the
  * database -- how many features, how many locations, the distribution of the list sizes, which locations a feature has -- and here the

@@ -226,6 +226,16 @@ public:
         if (mc_format_set_text(ctx_, which, bytes.data(), off.data(), strings.size()) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
     }
 
+    // the table of the all-hits column (mc_format_matches_set_text), per target: the text in front of "/window:length," (MC_MATCHES_WINDOWS)
+    // or ":length,"; no format_matches() may be in flight
+    void set_matches_text(const std::vector<std::string>& strings) const
+    {
+        std::string bytes;
+        std::vector<std::uint64_t> off(1, 0);
+        for (const std::string& t : strings) { bytes += t; off.push_back(bytes.size()); }
+        if (mc_format_matches_set_text(ctx_, bytes.data(), off.data(), strings.size()) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+    }
+
     // -precision / -taxon-coverage after the last batch: what the batches' evaluate() calls have counted (mc_evaluate_tally; reset: the
     // counters start from zero again)
     classification_statistics evaluation(bool reset = false) const
@@ -350,7 +360,8 @@ public:
         // _MAPPED_ONLY.  Line i is text[offsets[i] .. offsets[i + 1]).  Valid until the next format_mappings() or clear().
         struct mapping_lines { const std::string& text; const std::vector<std::uint64_t>& offsets; };
         mapping_lines format_mappings(const mc_format_options& opt, int flags, const char* names, span<const std::uint64_t> nameOff,
-                                      std::uint64_t firstQueryId, span<const std::uint32_t> truth = span<const std::uint32_t>())
+                                      std::uint64_t firstQueryId, span<const std::uint32_t> truth = span<const std::uint32_t>(),
+                                      const mapping_lines* extra = nullptr)      // extra: one more column behind the truth column, e.g. format_matches()
         {
             const std::uint32_t n = res_.num_queries;
             if (assigned_.size() != n || nameOff.size() != std::size_t(n) + 1 || ((flags & MC_FORMAT_TRUTH) && truth.size() != n))
@@ -358,14 +369,37 @@ public:
             lineOff_.resize(std::size_t(n) + 1);
             if (lines_.size() < std::size_t(n) * 128 + 16) lines_.resize(std::size_t(n) * 128 + 16);
             auto render = [&]() {
-                return mc_format_mappings(ctx_, &opt, res_.cands, res_.max_candidates, assigned_.data(), (flags & MC_FORMAT_TRUTH) ? truth.begin() : nullptr,
-                                          nullptr, firstQueryId, names, nameOff.begin(), n, flags | MC_FORMAT_HOST, &lines_[0], lines_.size(), lineOff_.data(), nullptr);
+                return mc_format_mappings_with(ctx_, &opt, res_.cands, res_.max_candidates, assigned_.data(), (flags & MC_FORMAT_TRUTH) ? truth.begin() : nullptr,
+                                               nullptr, firstQueryId, names, nameOff.begin(), n, flags | MC_FORMAT_HOST, &lines_[0], lines_.size(), lineOff_.data(), nullptr,
+                                               extra ? extra->text.data() : nullptr, extra ? extra->offsets.data() : nullptr);
             };
+            if (extra && (extra->offsets.size() != std::size_t(n) + 1 || &extra->text == &lines_))
+                throw std::runtime_error("format_mappings: the extra column has one piece per query of the batch");
             int rc = render();
             if (rc == MC_ERR_NOMEM) { lines_.resize(lineOff_[n]); rc = render(); }      // (line_off came back complete: now the lines fit)
             if (rc != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
             lines_.resize(lineOff_[n]);
             return mapping_lines{lines_, lineOff_};
+        }
+        // the batch's all-hits column (after wait_for_results; the database was read with copy_allhits): every query's location list
+        // run-length encoded as show_matches prints it (printing.cpp:315-365), rendered on the device from the slot's host arrays
+        // (mc_format_matches; the table: database::set_matches_text).  flags: 0 or MC_MATCHES_WINDOWS.  Piece i is
+        // text[offsets[i] .. offsets[i + 1]); format_mappings takes the result as its extra column.  Valid until the next format_matches() or clear().
+        mapping_lines format_matches(int flags)
+        {
+            const std::uint32_t n = res_.num_queries;
+            if (n && (!res_.hits || !res_.hit_offsets)) throw std::runtime_error("format_matches: the batch has no location lists (mc_config.copy_allhits)");
+            static const std::uint64_t none[1] = {0};
+            pieceOff_.resize(std::size_t(n) + 1);
+            if (pieces_.size() < 4096) pieces_.resize(4096);
+            auto render = [&]() {
+                return mc_format_matches(ctx_, res_.hits, n ? res_.hit_offsets : none, n, flags | MC_FORMAT_HOST, &pieces_[0], pieces_.size(), pieceOff_.data(), nullptr);
+            };
+            int rc = render();
+            if (rc == MC_ERR_NOMEM) { pieces_.resize(pieceOff_[n]); rc = render(); }   // (piece_off came back complete: now the pieces fit)
+            if (rc != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+            pieces_.resize(pieceOff_[n]);
+            return mapping_lines{pieces_, pieceOff_};
         }
         // -cov-percentile, first pass (after wait_for_results): the windows that this batch's qualifying candidates cover are marked in
         // the context's bitmap (matches_per_target::insert, matches_per_target.hpp:100-127; mc_coverage_add on the slot's host arrays)
@@ -397,7 +431,7 @@ public:
                                    MC_TARGET_HITS_HOST, nullptr) != MC_OK)
                 throw std::runtime_error(mc_last_error(ctx_));
         }
-        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); lineOff_.clear(); }   // query_batch.cuh:255-259
+        void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); lineOff_.clear(); pieceOff_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
         mc_ctx* ctx_ = nullptr; std::uint32_t slot_ = 0;
@@ -406,8 +440,8 @@ public:
         std::vector<mc_assignment> assigned_;
         std::vector<mc_candidate> kept_;
         std::vector<mc_verdict> verdicts_;
-        std::string lines_;
-        std::vector<std::uint64_t> lineOff_;
+        std::string lines_, pieces_;
+        std::vector<std::uint64_t> lineOff_, pieceOff_;
     };
 
     query_batch(const database& db, unsigned numHostThreads) : ctx_(db.ctx_), hosts_(numHostThreads)

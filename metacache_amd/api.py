@@ -26,6 +26,7 @@ TARGET_HITS_HOST = 1
 EVALUATE_HOST, EVALUATE_TALLY, EVALUATE_COVERAGE = 1, 2, 4
 FORMAT_HOST, FORMAT_QUERY_IDS, FORMAT_TRUTH, FORMAT_TOPHITS, FORMAT_LOCATIONS, FORMAT_MAPPED_ONLY = 1, 2, 4, 8, 16, 32
 FORMAT_SCRATCH = 2048                    # MC_FORMAT_SCRATCH: entries of workspace behind a device line_off
+MATCHES_WINDOWS = 2                      # MC_MATCHES_WINDOWS: mc_format_matches prints text/window:length, instead of text:length,
 TEXT_RESULT, TEXT_TARGET_RESULT, TEXT_CANDIDATE = 0, 1, 2
 verdict_dtype = np.dtype([("known", "u1"), ("correct", "u1"), ("flags", "u1"), ("reserved", "u1")])   # mc_verdict: kr, cr, bit 0 = counted wrong
 RANK_NAMES = ["sequence", "form", "variety", "subspecies", "species", "subgenus", "genus", "subtribe", "tribe", "subfamily", "family",
@@ -202,6 +203,16 @@ def mapping_texts(taxa, taxon_lin, target_lin, *, lowest: int = 0, highest: int 
     return {TEXT_RESULT: enc(result), TEXT_TARGET_RESULT: enc(target_result), TEXT_CANDIDATE: enc(cand)}
 
 
+def match_texts(taxa, target_lin, lowest: int = 0):
+    """The table of mc_format_matches_set_text as the command line prints -allhits (show_matches, printing.cpp:315-365): per target the
+    name of its own taxon (lowest == 0: the window form, MATCHES_WINDOWS; a target without a taxon has an empty entry and prints
+    nothing), else the name of its ancestor on exactly rank `lowest`, or of its own taxon where it has none there.
+    taxa / target_lin: as for mapping_texts.  -> [bytes per target]"""
+    def name(x):
+        return taxa[x - 1][3].encode() if x else b""
+    return [name(int(row[0])) if lowest == 0 else name(int(row[lowest]) or int(row[0])) for row in target_lin]
+
+
 class McEvaluation(C.Structure):
     _fields_ = [("assigned", C.c_uint64 * (NUM_RANKS + 1)), ("known", C.c_uint64 * (NUM_RANKS + 1)), ("correct", C.c_uint64 * (NUM_RANKS + 1)),
                 ("wrong", C.c_uint64 * (NUM_RANKS + 1)), ("coverage", (C.c_uint64 * 4) * (NUM_RANKS + 1)), ("reads", C.c_uint64),
@@ -305,6 +316,7 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_target_hits_reserve", "mc_target_hits_add", "mc_target_hits_collect",
            "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally",
            "mc_format_set_text", "mc_format_mappings", "mc_format_stats",
+           "mc_format_matches_set_text", "mc_format_matches", "mc_format_mappings_with", "mc_format_matches_stats",
            "mc_table_histogram", "mc_table_features", "mc_table_lookup"]
 
 _lib = None
@@ -383,6 +395,10 @@ def lib() -> C.CDLL:
         L.mc_format_mappings.argtypes = [C.c_void_p, C.POINTER(McFormatOptions), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mc_format_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_format_matches_set_text.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_format_matches.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mc_format_mappings_with.argtypes = L.mc_format_mappings.argtypes + [C.c_void_p, C.c_void_p]
+        L.mc_format_matches_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.mc_table_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mc_table_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
         L.mc_table_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
@@ -736,17 +752,23 @@ class Database:
 
     def format_device(self, opt: McFormatOptions, cands_ptr: int, stride: int, assigned_ptr: int, names_ptr: int, name_off_ptr: int, n: int, *,
                       flags: int = 0, truth_ptr: int = 0, query_ids_ptr: int = 0, first_query_id: int = 0, out_ptr: int, out_capacity: int,
-                      line_off_ptr: int, stream: int = 0):
+                      line_off_ptr: int, stream: int = 0, extra_ptr: int = 0, extra_off_ptr: int = 0, with_extra: bool = False):
         """renders n mapping lines from arrays in device memory into out_ptr (16-byte aligned); line_off_ptr: n + 1 + FORMAT_SCRATCH
-        uint64, entry n = the bytes all lines need (more than out_capacity: nothing was written); asynchronous on `stream`"""
-        self._check(lib().mc_format_mappings(self.h, C.byref(opt), cands_ptr or None, stride, assigned_ptr or None, truth_ptr or None,
-                                             query_ids_ptr or None, first_query_id, names_ptr or None, name_off_ptr or None, n, flags,
-                                             out_ptr or None, out_capacity, line_off_ptr or None, stream or None))
+        uint64, entry n = the bytes all lines need (more than out_capacity: nothing was written); asynchronous on `stream`.
+        extra_ptr / extra_off_ptr (or with_extra): through mc_format_mappings_with -- one more column, piece i of extra, behind the truth column"""
+        args = (self.h, C.byref(opt), cands_ptr or None, stride, assigned_ptr or None, truth_ptr or None,
+                query_ids_ptr or None, first_query_id, names_ptr or None, name_off_ptr or None, n, flags,
+                out_ptr or None, out_capacity, line_off_ptr or None, stream or None)
+        if extra_ptr or extra_off_ptr or with_extra:
+            self._check(lib().mc_format_mappings_with(*args, extra_ptr or None, extra_off_ptr or None))
+        else:
+            self._check(lib().mc_format_mappings(*args))
 
     def format_mappings(self, opt: McFormatOptions, cands: np.ndarray, assigned: np.ndarray, names, *, flags: int = 0, truth=None,
-                        query_ids=None, first_query_id: int = 0):
+                        query_ids=None, first_query_id: int = 0, extra=None, extra_off=None):
         """the same on host arrays: cands[n, stride] (cand_dtype), assigned[n] (assignment_dtype), names: n bytes objects
-        -> (bytes: all lines, line_off uint64 [n + 1])"""
+        -> (bytes: all lines, line_off uint64 [n + 1]).  extra (bytes) / extra_off (uint64 [n + 1]): one more column behind the truth
+        column, e.g. what format_matches returned (mc_format_mappings_with)"""
         cands = np.ascontiguousarray(cands, dtype=cand_dtype)
         assigned = np.ascontiguousarray(assigned, dtype=assignment_dtype)
         if cands.ndim != 2 or assigned.shape != (cands.shape[0],) or len(names) != cands.shape[0]:
@@ -760,19 +782,63 @@ class Database:
         args = lambda out, cap: (self.h, C.byref(opt), cands.ctypes.data if n else None, stride, assigned.ctypes.data if n else None,
                                  None if tr is None else tr.ctypes.data, None if ids is None else ids.ctypes.data, first_query_id,
                                  nbuf.ctypes.data, noff.ctypes.data, n, flags | FORMAT_HOST, out, cap, line_off.ctypes.data, None)
-        rc = lib().mc_format_mappings(*args(None, 0))                       # the size first: line_off is complete either way
+        call = lib().mc_format_mappings
+        if extra is not None:
+            xoff = np.ascontiguousarray(extra_off, dtype=np.uint64)
+            if xoff.shape != (n + 1,):
+                raise ValueError("format_mappings: extra_off must have n + 1 entries")
+            xbuf = np.frombuffer(bytes(extra) or b"\0", dtype=np.uint8)
+            call = lambda *a: lib().mc_format_mappings_with(*a, xbuf.ctypes.data, xoff.ctypes.data)
+        rc = call(*args(None, 0))                                           # the size first: line_off is complete either way
         if rc != -3:
             self._check(rc)
         total = int(line_off[n])
         out = np.zeros(max(total, 1), dtype=np.uint8)
         if total:
-            self._check(lib().mc_format_mappings(*args(out.ctypes.data, total)))
+            self._check(call(*args(out.ctypes.data, total)))
         return out[:total].tobytes(), line_off
 
     def format_stats(self):
         """-> [mc_format_mappings calls, reads, lines written, bytes written, result indices beyond their table]"""
         st = np.zeros(5, dtype=np.uint64)
         self._check(lib().mc_format_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    # ---- the all-hits column: location lists, run-length encoded (mc_format_matches*) ----------------
+    def format_matches_set_text(self, strings):
+        """the table of texts indexed by target: a list of bytes, e.g. from match_texts()"""
+        data, off = pack_strings([bytes(x) for x in strings])
+        buf = np.frombuffer(data, dtype=np.uint8) if data else np.zeros(1, dtype=np.uint8)
+        self._check(lib().mc_format_matches_set_text(self.h, buf.ctypes.data, off.ctypes.data, len(off) - 1))
+
+    def format_matches_device(self, hits_ptr: int, hit_off_ptr: int, n: int, *, flags: int = 0, out_ptr: int, out_capacity: int, piece_off_ptr: int,
+                              stream: int = 0):
+        """renders the pieces of n location lists in device memory into out_ptr (16-byte aligned); piece_off_ptr: n + 1 + FORMAT_SCRATCH
+        uint64, entry n = the bytes all pieces need (more than out_capacity: nothing was written); asynchronous on `stream`"""
+        self._check(lib().mc_format_matches(self.h, hits_ptr or None, hit_off_ptr or None, n, flags, out_ptr or None, out_capacity,
+                                            piece_off_ptr or None, stream or None))
+
+    def format_matches(self, hits: np.ndarray, hit_off: np.ndarray, *, flags: int = 0):
+        """the same on host arrays: hits (loc_dtype: win, tgt), hit_off uint64 [n + 1] -> (bytes: all pieces, piece_off uint64 [n + 1])"""
+        hits = np.ascontiguousarray(hits, dtype=loc_dtype)
+        hit_off = np.ascontiguousarray(hit_off, dtype=np.uint64)
+        n = len(hit_off) - 1
+        piece_off = np.zeros(n + 1, dtype=np.uint64)
+        args = lambda out, cap: (self.h, hits.ctypes.data if len(hits) else None, hit_off.ctypes.data, n, flags | FORMAT_HOST, out, cap,
+                                 piece_off.ctypes.data, None)
+        rc = lib().mc_format_matches(*args(None, 0))                         # the size first: piece_off is complete either way
+        if rc != -3:
+            self._check(rc)
+        total = int(piece_off[n])
+        out = np.zeros(max(total, 1), dtype=np.uint8)
+        if total:
+            self._check(lib().mc_format_matches(*args(out.ctypes.data, total)))
+        return out[:total].tobytes(), piece_off
+
+    def format_matches_stats(self):
+        """-> [mc_format_matches calls, reads, runs printed, bytes written, runs whose target lay beyond the table]"""
+        st = np.zeros(5, dtype=np.uint64)
+        self._check(lib().mc_format_matches_stats(self.h, st.ctypes.data))
         return [int(x) for x in st]
 
     # ---- target coverage: the two passes of -cov-percentile (mc_coverage_*) -----------------------

@@ -1501,6 +1501,7 @@ int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value)
     else if (n == "coverage_load_first") ctx->coverageLoadFirst = value != 0;   // mc_coverage_add: 0 = every mask goes out as an atomic (the form it was measured against)
     else if (n == "target_hits_max_mb") ctx->targetHitsMaxMb = std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 24));   // mc_target_hits_add(MC_TARGET_HITS_HOST): the log's largest size in MiB (default 8192)
     else if (n == "format_stage_rows") ctx->formatStageRows = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 26));   // mc_format_mappings(MC_FORMAT_HOST): reads per staged piece (0 = default)
+    else if (n == "format_stage_hits") ctx->formatStageHits = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 30));   // mc_format_matches(MC_FORMAT_HOST): locations per staged piece (0 = default)
     else if (n == "evaluate_stage_rows") ctx->evaluateStageRows = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 26));   // mc_evaluate_assignments(MC_EVALUATE_HOST): reads per staged piece (0 = default)
     else return fail(ctx, MC_ERR_INVALID, "mc_set_tuning: unknown switch '" + n + "'");
     return MC_OK;

@@ -243,6 +243,7 @@ struct mc_ctx {
     std::mutex formatMtx;
     mcamd::FormatState* format = nullptr;  // made by the first mc_format_set_text
     uint32_t formatStageRows = 0;          // MC_FORMAT_HOST: reads per staged piece (mc_set_tuning "format_stage_rows"; 0 = what 64 MB of candidates hold)
+    uint64_t formatStageHits = 0;          // mc_format_matches(MC_FORMAT_HOST): locations per staged piece (mc_set_tuning "format_stage_hits"; 0 = 4 Mi locations)
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

@@ -188,8 +188,9 @@ struct EvalClient {                          // a worker's pairs since its last 
 
 // ---- format (mc_format_*): the mapping lines rendered by the library --------------------------------------------------
 // With MCQ_FORMAT_DEVICE=1 a worker lays a batch's candidates out as flat rows, has the library vote (mc_classify_candidates) and render the
-// lines (mc_format_mappings), and takes its tallies from the assignments.  What the library does not print (-allhits, the alignment lines), what
-// classifies later or elsewhere (-cov-percentile, -maxcand 0's host candidates, the sharded command lines, merge) keeps the host loop.
+// lines (mc_format_mappings), and takes its tallies from the assignments.  What the library does not print (the alignment lines; -allhits unless
+// MCQ_ALLHITS_DEVICE=1 asks for mc_format_matches too), what classifies later or elsewhere (-cov-percentile, -maxcand 0's host candidates, the
+// sharded command lines, merge) keeps the host loop.
 // The three string tables of mc_format_set_text for this job's output options, from the functions the host loop prints with: the result
 // text of every taxon (entry 0: unclassified), the result text of every target (sequence-level results print the TARGET's lineage) and
 // the text a candidate of every target has in front of ":hits" (show_candidates).  false + why: the library did not take a table.
@@ -217,21 +218,44 @@ static bool set_format_tables(mc_ctx* ctx, const Options& o, const Taxonomy& tx,
     }
     return set(MC_TEXT_CANDIDATE);
 }
+// The table of mc_format_matches_set_text: what show_matches' emit prints in front of "/window:count," (-lowest sequence: the name of the target's
+// own taxon, nothing for a target without one) or ":count," (the name of the ancestor on exactly rank -lowest, else of the target's own taxon).
+static bool set_matches_table(mc_ctx* ctx, const Options& o, const Taxonomy& tx, std::string& why)
+{
+    FastOut t;
+    std::vector<uint64_t> off(1, 0);
+    for (uint64_t tgt = 0; tgt < tx.numTargets; ++tgt) {
+        const Lineage lin = tx.target_ranks((uint32_t)tgt);
+        const Taxon* x = tx.taxon(lin[o.lowest]);
+        if (!x && o.lowest != 0) x = tx.taxon(lin[0]);
+        if (x) t << x->name;
+        off.push_back(t.s.size());
+    }
+    const bool ok = mc_format_matches_set_text(ctx, t.s.data(), off.data(), off.size() - 1) == MC_OK;
+    if (!ok) why = mc_last_error(ctx);
+    return ok;
+}
 struct FormatStep : DeviceStep {
     mc_format_options opt{}; mc_classify_options vote{};
     uint64_t lines = 0; int flags = 0;       // flags: MC_FORMAT_HOST | what the output options ask for
+    bool allhits = false; int matchFlags = 0;   // MCQ_ALLHITS_DEVICE with -allhits: the column comes from mc_format_matches
+    uint64_t matchCalls = 0, matchReads = 0, matchBytes = 0;
     void took(uint64_t n, uint64_t l) { std::lock_guard<std::mutex> g(mtx); ++calls; reads += n; lines += l; }
+    void took_matches(uint64_t n, uint64_t bytes) { std::lock_guard<std::mutex> g(mtx); ++matchCalls; matchReads += n; matchBytes += bytes; }
     void open(const Session& S, const Options& o, bool merged, bool covMode, bool aligning)
     {
         const char* sw = std::getenv("MCQ_FORMAT_DEVICE");
         if (!sw || std::atoi(sw) == 0) return;
-        const char* first = o.mapView == Options::mv_none ? "no mapping lines are printed" : o.allhits ? "-allhits: the library does not print location lists"
+        const char* sa = std::getenv("MCQ_ALLHITS_DEVICE");
+        const bool matchesToo = o.allhits && sa && std::atoi(sa) != 0;
+        const char* first = o.mapView == Options::mv_none ? "no mapping lines are printed" : o.allhits && !matchesToo ? "-allhits: the library does not print location lists"
                           : aligning ? "-align: the alignment lines are put into the host's lines" : nullptr;
         const char* second = o.maxCand < 1 ? "-maxcand 0: lists longer than the device's are made on the host" : nullptr;
         off = shared_host_reason(S, merged, covMode, "-cov-percentile classifies on the host after the coverage filter", first, second);
         if (off.empty() && o.column.size() > sizeof opt.column) off = "a column separator of more than 16 bytes";
-        if (!off.empty() || !set_format_tables(S.ctx, o, S.tx, off)) return;
+        if (!off.empty() || !set_format_tables(S.ctx, o, S.tx, off) || (matchesToo && !set_matches_table(S.ctx, o, S.tx, off))) return;
         ctx = S.ctx;
+        allhits = matchesToo; matchFlags = MC_FORMAT_HOST | (o.lowest == 0 ? MC_MATCHES_WINDOWS : 0);
         std::memcpy(opt.column, o.column.data(), o.column.size());
         opt.column_len = (uint32_t)o.column.size(); opt.win_stride = S.dbStride; opt.win_len = S.dbWinlen;
         vote = mc_classify_options{(uint32_t)o.hitsMin, o.hitsDiff, o.lowest, o.highest};
@@ -242,12 +266,15 @@ struct FormatStep : DeviceStep {
     {
         DeviceStep::report(P, "mapping lines on the device: " + std::to_string(calls) + " mc_format_mappings calls, " + std::to_string(reads) + " reads, " + std::to_string(lines) + " lines, ",
                            " batches formatted on the host", "mapping lines formatted on the host");
+        if (P.on && ctx && allhits)
+            std::cerr << "mcq profile: all-hits columns on the device: " << matchCalls << " mc_format_matches calls, " << matchReads << " reads, " << matchBytes << " bytes\n";
     }
 };
 struct FormatClient {                        // a worker's batch as the library takes it, and what comes back
     FormatStep* step = nullptr;              // (null: the host loop classifies and prints read by read)
     std::vector<mc_candidate> rows; std::vector<mc_assignment> assigned; std::vector<uint32_t> truth;
     std::vector<uint64_t> ids, nameOff, lineOff; std::string names, bytes;
+    std::vector<mc_location> locs; std::vector<uint64_t> locOff, pieceOff; std::string pieces;   // (-allhits: the reads' lists, flat, and their rendered column)
     std::vector<Cand> cands;                 // (one read's, for -hits-per-ref)
     // One batch through the library: what the writer L (MappingWriter) does read by read -- vote, tallies, line -- for all its reads at once.
     // false: a call failed (the step says why) and NOTHING of the batch was counted or written, so that the caller's host loop does the whole batch.
@@ -257,6 +284,7 @@ struct FormatClient {                        // a worker's batch as the library 
         const Options& o = L.o;
         const uint32_t K = r.max_candidates;
         rows.clear(); ids.clear(); truth.clear(); names.clear(); nameOff.assign(1, 0);
+        locs.clear(); locOff.assign(1, 0);
         for (uint32_t i = 0; i < r.num_queries; ++i) {
             const auto& m = queries[i];
             if (m.empty) continue;                                   // processQuery, classification.cpp:780
@@ -266,16 +294,26 @@ struct FormatClient {                        // a worker's batch as the library 
             names.append(m.header.p, sp ? (size_t)((const char*)sp - m.header.p) : m.header.n);
             nameOff.push_back(names.size());
             if (o.determineGroundTruth) truth.push_back(ground_truth(L.tx, std::string(m.header.p, m.header.n)));
+            if (step->allhits) { locs.insert(locs.end(), r.hits + r.hit_offsets[i], r.hits + r.hit_offsets[i + 1]); locOff.push_back(locs.size()); }
         }
         const size_t n = ids.size();
         if (n == 0) return true;
         assigned.resize(n);
         if (mc_classify_candidates(step->ctx, &step->vote, rows.data(), (uint32_t)n, K, MC_CLASSIFY_HOST, assigned.data(), nullptr) != MC_OK) { step->note(mc_last_error(step->ctx)); return false; }
+        if (step->allhits) {                                         // the all-hits column first: its pieces go into the lines
+            pieceOff.resize(n + 1);
+            if (pieces.size() < locs.size() * 8 + 16) pieces.resize(locs.size() * 8 + 16);
+            auto column = [&]() { return mc_format_matches(step->ctx, locs.data(), locOff.data(), (uint32_t)n, step->matchFlags, &pieces[0], pieces.size(), pieceOff.data(), nullptr); };
+            int mrc = column();
+            if (mrc == MC_ERR_NOMEM) { pieces.resize(pieceOff[n] + pieceOff[n] / 4); mrc = column(); }   // (piece_off came back complete: now they fit)
+            if (mrc != MC_OK) { step->note(mc_last_error(step->ctx)); return false; }
+        }
         lineOff.resize(n + 1);
         if (bytes.size() < n * 128) bytes.resize(n * 128);
         auto render = [&]() {
-            return mc_format_mappings(step->ctx, &step->opt, rows.data(), K, assigned.data(), (step->flags & MC_FORMAT_TRUTH) ? truth.data() : nullptr,
-                                      ids.data(), 0, names.data(), nameOff.data(), (uint32_t)n, step->flags, &bytes[0], bytes.size(), lineOff.data(), nullptr);
+            return mc_format_mappings_with(step->ctx, &step->opt, rows.data(), K, assigned.data(), (step->flags & MC_FORMAT_TRUTH) ? truth.data() : nullptr,
+                                           ids.data(), 0, names.data(), nameOff.data(), (uint32_t)n, step->flags, &bytes[0], bytes.size(), lineOff.data(), nullptr,
+                                           step->allhits ? pieces.data() : nullptr, step->allhits ? pieceOff.data() : nullptr);
         };
         int rc = render();
         if (rc == MC_ERR_NOMEM) { bytes.resize(lineOff[n] + lineOff[n] / 4); rc = render(); }      // (line_off came back complete: now they fit)
@@ -288,6 +326,7 @@ struct FormatClient {                        // a worker's batch as the library 
         }
         out.write(bytes.data(), (std::streamsize)lineOff[n]);
         step->took(n, printed);
+        if (step->allhits) step->took_matches(n, pieceOff[n]);
         return true;
     }
 };
