@@ -159,6 +159,9 @@ __device__ __forceinline__ void gw_fill_rounds(uint64_t* T, uint32_t lane, uint3
     const uint32_t jlo = r0 > start ? r0 - start : 0u, jhi = min(myR, r0 + kGwRounds > start ? r0 + kGwRounds - start : 0u);
     for (uint32_t j = jlo; j < jhi; ++j) T[start + j - r0] = (pay + 16ull * j) | ((uint64_t)min(16u, sz - 16u * j) << 40);
 }
+// a lane's value handed to every lane that asks for it (src 0 .. 63): __shfl without its term from the lane's own number, which is zero in a
+// wave of 64 and which the compiler otherwise computes once per kernel and carries -- spilled, reloaded behind a full wait -- through every read
+__device__ __forceinline__ uint32_t gw_lane_value(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_ds_bpermute(src << 2, (int)v); }
 // The same table for a read whose rounds fit ONE batch (r0 = 0, Rc <= kGwRounds), in a fixed number of instructions: gw_fill_rounds has
 // every lane write its own rounds one after the other -- as many steps as the longest list has rounds (16 for the lists of 254
 // locations every read of a RefSeq-scale table meets): ~130 of the kernel's ~1 380 VALU instructions per read.  Here every lane leaves
@@ -177,8 +180,8 @@ __device__ __forceinline__ void gw_fill_rounds_scan(uint64_t* T, uint32_t* E, ui
     for (uint32_t h = 0; h < 2; ++h) {
         const uint32_t slot = lane + 64u * h, who = h ? hi : lo;
         const int src = (int)(who ? who - 1u : 0u);
-        const uint32_t eStart = (uint32_t)__shfl((int)start, src), eSz = (uint32_t)__shfl((int)sz, src);
-        const uint32_t eLo = (uint32_t)__shfl((int)payLo, src), eHi = (uint32_t)__shfl((int)payHi, src);
+        const uint32_t eStart = gw_lane_value(start, src), eSz = gw_lane_value(sz, src);
+        const uint32_t eLo = gw_lane_value(payLo, src), eHi = gw_lane_value(payHi, src);
         const uint32_t j = slot - eStart;
         const uint64_t ep = ((uint64_t)eHi << 32) | eLo;
         T[slot] = (who && slot < Rc) ? ((ep + 16ull * j) | ((uint64_t)min(16u, eSz - 16u * j) << 40)) : 0ull;
@@ -199,8 +202,8 @@ __device__ __forceinline__ void gw_fill_rounds_scan_at(uint64_t* T, uint32_t* E,
     for (uint32_t h = 0; h < 2; ++h) {
         const uint32_t slot = lane + 64u * h, who = h ? hi : lo;
         const int src = (int)(who ? who - 1u : 0u);
-        const uint32_t eStart = (uint32_t)__shfl((int)start, src), eSz = (uint32_t)__shfl((int)sz, src);
-        const uint32_t eLo = (uint32_t)__shfl((int)payLo, src), eHi = (uint32_t)__shfl((int)payHi, src);
+        const uint32_t eStart = gw_lane_value(start, src), eSz = gw_lane_value(sz, src);
+        const uint32_t eLo = gw_lane_value(payLo, src), eHi = gw_lane_value(payHi, src);
         const uint32_t j = r0 + slot - eStart;
         const uint64_t ep = ((uint64_t)eHi << 32) | eLo;
         T[slot] = (who && r0 + slot < Rc) ? ((ep + 16ull * j) | ((uint64_t)min(16u, eSz - 16u * j) << 40)) : 0ull;
@@ -221,14 +224,20 @@ __device__ __forceinline__ void gw_load_rounds(const uint64_t* T, const uint32_t
         }
     }
 }
+// LEAVE (the three loops below that follow the loads; gw_filter_count_kernel<LOOKUP>): the unrolled loop is left at the first load without
+// rounds -- a scalar compare and a branch per load -- instead of skipping every such load under a condition of its own: the compiler kept
+// the eight wave-uniform conditions u < nl as eight mask pairs per read, written to and read from the lanes of a register for each loop.
+// (Not gw_load_rounds: left early, every exit sets the registers of the loads not made to kGwNone again -- 166 moves in place of 64.)
 // phase A on a batch: every place of the loaded lines marks its block (places past a list's end hold other lists' numbers: more
 // marks, never fewer)
-template <class Bloom>
+template <class Bloom, bool LEAVE = false>
 __device__ __forceinline__ void gw_mark_rounds(uint32_t* bits, const uint4 (&x)[kGwLoads], uint32_t A, uint32_t nl = kGwLoads)
 {
 #pragma unroll
-    for (uint32_t u = 0; u < kGwLoads; ++u)                    // (lanes without a round hold kGwNone: sixty-four of them on ONE filter word would take turns)
-        if (u < nl && x[u].x != kGwNone) Bloom::mark4(bits, x[u].x >> A, x[u].y >> A, x[u].z >> A, x[u].w >> A);
+    for (uint32_t u = 0; u < kGwLoads; ++u) {                  // (lanes without a round hold kGwNone: sixty-four of them on ONE filter word would take turns)
+        if (u >= nl) { if constexpr (LEAVE) break; else continue; }
+        if (x[u].x != kGwNone) Bloom::mark4(bits, x[u].x >> A, x[u].y >> A, x[u].z >> A, x[u].w >> A);
+    }
 }
 // phase B: a number is kept if its block was marked twice or it lies within D of a block boundary; the kept ones are appended to dst
 // (ballot compaction), n2 counts them whether they fit or not
@@ -319,22 +328,26 @@ __device__ __forceinline__ void gw_take_rounds(const uint32_t* bits, const uint6
 
 // how many of a lane's four places per load hold numbers (0 .. 4), three bits per load: all that phase B needs of the round table -- the
 // table's place can go to something else once the loads are issued (gw_filter_count_kernel's seven-wave instance)
+template <bool LEAVE = false>
 __device__ __forceinline__ uint32_t gw_pack_rems(const uint64_t* T, uint32_t grp, uint32_t sub4, uint32_t nl)
 {
     uint32_t packed = 0;
 #pragma unroll
     for (uint32_t u = 0; u < kGwLoads; ++u) {
-        if (u >= nl) continue;
+        if (u >= nl) { if constexpr (LEAVE) break; else continue; }
         const uint32_t cnt = (uint32_t)(T[u * 16 + grp] >> 40);
         packed |= (cnt > sub4 ? min(cnt - sub4, 4u) : 0u) << (3u * u);
     }
     return packed;
 }
-template <class Bloom, bool CHECK>
+template <class Bloom, bool CHECK, bool LEAVE = false>
 __device__ __forceinline__ void gw_take_rounds_packed(const uint32_t* bits, const uint32_t packed, const GwFrame& F, GwSink& S, const uint4 (&x)[kGwLoads], uint32_t nl)
 {
 #pragma unroll
-    for (uint32_t u = 0; u < kGwLoads; ++u) if (u < nl) gw_take4<Bloom, CHECK>(bits, F, S, x[u], (int32_t)((packed >> (3u * u)) & 7u));
+    for (uint32_t u = 0; u < kGwLoads; ++u) {
+        if (u >= nl) { if constexpr (LEAVE) break; else continue; }
+        gw_take4<Bloom, CHECK>(bits, F, S, x[u], (int32_t)((packed >> (3u * u)) & 7u));
+    }
 }
 
 constexpr uint32_t kGwDefer = 0xFFFFFFFEu;                 // record of kListFiltered: left to gw_filter_stream_kernel
@@ -956,9 +969,10 @@ struct GwEntLookup {
 
 struct GwPend {
     bool pend = false;
-    uint32_t q = 0, wv = kGwNone, wh = 0, wd = 0, dir = 0, b0 = 0, b1 = 0, b2 = 0;
+    uint32_t q = 0, wv = kGwNone, whd = 0, dir = 0, b0 = 0, b1 = 0, b2 = 0;   // whd: hits | (end - begin) << 16, both below 2^16 (gw_pick's R): one register across the caller's next read
     __device__ __forceinline__ void bases(const DeviceTable& tab)   // stage 1: the three gwBase words behind the directory entry
     {
+        b0 = b1 = b2 = 0u;                                         // (set on every way through: nothing of them is carried from read to read)
         if (pend && wv != kGwNone) { b0 = tab.gwBase[dir]; b1 = tab.gwBase[dir + 1]; b2 = tab.gwBase[min(dir + 2, tab.gwTargets)]; }
     }
     template <bool TAX, class Ent>
@@ -972,7 +986,7 @@ struct GwPend {
             while (wv >= hi) { ++t; lo = hi; hi = tab.gwBase[t + 1]; }
         }
         uint32_t plo[kLaneK], phi[kLaneK];
-        const bool again = gw_winners_out<TAX>(lane, K, wv, wh, wd, t, lo, hi, cands + (size_t)q * K, plo, phi);
+        const bool again = gw_winners_out<TAX>(lane, K, wv, whd & 0xFFFFu, whd >> 16, t, lo, hi, cands + (size_t)q * K, plo, phi);
         if (again) ent.leave(ws, tab, q, lane);                    // (the read BEFORE the one the caller is at)
         if (lane == 0) {
             if (again) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
@@ -1059,7 +1073,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
     if constexpr (DEFER) {
         P.template finish<TAX>(lane, K, tab, ws, cands, ent);      // the previous read's candidates
         if (strong >= K) {                                         // this read's: later
-            P.pend = true; P.q = q; P.wv = wv; P.wh = wh; P.wd = wd;
+            P.pend = true; P.q = q; P.wv = wv; P.whd = wh | (wd << 16);
             P.dir = wv != kGwNone ? tab.gwDir[wv >> tab.gwDirShift] : 0u;
             wave_lds_sync();
             return true;
@@ -1253,10 +1267,13 @@ constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: th
 //
 // LOOKUP (round 7, "filter_lookup"): the kernel walks the READS the lane kernel sketched (kFlagProbe, at most 64 features) instead of the
 // records of kListFilter and does the direct-index lookups itself, one lane per feature -- the lane that loaded the hand-over entry of a
-// found feature now loads the index entry of feature `lane`, two reads ahead: the read's features (i + 2), their index entries (i + 1),
-// the entries of read i in registers.  The random 8-byte requests move from the lookup kernel, which runs at the request rate, into this
-// one, whose memory side is half idle.  The read's statistics and its class are written as probe_cands_one does; reads of another class go
-// to their work lists, reads of this class that the kernel does not finish get a record of kListFilter / kListFiltered (appended: one
+// found feature now loads the index entry of feature `lane`.  The pipeline per wave (round 9; DESIGN 12.2, the stages at their variables
+// below): while read i is worked on, only the index entries of read i + 1 are LIVE across the phases that hold the lists' numbers in
+// registers (they have arrived by then: the compiler's wait for the read's result stores takes them with it); the features of read i + 2 and the raw metadata of read i + 3 (one register, three lanes) are issued behind phase B and taken
+// at the top of read i + 1, where the metadata is decoded by v_readlane -- no wait for a load of the same iteration; the singleton's
+// gwBase word is requested in front of the list loads and added to behind them, so nothing waits between the two.  The random 8-byte
+// requests move from the lookup kernel, which runs at the request rate, into this one, whose memory side is half idle.  The read's
+// statistics and its class are written as probe_cands_one does; reads of another class go to their work lists, reads of this class that the kernel does not finish get a record of kListFilter / kListFiltered (appended: one
 // atomic each, they are few).  The hand-over entries (found features only, singletons first; the slots up to nf cleared) are written
 // for those two kinds of reads ONLY (round 8: lk_store_entries) -- a read the kernel finishes, 59 in 60 at RefSeq scale,
 // is never visited again (what the stores' share of the kernel's write requests was: docs/LAB_NOTEBOOK_r08.md).
@@ -1275,7 +1292,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     __shared__ __attribute__((aligned(16))) uint32_t bitS[WAVES][Bloom::kWords];
     __shared__ __attribute__((aligned(16))) uint64_t roundS[kSeven ? 1 : WAVES][kSeven ? 1 : kGwRounds];
     __shared__ __attribute__((aligned(16))) uint32_t keptS[WAVES][kKeep];
-    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    uint32_t lane = threadIdx.x & 63u;                             // (LOOKUP: hidden from the compiler at the top of every read, see the loop)
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t* bits = bitS[wave];
     uint64_t* T = kSeven ? reinterpret_cast<uint64_t*>(bits) : roundS[kSeven ? 0 : wave];
     uint32_t* kept = keptS[wave];
@@ -1298,28 +1316,53 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         epay = lane < ne ? ws.ppay[r.y + lane] : 0ull;
     };
     load_entries(rec);
-    // LOOKUP: {first feature slot, features} of reads i, i + 1, i + 2 (m0, m1, m2; kLkSkip: not this kernel's read), the index entries of
-    // read i + 1 (lkEnt: they are read i's when the loop takes them), the features of read i + 2 (lkFeat), how many features a read has (lkNfeat)
+    // LOOKUP: the per-wave pipeline over the wave's reads i = 0, 1, ... (read number w0 + i nWaves), four stages; DESIGN 12.2:
+    //   M  raw metadata of a read in ONE register: lanes 0, 1, 2 load winOff[q], winOff[q + 1], qflag[q]     issued behind phase B of read i for read i + 3
+    //   D  their decoding (three v_readlane) to {first feature slot, features} (kLkSkip: not this kernel's)   at the top of read i + 1 for read i + 3
+    //   F  the read's features, one per lane (lkFeat)                                                        issued behind phase B of read i for read i + 2
+    //   E  the features' index entries (lkEnt: the random 8-byte loads), how many features (lkNfeat)         issued at the top of read i for read i + 1
+    // Only lkEnt is live while the lists' numbers are in registers (gw_load_rounds .. phase B) -- requested at the top, and in the register
+    // by the early deferral test, where the wait for the result stores (issued behind it) takes it along; F and M are issued where x[] is
+    // dead, the counting covers them, and they are taken at the top of the next read -- before anything of that read is issued, so the
+    // wait for them waits for nothing younger.  mA, mB: the decoded metadata of reads i + 1, i + 2 while read i is worked on.
     // (a form that loaded the reads' offsets and flags 64 reads at a time, one per lane, and handed them out by v_readlane held two more
     // registers: 20 instead of 14 spilled, +0.3 ms per 5 x 10^6 reads; docs/LAB_NOTEBOOK_r07.md)
     constexpr uint32_t kLkSkip = 0xFFFFFFFFu;
-    auto load_meta = [&](uint32_t q) -> uint2 {
-        if (!LOOKUP || q >= b.n) return make_uint2(kLkSkip, 0u);
-        const uint32_t o0 = ws.winOff[q], nf = (ws.winOff[q + 1] - o0) * s;
-        return (ws.qflag[q] == kFlagProbe && nf <= 64u) ? make_uint2(o0 * s, nf) : make_uint2(kLkSkip, 0u);
+    auto load_raw = [&](uint32_t q) -> uint32_t {                  // stage M (reads past the batch: 0 in every lane -- qflag 0 is not kFlagProbe)
+        uint32_t raw = 0u;
+        if (LOOKUP && q < b.n && lane < 3u) raw = *(lane < 2u ? ws.winOff + q + lane : ws.qflag + q);
+        return raw;
     };
-    auto load_feat = [&](const uint2& m) -> uint32_t { return (m.x != kLkSkip && lane < m.y) ? ws.features[m.x + lane] : 0xFFFFFFFFu; };
-    uint2 m0 = load_meta(w0), m1 = load_meta(w0 + nWaves), m2 = load_meta(w0 + 2 * nWaves);
-    uint32_t lkFeat = 0xFFFFFFFFu, lkNfeat = 0; uint64_t lkEnt = 0;
+    auto decode_raw = [&](uint32_t raw) -> uint2 {                 // stage D
+        const uint32_t o0 = rdlane(raw, 0), nf = (rdlane(raw, 1) - o0) * s;
+        return (LOOKUP && rdlane(raw, 2) == kFlagProbe && nf <= 64u) ? make_uint2(o0 * s, nf) : make_uint2(kLkSkip, 0u);
+    };
+    auto load_feat = [&](const uint2& m) -> uint32_t { return (m.x != kLkSkip && lane < m.y) ? ws.features[m.x + lane] : 0xFFFFFFFFu; };   // stage F
+    uint2 mA = make_uint2(kLkSkip, 0u), mB = mA;
+    uint32_t lkFeat = 0xFFFFFFFFu, lkNfeat = 0, lkRaw = 0; uint64_t lkEnt = 0;
     if constexpr (LOOKUP) {
-        const uint32_t f0 = load_feat(m0);
-        lkFeat = load_feat(m1);
+        mA = decode_raw(load_raw(w0)); mB = decode_raw(load_raw(w0 + nWaves));
+        const uint32_t f0 = load_feat(mA);
+        lkFeat = load_feat(mB);
+        lkRaw = load_raw(w0 + 2 * nWaves);
         lkNfeat = (uint32_t)__popcll(__ballot(f0 != 0xFFFFFFFFu));
         lkEnt = f0 != 0xFFFFFFFFu ? tab.direct[f0] : 0ull;
     }
-    const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
+    uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
+    // LOOKUP: the lane number is made opaque at the top of every read and between its phases: what is one or two instructions from it --
+    // the lane's addresses in bits / T / kept, values32 + sub4 -- is computed where it is used instead of being carried, spilled,
+    // through every read or across the phase that holds the lists' numbers
+    auto hide_lane = [&]() {
+        if constexpr (LOOKUP) { asm volatile("" : "+v"(lane)); grp = lane >> 2; sub4 = (lane & 3u) * 4u; }
+    };
     GwPend P;
     for (uint32_t w = w0; w < total; w += nWaves) {
+      // LOOKUP: stages F and M, once per read -- behind phase B on the way to the counting, for every other way out of the read here below
+      bool advanced = false;
+      auto advance = [&]() {
+          if constexpr (LOOKUP) { lkFeat = load_feat(mB); lkRaw = load_raw(w + 3 * nWaves); advanced = true; }
+      };
+      do {                                                         // (no 'break' and no 'continue' of an inner loop in here: 'continue' means "leave the read")
         uint32_t q, nent, H, maxWin, sz, fbase = 0, nfs = 0; uint64_t pay;
         uint32_t rix = 0xFFFFFFFFu;                                // LOOKUP: the read's record in kListFilter, made when something is left to the later kernels
         if constexpr (!LOOKUP) {
@@ -1329,11 +1372,12 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             recNext = load_rec(w + 2 * nWaves);
             load_entries(rec);
         } else {
-            const uint2 cur = m0; const uint64_t e = lkEnt; const uint32_t nfeat = lkNfeat;
+            hide_lane();
+            const uint2 cur = mA; const uint64_t e = lkEnt; const uint32_t nfeat = lkNfeat;
+            const uint2 mC = decode_raw(lkRaw);                    // stage D, read i + 3 -> i + 2
             lkNfeat = (uint32_t)__popcll(__ballot(lkFeat != 0xFFFFFFFFu));
-            lkEnt = lkFeat != 0xFFFFFFFFu ? tab.direct[lkFeat] : 0ull;
-            lkFeat = load_feat(m2);
-            m0 = m1; m1 = m2; m2 = load_meta(w + 3 * nWaves);
+            lkEnt = lkFeat != 0xFFFFFFFFu ? tab.direct[lkFeat] : 0ull;   // stage E, read i + 1
+            mA = mB; mB = mC;
             if (cur.x == kLkSkip) continue;
             q = w; fbase = cur.x; nfs = cur.y;
             sz = (uint32_t)e & 0xFFFFu; pay = direct_payload(e);
@@ -1398,23 +1442,29 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         wave_lds_sync();
         const GwFrame F(maxWin);
         const uint32_t nl = (Rc + 15u) >> 4;
+        // the singleton's gwBase word is requested in front of the list loads and taken behind them (tab.gw_of in two halves: no wait
+        // between its load and the list loads; lanes without a singleton: kGwNone + 0)
+        const uint32_t svLow = sz == 1 ? (uint32_t)pay : 0u;
+        const uint32_t svBase = sz == 1 ? tab.gwBase[(uint32_t)(pay >> 32)] : kGwNone;
         uint4 x[kGwLoads];
         gw_load_rounds(T, tab.values32, grp, sub4, x, nl);
+        const uint32_t sv = svBase + svLow;
         uint32_t rems = 0;
         if constexpr (kSeven) {                                    // the table has been read: its place is the filter's now
-            rems = gw_pack_rems(T, grp, sub4, nl);
+            rems = gw_pack_rems<LOOKUP>(T, grp, sub4, nl);
+            hide_lane();
             wave_lds_sync();
             clear_bits();
             wave_lds_sync();
         }
         auto take_rounds = [&](auto check, GwSink& S) {
             constexpr bool CHECK = decltype(check)::value;
-            if constexpr (kSeven) gw_take_rounds_packed<Bloom, CHECK>(bits, rems, F, S, x, nl);
+            if constexpr (kSeven) gw_take_rounds_packed<Bloom, CHECK, LOOKUP>(bits, rems, F, S, x, nl);
             else gw_take_rounds<Bloom, CHECK>(bits, T, F, S, grp, sub4, x, nl);
         };
-        const uint32_t sv = sz == 1 ? tab.gw_of(pay) : kGwNone;
         if (sv != kGwNone) Bloom::mark(bits, sv >> F.A);
-        gw_mark_rounds<Bloom>(bits, x, F.A, nl);
+        gw_mark_rounds<Bloom, LOOKUP>(bits, x, F.A, nl);
+        hide_lane();
         wave_lds_sync();
         const bool here = maxWin <= kHashWin;
         uint32_t n2;
@@ -1430,6 +1480,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             n2 = S.n2;
         }
         if (here && n2 <= kKeep) {
+            hide_lane();                                           // (without this one and the one behind phase A a spill store comes back into the loop)
+            advance();                                             // (x[] is dead from here on)
             if constexpr (!LOOKUP) { if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwCounted | n2, maxWin); }   // (LOOKUP: a read finished here has no record)
             wave_lds_sync();
             auto count = [&](const auto& ent) {
@@ -1478,6 +1530,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         }
         if (!fallback) sliceUsed += n2;
         wave_lds_sync();
+      } while (false);                                             // (every 'continue' above comes out here)
+      if (!advanced) advance();
     }
     P.bases(tab);
     if constexpr (LOOKUP) P.template finish<TAX>(lane, K, tab, ws, cands, GwEntLookup{0u, 0u, s});
