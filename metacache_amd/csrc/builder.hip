@@ -543,14 +543,12 @@ int mc_build_finish(mc_builder* b, mc_ctx** outCtx)
     return MC_OK;
 }
 
-// what a finished builder's lists take in the location store with every list on lines of its own (kernels.h list_alloc): one number per block
+// what a finished builder's lists take in the location store with every list on lines of its own (table_rules.h list_alloc): one number per block
 __global__ __launch_bounds__(256) void padded_store_kernel(const uint8_t* __restrict__ sizes, uint64_t n, uint32_t rmOver, unsigned long long* __restrict__ out)
 {
     unsigned long long sum = 0;
     for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
-        uint32_t e = sizes[i];
-        if (rmOver && e > rmOver) e = 0;
-        sum += list_alloc(e, kListAlign);
+        sum += list_alloc(size_after_rules(sizes[i], rmOver, 0), kListAlign);
     }
     for (int off = 32; off > 0; off >>= 1) sum += __shfl_down(sum, off);
     if ((threadIdx.x & 63) == 0 && sum) atomicAdd(out, sum);
@@ -855,7 +853,7 @@ int mc_build_write_add(mc_db_writer* w, mc_builder* c)
         B_TRY(c, hipMemcpy(sizes.data(), c->rS + k0, nk, hipMemcpyDeviceToHost));
         if (vend > vbeg) B_TRY(c, hipMemcpy(values.data(), c->rV + vbeg, (vend - vbeg) * 8, hipMemcpyDeviceToHost));
         vbeg = vend;
-        auto kept = [&](uint64_t i) { return !(c->rmOver && sizes[i] > c->maxLocs - 1); };
+        auto kept = [&](uint64_t i) { return size_after_rules(sizes[i], c->rmOver ? c->maxLocs - 1 : 0, 0) == sizes[i]; };
         // the reader takes batches of exactly 'batch' keys (the last one may be shorter): a batch runs on across slices and shards
         uint64_t voff = 0;
         for (uint64_t i = 0; i < nk; ++i) {

@@ -63,7 +63,7 @@ struct Part {
     uint64_t dvaluesCap = 0;
     uint64_t* ddirect = nullptr;    // direct-address index (kernels.h DeviceTable::direct), built at mc_load_end where it pays and fits
     bool compact = false;
-    uint32_t listAlign = 1;         // lists begin at multiples of this many entries (kernels.h list_alloc; kListAlign when the padded total was announced and fits)
+    uint32_t listAlign = 1;         // lists begin at multiples of this many entries (table_rules.h list_alloc; kListAlign when the padded total was announced and fits)
     uint64_t expectStore = 0;       // entries of the store with the padding (0: unknown -> no alignment)
 };
 
@@ -113,12 +113,15 @@ struct CoDispatcher {
     uint32_t turn = 0;
 };
 
-// table_build: insert one chunk of a single-part database whose batch arrays already live in device memory
+int ensure(mc_ctx* ctx, DevBuf& b, size_t bytes);   // context.cpp: a grow-only buffer of at least `bytes` (hipFree + dev_malloc when it grows)
+hipError_t traced_sync(hipStream_t st);             // hipStreamSynchronize, counted by MC_SUBMIT_TRACE
+
+// table_load.cpp: insert one chunk of a single-part database whose batch arrays already live in device memory
 // (between mc_load_begin and mc_load_end; used by mc_load_batch after its upload and by the builder directly)
 int load_chunk_device(mc_ctx* ctx, const uint32_t* dkeys, const uint8_t* dsizes, const uint8_t* dvals, uint32_t nkeys, uint64_t fileVals);
-
 // the same without any synchronisation: what the chunk adds to the location store comes from the host (dbload.cpp)
-// list alignment of the compact store (kernels.h list_alloc): a loader that knows the lists' sizes announces what the store takes with
+int load_chunk_device_async(mc_ctx* ctx, const uint32_t* dkeys, const uint8_t* dsizes, const uint8_t* dvals, uint32_t nkeys, uint64_t fileVals, uint64_t stored);
+// list alignment of the compact store (table_rules.h list_alloc): a loader that knows the lists' sizes announces what the store takes with
 // every list on lines of its own -- before the first chunk, with which the store is allocated
 void announce_store(mc_ctx* ctx, uint64_t paddedEntries);
 // what the caller of mc_open_database / mc_create on THIS thread knows about the device's other tenants (partset.cpp): list alignment
@@ -126,10 +129,10 @@ void announce_store(mc_ctx* ctx, uint64_t paddedEntries);
 struct OpenHints { int listAlign = -1; double listAlignShare = 1.0; int directIndex = -1; };
 OpenHints& open_hints();
 int allocate_values(mc_ctx* ctx);
+int build_direct_index(mc_ctx* ctx);   // (mc_load_end; mc_set_tuning "direct_index" on a loaded table)
 int allocate_buckets(mc_ctx* ctx, uint64_t nkeys);
 int reserve_slot_pipes(mc_ctx* ctx, uint64_t locs, uint64_t keys, bool waitForStores = true);
 int reserve_query_pipes(mc_ctx* ctx, uint32_t n, uint64_t chars);
-int load_chunk_device_async(mc_ctx* ctx, const uint32_t* dkeys, const uint8_t* dsizes, const uint8_t* dvals, uint32_t nkeys, uint64_t fileVals, uint64_t stored);
 // dbload.cpp: a whole .cache file of a single-part context through reader threads, pinned slabs and a copy stream (between mc_load_begin
 // and mc_load_end).  stats (may be NULL): bytes read, nanoseconds in all, of the index pass, the feeder waited for readers
 int load_file_pipelined(mc_ctx* ctx, const std::string& fname, uint32_t targetBytes, uint64_t stats[4]);

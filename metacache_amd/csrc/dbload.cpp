@@ -80,97 +80,14 @@ struct BatchPlace { uint64_t off = 0, fileVals = 0; uint32_t nkeys = 0; };   // 
 
 inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
-// effective_size of table_build.hip on the host: what a key of `fileSize` locations adds to the location store
-inline uint32_t stored_of(uint32_t key, uint32_t fileSize, const LoadFilter& lf)
-{
-    uint32_t size = fileSize;
-    if (lf.rmOver && size > lf.rmOver) size = 0;
-    if (lf.maxLocs && size > lf.maxLocs) size = lf.maxLocs;
-    if (lf.shardCnt > 1 && key_owner(key, lf.shardCnt) != lf.shardIdx) size = 0;
-    return list_alloc(size, lf.align);
-}
+inline uint32_t stored_of(uint32_t key, uint32_t fileSize, const LoadFilter& lf) { return list_alloc(effective_size(key, fileSize, lf), lf.align); }   // what a key adds to the location store
 
 }  // namespace
 
-// One chunk (<= 2^22 keys, < 2^32 file values) whose arrays are in device memory, WITHOUT any synchronisation: `stored` (what the chunk adds
-// to the location store) comes from the host.  The scratch arrays are reused chunk after chunk: the stream's order protects them.
-int mcamd::load_chunk_device_async(mc_ctx* ctx, const uint32_t* dkeys, const uint8_t* dsizes, const uint8_t* dvals, uint32_t nb, uint64_t fileVals, uint64_t stored)
-{
-    Part& P = ctx->parts[0];
-    auto fail = [&](int code, const char* msg) { ctx->err = msg; return code; };
-    if (P.keysLoaded + nb > P.expectKeys) return fail(MC_ERR_INVALID, "database file: more keys than its header announces");
-    if (fileVals >= (1ull << 32)) return fail(MC_ERR_INVALID, "database file: a chunk holds 2^32 or more locations");
-    if (mcamd::allocate_buckets(ctx, 0) != MC_OK) return MC_ERR_NOMEM;
-    if (mcamd::allocate_values(ctx) != MC_OK) return fail(MC_ERR_NOMEM, "database load: cannot allocate the location store");
-    if (P.valuesStored + stored > P.dvaluesCap) return fail(MC_ERR_INVALID, "database file: more values than its header announces");
-    const uint32_t tb = ctx->cfg.target_id_bytes;
-    const LoadFilter lf{ctx->cfg.max_locations_per_feature, ctx->cfg.remove_overpopulated, ctx->cfg.key_shard_index, ctx->cfg.key_shard_count, ctx->parts[0].listAlign};
-    hipStream_t st = ctx->stream;
-    auto ensure = [&](DevBuf& b, size_t bytes) -> bool {
-        if (bytes <= b.cap) return true;
-        // (growing a scratch array the stream may still be reading: drain it first -- happens a few times per load, the sizes settle at once)
-        if (b.p) { (void)hipStreamSynchronize(st); (void)hipFree(b.p); }
-        b.p = nullptr; b.cap = 0;
-        const size_t want = bytes + bytes / 4 + 256;
-        if (mcamd::dev_malloc(&b.p, want) != hipSuccess) return false;
-        b.cap = want;
-        return true;
-    };
-    if (!ensure(ctx->bLdFileSz, (size_t)nb * 4) || !ensure(ctx->bLdStoreSz, (size_t)nb * 4) || !ensure(ctx->bLdFileOff, (size_t)(nb + 2) * 4) ||
-        !ensure(ctx->bLdStoreOff, (size_t)(nb + 2) * 4) || !ensure(ctx->bLdScan, scan_tmp_bytes(nb + 1)))
-        return fail(MC_ERR_NOMEM, "database load: cannot allocate the table-build scratch");
-    auto* fileSz = (uint32_t*)ctx->bLdFileSz.p; auto* storeSz = (uint32_t*)ctx->bLdStoreSz.p;
-    auto* fileOff = (uint32_t*)ctx->bLdFileOff.p; auto* storeOff = (uint32_t*)ctx->bLdStoreOff.p;
-    auto* counters = (unsigned long long*)ctx->bLdCounters.p;
-    launch_table_prep(dkeys, dsizes, nb, lf, fileSz, storeSz, counters, st);
-    launch_scan_u32(fileSz, 1, nb, fileOff, nullptr, ctx->bLdScan.p, st);
-    launch_scan_u32(storeSz, 1, nb, storeOff, nullptr, ctx->bLdScan.p, st);
-    const GwLayout gwl = P.compact ? GwLayout{ctx->dGwBase, ctx->gwTargets, ctx->gwGap} : GwLayout{};
-    launch_table_insert(dkeys, dsizes, nb, lf, fileOff, storeOff, dvals, tb, P.valuesStored, P.dbuckets, P.nbuckets,
-                        (unsigned int*)(counters + 2), (unsigned int*)(counters + 2) + 1, st, gwl, (unsigned int*)(counters + 3));
-    if (P.compact)
-        launch_table_values_compact(dkeys, dsizes, nb, lf, fileOff, storeOff, dvals, tb, fileVals, reinterpret_cast<uint32_t*>(P.dvalues) + P.valuesStored,
-                                    gwl, (unsigned int*)(counters + 3), st);
-    else
-        launch_table_values(dkeys, dsizes, nb, lf, fileOff, storeOff, dvals, tb, fileVals, P.dvalues + P.valuesStored, st);
-    if (hipGetLastError() != hipSuccess) return fail(MC_ERR_HIP, "database load: a table-build kernel failed to launch");
-    P.valuesStored += stored;
-    P.keysLoaded += nb;
-    return MC_OK;
-}
-
-// Mode T (mc_config.target_shard_*): the values of a batch that lie in the context's target range move to the front of the batch's value
-// array, bucket after bucket; a bucket is first cut as the whole table would cut it (remove-overpopulated empties it, max-locations
-// keeps its first n values: host_hashmap.hpp:454-495), so that the device's own size rules find nothing more to do.  A bucket none
-// of whose locations are in range keeps its key with size 0 (the table build skips it).
+// Mode T: a batch cut in place to the context's target range (table_rules.h)
 uint64_t mcamd::cut_batch_to_target_range(const mc_ctx* ctx, uint8_t* sizes, uint8_t* vals, uint32_t nkeys, uint32_t targetBytes)
 {
-    const uint32_t lo = ctx->tgtLo, hi = ctx->tgtHi;
-    const uint32_t rmOver = ctx->cfg.remove_overpopulated, maxLocs = ctx->cfg.max_locations_per_feature;
-    const size_t vb = 4 + targetBytes;
-    const uint8_t* src = vals;
-    uint8_t* dst = vals;
-    uint64_t kept = 0;
-    for (uint32_t i = 0; i < nkeys; ++i) {
-        const uint32_t fileSize = sizes[i];
-        uint32_t eff = fileSize;
-        if (rmOver && eff > rmOver) eff = 0;
-        if (maxLocs && eff > maxLocs) eff = maxLocs;
-        uint32_t n = 0;
-        for (uint32_t j = 0; j < eff; ++j) {
-            const uint8_t* v = src + (size_t)j * vb;
-            uint32_t tgt = (uint32_t)v[4] | ((uint32_t)v[5] << 8);
-            if (targetBytes == 4) tgt |= ((uint32_t)v[6] << 16) | ((uint32_t)v[7] << 24);
-            if (tgt >= lo && tgt < hi) {
-                if (dst != v) std::memmove(dst, v, vb);
-                dst += vb; ++n;
-            }
-        }
-        src += (size_t)fileSize * vb;
-        sizes[i] = (uint8_t)n;
-        kept += n;
-    }
-    return kept;
+    return cut_batch_values(sizes, vals, nkeys, targetBytes, ctx->tgtLo, ctx->tgtHi, ctx->cfg.remove_overpopulated, ctx->cfg.max_locations_per_feature);
 }
 
 // The whole .cache file of a single-part context (between mc_load_begin and mc_load_end, which the caller issues).
@@ -210,18 +127,12 @@ int mcamd::load_file_pipelined(mc_ctx* ctx, const std::string& fname, uint32_t t
             pieceThere[e] = there;                             // (the bucket table is sized by the keys that have a piece here)
             if (e >= 2) { pieceEntries[e] = e * sh; piecePadded[e] = e * sh + 0.5 * kListAlign * there; }
         }
-    const uint32_t rmOver0 = ctx->cfg.remove_overpopulated, maxLocs0 = ctx->cfg.max_locations_per_feature;
     {
         // The places are a chain (a batch's sizes say where the next batch begins): this thread reads the sizes and sums them; what else
         // is wanted of them -- the padded total, Mode T's model sums -- are functions of the batch's HISTOGRAM of sizes, taken by helper
         // threads from a ring of buffers (one thread doing both: 0.36 s per 4 x 10^8 keys, 40 % of a 19 GB part's load)
-        uint32_t effOf[256];                                   // (the load-time modifiers that look at the size alone: table_build.hip effective_size)
-        for (uint32_t v = 0; v < 256; ++v) {
-            uint32_t e = v;
-            if (rmOver0 && e > rmOver0) e = 0;
-            if (maxLocs0 && e > maxLocs0) e = maxLocs0;
-            effOf[v] = e;
-        }
+        uint32_t effOf[256];                                   // (the load-time modifiers that look at the size alone)
+        for (uint32_t v = 0; v < 256; ++v) effOf[v] = size_after_rules(v, ctx->cfg.remove_overpopulated, ctx->cfg.max_locations_per_feature);
         const size_t expectBatches = (size_t)((nkeys + batch - 1) / std::max<uint64_t>(batch, 1));
         if (targetCut) model.assign(expectBatches, ModelSums{0, 0, 0});
         constexpr uint32_t kRing = 8;

@@ -3,7 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
-#include <cstdint>
+#include "table_rules.h"   // TableBucket, the probe sequence, the load-time rules
 
 namespace mcamd {
 
@@ -14,51 +14,6 @@ constexpr uint32_t kNoTail = 0xFFFFFFFFu; // qinfo[3] marker: single sequence, t
 constexpr uint32_t kMaxHitsPerQuery = (1u << 20) - 1;  // packed candidate fields are 20 bits wide
 constexpr uint32_t kGwGap = 1024;         // compact location store: unused window numbers between two targets (DeviceTable); window ranges up to this width
                                           // (reads up to 114 kbp at the default stride) stay on the kernels that work on the numbers as they are
-
-// Table layout: an array of 64-byte BUCKETS of 4 slots, two per 128-byte line, structure-of-arrays so
-// that a single LANE looks a feature up with four 16-byte loads of ONE half line and has key, size and
-// payload of the match in registers -- no second, dependent access (a separate payload load re-fetched
-// the line from L2 because thousands of lines are in flight per CU and the L1 holds 256):
-//   key[4]     the features
-//   size[4]    bucket sizes (u16), 0 = free slot
-//   payload[4] size == 1: the location itself ((tgt << 32) | win);
-//              size  > 1: index of the first location in DeviceTable::values
-// Probe sequence of a key: its home bucket, the sibling bucket in the same line, then the following
-// buckets linearly.  Insertion uses the first bucket of that sequence with a free slot, so a lookup
-// ends at the first bucket that holds the key or has a free slot.
-struct __attribute__((aligned(64))) TableBucket {
-    uint32_t key[4];
-    uint16_t size[4];
-    uint32_t spare[2];
-    uint64_t payload[4];
-};
-static_assert(sizeof(TableBucket) == 64, "two buckets per 128-byte line");
-constexpr uint32_t kSlotsPerBucket = 4;
-
-__host__ __device__ inline uint32_t next_bucket(uint32_t home, uint32_t cur, uint32_t step, uint32_t nbuckets)
-{
-    // step = number of buckets already visited (>= 1)
-    if (step == 1) return home ^ 1u;                          // sibling half of the same line
-    const uint32_t nx = (step == 2 ? (home | 1u) : cur) + 1u;
-    return nx >= nbuckets ? 0u : nx;
-}
-
-// Mode K: which key shard owns a feature (a different mix than the bucket hash, so a shard's keys spread over its whole table)
-__host__ __device__ inline uint32_t key_owner(uint32_t key, uint32_t shards);
-
-// table hash: features are the SMALLEST hash values of a window, i.e. far from uniform in their
-// high bits, so they are mixed again (murmur3 fmix32) before the multiply-shift range reduction
-// bucket = (mix32(key) * nbuckets) >> 32.
-__host__ __device__ inline uint32_t mix32(uint32_t x)
-{
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-
-__host__ __device__ inline uint32_t key_owner(uint32_t key, uint32_t shards)
-{
-    return shards <= 1 ? 0u : (uint32_t)(((uint64_t)mix32(key ^ 0x9E3779B9u) * shards) >> 32);
-}
 
 struct DeviceTable {
     const TableBucket* buckets; // [nbuckets], nbuckets even
@@ -241,14 +196,7 @@ void launch_sketch_lane(const BatchView& b, const SketchParams& sp, const Worksp
 // quadMode: -1 = by table size, 0 = lane-private bucket loads, 1 = quad-cooperative bucket loads
 void launch_probe_cands(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                         const uint32_t* taxkey, void* cands, int quadMode, hipStream_t st);
-// table_build.hip: GPU-side table construction from the file's batch stream
-struct LoadFilter { uint32_t maxLocs, rmOver, shardIdx, shardCnt, align = 1; };   // load-time modifiers + key shard + list alignment (below)
-// LIST ALIGNMENT (round 5, compact store): a list of the location store may begin at a multiple of kListAlign numbers = 128 bytes.  The
-// memory system serves random reads line by line (47 x 10^9 requests of 128 bytes per second, whatever part of the line is wanted:
-// profiles/r05_fetch_calibration.md): a list of 196 bytes at an arbitrary 4-byte offset touches 2.6 lines, an aligned one 2.0 -- the
-// filter kernels of read pairs and long reads run at that request rate.  Space a list takes in the store: list_alloc(size, align).
-constexpr uint32_t kListAlign = 32;
-__host__ __device__ inline uint32_t list_alloc(uint32_t size, uint32_t align) { return size > 1 ? (size + align - 1) / align * align : 0; }
+// table_build.hip: GPU-side table construction from the file's batch stream (LoadFilter, list_alloc: table_rules.h)
 struct GwLayout { const uint32_t* base = nullptr; uint32_t targets = 0, gap = 0; };   // compact store: gwBase[targets + 1] (DeviceTable)
 // the direct-address index of a finished bucket table (DeviceTable::direct): every stored key's entry; *flag != 0: a payload does not fit 48 bits
 void launch_direct_index(const TableBucket* buckets, uint32_t nbuckets, uint64_t* direct, unsigned int* flag, hipStream_t st);

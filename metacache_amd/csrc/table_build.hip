@@ -3,7 +3,7 @@
 // (gpu_hashmap.cu:1319-1362, batch layout hash_multimap.hpp:1037-1082).  The host only forwards the file's
 // batches; slot claiming, payload placement and the location-list copy run as three small kernels per batch:
 //   table_prep    : per key, the size after the load-time modifiers (host_hashmap.hpp:454-495)
-//   table_insert  : one lane per key walks the key's probe sequence (kernels.h next_bucket) and claims the first
+//   table_insert  : one lane per key walks the key's probe sequence (table_rules.h next_bucket) and claims the first
 //                   free slot with a 64-bit CAS on the bucket's four u16 sizes; key and payload are written after
 //   table_values  : one lane per FILE value: binary search for its key, decode {win, tgt} -> (tgt << 32) | win, or -> the global
 //                   window number gwBase[tgt] + win of the compact store (kernels.h DeviceTable)
@@ -15,15 +15,7 @@ namespace mcamd {
 
 namespace {
 
-__device__ __forceinline__ uint32_t effective_size(uint32_t key, uint32_t fileSize, const LoadFilter& lf)
-{
-    uint32_t size = fileSize;
-    if (lf.rmOver && size > lf.rmOver) size = 0;           // bucket emptied (host_hashmap.hpp:480-495)
-    if (lf.maxLocs && size > lf.maxLocs) size = lf.maxLocs; // keep the FIRST n values (:454-466)
-    if (lf.shardCnt > 1 && key_owner(key, lf.shardCnt) != lf.shardIdx) size = 0;   // Mode K: another GPU's key
-    return size;
-}
-
+// (the size after the load-time modifiers: effective_size, table_rules.h)
 __device__ __forceinline__ uint64_t decode_value(const uint8_t* p, uint32_t tb)
 {
     // packed {window_id win (u32); target_id tgt (u16|u32)}, unaligned
