@@ -19,7 +19,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmetacache_amd.so")
 SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "table_load.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip", "evaluate.hip", "format.hip", "table_info.hip"]
-HEADERS = ["kernels.h", "table_rules.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", "rows_common.h", os.path.join(ROOT, "include", "metacache_amd.h")]
+HEADERS = ["kernels.h", "table_rules.h", "read_class.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", "rows_common.h", os.path.join(ROOT, "include", "metacache_amd.h")]
 ARCH = "gfx950"
 BINDIR = os.path.join(PKG, "bin")
 MCQ = os.path.join(BINDIR, "mcq")
@@ -149,7 +149,7 @@ def build_kernel_harness(force: bool = False, verbose: bool = False) -> str:
     """tests/cpp/kernel_harness.hip -> libmckharness.so: drives the sorted path's launchers (csrc/kernels.h) with inputs a test chooses
     (test infrastructure, tests/kernel_harness.py; links the product library, adds nothing to it)"""
     src = os.path.join(ROOT, "tests", "cpp", "kernel_harness.hip")
-    if force or _stale(HARNESS_LIB, [src, LIB, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "device_common.h")]):
+    if force or _stale(HARNESS_LIB, [src, LIB, os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "read_class.h"), os.path.join(CSRC, "device_common.h")]):
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O2", "-std=c++17", "-fPIC", "-shared", "-x", "hip", "-I", os.path.join(ROOT, "include"),
                "-I", CSRC, "-Wno-unused-result", src, "-o", HARNESS_LIB, "-L", LIBDIR, "-lmetacache_amd", "-Wl,-rpath,$ORIGIN"]
         if verbose:

@@ -1,5 +1,5 @@
 // metacache_amd/csrc/device_common.h -- what the kernel files (kernels.hip, gw_kernels.hip) share on the device side: per-query state
-// flags, wave64 primitives, the candidate record and the limits of the work-list classes.  Internal.
+// flags, wave64 primitives (the work lists' wave_append among them), the bucket lookup and the candidate record.  Internal.
 #pragma once
 
 #include "kernels.h"
@@ -94,6 +94,27 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v)
 }
 
 
+__device__ __forceinline__ uint4 as_uint4(WorkRecord r) { return make_uint4(r.query, r.first, r.packed, r.maxWin); }   // as the lists hold it
+// The lanes with `take` append their record to a work list: ONE atomic per wave reserves their places behind *counter (one per read --
+// 10^5 on one counter in a batch of long reads -- took 2.5 ms), the lanes fill them in lane order.  Callable under divergence: the
+// lanes that are there form the wave.
+__device__ __forceinline__ void wave_append(uint32_t* counter, uint4* list, bool take, WorkRecord r)
+{
+    const uint64_t mask = __ballot(take);
+    if (!take) return;
+    const uint32_t lane = lane_id(), leader = (uint32_t)__ffsll((unsigned long long)mask) - 1;
+    uint32_t base = 0;
+    if (lane == leader) base = atomicAdd(counter, (uint32_t)__popcll(mask));
+    base = __shfl(base, leader);
+    list[base + __popcll(mask & ((1ull << lane) - 1ull))] = as_uint4(r);
+}
+// *counter += the wave's lanes with `pred`, by one of them
+__device__ __forceinline__ void wave_count(uint32_t* counter, bool pred)
+{
+    const uint64_t mask = __ballot(pred);
+    if (mask && lane_id() == (uint32_t)__ffsll((unsigned long long)mask) - 1) atomicAdd(counter, (uint32_t)__popcll(mask));
+}
+
 __device__ __forceinline__ uint32_t home_group(uint32_t key, uint32_t nbuckets)
 {
     return (uint32_t)(((uint64_t)mix32(key) * nbuckets) >> 32);
@@ -111,6 +132,23 @@ __device__ __forceinline__ BucketRegs load_bucket(const DeviceTable& tab, uint32
     const uint4* p = reinterpret_cast<const uint4*>(tab.buckets + bi);
     BucketRegs r; r.k = p[0]; r.sz = p[1]; r.p0 = p[2]; r.p1 = p[3];
     return r;
+}
+// Feature f against the bucket's four slots: size and pay are set where a used slot holds it (else left as they are).  Returns whether
+// the bucket has a free slot: a lookup ends at the first bucket that holds the key or has one (insertion fills the first with room).
+__device__ __forceinline__ bool bucket_match(const BucketRegs& r, uint32_t f, uint32_t& size, uint64_t& pay)
+{
+    const uint32_t keys[4] = {r.k.x, r.k.y, r.k.z, r.k.w};
+    const uint32_t s01 = r.sz.x, s23 = r.sz.y;
+    const uint32_t sz[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
+    const uint64_t pl[4] = {((uint64_t)r.p0.y << 32) | r.p0.x, ((uint64_t)r.p0.w << 32) | r.p0.z,
+                            ((uint64_t)r.p1.y << 32) | r.p1.x, ((uint64_t)r.p1.w << 32) | r.p1.z};
+    bool anyFree = false;
+#pragma unroll
+    for (uint32_t i = 0; i < 4; ++i) {
+        anyFree = anyFree || sz[i] == 0;
+        if (sz[i] != 0 && keys[i] == f) { size = sz[i]; pay = pl[i]; }
+    }
+    return anyFree;
 }
 // Quad-cooperative bucket fetch.  A lane that loads its own 64-byte bucket with four 16-byte loads touches 64 different lines per
 // load instruction; on tables far larger than the infinity cache every one of these accesses pays the full price (measured,
@@ -162,13 +200,13 @@ __device__ __forceinline__ BucketRegs quad_collect(const QuadRaw& raw)
 }
 
 
+// hand-over entries (ws.psize): size | the list's start offset among the read's locations << 16 -- a field of 12 bits of its own, not the
+// work-list record's: the offsets matter up to kHashMax only
+constexpr uint32_t kEntOffMask = 0xFFFu;
+
 struct mc_candidate_dev { uint32_t tgt, hits, beg, end; };
 
-constexpr uint32_t kLaneK = 4;            // most candidates handled by one lane
-constexpr uint32_t kMidMax = 256;         // longest list taken by mid_cands_kernel
-constexpr uint32_t kHashMax = 1024, kHashEnt = 256, kHashWin = 8;   // hash_cands_kernel: longest list, entries, maxWindowsInRange
-constexpr uint32_t kBigEnt = 64;          // big_filter_kernel: found features per query, one lane each ...
-constexpr uint32_t kBigEPL = 3;           // ... or up to three per lane in its second instance (reads and pairs of 5 .. 10 windows: 2 x 250 bp, 500 bp)
+constexpr uint32_t kLaneK = 4;            // most candidates handled by one lane (the consumers' limits: read_class.h)
 
 struct LaneCand { uint32_t tgt, hits, beg, end; };
 
@@ -221,7 +259,6 @@ __device__ __forceinline__ void top_insert(LaneCand (&top)[kLaneK], uint32_t (&t
 
 // big_filter_kernel / gw_filter_kernel -> counting kernels: longest filtered list the counting kernels take
 constexpr uint32_t kBigMaxFilteredCount = 1024;
-constexpr uint32_t kGwSmallH = 2048;      // compact store: reads with more locations take gw_filter_kernel's instance with the larger filters
 
 constexpr uint32_t kGwMaxKept = kMaxHitsPerQuery;   // longest filtered list handed on (gw_filter kernels)
 // a filtered list (n2 numbers, window range maxWin) that is sorted instead of counted

@@ -384,14 +384,14 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_kernel(BatchView b,
     uint4 rec = load_rec(w0), recNext = load_rec(w0 + nWaves);
     uint32_t esz = 0; uint64_t epay = 0;                           // the read's entries, fetched one read ahead
     auto load_entries = [&](const uint4& r) {
-        const uint32_t ne = (r.z >> 12) <= kGwSmallH ? min(r.z & 0xFFFu, 64u) : 0u;
+        const uint32_t ne = rec_hits(r.z) <= kGwSmallH ? min(rec_entries(r.z), 64u) : 0u;
         esz = lane < ne ? ws.psize[r.y + lane] : 0u;
         epay = lane < ne ? ws.ppay[r.y + lane] : 0ull;
     };
     load_entries(rec);
     const uint32_t grp = lane >> 2, sub4 = (lane & 3u) * 4u;
     for (uint32_t w = w0; w < total; w += nWaves) {
-        const uint32_t q = rec.x, nent = rec.z & 0xFFFu, H = rec.z >> 12, maxWin = rec.w;
+        const uint32_t q = rec.x, nent = rec_entries(rec.z), H = rec_hits(rec.z), maxWin = rec.w;
         const uint32_t sz = esz & 0xFFFFu; const uint64_t pay = epay;
         rec = recNext;                                             // the next read's record and entries are on their way meanwhile
         recNext = load_rec(w + 2 * nWaves);
@@ -476,14 +476,14 @@ __global__ __launch_bounds__(WAVES * 64, T2LOG2 == TLOG2 ? MC_GW_FILTER_WPE : 6)
       const bool inb = chunk + lane < total;
       const uint4 myRec = inb ? work[chunk + lane] : make_uint4(0, 0, 0, 0);
       const uint32_t myZ = inb ? outRec[chunk + lane].z : 0u;
-      uint64_t todo = __ballot(inb && myZ == kGwDefer && (myRec.z >> 12) <= kMaxH && (myRec.z & 0xFFFu) <= 64u && myRec.w <= tab.gwGap);
-      if (todo) { const uint32_t j = (uint32_t)__ffsll((unsigned long long)todo) - 1; load_entries(rdlane(myRec.y, j), rdlane(myRec.z, j) & 0xFFFu); }
+      uint64_t todo = __ballot(inb && myZ == kGwDefer && rec_hits(myRec.z) <= kMaxH && rec_entries(myRec.z) <= 64u && myRec.w <= tab.gwGap);
+      if (todo) { const uint32_t j = (uint32_t)__ffsll((unsigned long long)todo) - 1; load_entries(rdlane(myRec.y, j), rec_entries(rdlane(myRec.z, j))); }
       while (todo) {
         const uint32_t j = (uint32_t)__ffsll((unsigned long long)todo) - 1;
         todo &= todo - 1;
-        const uint32_t w = chunk + j, q = rdlane(myRec.x, j), H = rdlane(myRec.z, j) >> 12, maxWin = rdlane(myRec.w, j);
+        const uint32_t w = chunk + j, q = rdlane(myRec.x, j), H = rec_hits(rdlane(myRec.z, j)), maxWin = rdlane(myRec.w, j);
         const uint32_t sz = esz & 0xFFFFu; const uint64_t pay = epay;
-        if (todo) { const uint32_t jn = (uint32_t)__ffsll((unsigned long long)todo) - 1; load_entries(rdlane(myRec.y, jn), rdlane(myRec.z, jn) & 0xFFFu); }
+        if (todo) { const uint32_t jn = (uint32_t)__ffsll((unsigned long long)todo) - 1; load_entries(rdlane(myRec.y, jn), rec_entries(rdlane(myRec.z, jn))); }
         const uint32_t myR = sz > 1 ? (sz + 15u) >> 4 : 0u;
         const uint32_t incl = wave_incl_scan_u32(myR, lane), Rc = rdlane(incl, 63), start = incl - myR;
         if (Rc > kMaxRounds || sliceCap - sliceUsed < kMaxRounds * 16u + 64u) continue;   // stays deferred: gw_filter_stream_kernel
@@ -640,7 +640,7 @@ __global__ __launch_bounds__(WAVES * 64) void gw_filter_stream_kernel(BatchView 
         const uint32_t w = side[i];
         const uint4 rec = work[w];
         const uint32_t q = rec.x, fbase = rec.y, recZ = rec.z, maxWin = rec.w;
-        const uint32_t nent = recZ & 0xFFFu, H = recZ >> 12;
+        const uint32_t nent = rec_entries(recZ), H = rec_hits(recZ);
         if (H <= hMin || H > hMax) continue;                       // (block-uniform) the other instance's read
         {
             uint4* z4 = reinterpret_cast<uint4*>(bits);
@@ -914,7 +914,7 @@ __device__ __forceinline__ void lk_store_entries(const Workspace& ws, const uint
     if (sz != 0u) {
         const uint32_t slot = sz == 1u ? sbelow : n1 + (below - sbelow);
         const uint32_t off = sz == 1u ? slot : n1 + lincl - lsz;
-        ws.psize[fbase + slot] = sz | ((off & 0xFFFu) << 16);
+        ws.psize[fbase + slot] = sz | ((off & kEntOffMask) << 16);
         ws.ppay[fbase + slot] = pay;
     } else if (lane < nf) ws.psize[fbase + nent + (lane - below)] = 0u;
 }
@@ -941,7 +941,7 @@ __device__ __forceinline__ void lk_load_entries(const Workspace& ws, const Devic
 // GwEntRecord: the lookup kernels wrote the entries, the read's record of kListFilter says where.
 struct GwEntRecord {
     const uint4* rec;
-    __device__ __forceinline__ uint2 where() const { const uint4 r6 = *rec; return make_uint2(r6.y, r6.z & 0xFFFu); }
+    __device__ __forceinline__ uint2 where() const { const uint4 r6 = *rec; return make_uint2(r6.y, rec_entries(r6.z)); }
     __device__ __forceinline__ void load(const Workspace& ws, const DeviceTable&, uint32_t, uint32_t fbase, uint32_t nent, uint32_t lane, uint32_t& sz, uint64_t& pay) const
     {
         sz = lane < nent ? (ws.psize[fbase + lane] & 0xFFFFu) : 0u;
@@ -1311,7 +1311,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
     uint32_t esz = 0; uint64_t epay = 0;
     auto load_entries = [&](const uint4& r) {
         if constexpr (LOOKUP) return;
-        const uint32_t ne = (r.z >> 12) <= kGwSmallH ? min(r.z & 0xFFFu, 64u) : 0u;
+        const uint32_t ne = rec_hits(r.z) <= kGwSmallH ? min(rec_entries(r.z), 64u) : 0u;
         esz = lane < ne ? ws.psize[r.y + lane] : 0u;
         epay = lane < ne ? ws.ppay[r.y + lane] : 0ull;
     };
@@ -1366,7 +1366,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         uint32_t q, nent, H, maxWin, sz, fbase = 0, nfs = 0; uint64_t pay;
         uint32_t rix = 0xFFFFFFFFu;                                // LOOKUP: the read's record in kListFilter, made when something is left to the later kernels
         if constexpr (!LOOKUP) {
-            q = rec.x; nent = rec.z & 0xFFFu; H = rec.z >> 12; maxWin = rec.w;
+            q = rec.x; nent = rec_entries(rec.z); H = rec_hits(rec.z); maxWin = rec.w;
             sz = esz & 0xFFFFu; pay = epay;
             rec = recNext;
             recNext = load_rec(w + 2 * nWaves);
@@ -1386,24 +1386,21 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             const uint32_t n1 = (uint32_t)__popcll(sm), lsz = sz > 1u ? sz : 0u;
             const uint32_t lincl = wave_incl_scan_u32(lsz, lane);
             H = n1 + rdlane(lincl, 63);
-            maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+            maxWin = b.max_win(q);
             if (lane == 0) { QueryStat qs; qs.hits = H; qs.nfeat = nfeat; qs.nfound = nent; qs.nsteps = nfeat; ws.qstat[q] = qs; }
             if (H == 0) {                                          // nothing found: empty candidates, as the lane kernel leaves them
                 if (lane < K) { mc_candidate_dev ev; ev.tgt = 0xFFFFFFFFu; ev.hits = 0; ev.beg = 0; ev.end = 0; cands[(size_t)q * K + lane] = ev; }
                 if (lane == 0) { ws.hitScan[q] = 0u; ws.qflag[q] = kFlagDone; }
                 continue;
             }
-            // the read's class (probe_cands_one); lists up to kLaneHits, which a lane of the lookup kernel finishes itself, are mid_cands_kernel<4>'s
-            const bool hashOK = nent <= kHashEnt && maxWin <= kHashWin;
-            const bool bigOK = H > ws.bigMin && H > 64u && nent <= 0xFFFu && maxWin <= tab.gwGap && H <= kMaxHitsPerQuery;
-            const uint32_t cls = bigOK ? kClassFilter : H <= 64 ? kListMid64 : H <= 128 ? (hashOK ? kListHash256 : kListMid128) : H <= kMidMax ? (hashOK ? kListHash256 : kListMid256)
-                               : (H <= kHashMax && hashOK) ? (H <= kHashMax / 2 ? kListHash512 : kListHash1024) : kClassWave;
-            if (lane == 0) {
-                ws.hitScan[q] = (H <= kMaxHitsPerQuery && H > kLdsCap && !(cls >= kListHash512 && cls != kClassWave)) ? H : 0u;
+            // the read's class (read_class.h); lists up to kLaneHits, which a lane of the lookup kernel finishes itself, are mid_cands_kernel<4>'s
+            const uint32_t cls = read_class(H, nent, maxWin, ClassLimits{ws.bigMin, tab.gwGap, true});
+            if (lane == 0) {                                       // (one read per wave: wave_append's one atomic per wave is this)
+                ws.hitScan[q] = segment_hits(H, cls);
                 ws.qflag[q] = cls != kClassWave ? kFlagMid : kFlagCands;
                 if (cls != kClassWave && cls != kClassFilter) {
                     const uint32_t at = atomicAdd(&ws.midCount[class_counter(cls)], 1u);
-                    ws.midList[list_at(class_list(cls), b.n) + at] = make_uint4(q, fbase, nent | (H << 12), maxWin);
+                    ws.midList[list_at(class_list(cls), b.n) + at] = as_uint4(work_record(q, fbase, nent, H, maxWin));
                 }
             }
             // the hand-over entries: for the reads that go to another kernel -- here the other classes', below the few of this class that
@@ -1417,7 +1414,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             else {
                 if (rix == 0xFFFFFFFFu) {
                     uint32_t at = 0;
-                    if (lane == 0) { at = atomicAdd(&ws.midCount[kCntFilter], 1u); work[at] = make_uint4(q, fbase, nent | (H << 12), maxWin); }
+                    if (lane == 0) { at = atomicAdd(&ws.midCount[kCntFilter], 1u); work[at] = as_uint4(work_record(q, fbase, nent, H, maxWin)); }
                     rix = rdlane(at, 0);
                 }
                 return rix;

@@ -271,7 +271,7 @@ __device__ __forceinline__ uint32_t order_key(const Workspace& ws, uint32_t n, u
     const uint32_t len = ws.midCount[list == kSideSorted ? kCntSorted : kCntStream];
     if (i >= len) return 0u;
     const uint32_t w = ws.sideList[list_at(list, n) + i];
-    return list == kSideSorted ? (ws.midList + list_at(kListFiltered, n))[w].z : (ws.midList + list_at(kListFilter, n))[w].z >> 12;
+    return list == kSideSorted ? (ws.midList + list_at(kListFiltered, n))[w].z : rec_hits((ws.midList + list_at(kListFilter, n))[w].z);
 }
 __global__ __launch_bounds__(256) void order_hist_kernel(Workspace ws, uint32_t n, uint32_t list, uint32_t count, uint32_t* __restrict__ hist)
 {

@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include "table_rules.h"   // TableBucket, the probe sequence, the load-time rules
+#include "read_class.h"    // the work lists' names, the rule that sorts a read into its class, the work-list record
 
 namespace mcamd {
 
@@ -11,7 +12,6 @@ constexpr uint32_t kWave = 64;
 constexpr uint32_t kMaxSketch = 32;       // MC_MAX_SKETCH
 constexpr uint32_t kMaxWinLen = 1024;     // MC_MAX_WINLEN
 constexpr uint32_t kNoTail = 0xFFFFFFFFu; // qinfo[3] marker: single sequence, tail window suppressed
-constexpr uint32_t kMaxHitsPerQuery = (1u << 20) - 1;  // packed candidate fields are 20 bits wide
 constexpr uint32_t kGwGap = 1024;         // compact location store: unused window numbers between two targets (DeviceTable); window ranges up to this width
                                           // (reads up to 114 kbp at the default stride) stay on the kernels that work on the numbers as they are
 
@@ -90,6 +90,7 @@ struct BatchView {           // device pointers describing one batch
     const uint32_t* maxWin;  // [n] or nullptr
     uint32_t maxWinUniform;
     uint32_t n;
+    __host__ __device__ __forceinline__ uint32_t max_win(uint32_t q) const { return maxWin ? maxWin[q] : maxWinUniform; }   // maxWindowsInRange of read q
 };
 
 struct Workspace {           // device buffers sized by the host for this batch
@@ -114,7 +115,7 @@ struct Workspace {           // device buffers sized by the host for this batch
     size_t    orderTemp;
     uint32_t  bigPoolCap;
     uint32_t  bigOvfCap;     // compact store: entries behind bigPoolCap for filtered lists that may not fit their wave's slice (cursor: kCntOverflow)
-    uint4*    midList;       // [kWorkLists][n] {query, first entry slot, entries | locations << 12, maxWindowsInRange} (lists: kList* below)
+    uint4*    midList;       // [kWorkLists][n] work-list records (work_record, read_class.h; the lists: table below)
     uint32_t* hitScan;       // [n]        hits that need a segment in 'hits' (all, or only lists too long for LDS)
     uint64_t* hitOff;        // [n+1]      exclusive scan of hitScan
     uint64_t* hits;          // [H]        gathered + sorted locations
@@ -130,9 +131,11 @@ struct Workspace {           // device buffers sized by the host for this batch
 };
 
 // ---- the lane path's work lists: who hands which reads to whom ------------------------------------------------------------------------
-// The probing kernels sort every read into a CLASS: classes 0 .. 5 are the midList lists of the same number, kClassWave the wave kernels
+// The probing kernels sort every read into a CLASS (read_class, read_class.h): classes 0 .. 5 are the midList lists of the same number, kClassWave the wave kernels
 // (no list), kClassFilter the filtered path (list kListFilter).  A list's length is a counter slot of ws.midCount; the host copies the
 // first kHostCounters slots (launch_flag_count_host) and launches only the kernels with work.  "8-byte" / "compact": the location stores.
+// Lists are appended to with one atomic per wave (wave_append, device_common.h).  probe_cands_one: and gw_filter_count_kernel<LOOKUP>
+// ("filter_lookup"), which stands in for it for the reads it looks up itself.
 //   slot  name            holds                                               written by                         read by
 //   0-2   kCntMid*        lengths of kListMid64 / 128 / 256                   probe_cands_one                    mid_cands_kernel, host
 //   3-4   kCntHash512/1024 lengths of kListHash512 / 1024                    probe_cands_one                    hash_cands_kernel<10/11>, host
@@ -151,16 +154,10 @@ struct Workspace {           // device buffers sized by the host for this batch
 //   14-15 kCnt512/1024    lengths of kSide512 / kSide1024                     gw_compact_kernel (stage 1)        gw_count_kernel<10> / <11>
 //   16-17 kCntOverflow    u64 cursor of the pool's overflow region            gw_filter_stream_kernel
 //   18    kCntSortedBig   sorted lists left to the 16-wave instance           gw_sorted_cands_kernel<BIG=false>  gw_sorted_cands_kernel<BIG=true>
-constexpr uint32_t kCntMid64 = 0, kCntMid128 = 1, kCntMid256 = 2, kCntHash512 = 3, kCntHash1024 = 4, kCntChunks = 5, kCntWaveSketch = 6,
-                   kCntWaveCands = 7, kCntHash256 = 8, kCntFilter = 9, kCntSecond = 10, kCntStream = 12, kCntSorted = 13, kCnt512 = 14,
-                   kCnt1024 = 15, kCntOverflow = 16, kCntSortedBig = 18;
+// (the kCnt* / kList* / kClass* names and class_counter / class_list: read_class.h)
 constexpr uint32_t kCounterWords = 32, kCounterBytes = kCounterWords * 4, kHostCounters = 16;   // midList = midCount + kCounterWords
-// midList: records {query, first entry slot, entries | locations << 12, maxWindowsInRange}; kListFiltered holds, at the place of the
+// midList: records work_record(query, first entry slot, entries, locations, maxWindowsInRange); kListFiltered holds, at the place of the
 // read's kListFilter record, what the filter kept {query, pool offset, kept numbers (or kGwDefer / kGwFallback), maxWindowsInRange}
-enum WorkList : uint32_t { kListMid64, kListMid128, kListMid256, kListHash512, kListHash1024, kListHash256, kListFilter, kListFiltered, kWorkLists };
-constexpr uint32_t kClassWave = 6, kClassFilter = 7;
-__host__ __device__ __forceinline__ constexpr uint32_t class_counter(uint32_t c) { return c < 5 ? c : c == 5 ? kCntHash256 : kCntFilter; }
-__host__ __device__ __forceinline__ constexpr uint32_t class_list(uint32_t c) { return c == kClassFilter ? kListFilter : c; }
 // sideList (compact store): record numbers of kListFilter / kListFiltered for the kernels that take few of them, made by gw_compact_kernel
 enum SideRow : uint32_t { kSideStream, kSide512, kSide1024, kSideSorted, kSideRows };   // the stream filter's reads, 257 .. 512 / 513 .. 1024 kept, the sorted class
 __host__ __device__ __forceinline__ constexpr uint32_t side_counter(uint32_t r) { return r == kSideStream ? kCntStream : r == kSide512 ? kCnt512 : r == kSide1024 ? kCnt1024 : kCntSorted; }
@@ -270,7 +267,6 @@ void launch_decode_union(const BatchView& b, const DeviceTable& tab, const Works
                          const KeyshardBases& bases, uint32_t S, hipStream_t st);
 bool lane_path_supported(const SketchParams& sp);
 bool lane_candidates_supported(uint32_t maxCand);
-constexpr uint32_t kLdsCap = 256;         // location lists up to this length are sorted in LDS
 void launch_sort_candidates(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws,
                             const uint32_t* taxkey, uint32_t maxCand, bool wantAllhits,
                             void* cands, hipStream_t st);

@@ -288,17 +288,7 @@ __device__ __forceinline__ void probe_finish(const DeviceTable& tab, uint32_t f,
     uint32_t cur = home;
     for (uint32_t step = 1;; ++step) {
         ++steps;
-        const uint32_t keys[4] = {r.k.x, r.k.y, r.k.z, r.k.w};
-        const uint32_t s01 = r.sz.x, s23 = r.sz.y;
-        const uint32_t sz[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
-        const uint64_t pl[4] = {((uint64_t)r.p0.y << 32) | r.p0.x, ((uint64_t)r.p0.w << 32) | r.p0.z,
-                                ((uint64_t)r.p1.y << 32) | r.p1.x, ((uint64_t)r.p1.w << 32) | r.p1.z};
-        bool anyFree = false;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-            anyFree = anyFree || sz[i] == 0;
-            if (sz[i] != 0 && keys[i] == f) { size = sz[i]; pay = pl[i]; }
-        }
+        const bool anyFree = bucket_match(r, f, size, pay);
         // found, or a bucket with a free slot ends the chain (insertion fills the first bucket with room)
         if (size != 0 || anyFree || step >= tab.maxProbe) return;
         cur = next_bucket(home, cur, step, tab.nbuckets);
@@ -573,7 +563,7 @@ __device__ __forceinline__ void sort_candidates_one(
     const uint32_t H = ws.qstat[q].hits;
     if (H == 0 || H > kMaxHitsPerQuery) { emit_empty(out, 0, K, lane); return; }
 
-    const uint32_t maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+    const uint32_t maxWin = b.max_win(q);
     const uint64_t hoff = ws.hitOff[q];
     const uint32_t fbeg = ws.winOff[q] * sp.s;
     const uint32_t nf = (ws.winOff[q + 1] - ws.winOff[q]) * sp.s;
@@ -629,7 +619,7 @@ __global__ __launch_bounds__(256) void cands_from_hits_kernel(BatchView b, Devic
     if (lane == 0) { QueryStat qs; qs.hits = (uint32_t)min(H64, (uint64_t)0xFFFFFFFFu); qs.nfeat = 0; qs.nfound = 0; qs.nsteps = 0; ws.qstat[q] = qs; }
     if (H64 == 0 || H64 > kMaxHitsPerQuery) { emit_empty(out, 0, K, lane); return; }
     const uint32_t H = (uint32_t)H64;
-    const uint32_t maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+    const uint32_t maxWin = b.max_win(q);
     if (H <= kLdsCap) {
         for (uint32_t i = lane; i < H; i += 64) L.buf[i] = ws.hits[hoff + i];
         wave_lds_sync();
@@ -683,13 +673,14 @@ __global__ __launch_bounds__(256) void union_copy_kernel(const uint32_t* __restr
 __global__ __launch_bounds__(256) void owner_classify_kernel(BatchView b, Workspace ws, uint32_t minLen)
 {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
     bool big = false;
     uint32_t H = 0, mw = 0;
     if (q < b.n) {
         const uint64_t H64 = ws.hitOff[q + 1] - ws.hitOff[q];
-        mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-        big = H64 > minLen && H64 <= 0xFFFFull && mw <= 8u;          // (8 = kHashWin, the widest window range the counting kernel takes)
+        mw = b.max_win(q);
+        // this site's own rule: the caller's minLen for ws.bigMin, one entry that is one list (a size of 16 bits), and of filter_takes
+        // (8-byte store) the widest window range the counting kernel takes
+        big = H64 > minLen && H64 <= 0xFFFFull && mw <= kHashWin;
         H = (uint32_t)min(H64, (uint64_t)0xFFFFFFFFu);
         ws.winOff[q] = q;
         if (q + 1 == b.n) ws.winOff[b.n] = b.n;
@@ -700,14 +691,7 @@ __global__ __launch_bounds__(256) void owner_classify_kernel(BatchView b, Worksp
             ws.qstat[q] = qs;
         }
     }
-    const uint64_t mask = __ballot(big);
-    if (big) {
-        const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(mask));
-        base = __shfl(base, leader);
-        ws.midList[list_at(kListFilter, b.n) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q, 1u | (H << 12), mw);
-    }
+    wave_append(&ws.midCount[kCntFilter], ws.midList + list_at(kListFilter, b.n), big, work_record(q, q, 1u, H, mw));
 }
 void launch_owner_classify(const BatchView& b, const Workspace& ws, uint32_t minLen, hipStream_t st)
 {
@@ -992,7 +976,7 @@ __device__ __forceinline__ void query_one(const BatchView& b, const SketchParams
     bool done = false;
     if (FUSE && single) {
         if (H <= kFuseCap) {
-            const uint32_t maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+            const uint32_t maxWin = b.max_win(q);
             fused_candidates(L, rsize, rpay, tab, H, maxWin, K, cands + (size_t)q * K, lane);
             done = true;
         } else if (lane < gslot * s) {                       // too many hits for the register path: hand over
@@ -1062,15 +1046,18 @@ void launch_query(const BatchView& b, const SketchParams& sp, const DeviceTable&
 // Lane-parallel fast path for short reads (the common case: 100-300 bp reads, small hit lists).
 //
 // Wave-per-query kernels spend most of their instructions on cross-lane bookkeeping that serves ONE
-// query.  Short reads are better served by giving every lane its own query for the irregular parts and
-// keeping only the memory-bound part cooperative:
-//   sketch_lane_kernel     one lane per query : rolling canonical k-mers straight from the characters,
-//                                                16-entry min/max insertion chain = the sketch
-//   probe_flat_kernel      8 lanes per feature: one 128-byte bucket group per load, several in flight
-//   candidates_lane_kernel one lane per query : the CPU algorithm verbatim on <= 32 locations
-// Queries that do not qualify (long reads, windows that do not partition the k-mers, duplicate
-// hashes inside a sketch, long hit lists, taxon merging, -allhits, K > 4) keep qflag != 0 and are
-// finished by the wave-per-query kernels (query_kernel / sort_candidates_kernel), which skip the rest.
+// query.  Short reads are better served by giving every lane its own query:
+//   sketch_lane_kernel       one lane per query: rolling canonical k-mers straight from the characters, the s smallest
+//                            hashes of a window kept in 16 registers (lane_sketch) = the sketch
+//   probe_cands_kernel       one lane per query: its features' lookups, several in flight (lane-private or quad-cooperative
+//                            bucket loads, or the direct-address index), then the CPU algorithm verbatim on <= kLaneHits locations
+//   sketch_probe_lane_kernel both in one launch
+//   chunk_sketch / chunk_probe / chunk_finish_kernel   long single reads, cut into chunks of kChunkWins windows: one lane per chunk
+// A read with more locations than a lane takes is sorted into a class (read_class.h) and handed over: to mid_cands_kernel,
+// hash_cands_kernel or the filtered path through their work lists (table: kernels.h).  Whatever does not qualify (sketching
+// parameters that lane_path_supported rejects, K > kLaneK, a mate beyond kLaneMaxLen in a pair, duplicate hashes inside a sketch,
+// the class kClassWave) keeps qflag != 0 and is finished by the wave-per-query kernels (query_kernel / sort_candidates_kernel),
+// which skip the rest.
 // ================================================================================================
 constexpr uint32_t kLaneMaxLen = 512;     // longest mate handled by one lane
 constexpr uint32_t kLaneS = 16;           // sketch entries held in registers
@@ -1256,11 +1243,19 @@ __device__ __forceinline__ void lane_sketch_span16(const uint8_t* __restrict__ s
     if (wpos > 0) { if (pending) flush(); emit(); }                     // tail window
 }
 
+// the window sketches of one span of characters: the batched form where k and the stride allow it
+__device__ __forceinline__ void lane_sketch(const uint8_t* __restrict__ seq, const uint64_t off, const uint32_t len, const SketchParams& sp,
+                                            uint32_t* out0, uint32_t& wcount, bool& dup)
+{
+    if (sp.k == 16 && (sp.stride & 15u) == 0) lane_sketch_span16(seq, off, len, sp.s, sp.stride, out0, wcount, dup);
+    else lane_sketch_span(seq, off, len, sp.k, sp.s, sp.stride, out0, wcount, dup);
+}
+
 __device__ __forceinline__ uint32_t sketch_lane_one(const BatchView& b, const SketchParams& sp, const uint32_t* __restrict__ winOff,
                                                     uint32_t* features, const uint32_t q)
 {
     const uint4 qi = reinterpret_cast<const uint4*>(b.qinfo)[q];
-    const uint32_t k = sp.k, s = sp.s, stride = sp.stride;
+    const uint32_t s = sp.s;
     const bool noTail = qi.w == kNoTail;
     const uint32_t widx0 = winOff[q];
     if (noTail || qi.y > kLaneMaxLen || qi.w > kLaneMaxLen) {
@@ -1273,9 +1268,8 @@ __device__ __forceinline__ uint32_t sketch_lane_one(const BatchView& b, const Sk
     for (uint32_t mate = 0; mate < 2; ++mate) {
         const uint32_t off = mate ? qi.z : qi.x;
         const uint32_t len = mate ? qi.w : qi.y;
-        if (len < k) continue;
-        if (k == 16 && (stride & 15u) == 0) lane_sketch_span16(b.seq, off, len, s, stride, features + (size_t)widx0 * s, wcount, dup);
-        else lane_sketch_span(b.seq, off, len, k, s, stride, features + (size_t)widx0 * s, wcount, dup);
+        if (len < sp.k) continue;
+        lane_sketch(b.seq, off, len, sp, features + (size_t)widx0 * s, wcount, dup);
     }
     return dup ? kFlagSketch : kFlagProbe;
 }
@@ -1347,8 +1341,7 @@ __global__ __launch_bounds__(128) void chunk_sketch_kernel(BatchView b, SketchPa
             uint4* z = reinterpret_cast<uint4*>(ws.psize + (size_t)w0 * sp.s);
             for (uint32_t i = 0; i < (w1 - w0) * sp.s / 4; ++i) z[i] = make_uint4(0, 0, 0, 0);
         } else for (uint32_t i = w0 * sp.s; i < w1 * sp.s; ++i) ws.psize[i] = 0u;
-        if (sp.k == 16 && (sp.stride & 15u) == 0) lane_sketch_span16(b.seq, (uint64_t)qi.x + p0, len, sp.s, sp.stride, ws.features + (size_t)w0 * sp.s, wcount, dup);
-        else lane_sketch_span(b.seq, (uint64_t)qi.x + p0, len, sp.k, sp.s, sp.stride, ws.features + (size_t)w0 * sp.s, wcount, dup);
+        lane_sketch(b.seq, (uint64_t)qi.x + p0, len, sp, ws.features + (size_t)w0 * sp.s, wcount, dup);
         if (dup) ws.qflag[q] = kFlagSketch;                                         // the wave kernel redoes the whole read
     }
 }
@@ -1373,8 +1366,7 @@ __global__ __launch_bounds__(256) void build_sketch_lanes_kernel(BatchView b, Sk
         const uint32_t len = lane == 63u ? qi.y - p0 : min(qi.y - p0, kBuildLaneWins * sp.stride + sp.k - 1);
         uint32_t wcount = 0;
         uint32_t* out = ws.features + (size_t)(w0 + first) * sp.s;
-        if (sp.k == 16 && (sp.stride & 15u) == 0) lane_sketch_span16(b.seq, (uint64_t)qi.x + p0, len, sp.s, sp.stride, out, wcount, dup);
-        else lane_sketch_span(b.seq, (uint64_t)qi.x + p0, len, sp.k, sp.s, sp.stride, out, wcount, dup);
+        lane_sketch(b.seq, (uint64_t)qi.x + p0, len, sp, out, wcount, dup);
     }
     const bool any = __ballot(dup) != 0;
     if (lane == 0) ws.qflag[q] = any ? kFlagSketch : kFlagDone;
@@ -1424,18 +1416,8 @@ __global__ __launch_bounds__(128) void chunk_probe_kernel(BatchView b, uint32_t 
                 if constexpr (QUAD) r = quad_collect(raw[u]);
                 else { r.k = raw[u].v[0]; r.sz = raw[u].v[1]; r.p0 = raw[u].v[2]; r.p1 = raw[u].v[3]; }
                 if (busy[u]) {
-                    const uint32_t keys[4] = {r.k.x, r.k.y, r.k.z, r.k.w};
-                    const uint32_t s01 = r.sz.x, s23 = r.sz.y;
-                    const uint32_t sz[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
-                    const uint64_t pl[4] = {((uint64_t)r.p0.y << 32) | r.p0.x, ((uint64_t)r.p0.w << 32) | r.p0.z,
-                                            ((uint64_t)r.p1.y << 32) | r.p1.x, ((uint64_t)r.p1.w << 32) | r.p1.z};
                     uint32_t size = 0; uint64_t pay = 0;
-                    bool anyFree = false;
-#pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i) {
-                        anyFree = anyFree || sz[i] == 0;
-                        if (sz[i] != 0 && keys[i] == f[u]) { size = sz[i]; pay = pl[i]; }
-                    }
+                    const bool anyFree = bucket_match(r, f[u], size, pay);
                     if (size || anyFree || step[u] >= tab.maxProbe) {
                         if (size) { ws.psize[fbase + slot[u]] = size; ws.ppay[fbase + slot[u]] = pay; }
                         busy[u] = false;
@@ -1504,33 +1486,22 @@ __global__ __launch_bounds__(256) void chunk_finish_kernel(uint32_t s, Workspace
             H = wave_sum_u32(H); nfound = wave_sum_u32(nfound); nfeat = wave_sum_u32(nfeat);
             if (lane == j) { myH = H; myFound = nfound; myFeat = nfeat; }
         }
-        // every lane finishes its own read; the work list's places are reserved with ONE atomic per wave and step (one per read --
-        // 10^5 on one counter in a batch of long reads -- took 2.5 ms)
-        bool filtered = false, wide = false;
-        const uint32_t q = rec.x;
-        uint32_t slots = 0, mw = 0;
+        // every lane finishes its own read: the filtered path where it takes it (compact store, and no lists wanted), else the wave kernel
+        bool filtered = false;
+        const uint32_t q = rec.x, H = myH;
+        uint32_t first = 0, slots = 0, mw = 0;
         if (mineRead) {
-            const uint32_t H = myH;
             QueryStat qs; qs.hits = H; qs.nfeat = myFeat; qs.nfound = myFound; qs.nsteps = myFeat;   // probe steps are not counted on this path
             ws.qstat[q] = qs;
-            slots = (ws.winOff[q + 1] - ws.winOff[q]) * s; mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-            filtered = tab.values32 && !ws.partialLists && H > ws.bigMin && H > 64u && H <= kMaxHitsPerQuery && slots <= 0xFFFu && mw <= tab.gwGap;
-            wide = filtered && H > kGwSmallH;
-            // (a key shard's partial lists are wanted as they are: gather_lists_kernel copies them -- no sort of tens of thousands of locations)
-            ws.hitScan[q] = filtered ? 0u : ((H <= kMaxHitsPerQuery && (H > kLdsCap || ws.partialLists)) ? H : 0u);   // (lists wanted: every query gets its segment)
+            first = ws.winOff[q] * s; slots = ws.winOff[q + 1] * s - first; mw = b.max_win(q);   // (the feature slots, found or not, are the entries)
+            filtered = tab.values32 && !ws.partialLists && filter_takes(H, slots, mw, ClassLimits{ws.bigMin, tab.gwGap, true});
+            // (a key shard's partial lists are wanted as they are: gather_lists_kernel copies them -- no sort of tens of thousands of
+            // locations -- and every read gets its segment)
+            ws.hitScan[q] = filtered ? 0u : ws.partialLists ? (H <= kMaxHitsPerQuery ? H : 0u) : segment_hits(H, kClassWave);
             ws.qflag[q] = filtered ? kFlagMid : ws.partialLists ? kFlagGatherAll : kFlagCands;
         }
-        const uint64_t fm = __ballot(filtered);
-        if (fm) {
-            const uint32_t leader = __ffsll((unsigned long long)fm) - 1;
-            uint32_t at = 0;
-            if (lane == leader) at = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(fm));
-            at = __shfl(at, leader);
-            if (filtered)
-                ws.midList[list_at(kListFilter, b.n) + at + __popcll(fm & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (myH << 12), mw);
-            const uint64_t wm = __ballot(wide);
-            if (wm && lane == leader) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wm));
-        }
+        wave_append(&ws.midCount[kCntFilter], ws.midList + list_at(kListFilter, b.n), filtered, work_record(q, first, slots, H, mw));
+        wave_count(&ws.midCount[kCntSecond], filtered && filter_second(H, slots, true));
     }
 }
 
@@ -1592,6 +1563,17 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
             goff += size;
         }
     };
+    // a found feature.  Singletons are the location itself; longer lists are only noted here (descriptor = first index | size << 48, kept
+    // at the END of the row, growing downwards) and fetched after the lookups.  A full row (pairs, rich tables) moves to the hand-over
+    // area; later entries go there directly.
+    auto found = [&](uint32_t size, uint64_t pay) {
+        ++nfound;
+        H += size;
+        if (!over && n + m >= kLaneHits) { dump_row(); over = true; }
+        if (over) { put_entry(size | (goff << 16), pay); goff += size; }
+        else if (size == 1) L[n++] = pay;
+        else { L[kLaneHits - m] = pay | ((uint64_t)size << 48); ++m; }
+    };
     // the lane's features arrive four at a time (s % 4 == 0: sketches are 16-byte aligned): every lane reads its own line, so what
     // counts is the number of requests, not their width
     uint32_t e = 0;                                                  // next feature of this lane
@@ -1618,14 +1600,7 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
                 if (f[u] == 0xFFFFFFFFu) continue;
                 ++nsteps;
                 const uint32_t size = (uint32_t)ent[u] & 0xFFFFu;
-                if (!size) continue;
-                const uint64_t pay = direct_payload(ent[u]);
-                ++nfound;
-                H += size;
-                if (!over && n + m >= kLaneHits) { dump_row(); over = true; }      // (as below: the row moves to the hand-over area)
-                if (over) { put_entry(size | (goff << 16), pay); goff += size; }
-                else if (size == 1) L[n++] = pay;
-                else { L[kLaneHits - m] = pay | ((uint64_t)size << 48); ++m; }
+                if (size) found(size, direct_payload(ent[u]));
             }
         }
     } else if constexpr (QUAD) {
@@ -1644,34 +1619,11 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
                 const BucketRegs r = quad_collect(raw[u]);
                 if (busy[u]) {
                     ++nsteps;
-                    const uint32_t keys[4] = {r.k.x, r.k.y, r.k.z, r.k.w};
-                    const uint32_t s01 = r.sz.x, s23 = r.sz.y;
-                    const uint32_t sz[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
-                    const uint64_t pl[4] = {((uint64_t)r.p0.y << 32) | r.p0.x, ((uint64_t)r.p0.w << 32) | r.p0.z,
-                                            ((uint64_t)r.p1.y << 32) | r.p1.x, ((uint64_t)r.p1.w << 32) | r.p1.z};
                     uint32_t size = 0; uint64_t pay = 0;
-                    bool anyFree = false;
-    #pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i) {
-                        anyFree = anyFree || sz[i] == 0;
-                        if (sz[i] != 0 && keys[i] == f[u]) { size = sz[i]; pay = pl[i]; }
-                    }
-                    if (size) {
-                        ++nfound;
-                        H += size;
-                        // singletons are the location itself; longer lists are only noted here (descriptor = first index |
-                        // size << 48, kept at the END of the row, growing downwards) and fetched after the lookups
-                        if (!over && n + m >= kLaneHits) { dump_row(); over = true; }   // row full (pairs, rich tables): it moves to
-                        if (over) {                                                      // the hand-over area, later entries go there directly
-                            put_entry(size | (goff << 16), pay);
-                            goff += size;
-                        }
-                        else if (size == 1) L[n++] = pay;
-                        else { L[kLaneHits - m] = pay | ((uint64_t)size << 48); ++m; }
-                        busy[u] = false;
-                    } else if (anyFree || step[u] >= tab.maxProbe) {
-                        busy[u] = false;                               // a bucket with a free slot ends the chain
-                    } else {
+                    const bool anyFree = bucket_match(r, f[u], size, pay);
+                    if (size) found(size, pay);
+                    if (size || anyFree || step[u] >= tab.maxProbe) busy[u] = false;   // (a bucket with a free slot ends the chain)
+                    else {
                         cur[u] = next_bucket(home[u], cur[u], step[u], tab.nbuckets);
                         ++step[u];                                     // stays busy: its next bucket is requested below
                     }
@@ -1723,34 +1675,11 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
             for (uint32_t u = 0; u < kLaneU; ++u) {
                 if (busy[u]) {
                     ++nsteps;
-                    const uint32_t keys[4] = {r[u].k.x, r[u].k.y, r[u].k.z, r[u].k.w};
-                    const uint32_t s01 = r[u].sz.x, s23 = r[u].sz.y;
-                    const uint32_t sz[4] = {s01 & 0xFFFFu, s01 >> 16, s23 & 0xFFFFu, s23 >> 16};
-                    const uint64_t pl[4] = {((uint64_t)r[u].p0.y << 32) | r[u].p0.x, ((uint64_t)r[u].p0.w << 32) | r[u].p0.z,
-                                            ((uint64_t)r[u].p1.y << 32) | r[u].p1.x, ((uint64_t)r[u].p1.w << 32) | r[u].p1.z};
                     uint32_t size = 0; uint64_t pay = 0;
-                    bool anyFree = false;
-    #pragma unroll
-                    for (uint32_t i = 0; i < 4; ++i) {
-                        anyFree = anyFree || sz[i] == 0;
-                        if (sz[i] != 0 && keys[i] == f[u]) { size = sz[i]; pay = pl[i]; }
-                    }
-                    if (size) {
-                        ++nfound;
-                        H += size;
-                        // singletons are the location itself; longer lists are only noted here (descriptor = first index |
-                        // size << 48, kept at the END of the row, growing downwards) and fetched after the lookups
-                        if (!over && n + m >= kLaneHits) { dump_row(); over = true; }   // row full (pairs, rich tables): it moves to
-                        if (over) {                                                      // the hand-over area, later entries go there directly
-                            put_entry(size | (goff << 16), pay);
-                            goff += size;
-                        }
-                        else if (size == 1) L[n++] = pay;
-                        else { L[kLaneHits - m] = pay | ((uint64_t)size << 48); ++m; }
-                        busy[u] = false;
-                    } else if (anyFree || step[u] >= tab.maxProbe) {
-                        busy[u] = false;                               // a bucket with a free slot ends the chain
-                    } else {
+                    const bool anyFree = bucket_match(r[u], f[u], size, pay);
+                    if (size) found(size, pay);
+                    if (size || anyFree || step[u] >= tab.maxProbe) busy[u] = false;   // (a bucket with a free slot ends the chain)
+                    else {
                         cur[u] = next_bucket(home[u], cur[u], step[u], tab.nbuckets);
                         ++step[u];
                         r[u] = load_bucket(tab, cur[u]);               // stays pending; resolved in the next iteration
@@ -1775,7 +1704,7 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
         for (uint32_t i = 0; i < m; ++i) {
             const uint64_t d = L[kLaneHits - i];
             const uint64_t size = d >> 48;
-            L[kLaneHits - i] = (d & 0xFFFFFFFFFull) | (size << 36) | ((uint64_t)(off & 0xFFFu) << 52);
+            L[kLaneHits - i] = (d & 0xFFFFFFFFFull) | (size << 36) | ((uint64_t)(off & kEntOffMask) << 52);
             off += (uint32_t)size;
         }
         gnent = n + m;
@@ -1811,40 +1740,18 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
         const uint32_t nent = gnent;
         // the wave kernel reads all nf slots -- it gets the lists beyond the lane kernels' reach and whatever the filtered path hands back
         if (H > kMidMax || H > ws.bigMin) for (uint32_t j = nent; j < nf; ++j) ws.psize[fbase + j] = 0u;
-        ws.hitScan[q] = (H <= kMaxHitsPerQuery && H > kLdsCap) ? H : 0u;
-        // lists of up to 256 locations: work lists of mid_cands_kernel (4 / 8 / 16 lanes per query); one atomic per wave and class
-        // ... and of hash_cands_kernel (257 .. 1024 locations, one wave per query, no sort); longer ones, wide window ranges -> wave kernel
-        const uint32_t mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-        // (classes: kernels.h).  From 129 locations on counting beats sorting (measured per list: 3.3 vs 4.7 ns at 129..256); below, the
-        // register sort wins (1.6 vs 2 ns)
-        const bool hashOK = nent <= kHashEnt && mw <= kHashWin;
-        // kClassFilter = the filtered path (filter first): lists beyond ws.bigMin locations from at most kBigEnt found features
-        // (compact store: any number of entries the record can name, any window range the gap between two targets covers; filtered lists
-        // the counting kernels do not take are sorted, gw_sorted_cands_kernel)
-        const bool bigOK = H > ws.bigMin && H > 64u &&              // (lists up to 64 are sorted in registers, mid_cands_kernel)
-                           (tab.values32 ? (nent <= 0xFFFu && mw <= tab.gwGap && H <= kMaxHitsPerQuery) : (nent <= kBigEnt * kBigEPL && mw <= kHashWin));
-        const uint32_t cls = bigOK ? kClassFilter : H <= 64 ? kListMid64 : H <= 128 ? (hashOK ? kListHash256 : kListMid128) : H <= kMidMax ? (hashOK ? kListHash256 : kListMid256)
-                           : (H <= kHashMax && hashOK) ? (H <= kHashMax / 2 ? kListHash512 : kListHash1024) : kClassWave;
+        // the read's class (read_class.h): the work lists of mid_cands_kernel (up to 256 locations; 4 / 8 / 16 lanes per query), of
+        // hash_cands_kernel (up to 1024, one wave per query, no sort) and of the filtered path; the rest is the wave kernels'
+        const uint32_t mw = b.max_win(q);
+        const bool compact = tab.values32 != nullptr;
+        const uint32_t cls = read_class(H, nent, mw, ClassLimits{ws.bigMin, tab.gwGap, compact});
         ws.qflag[q] = cls != kClassWave ? kFlagMid : kFlagCands;
-        if (cls >= kListHash512 && cls != kClassWave) ws.hitScan[q] = 0u;                            // no segment in HBM
-        const uint32_t lane = threadIdx.x & 63u;
+        ws.hitScan[q] = segment_hits(H, cls);
+        const WorkRecord rec = work_record(q, fbase, nent, H, mw);
 #pragma unroll
-        for (uint32_t c = 0; c < 8; ++c) {
-            if (c == kClassWave) continue;
-            const uint64_t mask = __ballot(cls == c);
-            if (cls == c) {
-                const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
-                uint32_t base = 0;
-                if (lane == leader) base = atomicAdd(&ws.midCount[class_counter(c)], (uint32_t)__popcll(mask));
-                base = __shfl(base, leader);
-                ws.midList[list_at(class_list(c), b.n) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, fbase, nent | (H << 12), b.maxWin ? b.maxWin[q] : b.maxWinUniform);
-            }
-        }
-        {   // kCntSecond: how many of the filter's queries have more than kBigEnt entries (its second instance runs only for those)
-            // (compact store: how many have more than kGwSmallH locations -- gw_filter_kernel's second instance)
-            const uint64_t wide = __ballot(cls == kClassFilter && (tab.values32 ? H > kGwSmallH : nent > kBigEnt));
-            if (wide && lane == (uint32_t)__ffsll((unsigned long long)wide) - 1) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wide));
-        }
+        for (uint32_t c = 0; c < 8; ++c)                          // one atomic per wave and class
+            if (c != kClassWave) wave_append(&ws.midCount[class_counter(c)], ws.midList + list_at(class_list(c), b.n), cls == c, rec);
+        wave_count(&ws.midCount[kCntSecond], cls == kClassFilter && filter_second(H, nent, compact));   // (the filter's second instance runs only for those)
         return;
     }
     // fetch the noted lists, lowest row position first: the slot of a consumed descriptor is free before the hits reach it
@@ -1867,7 +1774,7 @@ __device__ __forceinline__ void probe_cands_one(const BatchView& b, const uint32
     uint32_t toptax[kLaneK];                                      // taxon of each entry (taxon merging only)
 #pragma unroll
     for (uint32_t i = 0; i < kLaneK; ++i) { top[i].tgt = 0xFFFFFFFFu; top[i].hits = 0; top[i].beg = 0; top[i].end = 0; toptax[i] = 0; }
-    const uint32_t maxWin = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
+    const uint32_t maxWin = b.max_win(q);
     auto insert = [&](LaneCand c) { top_insert(top, toptax, c, K, taxkey, tab.tgtMask); };
     if (n > 0) {
         uint32_t fst = 0, hits = 1;
@@ -1929,17 +1836,29 @@ __global__ __launch_bounds__(kLaneBlock) void sketch_probe_lane_kernel(BatchView
 
 uint32_t lane_max_len() { return kLaneMaxLen; }
 
+// quad-cooperative bucket fetches (quad_issue): asked for (quadMode, kernels.h), else where the table reaches beyond the infinity cache and the TLBs
+static bool quad_lookups(const DeviceTable& tab, int quadMode)
+{
+    return quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
+}
+// the lookup flavour of a one-lane-per-read kernel: launch(kernel instance) with the direct-address index where the table has one, else
+// <QUAD> by quad_lookups.  One block of kLaneBlock reads each.
+template <class Launch>
+static void launch_lane_instance(const BatchView& b, const DeviceTable& tab, int quadMode, Launch&& launch)
+{
+    if (b.n == 0) return;
+    const dim3 grid((b.n + kLaneBlock - 1) / kLaneBlock), block(kLaneBlock);
+    if (tab.direct) launch(std::false_type{}, std::true_type{}, grid, block);
+    else if (quad_lookups(tab, quadMode)) launch(std::true_type{}, std::false_type{}, grid, block);
+    else launch(std::false_type{}, std::false_type{}, grid, block);
+}
+
 void launch_sketch_probe_lane(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                               const uint32_t* taxkey, void* cands, int quadMode, hipStream_t st)
 {
-    if (b.n == 0) return;
-    const bool quad = quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
-    if (tab.direct) hipLaunchKernelGGL((sketch_probe_lane_kernel<false, true>), dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp, tab, ws, maxCand,
-                                       taxkey, (mc_candidate_dev*)cands);
-    else if (quad) hipLaunchKernelGGL(sketch_probe_lane_kernel<true>, dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp, tab, ws, maxCand,
-                                 taxkey, (mc_candidate_dev*)cands);
-    else      hipLaunchKernelGGL(sketch_probe_lane_kernel<false>, dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp, tab, ws, maxCand,
-                                 taxkey, (mc_candidate_dev*)cands);
+    launch_lane_instance(b, tab, quadMode, [&](auto quad, auto direct, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((sketch_probe_lane_kernel<decltype(quad)::value, decltype(direct)::value>), grid, block, 0, st, b, sp, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands);
+    });
 }
 
 void launch_sketch_lane(const BatchView& b, const SketchParams& sp, const Workspace& ws, hipStream_t st)
@@ -1955,8 +1874,7 @@ void launch_chunk_sketch(const BatchView& b, const SketchParams& sp, const Works
 void launch_chunk_probe(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, int quadMode, hipStream_t st)
 {
     if (b.n == 0 || !ws.chunkList) return;
-    const bool quad = quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
-    if (quad) hipLaunchKernelGGL(chunk_probe_kernel<true>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
+    if (quad_lookups(tab, quadMode)) hipLaunchKernelGGL(chunk_probe_kernel<true>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
     else      hipLaunchKernelGGL(chunk_probe_kernel<false>, dim3(2048), dim3(128), 0, st, b, sp.s, tab, ws);
     hipLaunchKernelGGL(chunk_finish_kernel, dim3(1024), dim3(256), 0, st, sp.s, ws, b, tab);
 }
@@ -2044,15 +1962,9 @@ void launch_gather_lists(const BatchView& b, const SketchParams& sp, const Devic
 void launch_probe_cands(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                         const uint32_t* taxkey, void* cands, int quadMode, hipStream_t st)
 {
-    if (b.n == 0) return;
-    // tables that reach beyond the infinity cache and the TLBs: quad-cooperative bucket fetches (see quad_issue)
-    const bool quad = quadMode >= 0 ? quadMode != 0 : (uint64_t)tab.nbuckets * sizeof(TableBucket) > kQuadTableBytes;
-    if (tab.direct) hipLaunchKernelGGL((probe_cands_kernel<false, true>), dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp.s, tab, ws, maxCand,
-                                       taxkey, (mc_candidate_dev*)cands);
-    else if (quad) hipLaunchKernelGGL(probe_cands_kernel<true>, dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp.s, tab, ws, maxCand,
-                                 taxkey, (mc_candidate_dev*)cands);
-    else      hipLaunchKernelGGL(probe_cands_kernel<false>, dim3((b.n + kLaneBlock - 1) / kLaneBlock), dim3(kLaneBlock), 0, st, b, sp.s, tab, ws, maxCand,
-                                 taxkey, (mc_candidate_dev*)cands);
+    launch_lane_instance(b, tab, quadMode, [&](auto quad, auto direct, dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((probe_cands_kernel<decltype(quad)::value, decltype(direct)::value>), grid, block, 0, st, b, sp.s, tab, ws, maxCand, taxkey, (mc_candidate_dev*)cands);
+    });
 }
 // ================================================================================================
 // mid_cands_kernel<G>: location lists of 33 .. 16*G entries (G = 4, 8, 16 lanes per query; 64/G queries per wave).
@@ -2123,15 +2035,15 @@ __global__ __launch_bounds__(256) void mid_cands_kernel(BatchView b, DeviceTable
     // t+1 are requested while iteration t is processed (three dependent HBM round trips per query otherwise)
     auto load_rec = [&](uint32_t w) -> uint4 {
         const uint32_t slot = w * QPW + qi;
-        return (w * QPW < total && slot < total) ? work[slot] : make_uint4(0, 0, 0, 0);      // .z (entries | locations << 12) == 0: idle group
+        return (w * QPW < total && slot < total) ? work[slot] : make_uint4(0, 0, 0, 0);      // .z (entries and locations: work_record) == 0: idle group
     };
     uint32_t esz[kRounds]; uint64_t epay[kRounds];
     auto load_entries = [&](const uint4& rec) {
 #pragma unroll
         for (uint32_t u = 0; u < kRounds; ++u) {
             const uint32_t e = u * G + lg;
-            esz[u] = e < (rec.z & 0xFFFu) ? ws.psize[rec.y + e] : 0u;
-            epay[u] = e < (rec.z & 0xFFFu) ? ws.ppay[rec.y + e] : 0ull;
+            esz[u] = e < rec_entries(rec.z) ? ws.psize[rec.y + e] : 0u;
+            epay[u] = e < rec_entries(rec.z) ? ws.ppay[rec.y + e] : 0ull;
         }
     };
     const uint32_t w0 = blockIdx.x * 4 + wave;
@@ -2139,7 +2051,7 @@ __global__ __launch_bounds__(256) void mid_cands_kernel(BatchView b, DeviceTable
     load_entries(rec);
     for (uint32_t w = w0; w * QPW < total; w += nWaves) {
         const bool act = rec.z != 0;
-        const uint32_t q = rec.x, fbase = rec.y, nent = rec.z & 0xFFFu, H = rec.z >> 12, maxWin = rec.w;
+        const uint32_t q = rec.x, fbase = rec.y, nent = rec_entries(rec.z), H = rec_hits(rec.z), maxWin = rec.w;
         uint32_t klo[kMidR], khi[kMidR];
         if (act) {
             // ---- row 7a: entry table in LDS: payload in the list area, start offset in the segment area (at most one entry per
@@ -2517,15 +2429,15 @@ __global__ __launch_bounds__(WAVES * 64) void hash_cands_kernel(BatchView b, Dev
 #pragma unroll
         for (uint32_t u = 0; u < kRounds; ++u) {
             const uint32_t e = u * 64 + lane;
-            esz[u] = e < (rec.z & 0xFFFu) ? ws.psize[rec.y + e] : 0u;
-            epay[u] = e < (rec.z & 0xFFFu) ? ws.ppay[rec.y + e] : 0ull;
+            esz[u] = e < rec_entries(rec.z) ? ws.psize[rec.y + e] : 0u;
+            epay[u] = e < rec_entries(rec.z) ? ws.ppay[rec.y + e] : 0ull;
         }
     };
     const uint32_t w0 = blockIdx.x * WAVES + wave;
     uint4 rec = load_rec(w0), recNext = load_rec(w0 + nWaves);
     load_entries(rec);
     for (uint32_t w = w0; w < total; w += nWaves) {
-        const uint32_t q = rec.x, nent = rec.z & 0xFFFu, H = rec.z >> 12, maxWin = rec.w;
+        const uint32_t q = rec.x, nent = rec_entries(rec.z), H = rec_hits(rec.z), maxWin = rec.w;
         // ---- empty table; entry table (payload, first list index) in LDS
         {
             uint4* k4 = reinterpret_cast<uint4*>(keys);
@@ -2755,7 +2667,7 @@ __global__ __launch_bounds__(WAVES * 64) MC_BIG_WPE_ATTR void big_filter_kernel(
     uint4 rec = load_rec(w0), recNext = load_rec(w0 + nWaves);
     uint32_t esz[EPL]; uint64_t epay[EPL];
     auto load_entries = [&](const uint4& r) {
-        const uint32_t ne = mine(r.z & 0xFFFu) ? (r.z & 0xFFFu) : 0u;
+        const uint32_t ne = mine(rec_entries(r.z)) ? rec_entries(r.z) : 0u;
 #pragma unroll
         for (uint32_t e = 0; e < EPL; ++e) {
             esz[e] = e * 64 + lane < ne ? ws.psize[r.y + e * 64 + lane] : 0u;
@@ -2777,7 +2689,7 @@ __global__ __launch_bounds__(WAVES * 64) MC_BIG_WPE_ATTR void big_filter_kernel(
     };
     constexpr uint32_t kKeys = POS ? 2 : 1;
     for (uint32_t w = w0; w < total; w += nWaves) {
-        const uint32_t q = rec.x, nent = rec.z & 0xFFFu, H = rec.z >> 12, maxWin = rec.w;
+        const uint32_t q = rec.x, nent = rec_entries(rec.z), H = rec_hits(rec.z), maxWin = rec.w;
         if (!mine(nent)) {                                         // the other instance's query
             rec = recNext; recNext = load_rec(w + 2 * nWaves);
             load_entries(rec);
@@ -3081,25 +2993,16 @@ void launch_hash_cands(WorkList list, const BatchView& b, const DeviceTable& tab
 // having their whole location lists sorted by sort_candidates_kernel (a 10 kbp read: 3 x 10^4 locations, 0.2 ms of ONE wave).
 __global__ __launch_bounds__(256) void wave_rejoin_kernel(BatchView b, uint32_t s, DeviceTable tab, Workspace ws)
 {
-    const uint32_t q = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * 256 + threadIdx.x;
     bool join = false;
-    uint32_t H = 0, slots = 0, mw = 0;
+    uint32_t H = 0, first = 0, slots = 0, mw = 0;
     if (q < b.n && ws.qflag[q] == kFlagCands) {
-        H = ws.qstat[q].hits; slots = (ws.winOff[q + 1] - ws.winOff[q]) * s; mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-        join = H > ws.bigMin && H > 64u && H <= kMaxHitsPerQuery && slots <= 0xFFFu && mw <= tab.gwGap;
+        H = ws.qstat[q].hits; first = ws.winOff[q] * s; slots = ws.winOff[q + 1] * s - first; mw = b.max_win(q);
+        join = filter_takes(H, slots, mw, ClassLimits{ws.bigMin, tab.gwGap, true});
+        if (join) { ws.hitScan[q] = 0u; ws.qflag[q] = kFlagMid; }
     }
-    const uint64_t m = __ballot(join);
-    if (!m) return;
-    const uint32_t leader = __ffsll((unsigned long long)m) - 1;
-    uint32_t base = 0;
-    if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(m));
-    base = __shfl(base, leader);
-    const uint64_t large = __ballot(join && H > kGwSmallH);
-    if (large && lane == leader) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(large));
-    if (join) {
-        ws.midList[list_at(kListFilter, b.n) + base + __popcll(m & ((1ull << lane) - 1ull))] = make_uint4(q, ws.winOff[q] * s, slots | (H << 12), mw);
-        ws.hitScan[q] = 0u; ws.qflag[q] = kFlagMid;
-    }
+    wave_append(&ws.midCount[kCntFilter], ws.midList + list_at(kListFilter, b.n), join, work_record(q, first, slots, H, mw));
+    wave_count(&ws.midCount[kCntSecond], join && filter_second(H, slots, true));
 }
 void launch_wave_rejoin(const BatchView& b, const SketchParams& sp, const DeviceTable& tab, const Workspace& ws, hipStream_t st)
 {

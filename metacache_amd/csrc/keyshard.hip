@@ -96,9 +96,8 @@ __global__ __launch_bounds__(256) void owner_entries_kernel(BatchView b, DeviceT
                                                             const uint64_t* __restrict__ srcStart, KeyshardBases bases, uint32_t S)
 {
     const uint32_t q = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t lane = threadIdx.x & 63u;
     const uint32_t m = b.n;
-    bool take = false, wide = false;
+    bool take = false;
     uint32_t H = 0, mw = 0;
     if (q < m) {
         bool ok = true;
@@ -110,24 +109,16 @@ __global__ __launch_bounds__(256) void owner_entries_kernel(BatchView b, DeviceT
             // (a single location is its own payload in the 8-byte form, as in the table's buckets)
             ws.ppay[(size_t)q * S + s] = c == 1 ? tab.gw_widen(tab.values32[at]) : at;
         }
-        mw = b.maxWin ? b.maxWin[q] : b.maxWinUniform;
-        take = ok && H > 64u && H <= kMaxHitsPerQuery && mw <= tab.gwGap;
-        wide = take && H > kGwSmallH;
+        mw = b.max_win(q);
+        // (the owner takes every list the filtered path can: no bigMin.  What is left is sorted from a segment of its own, whatever its length)
+        take = ok && filter_takes(H, S, mw, ClassLimits{0u, tab.gwGap, true});
         QueryStat qs; qs.hits = H; qs.nfeat = 0; qs.nfound = S; qs.nsteps = 0;
         ws.qstat[q] = qs;
         ws.qflag[q] = take ? kFlagMid : kFlagCands;
         ws.hitScan[q] = take ? 0u : (H <= kMaxHitsPerQuery ? H : 0u);
     }
-    const uint64_t mask = __ballot(take);
-    if (take) {
-        const uint32_t leader = __ffsll((unsigned long long)mask) - 1;
-        uint32_t base = 0;
-        if (lane == leader) base = atomicAdd(&ws.midCount[kCntFilter], (uint32_t)__popcll(mask));
-        base = __shfl(base, leader);
-        ws.midList[list_at(kListFilter, m) + base + __popcll(mask & ((1ull << lane) - 1ull))] = make_uint4(q, q * S, S | (H << 12), mw);
-    }
-    const uint64_t wmask = __ballot(wide);
-    if (wmask && lane == (uint32_t)__ffsll((unsigned long long)wmask) - 1) atomicAdd(&ws.midCount[kCntSecond], (uint32_t)__popcll(wmask));
+    wave_append(&ws.midCount[kCntFilter], ws.midList + list_at(kListFilter, m), take, work_record(q, q * S, S, H, mw));
+    wave_count(&ws.midCount[kCntSecond], take && filter_second(H, S, true));
 }
 void launch_owner_entries(const BatchView& b, const DeviceTable& tab, const Workspace& ws, const uint32_t* counts, const uint64_t* srcStart,
                           const KeyshardBases& bases, uint32_t S, hipStream_t st)

@@ -139,17 +139,7 @@ __global__ __launch_bounds__(kBlock) void table_lookup_sizes_kernel(DeviceTable 
         uint32_t cur = home, size = 0;
         uint64_t pay = 0;
         for (uint32_t step = 1;; ++step) {
-            const BucketRegs r = load_bucket(tab, cur);
-            const uint32_t k[4] = {r.k.x, r.k.y, r.k.z, r.k.w};
-            const uint32_t sz[4] = {r.sz.x & 0xFFFFu, r.sz.x >> 16, r.sz.y & 0xFFFFu, r.sz.y >> 16};
-            const uint64_t pl[4] = {((uint64_t)r.p0.y << 32) | r.p0.x, ((uint64_t)r.p0.w << 32) | r.p0.z,
-                                    ((uint64_t)r.p1.y << 32) | r.p1.x, ((uint64_t)r.p1.w << 32) | r.p1.z};
-            bool anyFree = false;
-#pragma unroll
-            for (uint32_t j = 0; j < 4; ++j) {
-                anyFree = anyFree || sz[j] == 0;
-                if (sz[j] != 0 && k[j] == f) { size = sz[j]; pay = pl[j]; }
-            }
+            const bool anyFree = bucket_match(load_bucket(tab, cur), f, size, pay);
             if (size != 0 || anyFree || step >= tab.maxProbe) break;
             cur = next_bucket(home, cur, step, tab.nbuckets);
         }
