@@ -209,7 +209,22 @@ __device__ __forceinline__ void gw_fill_rounds_scan_at(uint64_t* T, uint32_t* E,
         T[slot] = (who && r0 + slot < Rc) ? ((ep + 16ull * j) | ((uint64_t)min(16u, eSz - 16u * j) << 40)) : 0ull;
     }
 }
+// four registers with whatever they hold: values the compiler takes as given and emits no instruction for.  They cannot be made again
+// as a constant can, so they are for registers whose life ends a few instructions on (gw_load_rounds<BARE>), not for ones to carry.
+__device__ __forceinline__ uint4 gw_left_as_is()
+{
+    uint4 r;
+    asm volatile("" : "=v"(r.x), "=v"(r.y), "=v"(r.z), "=v"(r.w));   // (volatile: every call its own registers)
+    return r;
+}
 // the batch's numbers: 16 bytes per lane and load, four lanes per round; places without a round read as kGwNone
+// BARE (gw_filter_count_kernel<LOOKUP>): of a load that is MADE only what is read of the places without a number is set -- the first
+// register, which tells phase A whether the lane has a round at all.  The other three are read under `rem` only (phase A marks a round's
+// four places or none; phase B hashes whatever they hold -- the filter word's index is nine bits of the hash, in the table whatever the
+// value -- and masks the result): one move per load made instead of four.  The registers of a load NOT made keep the four constants,
+// though the three loops behind the loads leave at nl and never read them: left as they are they stayed live across both phases, and
+// the last load's four were spilled (13 registers instead of 2; docs/LAB_NOTEBOOK_r10.md section 2).
+template <bool BARE = false>
 __device__ __forceinline__ void gw_load_rounds(const uint64_t* T, const uint32_t* __restrict__ values32, uint32_t grp, uint32_t sub4, uint4 (&x)[kGwLoads],
                                                uint32_t nl = kGwLoads)   // nl: loads of this batch that have rounds at all (wave-uniform: the others are skipped)
 {
@@ -217,6 +232,7 @@ __device__ __forceinline__ void gw_load_rounds(const uint64_t* T, const uint32_t
     for (uint32_t u = 0; u < kGwLoads; ++u) {
         x[u] = make_uint4(kGwNone, kGwNone, kGwNone, kGwNone);
         if (u >= nl) continue;
+        if constexpr (BARE) { x[u] = gw_left_as_is(); x[u].x = kGwNone; }
         const uint64_t rd = T[u * 16 + grp];
         if (sub4 < (uint32_t)(rd >> 40)) {
             const U4 t = *reinterpret_cast<const U4*>(values32 + (rd & 0xFFFFFFFFFFull) + sub4);
@@ -266,8 +282,16 @@ __device__ __forceinline__ void gw_take(const uint32_t* bits, const GwFrame& F, 
     S.n2 += (uint32_t)__popcll(m);
 }
 // four numbers at a time: the four filter words are read together (one LDS round trip), no branch but the ones around the stores.
-// CHECK = false: the caller has made sure that everything this read can keep fits the slice.
-template <class Bloom, bool CHECK, bool FINE = false>
+// CHECK: what a store has to ask before it writes.
+//   kGwFits      nothing: the caller has made sure that everything this read can keep fits the slice;
+//   kGwLaneRoom  every lane its own place against the room: the list is cut at S.room, what lies below it is valid;
+//   kGwWaveRoom  the wave, once per call, whether ALL the numbers of the four stores fit -- the running count, the ballots' population
+//                counts and the room are wave-uniform: one scalar compare and branch on a sum the code needs anyway, the stores
+//                themselves are the kGwFits ones.  Four stores that would cross S.room are left out as a whole, so what the list holds
+//                is valid only while n2 <= S.room: for sinks whose list is dropped when n2 passes the room (gw_filter_count_kernel<LOOKUP>'s
+//                kept numbers in LDS; a compare per store, and either form in the instances without LOOKUP, cost registers: notebook r10).
+constexpr int kGwFits = 0, kGwLaneRoom = 1, kGwWaveRoom = 2;
+template <class Bloom, int CHECK, bool FINE = false>
 __device__ __forceinline__ void gw_take4(const uint32_t* bits, const GwFrame& F, GwSink& S, const uint4 x, const int32_t rem)
 {
     const uint32_t v[4] = {x.x, x.y, x.z, x.w};
@@ -302,19 +326,35 @@ __device__ __forceinline__ void gw_take4(const uint32_t* bits, const GwFrame& F,
     }
     if (S.shared) S.n2 = gw_reserve(S.shared, (uint32_t)(__popcll(km[0]) + __popcll(km[1]) + __popcll(km[2]) + __popcll(km[3])));
     uint32_t n2 = S.n2;
+    if constexpr (CHECK == kGwWaveRoom) {
+        // one compare and one branch of the scalar unit for the four stores (the four counts are added up for the running count anyway)
+        const uint32_t end = n2 + (uint32_t)__popcll(km[0]) + (uint32_t)__popcll(km[1]) + (uint32_t)__popcll(km[2]) + (uint32_t)__popcll(km[3]);
+        if (end <= S.room) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (kb[j]) {
+                    const uint32_t mine = __builtin_amdgcn_mbcnt_hi((uint32_t)(km[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km[j], 0u));
+                    (S.dst + n2)[mine] = v[j];
+                }
+                n2 += (uint32_t)__popcll(km[j]);
+            }
+        }
+        S.n2 = end;
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (kb[j]) {
             // (the running count goes into the UNIFORM base of the store -- scalar arithmetic --, the lane adds its place among the kept ones)
             const uint32_t mine = __builtin_amdgcn_mbcnt_hi((uint32_t)(km[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)km[j], 0u));
             uint32_t* const to = S.dst + n2;
-            if (!CHECK || n2 + mine < S.room) to[mine] = v[j];
+            if (CHECK != kGwLaneRoom || n2 + mine < S.room) to[mine] = v[j];
         }
         n2 += (uint32_t)__popcll(km[j]);
     }
     S.n2 = n2;
 }
-template <class Bloom, bool CHECK, bool FINE = false>
+template <class Bloom, int CHECK, bool FINE = false>
 __device__ __forceinline__ void gw_take_rounds(const uint32_t* bits, const uint64_t* T, const GwFrame& F, GwSink& S, uint32_t grp, uint32_t sub4,
                                                const uint4 (&x)[kGwLoads], uint32_t nl = kGwLoads)
 {
@@ -340,7 +380,7 @@ __device__ __forceinline__ uint32_t gw_pack_rems(const uint64_t* T, uint32_t grp
     }
     return packed;
 }
-template <class Bloom, bool CHECK, bool LEAVE = false>
+template <class Bloom, int CHECK, bool LEAVE = false>
 __device__ __forceinline__ void gw_take_rounds_packed(const uint32_t* bits, const uint32_t packed, const GwFrame& F, GwSink& S, const uint4 (&x)[kGwLoads], uint32_t nl)
 {
 #pragma unroll
@@ -424,7 +464,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_kernel(BatchView b,
         wave_lds_sync();
         // ---- B
         gw_take<Bloom>(bits, F, S, sv, sv != kGwNone);
-        gw_take_rounds<Bloom, false>(bits, T, F, S, grp, sub4, x, nl);
+        gw_take_rounds<Bloom, kGwFits>(bits, T, F, S, grp, sub4, x, nl);
         const bool fallback = S.n2 > S.room;                       // longer than what is handed on, or the slice is full
         if (lane == 0) {
             if (fallback) { ws.hitScan[q] = H; ws.qflag[q] = kFlagCands; outRec[w] = make_uint4(q, 0u, kGwFallback, maxWin); }
@@ -517,13 +557,13 @@ __global__ __launch_bounds__(WAVES * 64, T2LOG2 == TLOG2 ? MC_GW_FILTER_WPE : 6)
         wave_lds_sync();
         // ---- B: the batch in registers, then (two batches) batch 0 again
         gw_take<Bloom>(bits, F, S, sv, sv != kGwNone);
-        gw_take_rounds<Bloom, false>(bits, T, F, S, grp, sub4, x);
+        gw_take_rounds<Bloom, kGwFits>(bits, T, F, S, grp, sub4, x);
         if (two) {
             wave_lds_sync();
             gw_fill_rounds_scan_at(T, E, lane, 0, Rc, start, myR, sz, pay);
             wave_lds_sync();
             gw_load_rounds(T, tab.values32, grp, sub4, x);
-            gw_take_rounds<Bloom, false>(bits, T, F, S, grp, sub4, x);
+            gw_take_rounds<Bloom, kGwFits>(bits, T, F, S, grp, sub4, x);
         }
         if (lane == 0) outRec[w] = make_uint4(q, (uint32_t)((uint64_t)w0 * sliceCap + sliceUsed), S.n2, maxWin);
         sliceUsed += S.n2;
@@ -682,7 +722,7 @@ __global__ __launch_bounds__(WAVES * 64) void gw_filter_stream_kernel(BatchView 
                         wave_lds_sync();
                         uint4 x[kGwLoads];
                         gw_load_rounds(T, tab.values32, grp, sub4, x);
-                        if (pass == 0) gw_mark_rounds<Bloom>(bits, x, F.A); else gw_take_rounds<Bloom, true, FINE>(bits, T, F, S, grp, sub4, x);
+                        if (pass == 0) gw_mark_rounds<Bloom>(bits, x, F.A); else gw_take_rounds<Bloom, kGwLaneRoom, FINE>(bits, T, F, S, grp, sub4, x);
                         wave_lds_sync();                           // the table is rewritten by the next batch
                     }
                 }
@@ -1444,8 +1484,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         const uint32_t svLow = sz == 1 ? (uint32_t)pay : 0u;
         const uint32_t svBase = sz == 1 ? tab.gwBase[(uint32_t)(pay >> 32)] : kGwNone;
         uint4 x[kGwLoads];
-        gw_load_rounds(T, tab.values32, grp, sub4, x, nl);
-        const uint32_t sv = svBase + svLow;
+        gw_load_rounds<LOOKUP>(T, tab.values32, grp, sub4, x, nl);
+        uint32_t svTop = svBase;
         uint32_t rems = 0;
         if constexpr (kSeven) {                                    // the table has been read: its place is the filter's now
             rems = gw_pack_rems<LOOKUP>(T, grp, sub4, nl);
@@ -1453,9 +1493,13 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             wave_lds_sync();
             clear_bits();
             wave_lds_sync();
+            // LOOKUP: the singleton's number is put together behind the clearing -- the add is the first use of a loaded value, and the
+            // wait for ALL the loads goes where it stands: in front of the clearing it held back work that needs none of them
+            if constexpr (LOOKUP) asm volatile("" : "+v"(svTop));
         }
+        const uint32_t sv = svTop + svLow;
         auto take_rounds = [&](auto check, GwSink& S) {
-            constexpr bool CHECK = decltype(check)::value;
+            constexpr int CHECK = decltype(check)::value;
             if constexpr (kSeven) gw_take_rounds_packed<Bloom, CHECK, LOOKUP>(bits, rems, F, S, x, nl);
             else gw_take_rounds<Bloom, CHECK>(bits, T, F, S, grp, sub4, x, nl);
         };
@@ -1468,12 +1512,12 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         if (here) {
             GwSink S{kept, kKeep, 0u};
             gw_take<Bloom>(bits, F, S, sv, sv != kGwNone);
-            take_rounds(std::true_type{}, S);
+            take_rounds(std::integral_constant<int, LOOKUP ? kGwWaveRoom : kGwLaneRoom>{}, S);
             n2 = S.n2;
         } else {
             GwSink S{slice + sliceUsed, (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - sliceUsed), 0u};
             gw_take<Bloom>(bits, F, S, sv, sv != kGwNone);
-            take_rounds(std::false_type{}, S);
+            take_rounds(std::integral_constant<int, kGwFits>{}, S);
             n2 = S.n2;
         }
         if (here && n2 <= kKeep) {
@@ -1514,7 +1558,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         if (here) {
             GwSink S{slice + sliceUsed, (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - sliceUsed), 0u};
             gw_take<Bloom>(bits, F, S, sv, sv != kGwNone);
-            take_rounds(std::false_type{}, S);
+            take_rounds(std::integral_constant<int, kGwFits>{}, S);
             n2 = S.n2;
         }
         const uint32_t room = (uint32_t)min((uint64_t)kGwMaxKept, sliceCap - sliceUsed);
