@@ -769,6 +769,85 @@ int mc_format_mappings_with(mc_ctx* ctx, const mc_format_options* opt, const mc_
                             const char* extra, const uint64_t* extra_off);
 int mc_format_matches_stats(mc_ctx* ctx, uint64_t stats[5]);
 
+/* ---- reads out of a FASTA / FASTQ byte range: the input side of a query on the device ------
+ * THE RECORD RULE (sequence_reader::read_next, sequence_io.cpp:160-236, for regular input).  The range is bytes[0, nbytes); bytes[0] is
+ * '>' (FASTA) or '@' (FASTQ) and selects the kind; the range holds whole records, the last one ends at nbytes.  A line start is position
+ * 0 or the byte after a '\n'; "trimmed" means without the trailing run of '\r' / '\n'.
+ *   FASTA: a record starts at every line start that holds '>'; the header is the rest of that line, trimmed; the sequence is the record's
+ *          other lines in order, each trimmed (empty lines add nothing).  A line start that holds '+' makes the range IRREGULAR.
+ *   FASTQ: lines count from 0.  Line 4k starts with '@' and is the header (without the marker, trimmed); line 4k + 1 is the sequence,
+ *          trimmed, and does not start with '+', '>', '\n' or '\r'; line 4k + 2 starts with '+'; line 4k + 3 is dropped.  Any violation,
+ *          or a number of lines that is no multiple of 4, makes the range IRREGULAR.
+ *   The name is the header up to its first ' '.  MC_PARSE_PAIRS: query q is records 2q and 2q + 1 under the first one's name; an odd
+ *   count leaves a last query with len2 = 0 (status[7] = 1).
+ *   The device refuses MORE than the rule does -- a '\r' that is not followed by '\n' or by the end of the range is IRREGULAR -- and never
+ *   cuts an accepted range differently from the rule.  The offence (status[5]) is the offset of the first line start, or '\r', that broke
+ *   the rule; nbytes for an incomplete last FASTQ group.
+ * mc_parse_records fills, in file order: hdr[records][2] = offset and length of each header in bytes; qinfo[queries][4] as
+ *   mc_device_batch takes it (offsets into seq; every sequence begins at a multiple of 4, the padding bytes and the 16 bytes behind the
+ *   last sequence are 0; a query without a second mate has qinfo[2] = the end of the first, padded, and qinfo[3] = 0, as mc_batch_add
+ *   leaves it); names + name_off[queries + 1] as mc_format_mappings takes them; max_win[queries] = 2 + max(len1 + len2,
+ *   insert_size_max) / the database's window stride; status[8] = records, queries, bytes of seq needed (with the 16 behind), bytes of
+ *   names needed, verdict, offence, the longest len1 + len2, half pair.  With a verdict other than MC_PARSE_OK NOTHING but status is
+ *   written; with MC_PARSE_OVERFLOW (more than max_records records, or a capacity too small) status holds what a second call needs; with
+ *   MC_PARSE_IRREGULAR only verdict and offence mean anything.  The arrays have room for max_records records (name_off: one more).
+ *   Without MC_PARSE_HOST all arrays are DEVICE pointers (bytes, seq and workspace 16-byte, name_off and status 8-byte, the others 4-byte
+ *   aligned) and the call is enqueued on `stream` (NULL: the context's) without any synchronisation: in front of mc_query_device, whose
+ *   mc_device_batch it fills.  The caller owns the workspace (mc_parse_scratch_bytes(nbytes) bytes); the context keeps nothing per call,
+ *   so calls on different streams may run at once.  The same bytes give the same outputs, byte for byte.  bytes[0] is part of the verdict.
+ *   With MC_PARSE_HOST all arrays are HOST arrays (workspace may be NULL), staged through buffers of the context, one caller at a time;
+ *   the call returns when they are filled.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, out, bytes or status, nbytes == 0 or > 2^31, unknown flags, NULL
+ *   arrays with max_records > 0, a capacity without its array or beyond 2^32 - 1, MC_PARSE_HOST: bytes[0] that is no marker; device form:
+ *   a workspace that is too small, misaligned arrays.  MC_ERR_STATE: a context without a device (mc_open_metadata).
+ * mc_parse_stats: stats[0..3] = calls, bytes handed over, records of the accepted ranges, ranges refused (irregular or overflow); waits
+ *   for the device.  mc_timing_get names: "parse_classify" (the three tile passes and their scans), "parse_write". */
+#define MC_PARSE_HOST       1
+#define MC_PARSE_PAIRS      2
+#define MC_PARSE_OK         0
+#define MC_PARSE_IRREGULAR  1
+#define MC_PARSE_OVERFLOW   2
+typedef struct {
+    uint32_t* hdr;            /* [max_records][2] */
+    uint32_t* qinfo;          /* [max_records][4] */
+    uint8_t*  seq;
+    uint64_t  seq_capacity;
+    char*     names;
+    uint64_t  names_capacity;
+    uint64_t* name_off;       /* [max_records + 1] */
+    uint32_t* max_win;        /* [max_records] */
+    uint64_t* status;         /* [8] */
+    uint32_t  max_records;
+} mc_parse_output;
+extern const uint32_t mc_parse_tile;   /* bytes one block classifies: what lies in front of a tile comes from a scan over the tiles (for tests and tools) */
+uint64_t mc_parse_scratch_bytes(uint64_t nbytes);
+int mc_parse_records(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags, uint64_t insert_size_max, const mc_parse_output* out,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+int mc_parse_stats(mc_ctx* ctx, uint64_t stats[4]);
+
+/* raw bytes into a batch slot: the slot's reads are cut on the device
+ * mc_batch_add_file_bytes fills an EMPTY slot with a byte range of a FASTA / FASTQ file (whole records; flags: 0 or MC_PARSE_PAIRS): one
+ *   copy into the slot's pinned input.  MC_BATCH_FULL, and nothing added, when nbytes exceeds the slot's character capacity; MC_ERR_STATE
+ *   when the slot holds reads already or is in flight; mc_batch_add on a slot that holds a raw range is MC_ERR_STATE as well.
+ *   mc_batch_submit uploads the bytes, has mc_parse_records cut them into the slot's device input and runs the unchanged query on that;
+ *   it waits once for the device, for the number of reads.  A raw slot is never united with other slots: where the context unites its
+ *   slots (small slots, no all-hits lists) it goes alone and mc_batch_submit returns when it is through.  mc_batch_wait and
+ *   mc_batch_clear work as before.
+ * mc_batch_records, after mc_batch_wait: the verdict of mc_parse_records and its offence, the numbers of records and queries, the half
+ *   pair, and host views of hdr [records][2] and qinfo [queries][4] (valid until mc_batch_clear; NULL with another verdict than
+ *   MC_PARSE_OK).  With such a verdict mc_results.num_queries is 0 and the caller takes the batch the old way: MC_PARSE_IRREGULAR, or
+ *   MC_PARSE_OVERFLOW for more queries than slot_max_queries, more characters than the slot's capacity, or a read (pair) of len + 8 >
+ *   slot_max_chars.  MC_ERR_STATE: a slot without a submitted raw range. */
+typedef struct {
+    uint32_t        verdict;
+    uint32_t        records, queries, half_pair;
+    uint64_t        offence;
+    const uint32_t* hdr;
+    const uint32_t* qinfo;
+} mc_batch_record_info;
+int mc_batch_add_file_bytes(mc_ctx* ctx, uint32_t slot, const char* bytes, uint64_t nbytes, int flags, uint64_t insert_size_max);
+int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out);
+
 /* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
  * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the
  * database -- how many features, how many locations, the distribution of the list sizes, which locations a feature has -- and here the

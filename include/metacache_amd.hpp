@@ -236,6 +236,37 @@ public:
         if (mc_format_matches_set_text(ctx_, bytes.data(), off.data(), strings.size()) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
     }
 
+    // the reads of a FASTA / FASTQ byte range, cut on the device (mc_parse_records on host arrays; the record rule: metacache_amd.h).
+    // verdict MC_PARSE_OK: record r's header is bytes[hdr[2r] .. + hdr[2r + 1]), query q's reads are seq[qinfo[4q] .. + qinfo[4q + 1])
+    // and seq[qinfo[4q + 2] .. + qinfo[4q + 3]), its name is names[nameOff[q] .. nameOff[q + 1]).  Another verdict: the arrays are empty
+    // and offence says where the range broke the rule -- the caller cuts that range itself.
+    struct parsed_records {
+        int verdict = MC_PARSE_IRREGULAR; std::uint64_t offence = 0; std::uint32_t records = 0, queries = 0; bool halfPair = false;
+        std::vector<std::uint32_t> hdr, qinfo, maxWin; std::vector<std::uint8_t> seq; std::string names; std::vector<std::uint64_t> nameOff;
+    };
+    parsed_records parse_records(const char* bytes, std::size_t nbytes, bool pairs = false, std::uint64_t insertSizeMax = 0) const
+    {
+        parsed_records p;
+        std::uint64_t status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int pass = 0; pass < 2; ++pass) {                                   // (the first call reports what the second needs)
+            mc_parse_output o{};
+            const std::uint32_t mr = std::uint32_t(status[0]);
+            p.hdr.assign(std::size_t(mr) * 2 + 1, 0); p.qinfo.assign(std::size_t(mr) * 4 + 1, 0); p.maxWin.assign(std::size_t(mr) + 1, 0);
+            p.seq.assign(std::size_t(status[2]) + 1, 0); p.names.assign(std::size_t(status[3]) + 1, char(0)); p.nameOff.assign(std::size_t(mr) + 1, 0);
+            o.hdr = p.hdr.data(); o.qinfo = p.qinfo.data(); o.seq = p.seq.data(); o.seq_capacity = status[2]; o.names = &p.names[0];
+            o.names_capacity = status[3]; o.name_off = p.nameOff.data(); o.max_win = p.maxWin.data(); o.status = status; o.max_records = mr;
+            if (mc_parse_records(ctx_, bytes, nbytes, MC_PARSE_HOST | (pairs ? MC_PARSE_PAIRS : 0), insertSizeMax, &o, nullptr, 0, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            if (status[4] != MC_PARSE_OVERFLOW) break;
+        }
+        p.verdict = int(status[4]); p.offence = status[5];
+        const bool ok = status[4] == MC_PARSE_OK;
+        p.records = ok ? std::uint32_t(status[0]) : 0; p.queries = ok ? std::uint32_t(status[1]) : 0; p.halfPair = ok && status[7] != 0;
+        p.hdr.resize(std::size_t(p.records) * 2); p.qinfo.resize(std::size_t(p.queries) * 4); p.maxWin.resize(p.queries);
+        p.seq.resize(ok ? std::size_t(status[2]) : 0); p.names.resize(ok ? std::size_t(status[3]) : 0); p.nameOff.resize(ok ? std::size_t(p.queries) + 1 : 0);
+        return p;
+    }
+
     // -precision / -taxon-coverage after the last batch: what the batches' evaluate() calls have counted (mc_evaluate_tally; reset: the
     // counters start from zero again)
     classification_statistics evaluation(bool reset = false) const
@@ -431,6 +462,14 @@ public:
                                    MC_TARGET_HITS_HOST, nullptr) != MC_OK)
                 throw std::runtime_error(mc_last_error(ctx_));
         }
+        // what the device made of a batch filled by add_file_bytes (after wait_for_results; mc_batch_records): the verdict, and with
+        // MC_PARSE_OK the records' headers and the queries' lengths as views that are valid until clear()
+        mc_batch_record_info records() const
+        {
+            mc_batch_record_info info{};
+            if (mc_batch_records(ctx_, slot_, &info) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+            return info;
+        }
         void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); lineOff_.clear(); pieceOff_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
@@ -455,6 +494,14 @@ public:
     {
         const int rc = mc_batch_add(ctx_, hostId, seq1.data(), std::uint32_t(seq1.size()), seq2.data(), std::uint32_t(seq2.size()),
                                     rules.maxWindowsInRange);
+        if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
+        return rc == MC_OK;
+    }
+    // a byte range of a FASTA / FASTQ file (whole records) into an EMPTY batch: the reads are cut on the device when the batch is
+    // submitted (mc_batch_add_file_bytes).  Returns false if the range exceeds the batch's character capacity.
+    bool add_file_bytes(unsigned hostId, const char* bytes, std::size_t nbytes, bool pairs = false, std::uint64_t insertSizeMax = 0)
+    {
+        const int rc = mc_batch_add_file_bytes(ctx_, hostId, bytes, nbytes, pairs ? MC_PARSE_PAIRS : 0, insertSizeMax);
         if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
         return rc == MC_OK;
     }

@@ -116,6 +116,30 @@ def target_hits_tile() -> int:
     return int(C.c_uint32.in_dll(lib(), "mc_target_hits_tile").value)
 
 
+def parse_tile() -> int:
+    """bytes one block of the parse kernels classifies (the library's mc_parse_tile): what lies in front of a tile comes from a scan over the tiles"""
+    return int(C.c_uint32.in_dll(lib(), "mc_parse_tile").value)
+
+
+def parse_scratch_bytes(nbytes: int) -> int:
+    """the workspace a device call of mc_parse_records needs for a range of nbytes"""
+    return int(lib().mc_parse_scratch_bytes(nbytes))
+
+
+PARSE_HOST, PARSE_PAIRS = 1, 2
+PARSE_OK, PARSE_IRREGULAR, PARSE_OVERFLOW = 0, 1, 2
+
+
+class McParseOutput(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("qinfo", C.c_void_p), ("seq", C.c_void_p), ("seq_capacity", C.c_uint64), ("names", C.c_void_p),
+                ("names_capacity", C.c_uint64), ("name_off", C.c_void_p), ("max_win", C.c_void_p), ("status", C.c_void_p), ("max_records", C.c_uint32)]
+
+
+class McBatchRecordInfo(C.Structure):
+    _fields_ = [("verdict", C.c_uint32), ("records", C.c_uint32), ("queries", C.c_uint32), ("half_pair", C.c_uint32), ("offence", C.c_uint64),
+                ("hdr", C.c_void_p), ("qinfo", C.c_void_p)]
+
+
 def classify_options(hitmin: int = 0, hitdiff: float = 1.0, lowest: int = 0, highest: int = NUM_RANKS - 1) -> McClassifyOptions:
     return McClassifyOptions(int(hitmin), hitdiff_factor(hitdiff), int(lowest), int(highest))
 
@@ -317,7 +341,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_set_taxon_table", "mc_db_taxon_table", "mc_evaluate_assignments", "mc_evaluate_tally",
            "mc_format_set_text", "mc_format_mappings", "mc_format_stats",
            "mc_format_matches_set_text", "mc_format_matches", "mc_format_mappings_with", "mc_format_matches_stats",
-           "mc_table_histogram", "mc_table_features", "mc_table_lookup"]
+           "mc_table_histogram", "mc_table_features", "mc_table_lookup",
+           "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records"]
 
 _lib = None
 
@@ -402,6 +427,12 @@ def lib() -> C.CDLL:
         L.mc_table_histogram.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]
         L.mc_table_features.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_int]
         L.mc_table_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int]
+        L.mc_parse_scratch_bytes.argtypes = [C.c_uint64]
+        L.mc_parse_scratch_bytes.restype = C.c_uint64
+        L.mc_parse_records.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(McParseOutput), C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_parse_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_batch_add_file_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64]
+        L.mc_batch_records.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(McBatchRecordInfo)]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -802,6 +833,90 @@ class Database:
         """-> [mc_format_mappings calls, reads, lines written, bytes written, result indices beyond their table]"""
         st = np.zeros(5, dtype=np.uint64)
         self._check(lib().mc_format_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    # ---- reads out of a FASTA / FASTQ byte range (mc_parse_*) -----------------------------------------
+    def parse_device(self, bytes_ptr: int, nbytes: int, *, hdr_ptr: int, qinfo_ptr: int, seq_ptr: int, seq_capacity: int, names_ptr: int,
+                     names_capacity: int, name_off_ptr: int, max_win_ptr: int, status_ptr: int, max_records: int, workspace_ptr: int,
+                     workspace_bytes: int, pairs: bool = False, insert_max: int = 0, stream: int = 0):
+        """cuts the range at bytes_ptr (device memory, 16-byte aligned) into reads: hdr [max_records, 2] uint32, qinfo [max_records, 4]
+        uint32, seq, names, name_off [max_records + 1] uint64, max_win [max_records] uint32, status [8] uint64 -- all device memory;
+        workspace of parse_scratch_bytes(nbytes); asynchronous on `stream`.  status[4] is the verdict (PARSE_OK: the arrays are filled)"""
+        o = McParseOutput(hdr_ptr or None, qinfo_ptr or None, seq_ptr or None, seq_capacity, names_ptr or None, names_capacity,
+                          name_off_ptr or None, max_win_ptr or None, status_ptr or None, max_records)
+        self._check(lib().mc_parse_records(self.h, bytes_ptr or None, nbytes, PARSE_PAIRS if pairs else 0, insert_max, C.byref(o),
+                                           workspace_ptr or None, workspace_bytes, stream or None))
+
+    def parse_records(self, data, pairs: bool = False, insert_max: int = 0, *, max_records=None, seq_capacity=None, names_capacity=None):
+        """the same on host memory: data (bytes) -> dict(status uint64 [8], and with the verdict PARSE_OK: hdr [records, 2], qinfo
+        [queries, 4], seq (bytes, with the 16 behind the last read), names (bytes), name_off [queries + 1], max_win [queries]).
+        Capacities that are left out are taken from a first call's status (PARSE_OVERFLOW reports what is needed).  "raw": the arrays as the
+        last call left them, at their capacities (with another verdict than PARSE_OK: untouched)."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        status = np.zeros(8, dtype=np.uint64)
+
+        def run(mr, sc, nc):
+            a = dict(hdr=np.zeros((max(mr, 1), 2), dtype=np.uint32), qinfo=np.zeros((max(mr, 1), 4), dtype=np.uint32), seq=np.zeros(max(sc, 1), dtype=np.uint8),
+                     names=np.zeros(max(nc, 1), dtype=np.uint8), name_off=np.zeros(mr + 1, dtype=np.uint64), max_win=np.zeros(max(mr, 1), dtype=np.uint32))
+            o = McParseOutput(a["hdr"].ctypes.data, a["qinfo"].ctypes.data, a["seq"].ctypes.data, sc, a["names"].ctypes.data, nc,
+                              a["name_off"].ctypes.data, a["max_win"].ctypes.data, status.ctypes.data, mr)
+            self._check(lib().mc_parse_records(self.h, buf.ctypes.data if len(buf) else None, len(buf), PARSE_HOST | (PARSE_PAIRS if pairs else 0),
+                                               insert_max, C.byref(o), None, 0, None))
+            return a
+
+        sized = max_records is not None and seq_capacity is not None and names_capacity is not None
+        a = run(max_records or 0, seq_capacity or 0, names_capacity or 0)
+        if not sized and int(status[4]) == PARSE_OVERFLOW:
+            a = run(int(status[0]) if max_records is None else max_records, int(status[2]) if seq_capacity is None else seq_capacity,
+                    int(status[3]) if names_capacity is None else names_capacity)
+        out = dict(status=status.copy())
+        if int(status[4]) == PARSE_OK:
+            r, q = int(status[0]), int(status[1])
+            out.update(hdr=a["hdr"][:r].copy(), qinfo=a["qinfo"][:q].copy(), seq=a["seq"][:int(status[2])].tobytes(), names=a["names"][:int(status[3])].tobytes(),
+                       name_off=a["name_off"][:q + 1].copy(), max_win=a["max_win"][:q].copy())
+        out["raw"] = a
+        return out
+
+    def batch_records(self, slot: int = 0) -> dict:
+        """what the device made of a raw slot (mc_batch_records, after the wait): verdict, offence, records, queries, half_pair, and copies
+        of hdr [records, 2] and qinfo [queries, 4] (empty with another verdict than PARSE_OK)"""
+        info = McBatchRecordInfo()
+        self._check(lib().mc_batch_records(self.h, slot, C.byref(info)))
+        return dict(verdict=info.verdict, offence=info.offence, records=info.records, queries=info.queries, half_pair=info.half_pair,
+                    hdr=_view(info.hdr, 2 * info.records, np.dtype("<u4")).reshape(info.records, 2).copy(),
+                    qinfo=_view(info.qinfo, 4 * info.queries, np.dtype("<u4")).reshape(info.queries, 4).copy())
+
+    def query_file_bytes(self, data, pairs: bool = False, lowest: int = 0, insert_max: int = 0, slot: int = 0):
+        """one slot batch from a byte range of a FASTA / FASTQ file, cut into reads on the device (mc_batch_add_file_bytes)
+        -> (cands[n, K], hit_counts[n], allhits list or None, records: batch_records()); n = 0 where the device refused the range
+        (records["verdict"] says why) -- the caller then cuts that batch itself.  Raises McError("... does not fit ...") on MC_BATCH_FULL."""
+        L = lib()
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        rc = self._check(L.mc_batch_add_file_bytes(self.h, slot, buf.ctypes.data if len(buf) else None, len(buf), PARSE_PAIRS if pairs else 0, insert_max))
+        if rc == MC_BATCH_FULL:
+            raise McError("the byte range does not fit the slot's character capacity")
+        K = self.cfg.max_candidates
+        try:
+            self._check(L.mc_batch_submit(self.h, slot, lowest))
+            res = McResults()
+            self._check(L.mc_batch_wait(self.h, slot, C.byref(res)))
+            m = res.num_queries
+            cands = _view(res.cands, m * K, cand_dtype).reshape(m, K).copy()
+            counts = _view(res.hit_counts, m, np.dtype("<u4")).copy()
+            allhits = None
+            if self.cfg.copy_allhits:
+                off = _view(res.hit_offsets, m + 1, np.dtype("<u8")) if m else np.zeros(1, dtype=np.uint64)
+                hits = _view(res.hits, int(off[m]), loc_dtype)
+                allhits = [hits[int(off[i]):int(off[i + 1])].copy() for i in range(m)]
+            records = self.batch_records(slot)
+        finally:
+            self._check(L.mc_batch_clear(self.h, slot))
+        return cands, counts, allhits, records
+
+    def parse_stats(self):
+        """-> [mc_parse_records calls, bytes handed over, records of the accepted ranges, ranges refused]"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_parse_stats(self.h, st.ctypes.data))
         return [int(x) for x in st]
 
     # ---- the all-hits column: location lists, run-length encoded (mc_format_matches*) ----------------

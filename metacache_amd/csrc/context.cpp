@@ -277,6 +277,7 @@ void mc_destroy(mc_ctx* ctx)
     free_target_hits_state(ctx);
     free_evaluate_state(ctx);
     free_format_state(ctx);
+    free_parse_state(ctx);
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);
@@ -302,6 +303,8 @@ void mc_destroy(mc_ctx* ctx)
     for (auto& s : ctx->slots) {
         if (s.hseq) (void)hipHostFree(s.hseq); if (s.hqinfo) (void)hipHostFree(s.hqinfo); if (s.hmaxwin) (void)hipHostFree(s.hmaxwin);
         if (s.dseq) (void)hipFree(s.dseq); if (s.dqinfo) (void)hipFree(s.dqinfo); if (s.dmaxwin) (void)hipFree(s.dmaxwin);
+        for (void* p : {(void*)s.draw, s.dparseWs, (void*)s.dhdr, (void*)s.dnames, (void*)s.dnameoff, (void*)s.dstatus}) if (p) (void)hipFree(p);
+        if (s.hhdr) (void)hipHostFree(s.hhdr); if (s.hstatus) (void)hipHostFree(s.hstatus);
         if (s.hcands) (void)hipHostFree(s.hcands); if (s.hqstat) (void)hipHostFree(s.hqstat);
         if (s.hhitcounts) (void)hipHostFree(s.hhitcounts); if (s.hhitoff) (void)hipHostFree(s.hhitoff);
         if (s.hhits) (void)hipHostFree(s.hhits); if (s.done) (void)hipEventDestroy(s.done);
@@ -1173,6 +1176,7 @@ int mc_batch_add(mc_ctx* ctx, uint32_t slot, const char* s1, uint32_t l1, const 
     if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
     Slot& S = ctx->slots[slot];
     if (S.submitted) return fail(ctx, MC_ERR_STATE, "mc_batch_add: slot is in flight, call mc_batch_wait + mc_batch_clear");
+    if (S.raw) return fail(ctx, MC_ERR_STATE, "mc_batch_add: the slot holds a raw byte range (mc_batch_add_file_bytes), call mc_batch_submit");
     if (l2 == kNoTail) return fail(ctx, MC_ERR_INVALID, "sequence too long");
     const uint64_t need = ((uint64_t)l1 + 3) / 4 * 4 + ((uint64_t)l2 + 3) / 4 * 4;
     if (need > ctx->cfg.slot_max_chars) return fail(ctx, MC_ERR_INVALID, "query longer than the slot's character capacity");
@@ -1206,6 +1210,70 @@ int64_t mc_batch_add_bulk(mc_ctx* ctx, uint32_t slot, const char* seqs, const ui
     return (int64_t)i;
 }
 
+int mc_batch_add_file_bytes(mc_ctx* ctx, uint32_t slot, const char* bytes, uint64_t nbytes, int flags, uint64_t insertMax)
+{
+    if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
+    if (!bytes || nbytes == 0) return fail(ctx, MC_ERR_INVALID, "mc_batch_add_file_bytes: no bytes");
+    if (flags & ~MC_PARSE_PAIRS) return fail(ctx, MC_ERR_INVALID, "mc_batch_add_file_bytes: unknown flag");
+    Slot& S = ctx->slots[slot];
+    if (S.submitted) return fail(ctx, MC_ERR_STATE, "mc_batch_add_file_bytes: slot is in flight, call mc_batch_wait + mc_batch_clear");
+    if (S.nq || S.raw) return fail(ctx, MC_ERR_STATE, "mc_batch_add_file_bytes: the slot already holds reads");
+    if (nbytes > ctx->cfg.slot_max_chars) return MC_BATCH_FULL;
+    std::memcpy(S.hseq, bytes, nbytes);
+    S.raw = true; S.rawBytes = nbytes; S.rawFlags = flags; S.rawInsertMax = insertMax;
+    return MC_OK;
+}
+
+// a raw slot's range to the device and through mc_parse_records on st; the stream is drained once, for the status: the query's launches
+// need the number of reads.  Leaves the slot as mc_batch_add would have (nq, nchars, maxSingle) -- with no reads where the range was
+// refused, or holds more than a slot takes (then status[4] says MC_PARSE_OVERFLOW)
+static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
+{
+    const uint64_t nq = ctx->cfg.slot_max_queries, nc = (uint64_t)ctx->cfg.slot_max_chars + 16;
+    if (!S.draw) {
+        HIP_TRY(ctx, hipMalloc((void**)&S.draw, nc));
+        HIP_TRY(ctx, hipMalloc(&S.dparseWs, mc_parse_scratch_bytes(ctx->cfg.slot_max_chars)));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dhdr, nq * 16));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dnames, nc));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dnameoff, (nq + 1) * 8));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dstatus, 64));
+        HIP_TRY(ctx, hipHostMalloc((void**)&S.hhdr, nq * 16));
+        HIP_TRY(ctx, hipHostMalloc((void**)&S.hstatus, 64));
+    }
+    const bool pairs = (S.rawFlags & MC_PARSE_PAIRS) != 0;
+    HIP_TRY(ctx, hipMemcpyAsync(S.draw, S.hseq, S.rawBytes, hipMemcpyHostToDevice, st));
+    mc_parse_output o{};
+    o.hdr = S.dhdr; o.qinfo = S.dqinfo; o.seq = S.dseq; o.seq_capacity = nc; o.names = (char*)S.dnames; o.names_capacity = nc;
+    o.name_off = S.dnameoff; o.max_win = S.dmaxwin; o.status = S.dstatus;
+    o.max_records = (uint32_t)(pairs ? 2 * nq : nq);             // (qinfo, name_off and max_win take a row per QUERY)
+    if (const int rc = mc_parse_records(ctx, (const char*)S.draw, S.rawBytes, S.rawFlags, S.rawInsertMax, &o, S.dparseWs, mc_parse_scratch_bytes(ctx->cfg.slot_max_chars), st)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(S.hstatus, S.dstatus, 64, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, traced_sync(st));
+    uint64_t* status = S.hstatus;
+    if (status[4] == MC_PARSE_OK && status[6] + 8 > ctx->cfg.slot_max_chars) status[4] = MC_PARSE_OVERFLOW;   // (a read the slot's loop would have refused)
+    S.nq = 0; S.nchars = 0; S.maxSingle = 0;
+    if (status[4] != MC_PARSE_OK) return MC_OK;
+    S.nq = (uint32_t)status[1]; S.nchars = status[2] - 16;
+    S.maxSingle = (uint32_t)std::min<uint64_t>(status[6], 0xFFFFFFFFull);   // (pairs: an upper bound of the half pair's length)
+    HIP_TRY(ctx, hipMemcpyAsync(S.hhdr, S.dhdr, status[0] * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(S.hqinfo, S.dqinfo, (size_t)S.nq * 16, hipMemcpyDeviceToHost, st));
+    return MC_OK;
+}
+
+static int submit_raw_coalesced(mc_ctx* ctx, Slot& S, int lowestRank);
+
+int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out)
+{
+    if (!ctx || slot >= ctx->slots.size() || !out) return MC_ERR_INVALID;
+    Slot& S = ctx->slots[slot];
+    if (!S.raw || !S.submitted || !S.hstatus) return fail(ctx, MC_ERR_STATE, "mc_batch_records: the slot holds no submitted raw range (mc_batch_add_file_bytes, mc_batch_submit, mc_batch_wait)");
+    const bool ok = S.hstatus[4] == MC_PARSE_OK;
+    out->verdict = (uint32_t)S.hstatus[4]; out->offence = S.hstatus[5];
+    out->records = ok ? (uint32_t)S.hstatus[0] : 0; out->queries = ok ? (uint32_t)S.hstatus[1] : 0; out->half_pair = ok ? (uint32_t)S.hstatus[7] : 0;
+    out->hdr = ok ? S.hhdr : nullptr; out->qinfo = ok ? S.hqinfo : nullptr;
+    return MC_OK;
+}
+
 int mc_batch_submit(mc_ctx* ctx, uint32_t slot, int lowestRank)
 {
     if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
@@ -1214,6 +1282,7 @@ int mc_batch_submit(mc_ctx* ctx, uint32_t slot, int lowestRank)
     // every slot has its own stream and device workspace: batches of different slots overlap on the device (the reference orders
     // submissions with a mutex and overlaps through per-batch CUDA streams, database_query.hpp:110-113, query_batch.cu)
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (S.raw && ctx->coalesce) return submit_raw_coalesced(ctx, S, lowestRank);   // (never united with other slots)
     if (ctx->coalesce) {
         // hand the slot to the dispatchers: whatever is waiting when one of them comes free goes to the device as ONE batch
         S.submittedQueries = S.nq; S.coLowest = lowestRank; S.coRc = MC_OK; S.coEvent = false; S.coErr.clear();
@@ -1252,14 +1321,17 @@ int mc_batch_submit(mc_ctx* ctx, uint32_t slot, int lowestRank)
     } giveback{ctx, S};
     Pipe& P = *S.pipe;
     hipStream_t st = P.stream;
+    if (S.raw) { if (const int rc = raw_parse(ctx, S, st)) return rc; }   // (the reads are cut on the device, into the slot's device input)
     const uint32_t n = S.nq;
     S.submittedQueries = n;
     if (n == 0) { HIP_TRY(ctx, hipEventRecord(S.done, st)); S.submitted = true; return MC_OK; }
     const uint64_t te0 = trace_now();
+    if (!S.raw) {
     HIP_TRY(ctx, hipMemcpyAsync(S.dseq, S.hseq, S.nchars + 16, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(S.dqinfo, S.hqinfo, (size_t)n * 16, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(S.dmaxwin, S.hmaxwin, (size_t)n * 4, hipMemcpyHostToDevice, st));
     note_enqueues(trace_now() - te0, 3);
+    }
     mc_device_batch in{S.dseq, S.dqinfo, S.dmaxwin, 0, n, S.nchars};
     mc_device_results res{};
     const int wantAll = ctx->cfg.copy_allhits ? 1 : 0;
@@ -1425,6 +1497,41 @@ static void co_run(mc_ctx* ctx, mcamd::CoDispatcher* D, const std::vector<uint32
     t_errSink = sinkBefore;
 }
 
+// a raw slot of a context whose slots are united: it goes alone, on a dispatcher's pipe that the submitter borrows, and is THROUGH when
+// this returns (its reads are known only after the device has cut them: there is nothing to unite it by)
+static int submit_raw_coalesced(mc_ctx* ctx, Slot& S, int lowestRank)
+{
+    mcamd::CoDispatcher* D = nullptr;
+    {
+        std::unique_lock<std::mutex> l(ctx->coMu);
+        while (ctx->coFree.empty()) ctx->coCv.wait_for(l, std::chrono::microseconds(200));   // (coCv wakes ONE waiter, which may be a dispatcher: look again)
+        D = ctx->coFree.back(); ctx->coFree.pop_back();
+    }
+    Pipe& P = *D->pipe;
+    hipStream_t st = P.stream;
+    int rc = raw_parse(ctx, S, st);
+    const uint32_t n = S.nq;
+    if (!rc && n) {
+        mc_device_batch in{S.dseq, S.dqinfo, S.dmaxwin, 0, n, S.nchars};
+        mc_device_results res{};
+        rc = query_on_pipe(ctx, P, &in, lowestRank, S.maxSingle <= mcamd::lane_max_len() ? mcamd::kQueryNoLongReads : 0, &res, st);
+        if (!rc) {
+            DeliverTable dt{};
+            dt.e[0] = DeliverEntry{S.hcands, S.hqstat, 0u, n}; dt.n = 1;
+            launch_deliver(dt, res.cands, P.bQstat.p, (uint32_t)ctx->cfg.max_candidates, st);
+        }
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    if (!rc && e != hipSuccess) rc = fail(ctx, MC_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
+    { std::lock_guard<std::mutex> l(ctx->coMu); ctx->coFree.push_back(D); }
+    ctx->coCv.notify_one();
+    if (rc) return rc;
+    S.submittedQueries = n; S.coRc = MC_OK; S.coEvent = false; S.coErr.clear();
+    { std::lock_guard<std::mutex> l(ctx->coMu); S.coState = 3; }
+    S.submitted = true;
+    return MC_OK;
+}
+
 static void release_pipe(mc_ctx* ctx, Slot& S)
 {
     if (!S.pipe) return;
@@ -1488,6 +1595,7 @@ int mc_batch_clear(mc_ctx* ctx, uint32_t slot)
     } else if (S.submitted) (void)hipEventSynchronize(S.done);
     release_pipe(ctx, S);
     S.submitted = false; S.nq = 0; S.nchars = 0; S.maxSingle = 0;
+    S.raw = false; S.rawBytes = 0;
     return MC_OK;
 }
 

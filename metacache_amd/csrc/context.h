@@ -84,6 +84,11 @@ struct Slot {
     // pinned results
     mc_candidate* hcands = nullptr; QueryStat* hqstat = nullptr; uint32_t* hhitcounts = nullptr;
     uint64_t* hhitoff = nullptr; mc_location* hhits = nullptr; size_t hhitsCap = 0;
+    // raw input (mc_batch_add_file_bytes): hseq holds a byte range of a FASTA / FASTQ file; mc_batch_submit uploads it to draw and has
+    // mc_parse_records cut it into dseq / dqinfo / dmaxwin -- the buffers of its own are made by the slot's first raw batch
+    bool raw = false; uint64_t rawBytes = 0, rawInsertMax = 0; int rawFlags = 0;
+    uint8_t* draw = nullptr; void* dparseWs = nullptr; uint32_t* dhdr = nullptr; uint8_t* dnames = nullptr; uint64_t* dnameoff = nullptr; uint64_t* dstatus = nullptr;
+    uint32_t* hhdr = nullptr; uint64_t* hstatus = nullptr;   // pinned: the headers' places in the range, mc_parse_records' status
     hipEvent_t done = nullptr;
     bool submitted = false;
     uint32_t submittedQueries = 0;
@@ -190,6 +195,10 @@ void free_evaluate_state(mc_ctx* ctx);
 struct FormatState;
 void free_format_state(mc_ctx* ctx);
 
+// parse.hip: the counters and the staging of mc_parse_* (made on first use), freed with the context
+struct ParseState;
+void free_parse_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -247,6 +256,9 @@ struct mc_ctx {
     mcamd::FormatState* format = nullptr;  // made by the first mc_format_set_text
     uint32_t formatStageRows = 0;          // MC_FORMAT_HOST: reads per staged piece (mc_set_tuning "format_stage_rows"; 0 = what 64 MB of candidates hold)
     uint64_t formatStageHits = 0;          // mc_format_matches(MC_FORMAT_HOST): locations per staged piece (mc_set_tuning "format_stage_hits"; 0 = 4 Mi locations)
+
+    std::mutex parseMtx;
+    mcamd::ParseState* parse = nullptr;    // made by the first mc_parse_records that reaches the device
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

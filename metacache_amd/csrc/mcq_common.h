@@ -224,6 +224,26 @@ public:
     }
     size_t records() const { return streaming_ ? streamCount_.load() + recs_.size() : (exact_ ? recs_.size() : starts_.size()); }
 
+    // the bytes [b, e) of the mapping that hold exactly the records [i, j), i < j <= the records that can be read -- where all of them
+    // come from the fast scan of a plain mapped file (not from the exact reader, not from inflated input): a range that is regular
+    // under the record rule of mc_parse_records
+    bool byte_range(size_t i, size_t j, const char*& base, size_t& b, size_t& e) const
+    {
+        if (!mapped_ || i >= j) return false;
+        if (streaming_) {
+            const size_t sc = streamCount_.load(std::memory_order_acquire);
+            if (j > sc) return false;
+            b = stream_start(i);
+            e = j < sc ? stream_start(j) : streamEnd_.load(std::memory_order_acquire);
+        } else {
+            if (exact_ || j > starts_.size()) return false;
+            b = (size_t)starts_[i];
+            e = j < starts_.size() ? (size_t)starts_[j] : size_;
+        }
+        base = data_;
+        return true;
+    }
+
     // sequence_reader::read_next: header without the marker, sequence lines joined ('scratch' only for multi-line records)
     void record(size_t i, View& header, View& seq, std::string& scratch) const
     {

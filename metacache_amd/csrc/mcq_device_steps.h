@@ -331,4 +331,41 @@ struct FormatClient {                        // a worker's batch as the library 
     }
 };
 
+// ---- parse (mc_batch_add_file_bytes): a batch's reads cut out of the file's bytes on the device ---------------------------
+// MCQ_PARSE_DEVICE=1.  The host index (SeqFile) stays: it numbers the queries, cuts the batches and hands irregular files to its exact
+// reader.  A batch whose records all come from the fast scan of a plain mapped file goes to its slot as ONE byte range; the library cuts
+// it, and the step takes the headers' places and the reads' lengths from mc_batch_records.  Whatever the device refuses, a record count
+// that differs from the index's, or a range the slot cannot take leaves the WHOLE batch to the host loop (SlotStep).
+struct ParseStep : DeviceStep {
+    uint64_t bytes = 0, records = 0; int flags = 0;
+    void took(uint64_t nbytes, uint64_t nrecords) { std::lock_guard<std::mutex> g(mtx); ++calls; bytes += nbytes; records += nrecords; }
+    static bool any_gzip(const Options& o)
+    {
+        for (const std::string& f : o.infiles) {
+            unsigned char m[2] = {0, 0};
+            std::ifstream is(f, std::ios::binary);
+            if (is.read((char*)m, 2) && m[0] == 0x1f && m[1] == 0x8b) return true;
+        }
+        return false;
+    }
+    void open(const Session& S, const Options& o, bool merged)
+    {
+        const char* sw = std::getenv("MCQ_PARSE_DEVICE");
+        if (!sw || std::atoi(sw) == 0) return;
+        const bool selects = o.minReadLen > 0 || o.maxReadLen < std::numeric_limits<uint64_t>::max() || o.queryLimit < ((int64_t)1 << 62);
+        const char* first = o.pairing == Options::files ? "-pairfiles: a query's two reads lie in two files"
+                          : selects ? "length filters and -query-limit select the reads on the host"
+                          : any_gzip(o) ? "gzip input is inflated on the host" : nullptr;
+        off = shared_host_reason(S, merged, false, "", first);
+        if (!off.empty()) return;
+        ctx = S.ctx;
+        flags = o.pairing == Options::sequences ? MC_PARSE_PAIRS : 0;
+    }
+    void report(const Profile& P) const
+    {
+        DeviceStep::report(P, "reads parsed on the device: " + std::to_string(calls) + " batches, " + std::to_string(bytes) + " bytes, " + std::to_string(records) + " records, ",
+                           " batches parsed on the host", "reads parsed on the host");
+    }
+};
+
 #endif  // MCQ_DEVICE_STEPS_H_

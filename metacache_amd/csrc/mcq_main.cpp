@@ -975,10 +975,55 @@ struct SlotStep {
     const Session& S; const Options& o; BatchQueue& Q; Profile& P; mc_ctx* const ctx; const unsigned slot;
     const bool prints = true;
     std::vector<Query> queries = {}; Records rec = {};
+    ParseStep* parse = nullptr;                                             // MCQ_PARSE_DEVICE: the batch's byte range goes to the slot, the library cuts it
+
+    // the whole batch through mc_batch_add_file_bytes.  true: it was emitted; false: nothing was, and the host loop takes it (or the job has failed)
+    template <class Emit>
+    bool parsed_on_device(Batch& B, Emit&& emit)
+    {
+        const size_t per = o.pairing == Options::sequences ? 2 : 1;
+        if (B.sel || B.qEnd <= B.qBeg) return false;
+        const size_t r0 = B.qBeg * per, r1 = B.qEnd * per - (B.halfLast ? 1 : 0);
+        const char* base = nullptr; size_t b = 0, e = 0;
+        if (!Q.files[B.f1]->byte_range(r0, r1, base, b, e)) { parse->note("its records come from the exact reader"); return false; }
+        const uint64_t tp0 = now_ns();
+        const int rc = mc_batch_add_file_bytes(ctx, slot, base + b, e - b, parse->flags, o.insertMax);
+        if (rc == MC_BATCH_FULL) { parse->note("its bytes exceed the slot's character capacity"); return false; }
+        if (rc < 0) { Q.fail(mc_last_error(ctx)); return false; }
+        mc_results r;
+        mc_batch_record_info info;
+        const uint64_t tp1 = now_ns();
+        if (mc_batch_submit(ctx, slot, o.lowest) != MC_OK) { Q.fail(mc_last_error(ctx)); mc_batch_clear(ctx, slot); return false; }
+        const uint64_t tp2 = now_ns();
+        if (mc_batch_wait(ctx, slot, &r) != MC_OK || mc_batch_records(ctx, slot, &info) != MC_OK) { Q.fail(mc_last_error(ctx)); mc_batch_clear(ctx, slot); return false; }
+        const uint64_t tp3 = now_ns();
+        std::string why;
+        if (info.verdict == MC_PARSE_IRREGULAR) why = "irregular at byte " + std::to_string(b + info.offence);
+        else if (info.verdict != MC_PARSE_OK) why = "more reads or characters than the slot takes";
+        else if (info.records != r1 - r0 || r.num_queries != B.qEnd - B.qBeg) why = "the device counts " + std::to_string(info.records) + " records, the index " + std::to_string(r1 - r0);
+        if (!why.empty()) { mc_batch_clear(ctx, slot); parse->note(why); return false; }
+        queries.clear();
+        for (size_t q = B.qBeg; q < B.qEnd; ++q) {
+            const size_t i = q - B.qBeg, rr = i * per;
+            const bool halfPair = B.halfLast && q + 1 == B.qEnd;
+            const View h{base + b + info.hdr[2 * rr], info.hdr[2 * rr + 1]};
+            const uint64_t l1 = info.qinfo[4 * i + 1], l2 = info.qinfo[4 * i + 3];
+            queries.push_back(Query{B.idBase + q + (halfPair ? 0 : 1), h, h.empty() || l1 == 0, l1 + l2, q});
+        }
+        emit(queries, r);
+        mc_batch_clear(ctx, slot);
+        parse->took(e - b, info.records);
+        if (P.on) { P.parse += tp1 - tp0; P.submit += tp2 - tp1; P.wait += tp3 - tp2; P.classify += now_ns() - tp3; }
+        return true;
+    }
 
     template <class Emit>
     bool operator()(Batch& B, Emit&& emit)
     {
+        if (parse && parse->ctx) {
+            if (parsed_on_device(B, emit)) return true;
+            if (Q.failed()) return false;
+        }
         for (size_t q = B.qBeg; q < B.qEnd;) {
             if (Q.failed()) return false;
             queries.clear();
@@ -1399,7 +1444,8 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     std::vector<Tally> tallies(S.workers);
     TargetCache targets(o.showErrors);                                      // -align: the target records of this job
     const bool aligning = o.align && !merged;
-    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep;              // the hand-offs to the library (mcq_device_steps.h)
+    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep; ParseStep parseStep;   // the hand-offs to the library (mcq_device_steps.h)
+    parseStep.open(S, o, merged != nullptr);
     hitsStep.open(S, o, merged != nullptr, covMode);
     evalStep.open(S, o, merged != nullptr, covMode);
     fmtStep.open(S, o, merged != nullptr, covMode, aligning);
@@ -1423,7 +1469,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
             Q.rewind();
             run_workers(S.workers, [&](unsigned w) { worker(w, SetStep{S, o, Q, g > 0, g + 1 == groups}); });
         }
-    } else run_workers(S.workers, [&](unsigned w) { worker(w, SlotStep{S, o, Q, P, S.replica(w % S.replication), w / S.replication}); });
+    } else run_workers(S.workers, [&](unsigned w) { worker(w, SlotStep{S, o, Q, P, S.replica(w % S.replication), w / S.replication, true, {}, {}, &parseStep}); });
     Q.finish();
     W.close();
     Q.rethrow();
@@ -1449,6 +1495,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    parseStep.report(P);
     fmtStep.report(P);
     evalStep.report(P);
     hitsStep.report(P, T.covers.size());
