@@ -1,5 +1,6 @@
-// metacache_amd/csrc/context.cpp -- host side of the C ABI: context, the per-batch pipeline, host slots, timing (table loading:
-// table_load.cpp).  (Compiled with hipcc; the kernels live in kernels.hip.)
+// metacache_amd/csrc/context.cpp -- host side of the C ABI: context, tuning, timing, the host slots with their coalescer, the pipes'
+// reservations (the per-batch pipeline: query_pipe.cpp, its plan: query_rules.h; table loading: table_load.cpp).  (Compiled with hipcc;
+// the kernels live in kernels.hip.)
 #include "context.h"
 #include "devcache.h"
 #include "rows_common.h"
@@ -282,15 +283,13 @@ void mc_destroy(mc_ctx* ctx)
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);
     auto free_pipe = [](Pipe& P, bool ownStream) {
-        DevBuf* pb[] = {&P.bWinCount, &P.bWinOff, &P.bFeatures, &P.bPsize, &P.bPpay, &P.bQstat, &P.bHitOff, &P.bHits, &P.bCscr, &P.bCscr2,
-                        &P.bScan, &P.bStats, &P.bCands, &P.bScanIn, &P.bQflag, &P.bMid, &P.bChunkList, &P.bBigPool, &P.bSliceFill, &P.bBigPool2, &P.bSortTmp, &P.bSide, &P.bNumbers, &P.bCounts, &P.bOrder};
         if (P.stream) (void)hipStreamSynchronize(P.stream);
         if (P.hTotal) (void)hipHostFree(P.hTotal);
         if (P.tail.mainDone) (void)hipEventDestroy(P.tail.mainDone);
         if (P.sortSide.stream) { (void)hipStreamSynchronize(P.sortSide.stream); (void)hipStreamDestroy(P.sortSide.stream); }
         if (P.sortSide.fork) (void)hipEventDestroy(P.sortSide.fork);
         if (P.sortSide.join) (void)hipEventDestroy(P.sortSide.join);
-        for (auto* b : pb) if (b->p) (void)hipFree(b->p);
+        for (DevBuf* b : P.buffers()) if (b->p) (void)hipFree(b->p);
         if (ownStream && P.stream) (void)hipStreamDestroy(P.stream);
     };
     free_pipe(ctx->pipe0, false);
@@ -358,8 +357,10 @@ int mc_db_info(const mc_ctx* ctx, uint64_t info[8])
     return MC_OK;
 }
 
+}  // extern "C"
+
 // taxkey[tgt] = lowest_ranked_ancestor(tgt, rank) as taxon index + 1 (taxonomy.hpp:1260-1267)
-static int taxkey_for_rank(mc_ctx* ctx, int rank, const uint32_t** out)
+int mcamd::taxkey_for_rank(mc_ctx* ctx, int rank, const uint32_t** out)
 {
     *out = nullptr;
     if (rank <= 0) return MC_OK;
@@ -381,690 +382,7 @@ static int taxkey_for_rank(mc_ctx* ctx, int rank, const uint32_t** out)
     return MC_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// the per-batch pipeline
-// ------------------------------------------------------------------------------------------------
-// the pinned words a batch's host round trips land in (Pipe::hTotal), made on the pipe's first use
-static int ensure_host_words(mc_ctx* ctx, Pipe& P) { if (!P.hTotal) HIP_TRY(ctx, hipHostMalloc((void**)&P.hTotal, 128)); return MC_OK; }
-// a Workspace that carries the context's tuning (mc_set_tuning), no buffers yet
-static Workspace tuned_workspace(const mc_ctx* ctx)
-{
-    Workspace ws{};
-    ws.filterBpc = ctx->filterBpc; ws.countBpc = ctx->countBpc; ws.gwFuse = ctx->gwFuse; ws.gwBigH = ctx->gwBigH; ws.gwMidH = ctx->gwMidH;
-    return ws;
-}
-// the global window numbers of the compact store (mc_load_target_windows) for the kernels that decode them
-static void set_window_numbering(const mc_ctx* ctx, DeviceTable& tab)
-{
-    tab.gwBase = ctx->dGwBase; tab.gwDir = ctx->dGwDir; tab.gwDirShift = ctx->gwDirShift; tab.gwGap = ctx->gwGap; tab.gwTargets = ctx->gwTargets;
-}
-// room for `entries` locations to be sorted: the lists, the sort's scratch (a second one only where a taxon key is sorted along)
-static int ensure_sort_space(mc_ctx* ctx, Pipe& P, uint64_t entries, const uint32_t* taxkey, Workspace& ws)
-{
-    int rc = MC_OK;
-    const size_t hb = (size_t)(entries + 1) * 8;
-    if ((rc = ensure(ctx, P.bHits, hb)) || (rc = ensure(ctx, P.bCscr, hb)) || (taxkey && (rc = ensure(ctx, P.bCscr2, hb)))) return rc;
-    ws.hits = (uint64_t*)P.bHits.p; ws.cscr = (uint64_t*)P.bCscr.p; ws.cscr2 = (uint64_t*)P.bCscr2.p;
-    return MC_OK;
-}
-// what every candidate call hands back: the pipe's candidates and hit counts, the sorted location lists where the call delivers them
-static void publish_results(mc_device_results* out, const Pipe& P, const Workspace& ws, bool withLists)
-{
-    out->cands = (const mc_candidate*)P.bCands.p; out->hit_counts = (const uint32_t*)P.bQstat.p;   // (QueryStat.hits: stride 4 words)
-    out->hit_offsets = withLists ? ws.hitOff : nullptr;
-    out->hits = withLists ? (const mc_location*)ws.hits : nullptr;
-    out->features = nullptr; out->win_offsets = nullptr;
-}
-
-// the sorted class of the filtered path: filtered lists the counting kernels do not take (long reads: thousands of numbers, wide window
-// ranges) are sorted -- one segmented sort over the pool -- and scanned (gw_sorted_cands_kernel); the filter kernels counted them.
-// The one place of the filtered path where the host looks at a device counter (how many such lists: the sort's segment count).
-static int run_sorted_tail(mc_ctx* ctx, Pipe& P, BatchRun& r, bool counterCopied)
-{
-    int rc = MC_OK;
-    Workspace& ws = r.ws;
-    const uint32_t n = r.b.n;
-    hipStream_t st = r.st;
-    if ((rc = ensure_host_words(ctx, P))) return rc;
-    uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
-    if (!counterCopied) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
-    HIP_TRY(ctx, traced_sync(st));
-    {   // MC_GW_DIAG=1: the batch's work-list counters on stderr (the classes of the filtered path)
-        static const bool diag = [] { const char* e = std::getenv("MC_GW_DIAG"); return e && e[0] == '1'; }();
-        if (diag) {
-            uint32_t mc[kCounterWords];
-            HIP_TRY(ctx, hipMemcpy(mc, ws.midCount, sizeof mc, hipMemcpyDeviceToHost));
-            std::fprintf(stderr, "[gw diag] n %u filtered %u | stream filter %u | counted apart: 257..512 %u, 513..1024 %u | sorted %u\n",
-                         n, mc[kCntFilter], mc[kCntStream], mc[kCnt512], mc[kCnt1024], mc[kCntSorted]);
-        }
-    }
-    if (!*nsorted) return MC_OK;
-    if ((rc = ensure(ctx, P.bBigPool2, r.poolEntries * 4))) return rc;
-    ws.bigPool2 = (uint32_t*)P.bBigPool2.p;
-    const uint32_t nseg = std::min(*nsorted, n);
-    // the sorted class longest list first: the segmented sort (a block per segment) and the scan (a wave per list) take them in this order
-    size_t ordBytes = 0;
-    if (launch_gw_order(kSideSorted, ws, n, nseg, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists: size query failed");
-    if ((rc = ensure(ctx, P.bOrder, (size_t)3 * std::max<uint32_t>(n, 1) * 4 + ordBytes + 256))) return rc;
-    size_t tmpBytes = 0;
-    if (launch_gw_segsort(nullptr, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, r.poolEntries, ws, n, nseg, ctx->gwBits, st) != 0)
-        return fail(ctx, MC_ERR_HIP, "segmented sort: size query failed");
-    if ((rc = ensure(ctx, P.bSortTmp, tmpBytes + 256))) return rc;
-    {
-        ScopedTimer t(ctx, "gw_sort", st);
-        if (launch_gw_order(kSideSorted, ws, n, nseg, (uint32_t*)P.bOrder.p, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the sorted lists failed");
-        if (!P.sortSide.stream) {
-            if (hipStreamCreateWithFlags(&P.sortSide.stream, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&P.sortSide.fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&P.sortSide.join, hipEventDisableTiming) != hipSuccess) P.sortSide = GwSortSide{};
-        }
-        if (launch_gw_segsort(P.bSortTmp.p, tmpBytes, (const uint32_t*)ws.bigPool, ws.bigPool2, r.poolEntries, ws, n, nseg, ctx->gwBits, st, &P.sortSide) != 0)
-            return fail(ctx, MC_ERR_HIP, "segmented sort failed");
-    }
-    { ScopedTimer t(ctx, "gw_sorted_cands", st); launch_big_cands(FilterStep::SortedCands, r.b, r.sp, r.tab, ws, r.K, r.taxkey, r.cands, st); }
-    return MC_OK;
-}
-
-// The filtered candidate path on the work list the probing kernels (or, on the owner side of Mode K, owner_entries_kernel) left
-// in kListFilter: filter -> counting -> [segmented sort -> scan of the sorted lists].
-// second (8-byte store): reads beyond the first filter's reach take its second instance.
-// deferSorted: the sorted class is left to the caller (mc_query_finish runs run_sorted_tail).
-// The path's first step alone: the filter (compact store, "filter_lookup": followed by gw_filter_count_kernel<LOOKUP> inside the SAME pair of
-// timer events -- the timer's count stays one per batch).  The caller launches what waits for the LOOKUP instance's work lists (the mid / hash
-// kernels) between this and run_filtered_path(.., filterDone = true).
-static void run_filter_step(mc_ctx* ctx, BatchRun& r)
-{
-    ScopedTimer t(ctx, r.compact ? (r.ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", r.st);
-    launch_big_cands(FilterStep::Filter, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
-    if (r.compact && r.ws.filterLookup) launch_big_cands(FilterStep::FilterLookup, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
-}
-
-static int run_filtered_path(mc_ctx* ctx, Pipe& P, BatchRun& r, bool second, bool deferSorted = false, bool filterDone = false)
-{
-    // timers carry the kernels' own names, one kernel each (a bench line's dominant "kernel" must be one): compact store gw_filter_count_kernel
-    // (or gw_filter_kernel with "gw_fuse" 0), gw_filter2, gw_compact (+ the ordering of the stream filter's reads), gw_filter_stream<fine>,
-    // <mid>, gw_filter_stream (+ the second compaction), gw_count_kernel<9>, <10>, <11>; 8-byte store: big_*
-    // (compact store: gw_filter_kernel itself may leave reads to the second kernel -- it counts them on the device, after the
-    // host's look at the counters: always launched, returns at once with nothing to do)
-    if (!filterDone) run_filter_step(ctx, r);
-    const bool compact = r.compact, always = true, compactOnly = compact, wideSecond = !compact && second;   // when a step runs
-    const struct { FilterStep step; const char* timer; bool when; } steps[] = {
-        {FilterStep::PairFilter, "gw_filter2", compactOnly},
-        {FilterStep::Compact, "gw_compact", compactOnly},
-        {FilterStep::StreamFine, "gw_filter_stream_fine", compactOnly},
-        {FilterStep::StreamMid, "gw_filter_stream_mid", compactOnly},
-        {FilterStep::Stream, "gw_filter_stream", compactOnly},
-        {FilterStep::BigFilter2, "big_filter_2", wideSecond},
-        {FilterStep::Count, compact ? "gw_count" : "big_count", always},
-        {FilterStep::Count512, "gw_count_512", compactOnly},
-        {FilterStep::Count1024, compact ? "gw_count_1024" : "big_count_2", always},
-    };
-    for (const auto& s : steps)
-        if (s.when) { ScopedTimer t(ctx, s.timer, r.st); launch_big_cands(s.step, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st); }
-    if (compact && !deferSorted) return run_sorted_tail(ctx, P, r, false);
-    return MC_OK;
-}
-
-// What the lane path did not finish goes through the exact wave kernels (long reads, duplicate hashes, reads the filtered path handed
-// back, -allhits, ...): sketch + probe unless done, segments for their location lists (the host sizes them: one round trip), sort + candidates.
-// sortedIsMine (small batches whose filtered path left its sorted class to this call): the host's look at that class's counter shares this
-// call's one round trip -- the wave kernels' sketching and the scan go out first; in the rare batch that has sorted lists they run again
-// behind run_sorted_tail (query_kernel takes the reads still flagged for it: a second pass finds only what the sorted class handed back).
-static int run_wave_tail(mc_ctx* ctx, Pipe& P, BatchRun& r, bool sortedIsMine = false)
-{
-    int rc = MC_OK;
-    Workspace& ws = r.ws;
-    const BatchView& b = r.b;
-    const uint32_t n = b.n;
-    hipStream_t st = r.st;
-    if ((rc = ensure_host_words(ctx, P))) return rc;
-    auto sketch_and_scan = [&]() {
-        if (!r.skipWaveSketch) { ScopedTimer t(ctx, "query_wave", st); launch_query(b, r.sp, r.tab, r.fuse, r.wantAllhits, ws, r.K, r.cands, st); }
-        ScopedTimer t(ctx, "scan", st);
-        // (how many locations need a segment in HBM: the total goes to pinned host memory with the scan)
-        launch_scan_u32(ws.hitScan, 1, n, nullptr, ws.hitOff, ws.scanTmp, st, P.hTotal);
-    };
-    sketch_and_scan();
-    uint32_t* nsorted = reinterpret_cast<uint32_t*>(P.hTotal + 9);
-    if (sortedIsMine) launch_words_to_host(nsorted, ws.midCount + kCntSorted, 1, st);
-    HIP_TRY(ctx, traced_sync(st));
-    if (sortedIsMine && *nsorted) {
-        if ((rc = run_sorted_tail(ctx, P, r, true))) return rc;
-        sketch_and_scan();
-        HIP_TRY(ctx, traced_sync(st));
-    }
-    const uint64_t totalHits = *P.hTotal;
-    if ((rc = ensure_sort_space(ctx, P, totalHits, r.taxkey, ws))) return rc;
-    if (r.wantNumbers && ((rc = ensure(ctx, P.bNumbers, (size_t)(totalHits + 8) * 4)) || (rc = ensure(ctx, P.bCounts, (size_t)(n + 1) * 4)))) return rc;
-    if (r.wantPartial && r.lanePath && !r.wantNumbers) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, r.sp, r.tab, ws, nullptr, st); }
-    { ScopedTimer t(ctx, "sort_candidates", st); launch_sort_candidates(b, r.sp, r.tab, ws, r.taxkey, r.K, r.wantAllhits, r.cands, st); }
-    if (r.wantNumbers) {
-        // what the wave kernels left in ws.hits -> numbers, then the lane path's (and the chunk lanes') lists straight from the table
-        { ScopedTimer t(ctx, "pack_numbers", st); launch_pack_other_reads(b, r.tab, ws, (uint32_t*)P.bNumbers.p, (uint32_t*)P.bCounts.p, st); }
-        if (r.lanePath) { ScopedTimer t(ctx, "gather_lists", st); launch_gather_lists(b, r.sp, r.tab, ws, (uint32_t*)P.bNumbers.p, st); }
-        P.numbersN = n; P.numbersTotal = totalHits;
-    }
-    return MC_OK;
-}
-
-// the rare classes of a batch whose main kernels mc_query_device(MC_DEFER_TAIL) enqueued: sorted lists, then the exact wave kernels
-static int finish_on_pipe(mc_ctx* ctx, Pipe& P)
-{
-    Pipe::Tail& tl = P.tail;
-    if (!tl.pending) return MC_OK;
-    tl.pending = false;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipEventSynchronize(tl.mainDone));
-    int rc = MC_OK;
-    tl.run.wantAllhits = false; tl.run.wantPartial = false; tl.run.wantNumbers = false; tl.run.lanePath = true;   // (only top candidates on the lane path are deferred)
-    if (tl.sortedPath && (rc = run_sorted_tail(ctx, P, tl.run, true))) return rc;
-    if ((rc = run_wave_tail(ctx, P, tl.run))) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    return MC_OK;
-}
-
-// A call takes pipe P: the device, pipe1's stream on its first use, the tail of a batch the caller deferred on P and never asked for (it
-// still owns the workspace this call is about to reuse), and the stream the call enqueues on -- the caller's, else the pipe's own
-static int enter_pipe(mc_ctx* ctx, Pipe& P, void* streamv, hipStream_t& st)
-{
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (&P == &ctx->pipe1 && !ctx->pipe1.stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->pipe1.stream, hipStreamNonBlocking));
-    if (const int rc = finish_on_pipe(ctx, P)) return rc;
-    st = streamv ? (hipStream_t)streamv : P.stream;
-    return MC_OK;
-}
-
-// A pipe's buffers whose sizes follow from the batch's size (n queries, numChars characters) and the table's mean list length alone --
-// everything mc_query_device needs before its first host round trip.  mc_open_database calls this for every slot pipe WHILE the file
-// loads (reserve_slot_pipes): a hipMalloc of memory another process has just given back takes 100-200 ms per 600 MB, and eight pipes
-// growing their pools inside the first batches made the same `mcq query` run take 81 or 390 ms per 10^7 reads.
-struct PipeSizes { uint64_t poolCap = 0, ovfCap = 0; size_t nfeat = 0; };
-static int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool wantFeatures, bool lanePath, uint64_t locs, uint64_t keys, PipeSizes& out)
-{
-    int rc = MC_OK;
-    const SketchParams sp = ctx->querySketch;
-    const uint32_t K = ctx->cfg.max_candidates;
-    // windows <= chars/stride + 2 per sequence (row 1), so the sketch buffers can be sized without a sync
-    const uint64_t maxWindows = numChars / sp.stride + 4ull * n + 1;
-    if (maxWindows * sp.s > 0xFFFFFFF0ull) return fail(ctx, MC_ERR_UNSUPPORTED, "batch too large (feature index exceeds 32 bits)");
-    const size_t nfeat = (size_t)maxWindows * sp.s;
-    if ((rc = ensure(ctx, P.bWinCount, (size_t)(n + 1) * 4))) return rc;
-    if ((rc = ensure(ctx, P.bWinOff, (size_t)(n + 2) * 4))) return rc;
-    // (the lane path delivers top candidates only: -allhits and K > 4 go through the wave kernels)
-    if ((wantFeatures || lanePath) && (rc = ensure(ctx, P.bFeatures, nfeat * 4))) return rc;
-    if ((rc = ensure(ctx, P.bPsize, nfeat * 4))) return rc;
-    if ((rc = ensure(ctx, P.bPpay, nfeat * 8))) return rc;
-    if ((rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat)))) return rc;
-    if ((rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4))) return rc;
-    if ((rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4))) return rc;
-    if (lanePath && (rc = ensure(ctx, P.bMid, work_lists_bytes(n)))) return rc;
-    // pool of the filtered location lists (big_filter_kernel -> big_count_kernel): 384 per query on average, at least 4 MB
-    // (tables whose features have few locations each never produce such lists: a token pool; a full pool sends lists to the wave kernel)
-    const Part& T0 = ctx->parts[0];
-    const bool longLists = (double)locs / (double)std::max<uint64_t>(keys, 1) * 2.0 * sp.s > 64.0;   // mean list of a 2-window read
-    // (448 per 150 bp read = 3 per base: longer reads collect -- and keep -- in proportion)
-    const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(longLists ? std::max<uint64_t>((uint64_t)n * 448, numChars * 3) : (uint64_t)n * 8,
-                                                                                  (uint64_t)big_filter_grid(n, T0.compact, ctx->filterBpc) * 4 * std::min<uint64_t>(131072, std::max<uint64_t>(4096, 64 * (numChars / std::max<uint32_t>(n, 1))))));   // per wave: one full batch of gw_filter_kernel (2 112 numbers); long reads keep up to 65 535
-    // compact store: behind the waves' slices an OVERFLOW region for filtered lists that may not fit their wave's slice (the longest
-    // reads of a batch keep 10^5 numbers): reserved with one atomic per such read (kCntOverflow)
-    const uint64_t ovfCap = T0.compact ? std::min<uint64_t>(0xFFFFFFF0ull - poolCap, std::max<uint64_t>(poolCap / 4, 8ull << 20)) : 0;
-    if (lanePath && (rc = ensure(ctx, P.bBigPool, (poolCap + ovfCap) * (T0.compact ? 4 : 8)))) return rc;   // the pool holds the table's location form
-    if (lanePath && (rc = ensure(ctx, P.bSliceFill, (size_t)big_filter_grid(n, T0.compact, ctx->filterBpc) * 4 * 4 + 64))) return rc;
-    if (lanePath && T0.compact && (rc = ensure(ctx, P.bSide, (size_t)kSideRows * std::max<uint32_t>(n, 1) * 4))) return rc;
-    if (lanePath && (rc = ensure(ctx, P.bChunkList, (size_t)(maxWindows + n + 1) * 8))) return rc;
-    if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8))) return rc;
-    if ((rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1)))) return rc;
-    if ((rc = ensure(ctx, P.bStats, 64))) return rc;
-    if ((rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate)))) return rc;
-    out.poolCap = poolCap; out.ovfCap = ovfCap; out.nfeat = nfeat;
-    return MC_OK;
-}
-
-static int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
-{
-    // MC_WANT_PARTIAL_HITS: the location lists as they are (unsorted), lane path allowed -- a key shard's side of Mode K; the queries the
-    // lane path does not take go through the wave kernels as with MC_WANT_ALLHITS (their lists come out sorted, which is allowed)
-    // MC_WANT_PARTIAL_NUMBERS: the same, and the lists are left as the 4-byte global window numbers they are stored as (mc_partial_numbers)
-    const bool wantNumbers = (flags & MC_WANT_PARTIAL_NUMBERS) != 0 && !(flags & MC_WANT_ALLHITS);
-    const bool wantPartial = ((flags & MC_WANT_PARTIAL_HITS) != 0 || wantNumbers) && !(flags & MC_WANT_ALLHITS);
-    const int wantAllhits = (flags & MC_WANT_ALLHITS) | (wantPartial ? 1 : 0);
-    const bool wantFeatures = (flags & MC_WANT_FEATURES) != 0;
-    if (!ctx->tableReady) return fail(ctx, MC_ERR_STATE, "no database loaded (every part needs mc_load_begin .. mc_load_end)");
-    if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    if (wantNumbers && (ctx->parts.size() != 1 || !ctx->parts[0].compact || !ctx->dGwBase))
-        return fail(ctx, MC_ERR_UNSUPPORTED, "MC_WANT_PARTIAL_NUMBERS: the database has no global window numbers (compact location store)");
-    hipStream_t st = nullptr;
-    int rc = enter_pipe(ctx, P, streamv, st);
-    if (rc) return rc;
-    const uint32_t n = in->num_queries;
-    P.numbersN = 0xFFFFFFFFu;
-    const SketchParams sp = ctx->querySketch;
-    const uint32_t K = ctx->cfg.max_candidates;
-    const uint32_t* taxkey = nullptr;
-    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
-
-    // the pipe's buffers that depend on the batch's size alone (size_pipe; mc_open_database reserves them beside the file load)
-    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && (!wantAllhits || wantPartial) && lane_candidates_supported(K);
-    const Part& T = ctx->parts[0];
-    uint64_t locs = 0;
-    for (auto& p : ctx->parts) locs += p.locations;
-    PipeSizes sz{};
-    if ((rc = size_pipe(ctx, P, n, in->num_chars, wantFeatures, lanePath, locs, T.keysStored, sz))) return rc;
-
-    BatchRun run{tuned_workspace(ctx)};                          // (filled on the way: its flags are known when the tails are reached)
-    Workspace& ws = run.ws;
-    ws.winCount = (uint32_t*)P.bWinCount.p; ws.winOff = (uint32_t*)P.bWinOff.p;
-    ws.features = (wantFeatures || lanePath) ? (uint32_t*)P.bFeatures.p : nullptr; ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = (uint64_t*)P.bPpay.p;
-    ws.qstat = (QueryStat*)P.bQstat.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
-    ws.scanTmp = P.bScan.p; ws.stats = (uint64_t*)P.bStats.p;
-    if (lanePath) {
-        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
-        ws.bigMin = ctx->bigMin;
-        ws.partialLists = wantPartial ? 1u : 0u;
-        ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)sz.poolCap; ws.bigOvfCap = (uint32_t)sz.ovfCap;
-        ws.sliceFill = (uint32_t*)P.bSliceFill.p;
-        ws.sideList = (uint32_t*)P.bSide.p;
-        ws.chunkList = (flags & kQueryNoLongReads) ? nullptr : (uint2*)P.bChunkList.p;   // (null: no read is cut into chunks, the chunk launchers launch nothing)
-    }
-
-    BatchView b{in->seq, in->qinfo, in->max_win, in->max_win_uniform, n};
-    const bool multiPart = ctx->parts.size() > 1;
-    DeviceTable tab{T.dbuckets, T.dvalues, T.nbuckets, multiPart ? 0x00FFFFFFu : 0xFFFFFFFFu, T.maxProbe};
-    if (T.compact) {
-        tab.values = nullptr; tab.values32 = reinterpret_cast<const uint32_t*>(T.dvalues);
-        set_window_numbering(ctx, tab);
-    }
-    tab.direct = T.ddirect;                                       // (the lane path's lookups; every other kernel goes through the buckets)
-
-    bool planSmall = false;                                      // small batches: plan + scan + the work-list counters' clearing in one launch
-    {
-        ScopedTimer t(ctx, "plan", st);
-        planSmall = launch_plan_scan_small(b, sp, ws.winCount, ws.winOff, lanePath ? ws.midCount : nullptr, st);
-        if (!planSmall) {
-            launch_plan(b, sp, ws.winCount, st);
-            launch_scan_u32(ws.winCount, 1, n, ws.winOff, nullptr, ws.scanTmp, st);
-        }
-    }
-    const bool fuse = !wantAllhits && !taxkey;
-    run.b = b; run.sp = sp; run.tab = tab; run.K = K; run.taxkey = taxkey; run.cands = P.bCands.p; run.st = st; run.poolEntries = sz.poolCap + sz.ovfCap;
-    run.compact = T.compact; run.fuse = fuse; run.wantAllhits = wantAllhits != 0; run.wantPartial = wantPartial; run.wantNumbers = wantNumbers; run.lanePath = lanePath;
-    bool waveWork = true;                                        // wave kernels needed (always without the lane path)
-    bool sortedInTail = false;                                   // the filtered path's sorted class is run_wave_tail's to look at
-    if (lanePath) {
-        // short reads: one lane per query for sketching and candidates, cooperative probing in between
-        if (!planSmall) HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
-        // sketching + probing in ONE kernel where the lookups wait for HBM (tables beyond the infinity cache: quad-cooperative fetches) -- the
-        // sketching of some waves runs under the waiting of others (5.27 -> 5.08 ms per 5 x 10^6 reads at full scale); small tables keep
-        // the two kernels (the ALU phase at the probe kernel's occupancy cost 5 % on configs[1]).  "lane_fusion" / MC_LANE_FUSION: 0 / 1 force it.
-        // (A key shard's side of Mode K masks the features it does not own between the two: not fused.)
-        const bool maskFeatures = wantPartial && !wantFeatures && ctx->cfg.key_shard_count > 1;
-        const bool quadTable = ctx->quadLookup >= 0 ? ctx->quadLookup != 0 : (uint64_t)tab.nbuckets * 64ull > (1ull << 30);
-        const bool fuseSketch = !maskFeatures && (ctx->fuseLane >= 0 ? ctx->fuseLane != 0 : quadTable);
-        // "filter_lookup": the lookups of reads of up to 64 features inside the filter kernel (gw_filter_count_kernel<LOOKUP>, behind the wave
-        // kernel's rejoin); the lane kernel only sketches, the mid / hash kernels wait for the filter's work lists.  Every kernel is launched
-        // without a look at the counters.  -1: tables whose direct index the size rule built (bucket table of 8 GiB or more), on batches that
-        // skip the host's look anyway (MC_DEFER_TAIL or more than 2^20 reads); 1: wherever a direct index exists (tests, A/B runs); 0: never.
-        const bool noHostLook = (flags & MC_DEFER_TAIL) != 0 || n > (1u << 20);
-        // (auto only for the batches it was measured on and won: one window range for all reads, of at most 3 windows -- single reads of up to
-        // two windows.  Batches with a window range per read (long reads, mixed lengths) were measured 1.5 ms per step SLOWER with it, read pairs
-        // (range 4) have not been measured: both keep the old order.  docs/LAB_NOTEBOOK_r07.md section 5)
-        const bool shortSingles = in->max_win == nullptr && in->max_win_uniform <= 3u;
-        const bool filterLookup = T.compact && tab.direct && !wantPartial && !wantAllhits && !maskFeatures && ctx->gwFuse == 1 &&
-                                  (ctx->filterLookup > 0 || (ctx->filterLookup < 0 && noHostLook && shortSingles && (uint64_t)T.nbuckets * sizeof(TableBucket) >= (8ull << 30)));
-        ws.filterLookup = filterLookup ? 1u : 0u;
-        if (filterLookup) {
-            { ScopedTimer t(ctx, "sketch_lane", st); launch_sketch_lane(b, sp, ws, st); }
-            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
-            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
-            { ScopedTimer t(ctx, "probe_cands", st); launch_probe_cands(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }   // (reads of more than 64 features)
-        } else if (fuseSketch) {
-            { ScopedTimer t(ctx, "sketch_probe", st); launch_sketch_probe_lane(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
-            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
-            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
-        } else {
-            { ScopedTimer t(ctx, "sketch_lane", st); launch_sketch_lane(b, sp, ws, st); }
-            { ScopedTimer t(ctx, "chunk_sketch", st); launch_chunk_sketch(b, sp, ws, st); }
-            // a key shard's side of Mode K: only the features this shard owns are looked up (the others cannot be in its table)
-            if (maskFeatures) {
-                ScopedTimer t(ctx, "mask_features", st);
-                launch_mask_foreign_features(ws.features, ws.winOff + n, sp.s, sz.nfeat, ctx->cfg.key_shard_index, ctx->cfg.key_shard_count, st);
-            }
-            { ScopedTimer t(ctx, "chunk_probe", st); launch_chunk_probe(b, sp, tab, ws, ctx->quadLookup, st); }
-            { ScopedTimer t(ctx, "probe_cands", st); launch_probe_cands(b, sp, tab, ws, K, taxkey, P.bCands.p, ctx->quadLookup, st); }
-        }
-        // small batches take one look at the work lists and launch only the kernels with work (a launch costs as much as such a
-        // batch's kernel: 0.37 -> 0.32 ms per 65 536 reads); large ones skip the round trip and launch everything
-        uint32_t all[kHostCounters], none[kHostCounters] = {};   // none (partial lists): no candidate kernels, the wave kernels for the rest
-        std::fill(all, all + kHostCounters, 1u);
-        none[kCntWaveSketch] = none[kCntWaveCands] = 1;
-        uint32_t* hcnt = wantPartial ? none : all;
-        // (MC_DEFER_TAIL: no look at the counters either -- everything is launched, the caller has another batch to enqueue)
-        if (!wantPartial && n <= (1u << 20) && !(flags & MC_DEFER_TAIL) && !filterLookup) {
-            if ((rc = ensure_host_words(ctx, P))) return rc;
-            hcnt = reinterpret_cast<uint32_t*>(P.hTotal + 1);
-            launch_flag_count_host(ws, n, hcnt, st);
-            HIP_TRY(ctx, traced_sync(st));
-        }
-        auto mid_and_hash = [&]() {
-            if (hcnt[kCntMid64]) { ScopedTimer t(ctx, "mid_cands_64", st); launch_mid_cands(kListMid64, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[kCntMid128]) { ScopedTimer t(ctx, "mid_cands_128", st); launch_mid_cands(kListMid128, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[kCntMid256]) { ScopedTimer t(ctx, "mid_cands_256", st); launch_mid_cands(kListMid256, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[kCntHash256]) { ScopedTimer t(ctx, "hash_cands_256", st); launch_hash_cands(kListHash256, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[kCntHash512]) { ScopedTimer t(ctx, "hash_cands_512", st); launch_hash_cands(kListHash512, b, tab, ws, K, taxkey, P.bCands.p, st); }
-            if (hcnt[kCntHash1024]) { ScopedTimer t(ctx, "hash_cands_1024", st); launch_hash_cands(kListHash1024, b, tab, ws, K, taxkey, P.bCands.p, st); }
-        };
-        if (!filterLookup) mid_and_hash();
-        bool waveDone = false;
-        if (T.compact && !wantPartial && hcnt[kCntWaveSketch]) {
-            // compact store: the wave kernel's sketching and probing first, so that its reads can join the filtered path
-            { ScopedTimer t(ctx, "query_wave", st); launch_query(b, sp, tab, fuse, false, ws, K, P.bCands.p, st); }
-            launch_wave_rejoin(b, sp, tab, ws, st);
-            waveDone = true;
-        }
-        if (T.compact && !wantPartial && n <= (1u << 20) && (hcnt == all || hcnt[kCntSecond])) {
-            // reads beyond kGwSmallH locations (long reads): the stream filter takes them longest first (launch_gw_order)
-            size_t ordBytes = 0;
-            if (launch_gw_order(kSideStream, ws, n, n, nullptr, ordBytes, st) != 0) return fail(ctx, MC_ERR_HIP, "ordering of the stream filter's reads: size query failed");
-            if ((rc = ensure(ctx, P.bOrder, (size_t)3 * std::max<uint32_t>(n, 1) * 4 + ordBytes + 256))) return rc;
-            ws.orderScratch = (uint32_t*)P.bOrder.p; ws.orderTemp = ordBytes;
-        }
-        // MC_DEFER_TAIL (large batches on the lane path): everything the host has to look at device counters for -- the sorted class of the
-        // filtered path, the segment sizes of the exact wave kernels' leftovers -- waits for mc_query_finish; this call returns with
-        // the main kernels enqueued and NO synchronisation, so that the caller can enqueue the next batch on the other pipe first
-        const bool defer = (flags & MC_DEFER_TAIL) != 0 && hcnt == all && !wantFeatures;
-        waveWork = wantPartial || hcnt[kCntWaveSketch] != 0 || hcnt[kCntWaveCands] != 0 || hcnt[kCntFilter] != 0;   // big_cands hands a few queries on to the wave kernels
-        // small batches: the sorted class's counter is looked at together with the wave tail's total (run_wave_tail: one round trip for both)
-        sortedInTail = hcnt != all && !defer && T.compact && waveWork && (hcnt[kCntFilter] || waveDone);
-        if (hcnt[kCntFilter] || waveDone) {
-            if (filterLookup) { run_filter_step(ctx, run); mid_and_hash(); }     // (the mid / hash kernels' lists are the LOOKUP instance's)
-            if ((rc = run_filtered_path(ctx, P, run, hcnt[kCntSecond] != 0, defer || sortedInTail, filterLookup))) return rc;
-        }
-        run.skipWaveSketch = waveDone;                           // (the wave kernels' sketching and probing has run already)
-        if (defer) {
-            Pipe::Tail& tl = P.tail;
-            if ((rc = ensure_host_words(ctx, P))) return rc;
-            if (!tl.mainDone) HIP_TRY(ctx, hipEventCreateWithFlags(&tl.mainDone, hipEventDisableTiming));
-            tl.sortedPath = T.compact && (hcnt[kCntFilter] || waveDone);
-            if (tl.sortedPath) HIP_TRY(ctx, hipMemcpyAsync(reinterpret_cast<uint32_t*>(P.hTotal + 9), ws.midCount + kCntSorted, 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(ctx, hipEventRecord(tl.mainDone, st));
-            tl.run = run;
-            tl.pending = true;
-            HIP_TRY(ctx, hipGetLastError());
-            P.lastN = n;
-            publish_results(out, P, ws, false);
-            out->features = ws.features; out->win_offsets = ws.winOff;
-            return MC_OK;
-        }
-    } else {
-        HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)ws.qflag, 1, n, st));     // every query: needs sketch + probe
-    }
-    if (waveWork && (rc = run_wave_tail(ctx, P, run, sortedInTail))) return rc;
-    HIP_TRY(ctx, hipGetLastError());
-    P.lastN = n;
-    publish_results(out, P, ws, wantAllhits != 0);
-    out->features = ws.features; out->win_offsets = ws.winOff;
-    return MC_OK;
-}
-
-int mc_query_device(mc_ctx* ctx, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
-{
-    if (!ctx || !in || !out) return MC_ERR_INVALID;
-    flags &= ~mcamd::kQueryNoLongReads;                           // (internal: the caller of this entry point has not seen the reads)
-    return query_on_pipe(ctx, (flags & MC_SECOND_PIPE) ? ctx->pipe1 : ctx->pipe0, in, lowestRank, flags, out, streamv);
-}
-
-int mc_query_finish(mc_ctx* ctx, int flags)
-{
-    if (!ctx) return MC_ERR_INVALID;
-    return finish_on_pipe(ctx, (flags & MC_SECOND_PIPE) ? ctx->pipe1 : ctx->pipe0);
-}
-
-uint32_t mc_key_owner(uint32_t feature, uint32_t shardCount) { return key_owner(feature, shardCount); }
-
-int mc_candidates_from_hits(mc_ctx* ctx, const mc_device_hits* in, int lowestRank, mc_device_results* out, void* streamv)
-{
-    if (!ctx || !in || !out || !in->hit_offsets) return MC_ERR_INVALID;
-    if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    Pipe& P = ctx->pipe0;
-    hipStream_t st = nullptr;
-    int rc = enter_pipe(ctx, P, streamv, st);
-    if (rc) return rc;
-    const uint32_t n = in->num_queries;
-    const uint32_t K = ctx->cfg.max_candidates;
-    const uint32_t* taxkey = nullptr;
-    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
-    uint64_t total = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&total, in->hit_offsets + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, traced_sync(st));
-    Workspace ws = tuned_workspace(ctx);
-    if ((rc = ensure_sort_space(ctx, P, total, taxkey, ws))) return rc;
-    if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) ||
-        (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))))
-        return rc;
-    // the lists are sorted in place: work on a copy inside the context
-    if (total) HIP_TRY(ctx, hipMemcpyAsync(P.bHits.p, in->hits, total * 8, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(P.bHitOff.p, in->hit_offsets, (size_t)(n + 1) * 8, hipMemcpyDeviceToDevice, st));
-    ws.hitOff = (uint64_t*)P.bHitOff.p; ws.qstat = (QueryStat*)P.bQstat.p;
-    BatchView b{nullptr, nullptr, in->max_win, in->max_win_uniform, n};
-    DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-    {
-        ScopedTimer t(ctx, "cands_from_hits", st);
-        launch_cands_from_hits(b, tab, ws, taxkey, K, P.bCands.p, st);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    P.lastN = 0;
-    publish_results(out, P, ws, true);
-    return MC_OK;
-}
-
-// Mode K, owner side in one call: union of the sources' partial lists (device side, no host round trip), then rows 8-10 on it
-int mc_candidates_from_partial_hits(mc_ctx* ctx, const mc_device_partial_hits* in, int lowestRank, mc_device_results* out, void* streamv)
-{
-    if (!ctx || !in || !out || !in->counts || (!in->hits && in->total_hits) || in->num_sources < 1) return MC_ERR_INVALID;
-    if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    Pipe& P = ctx->pipe0;
-    hipStream_t st = nullptr;
-    int rc = enter_pipe(ctx, P, streamv, st);
-    if (rc) return rc;
-    const uint32_t n = in->num_queries, S = in->num_sources;
-    const uint32_t K = ctx->cfg.max_candidates;
-    const uint32_t* taxkey = nullptr;
-    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
-    Workspace ws = tuned_workspace(ctx);
-    if ((rc = ensure_sort_space(ctx, P, in->total_hits, taxkey, ws))) return rc;
-    if ((rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) ||
-        (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))) ||
-        (rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1))) ||
-        (rc = ensure(ctx, P.bPpay, ((size_t)S * (n + 2) + n + 1) * 8)) || (rc = ensure(ctx, P.bPsize, (size_t)(n + 1) * 4)) ||
-        (rc = ensure(ctx, P.bWinOff, (size_t)(n + 2) * 4)) || (rc = ensure(ctx, P.bWinCount, (size_t)(n + 1) * 4)) ||
-        (rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bMid, work_lists_bytes(n))))
-        return rc;
-    const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>((uint64_t)n * 448, (uint64_t)big_filter_grid(n, false, ctx->filterBpc) * 4 * 1024));
-    if ((rc = ensure(ctx, P.bBigPool, poolCap * 8))) return rc;
-    // srcStart (union) and the one-entry-per-read tables of the filtered path share bPpay: [S * (n + 2)] u64 | [n] u64
-    uint64_t* srcStart = (uint64_t*)P.bPpay.p;
-    launch_union_partial(in->counts, S, n, reinterpret_cast<const uint64_t*>(in->hits), (uint32_t*)P.bScanIn.p, srcStart, (uint64_t*)P.bHitOff.p,
-                         (uint64_t*)P.bHits.p, P.bScan.p, st);
-    ws.hitOff = (uint64_t*)P.bHitOff.p; ws.qstat = (QueryStat*)P.bQstat.p;
-    BatchView b{nullptr, nullptr, in->max_win, in->max_win_uniform, n};
-    // Long united lists (RefSeq scale: 1 300 locations per read) take the filtered path of the replicated mode instead of a sort: the union
-    // buffer stands in for the table's location store, a read's whole list is ONE entry of it (rounds of 16 / 64 locations); what the
-    // filter cannot take (more than 16 384 locations, wide window ranges) and what it hands back goes through the sort as before.
-    const bool filtered = lane_candidates_supported(K) && ctx->useLanePath;
-    if (filtered) {
-        ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
-        ws.bigMin = ctx->bigMin; ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap;
-        ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = srcStart + (size_t)S * (n + 2);
-        ws.winOff = (uint32_t*)P.bWinOff.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitScan = (uint32_t*)P.bWinCount.p;
-        HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
-        launch_owner_classify(b, ws, std::max<uint32_t>(ctx->bigMin, 256u), st);
-        DeviceTable utab{nullptr, ws.hits, 0, 0xFFFFFFFFu, 1};
-        const SketchParams one{16, 1, 16, 1};                                  // step D finds a read's entry at winOff[q] * s = q
-        { ScopedTimer t(ctx, "big_filter", st); launch_big_cands(FilterStep::Filter, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "big_count", st); launch_big_cands(FilterStep::Count, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
-        { ScopedTimer t(ctx, "big_count_2", st); launch_big_cands(FilterStep::Count1024, b, one, utab, ws, K, taxkey, P.bCands.p, st); }
-    }
-    DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-    {
-        ScopedTimer t(ctx, "cands_from_hits", st);
-        launch_cands_from_hits(b, tab, ws, taxkey, K, P.bCands.p, st);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    P.lastN = 0;
-    publish_results(out, P, ws, true);
-    return MC_OK;
-}
-
-// ---- Mode K with 4-byte locations on the wire (keyshard.hip) --------------------------------------------------------------------------
-// shard side: the partial lists of the last mc_query_device(MC_WANT_PARTIAL_HITS) call as global window numbers + per-read counts
-int mc_partial_numbers(mc_ctx* ctx, const mc_device_results* res, uint32_t n, const uint32_t* cutQueries, uint32_t numCuts, uint64_t* cutOffsets,
-                       mc_device_partial_numbers* out, void* streamv)
-{
-    if (!ctx || !res || !out || (numCuts && (!cutQueries || !cutOffsets))) return MC_ERR_INVALID;
-    if (!res->hit_offsets) return fail(ctx, MC_ERR_STATE, "mc_partial_numbers: the results hold no location lists (MC_WANT_PARTIAL_HITS)");
-    if (ctx->parts.size() != 1 || !ctx->parts[0].compact || !ctx->dGwBase)
-        return fail(ctx, MC_ERR_UNSUPPORTED, "mc_partial_numbers: the database has no global window numbers (compact location store)");
-    // (the pipe whose batch these results are: a caller with two batches in flight -- keyset.cpp's lanes -- runs the shards' lookups on either)
-    Pipe& P = (ctx->pipe1.bHitOff.p && res->hit_offsets == (const uint64_t*)ctx->pipe1.bHitOff.p) ? ctx->pipe1 : ctx->pipe0;
-    hipStream_t st = nullptr;
-    int rc = enter_pipe(ctx, P, streamv, st);
-    if (rc) return rc;
-    for (uint32_t i = 0; i < numCuts; ++i) {
-        if (cutQueries[i] > n) return fail(ctx, MC_ERR_INVALID, "mc_partial_numbers: cut beyond the batch");
-        HIP_TRY(ctx, hipMemcpyAsync(&cutOffsets[i], res->hit_offsets + cutQueries[i], 8, hipMemcpyDeviceToHost, st));
-    }
-    uint64_t total = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&total, res->hit_offsets + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, traced_sync(st));                    // the one host round trip of the exchange: its split sizes
-    if (P.numbersN == n && P.numbersTotal == total && res->hit_offsets == (const uint64_t*)P.bHitOff.p) {
-        // mc_query_device(MC_WANT_PARTIAL_NUMBERS) left the numbers and the counts where they belong
-    } else {
-        if ((rc = ensure(ctx, P.bNumbers, (size_t)(total + 8) * 4)) || (rc = ensure(ctx, P.bCounts, (size_t)(n + 1) * 4))) return rc;
-        DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-        set_window_numbering(ctx, tab);
-        {
-            ScopedTimer t(ctx, "pack_numbers", st);
-            launch_pack_numbers(reinterpret_cast<const uint64_t*>(res->hits), res->hit_offsets, total, n, tab, (uint32_t*)P.bNumbers.p, (uint32_t*)P.bCounts.p, st);
-        }
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    out->counts = (const uint32_t*)P.bCounts.p;
-    out->numbers = (const uint32_t*)P.bNumbers.p;
-    out->total = total;
-    return MC_OK;
-}
-
-// owner side: rows 8-10 on the pieces the key shards sent for this rank's reads, where they lie in the receive buffer
-int mc_candidates_from_partial_numbers(mc_ctx* ctx, const mc_device_partial_numbers_in* in, int lowestRank, mc_device_results* out, void* streamv)
-{
-    return mc_candidates_from_partial_numbers_on(ctx, in, lowestRank, 0, out, streamv);
-}
-
-int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_numbers_in* in, int lowestRank, int flags, mc_device_results* out, void* streamv)
-{
-    if (!ctx || !in || !out || !in->counts || !in->source_offsets || in->num_sources < 1 || in->num_sources > 64) return MC_ERR_INVALID;
-    if (!in->max_win && in->max_win_uniform < 1) return fail(ctx, MC_ERR_INVALID, "max_win or max_win_uniform required");
-    if (ctx->parts.size() != 1 || !ctx->parts[0].compact || !ctx->dGwBase)
-        return fail(ctx, MC_ERR_UNSUPPORTED, "mc_candidates_from_partial_numbers: the database has no global window numbers (compact location store)");
-    const uint32_t n = in->num_queries, S = in->num_sources;
-    const uint32_t K = ctx->cfg.max_candidates;
-    if (!lane_candidates_supported(K)) return fail(ctx, MC_ERR_UNSUPPORTED, "mc_candidates_from_partial_numbers: max_candidates above 4");
-    if ((uint64_t)n * S > 0xFFFFFFF0ull) return fail(ctx, MC_ERR_UNSUPPORTED, "mc_candidates_from_partial_numbers: batch too large");
-    const uint64_t totalIn = in->source_offsets[S];
-    if (totalIn && !in->numbers) return MC_ERR_INVALID;
-    Pipe& P = (flags & MC_SECOND_PIPE) ? ctx->pipe1 : ctx->pipe0;
-    hipStream_t st = nullptr;
-    int rc = enter_pipe(ctx, P, streamv, st);
-    if (rc) return rc;
-    const uint32_t* taxkey = nullptr;
-    if ((rc = taxkey_for_rank(ctx, lowestRank, &taxkey))) return rc;
-    const uint64_t avg = totalIn / std::max<uint32_t>(n, 1);
-    const uint64_t poolCap = std::min<uint64_t>(0xFFFFFFF0ull, std::max<uint64_t>(std::max<uint64_t>((uint64_t)n * 448, totalIn / 2),
-                                                                                  (uint64_t)big_filter_grid(n, true, ctx->filterBpc) * 4 * std::min<uint64_t>(131072, std::max<uint64_t>(4096, avg))));
-    const uint64_t ovfCap = std::min<uint64_t>(0xFFFFFFF0ull - poolCap, std::max<uint64_t>(poolCap / 4, 8ull << 20));
-    if ((rc = ensure(ctx, P.bPsize, ((size_t)n * S + 4) * 4)) || (rc = ensure(ctx, P.bPpay, ((size_t)n * S + (size_t)S * (n + 2) + 4) * 8)) ||
-        (rc = ensure(ctx, P.bQstat, (size_t)(n + 1) * sizeof(QueryStat))) || (rc = ensure(ctx, P.bQflag, (size_t)(n + 1) * 4)) ||
-        (rc = ensure(ctx, P.bScanIn, (size_t)(n + 1) * 4)) || (rc = ensure(ctx, P.bScan, scan_tmp_bytes(n + 1))) ||
-        (rc = ensure(ctx, P.bHitOff, (size_t)(n + 2) * 8)) || (rc = ensure(ctx, P.bMid, work_lists_bytes(n))) ||
-        (rc = ensure(ctx, P.bBigPool, (poolCap + ovfCap) * 4)) || (rc = ensure(ctx, P.bSliceFill, (size_t)big_filter_grid(n, true, ctx->filterBpc) * 4 * 4 + 64)) ||
-        (rc = ensure(ctx, P.bSide, (size_t)kSideRows * std::max<uint32_t>(n, 1) * 4)) ||
-        (rc = ensure(ctx, P.bCands, (size_t)std::max<uint32_t>(n, 1) * K * sizeof(mc_candidate))))
-        return rc;
-    BatchRun run{tuned_workspace(ctx)};
-    Workspace& ws = run.ws;
-    ws.psize = (uint32_t*)P.bPsize.p; ws.ppay = (uint64_t*)P.bPpay.p;
-    uint64_t* srcStart = ws.ppay + (size_t)n * S + 2;                 // [S][n + 1] exclusive scans of the sources' counts
-    ws.qstat = (QueryStat*)P.bQstat.p; ws.qflag = (uint32_t*)P.bQflag.p; ws.hitScan = (uint32_t*)P.bScanIn.p; ws.hitOff = (uint64_t*)P.bHitOff.p;
-    ws.scanTmp = P.bScan.p;
-    ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords);
-    ws.bigMin = ctx->bigMin;
-    ws.bigPool = (uint64_t*)P.bBigPool.p; ws.bigPoolCap = (uint32_t)poolCap; ws.bigOvfCap = (uint32_t)ovfCap;
-    ws.sliceFill = (uint32_t*)P.bSliceFill.p; ws.sideList = (uint32_t*)P.bSide.p;
-    BatchView b{nullptr, nullptr, in->max_win, in->max_win_uniform, n};
-    // the receive buffer stands in for the table's location store
-    DeviceTable tab{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-    tab.values32 = in->numbers;
-    set_window_numbering(ctx, tab);
-    KeyshardBases bases{};
-    for (uint32_t s = 0; s < S; ++s) bases.b[s] = in->source_offsets[s];
-    HIP_TRY(ctx, hipMemsetAsync(ws.midCount, 0, kCounterBytes, st));
-    {
-        ScopedTimer t(ctx, "owner_entries", st);
-        for (uint32_t s = 0; s < S; ++s) launch_scan_u32(in->counts + (size_t)s * n, 1, n, nullptr, srcStart + (size_t)s * (n + 1), ws.scanTmp, st);
-        launch_owner_entries(b, tab, ws, in->counts, srcStart, bases, S, st);
-    }
-    run.b = b; run.sp = SketchParams{16, 1, 16, 1}; run.tab = tab; run.K = K; run.taxkey = taxkey; run.cands = P.bCands.p; run.st = st;
-    run.poolEntries = poolCap + ovfCap; run.compact = true;
-    if ((rc = run_filtered_path(ctx, P, run, true))) return rc;
-    // what is left (short lists, reads the filtered path handed back): decoded to (target, window) lists and sorted
-    launch_scan_u32(ws.hitScan, 1, n, nullptr, ws.hitOff, ws.scanTmp, st);
-    if ((rc = ensure_host_words(ctx, P))) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(P.hTotal, ws.hitOff + n, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(P.hTotal + 10, ws.midCount + kCntFilter, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, traced_sync(st));
-    ctx->ownerStats[0] += n; ctx->ownerStats[1] += *reinterpret_cast<const uint32_t*>(P.hTotal + 10); ctx->ownerStats[2] += totalIn; ctx->ownerStats[3] += *P.hTotal;
-    if ((rc = ensure_sort_space(ctx, P, *P.hTotal, taxkey, ws))) return rc;
-    { ScopedTimer t(ctx, "decode_union", st); launch_decode_union(b, tab, ws, in->counts, srcStart, bases, S, st); }
-    DeviceTable none{nullptr, nullptr, 0, 0xFFFFFFFFu, 1};
-    { ScopedTimer t(ctx, "cands_from_hits", st); launch_cands_from_hits(b, none, ws, taxkey, K, P.bCands.p, st); }
-    HIP_TRY(ctx, hipGetLastError());
-    P.lastN = 0;
-    publish_results(out, P, ws, false);
-    return MC_OK;
-}
-
-int mc_owner_stats(const mc_ctx* ctx, uint64_t stats[4])
-{
-    if (!ctx || !stats) return MC_ERR_INVALID;
-    for (int i = 0; i < 4; ++i) stats[i] = ctx->ownerStats[i];
-    return MC_OK;
-}
-
-// Mode P / part groups: per-part candidate lists of the same reads (device pointers, [n][max_candidates] each, in part order) -> one list
-// per read, as if the parts had been queried one after the other with one candidate list (candidate_generation.hpp:172-231).  Target ids
-// must be the database's own (mc_open_database with single_part keeps them), lowest_rank > 0 uses this context's lineages.
-int mc_merge_part_candidates(mc_ctx* ctx, const mc_candidate* const* lists, uint32_t numLists, uint32_t n, int lowestRank, mc_candidate* out, void* streamv)
-{
-    if (!ctx || !lists || !out || numLists == 0) return MC_ERR_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
-    const uint32_t* taxkey = nullptr;
-    int rc = taxkey_for_rank(ctx, lowestRank, &taxkey);
-    if (rc) return rc;
-    const uint32_t K = ctx->cfg.max_candidates;
-    // more than 16 lists: in rounds, the merged list of a round leads the next one (the insert is sequential anyway)
-    const void* ptrs[16];
-    uint32_t done = 0;
-    bool lead = false;
-    while (done < numLists) {
-        uint32_t m = 0;
-        if (lead) ptrs[m++] = out;
-        while (m < 16 && done < numLists) ptrs[m++] = lists[done++];
-        if (launch_merge_parts(ptrs, m, n, K, taxkey, out, st) != 0) return fail(ctx, MC_ERR_UNSUPPORTED, "mc_merge_part_candidates: max_candidates above 4");
-        lead = true;
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return MC_OK;
-}
+extern "C" {
 
 // tuning / test hook: the switches the MC_* environment variables set at mc_create, changeable on a live context (no batch in flight)
 int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value)
@@ -1130,23 +448,6 @@ int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, 
     hipStream_t st = stream ? (hipStream_t)stream : (kind & MC_SECOND_PIPE) ? ctx->pipe1.stream : ctx->stream;
     const hipMemcpyKind how = (kind & 1) ? hipMemcpyDeviceToHost : (kind & 2) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, how, st));
-    return MC_OK;
-}
-
-int mc_last_batch_stats(mc_ctx* ctx, uint64_t stats[8])
-{
-    if (!ctx) return MC_ERR_INVALID;
-    std::memset(stats, 0, 64);
-    Pipe& P = ctx->pipe0;
-    hipStream_t st = nullptr;
-    if (const int rc = enter_pipe(ctx, P, nullptr, st)) return rc;
-    if (!P.bStats.p || !P.bQstat.p) return MC_OK;
-    Workspace ws = tuned_workspace(ctx);
-    ws.qstat = (QueryStat*)P.bQstat.p; ws.winOff = (uint32_t*)P.bWinOff.p; ws.stats = (uint64_t*)P.bStats.p;
-    if (P.bMid.p) { ws.midCount = (uint32_t*)P.bMid.p; ws.midList = reinterpret_cast<uint4*>(ws.midCount + kCounterWords); }
-    launch_batch_stats(ws, P.lastN, ctx->stream);
-    HIP_TRY(ctx, hipMemcpyAsync(stats, ws.stats, 64, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return MC_OK;
 }
 
@@ -1262,6 +563,16 @@ static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
 
 static int submit_raw_coalesced(mc_ctx* ctx, Slot& S, int lowestRank);
 
+// what the slot paths, which see every read on the host, tell query_on_pipe: no single read beyond a lane's reach (maxSingle: the longest)
+static int slot_query_flags(uint32_t maxSingle) { return maxSingle <= mcamd::lane_max_len() ? mcamd::kQueryNoLongReads : 0; }
+// ONE slot's batch: its n candidates and statistics to the slot's pinned buffers by one kernel (launch_deliver) instead of two copies
+static void deliver_slot(const mc_ctx* ctx, Slot& S, const Pipe& P, const mc_device_results& res, uint32_t n, hipStream_t st)
+{
+    DeliverTable dt{};
+    dt.e[0] = DeliverEntry{S.hcands, S.hqstat, 0u, n}; dt.n = 1;
+    launch_deliver(dt, res.cands, P.bQstat.p, (uint32_t)ctx->cfg.max_candidates, st);
+}
+
 int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out)
 {
     if (!ctx || slot >= ctx->slots.size() || !out) return MC_ERR_INVALID;
@@ -1336,15 +647,10 @@ int mc_batch_submit(mc_ctx* ctx, uint32_t slot, int lowestRank)
     mc_device_results res{};
     const int wantAll = ctx->cfg.copy_allhits ? 1 : 0;
     const uint64_t tt2 = g_submitTrace ? trace_now() : 0;
-    int rc = query_on_pipe(ctx, P, &in, lowestRank, wantAll | (S.maxSingle <= mcamd::lane_max_len() ? mcamd::kQueryNoLongReads : 0), &res, st);
+    int rc = query_on_pipe(ctx, P, &in, lowestRank, wantAll | slot_query_flags(S.maxSingle), &res, st);
     if (rc) return rc;
     const uint64_t tt3 = g_submitTrace ? trace_now() : 0;
-    const size_t K = ctx->cfg.max_candidates;
-    {   // candidates and statistics to the slot's pinned buffers by one kernel (launch_deliver) instead of two copies
-        DeliverTable dt{};
-        dt.e[0] = DeliverEntry{S.hcands, S.hqstat, 0u, n}; dt.n = 1;
-        launch_deliver(dt, res.cands, P.bQstat.p, (uint32_t)K, st);
-    }
+    deliver_slot(ctx, S, P, res, n, st);
     if (wantAll) {
         HIP_TRY(ctx, hipMemcpyAsync(S.hhitoff, res.hit_offsets, (size_t)(n + 1) * 8, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, traced_sync(st));
@@ -1464,7 +770,7 @@ static void co_run(mc_ctx* ctx, mcamd::CoDispatcher* D, const std::vector<uint32
             // reads per slot, 32 threads: 4 019 against 4 189 Mreads/min for the synchronous call, profiles/r06_slot_path.json: off)
             static const bool defer = [] { const char* e = std::getenv("MC_SLOT_DEFER"); return e && e[0] == '1'; }();
             const uint64_t ttB = g_submitTrace ? trace_now() : 0;
-            rc = query_on_pipe(ctx, P, &in, lowest, (defer ? MC_DEFER_TAIL : 0) | (maxSingle <= mcamd::lane_max_len() ? mcamd::kQueryNoLongReads : 0), &res, st);
+            rc = query_on_pipe(ctx, P, &in, lowest, (defer ? MC_DEFER_TAIL : 0) | slot_query_flags(maxSingle), &res, st);
             if (!rc && defer) rc = finish_on_pipe(ctx, P);
             if (g_submitTrace) { g_trace[2] += trace_now() - ttB; ++g_trace[5]; }
         }
@@ -1514,12 +820,8 @@ static int submit_raw_coalesced(mc_ctx* ctx, Slot& S, int lowestRank)
     if (!rc && n) {
         mc_device_batch in{S.dseq, S.dqinfo, S.dmaxwin, 0, n, S.nchars};
         mc_device_results res{};
-        rc = query_on_pipe(ctx, P, &in, lowestRank, S.maxSingle <= mcamd::lane_max_len() ? mcamd::kQueryNoLongReads : 0, &res, st);
-        if (!rc) {
-            DeliverTable dt{};
-            dt.e[0] = DeliverEntry{S.hcands, S.hqstat, 0u, n}; dt.n = 1;
-            launch_deliver(dt, res.cands, P.bQstat.p, (uint32_t)ctx->cfg.max_candidates, st);
-        }
+        rc = query_on_pipe(ctx, P, &in, lowestRank, slot_query_flags(S.maxSingle), &res, st);
+        if (!rc) deliver_slot(ctx, S, P, res, n, st);
     }
     const hipError_t e = hipStreamSynchronize(st);
     if (!rc && e != hipSuccess) rc = fail(ctx, MC_ERR_HIP, std::string("hipStreamSynchronize: ") + hipGetErrorString(e));
@@ -1617,8 +919,7 @@ int mcamd::reserve_slot_pipes(mc_ctx* ctx, uint64_t locs, uint64_t keys, bool wa
     }
     const SketchParams sp = ctx->querySketch;
     const uint32_t K = ctx->cfg.max_candidates, n = ctx->coalesce ? ctx->coMaxQueries : ctx->cfg.slot_max_queries;   // (coalescer: a dispatcher's pipe takes a united batch)
-    const bool wantAll = ctx->cfg.copy_allhits != 0;
-    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && !wantAll && lane_candidates_supported(K);
+    const bool lanePath = lane_path_takes(lane_path_supported(sp), lane_candidates_supported(K), ctx->useLanePath, query_wants(ctx->cfg.copy_allhits ? MC_WANT_ALLHITS : 0));
     // (a slot of short reads: 152 characters each -- a slot filled with longer reads has fewer of them and grows its buffers as before)
     const uint64_t chars = std::min<uint64_t>(ctx->coalesce ? ctx->coMaxChars : ctx->cfg.slot_max_chars, (uint64_t)n * 152);
     int rc = MC_OK;
@@ -1635,7 +936,7 @@ int mcamd::reserve_query_pipes(mc_ctx* ctx, uint32_t n, uint64_t chars)
 {
     if (!ctx || ctx->parts.empty() || !ctx->tableReady) return MC_OK;
     const SketchParams sp = ctx->querySketch;
-    const bool lanePath = lane_path_supported(sp) && ctx->useLanePath && lane_candidates_supported(ctx->cfg.max_candidates);
+    const bool lanePath = lane_path_takes(lane_path_supported(sp), lane_candidates_supported(ctx->cfg.max_candidates), ctx->useLanePath, QueryWants{});   // (whatever the calls will want)
     uint64_t locs = 0;
     for (auto& p : ctx->parts) locs += p.locations;
     for (Pipe* P : {&ctx->pipe0, &ctx->pipe1}) {

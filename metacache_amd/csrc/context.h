@@ -3,6 +3,7 @@
 
 #include "../../include/metacache_amd.h"
 #include "kernels.h"
+#include "query_rules.h"
 
 #include <atomic>
 #include <condition_variable>
@@ -20,7 +21,7 @@ struct DevBuf {                 // grow-only device allocation
     size_t cap = 0;
 };
 
-struct BatchRun {               // the state of ONE batch on a pipe: what run_sorted_tail / run_filtered_path / run_wave_tail (context.cpp) work on
+struct BatchRun {               // the state of ONE batch on a pipe: what run_sorted_tail / run_filtered_path / run_wave_tail (query_pipe.cpp) work on
     Workspace ws{}; BatchView b{}; SketchParams sp{}; DeviceTable tab{};
     uint32_t K = 0; const uint32_t* taxkey = nullptr;
     void* cands = nullptr;          // the pipe's candidate buffer
@@ -36,6 +37,12 @@ struct Pipe {                   // the device workspace of ONE batch in flight +
         bCands, bScanIn, bQflag, bMid, bChunkList, bBigPool, bSliceFill, bBigPool2, bSortTmp, bSide,
         bOrder,              // scratch of launch_gw_order (work lists longest first)
         bNumbers, bCounts;   // Mode K shard side: the partial lists as global window numbers + per-read counts (mc_partial_numbers)
+    // every buffer above, for whoever frees them (mc_destroy)
+    std::vector<DevBuf*> buffers()
+    {
+        return {&bWinCount, &bWinOff, &bFeatures, &bPsize, &bPpay, &bQstat, &bHitOff, &bHits, &bCscr, &bCscr2, &bScan, &bStats, &bCands, &bScanIn, &bQflag, &bMid,
+                &bChunkList, &bBigPool, &bSliceFill, &bBigPool2, &bSortTmp, &bSide, &bOrder, &bNumbers, &bCounts};
+    }
     uint32_t lastN = 0;
     uint32_t numbersN = 0xFFFFFFFFu; uint64_t numbersTotal = 0;   // MC_WANT_PARTIAL_NUMBERS: bNumbers / bCounts hold this batch's lists already
     uint64_t* hTotal = nullptr;   // pinned: the one host round trip of a batch lands here (a pageable target makes the copy blocking)
@@ -102,10 +109,6 @@ struct Slot {
 };
 
 // one dispatcher thread of the slot coalescer: a pipe of its own, the united batch's device input, pinned staging (twice) for the rebased qinfo rows
-// query_on_pipe, internal (the slots, which see every read on the host): no single read is longer than one lane takes -- the chunk lanes'
-// kernels (launched for their work list, which would be empty) are left out.  Masked out of mc_query_device's flags.
-constexpr int kQueryNoLongReads = 1 << 24;
-
 struct CoDispatcher {
     std::thread th;
     Pipe* pipe = nullptr;
@@ -120,6 +123,14 @@ struct CoDispatcher {
 
 int ensure(mc_ctx* ctx, DevBuf& b, size_t bytes);   // context.cpp: a grow-only buffer of at least `bytes` (hipFree + dev_malloc when it grows)
 hipError_t traced_sync(hipStream_t st);             // hipStreamSynchronize, counted by MC_SUBMIT_TRACE
+int taxkey_for_rank(mc_ctx* ctx, int rank, const uint32_t** out);   // context.cpp: taxkey[tgt] = the target's lowest ancestor at `rank` or above, on the device (null: rank 0)
+
+// query_pipe.cpp: the per-batch pipeline, for the slot paths and the reservations of context.cpp
+struct PipeSizes { uint64_t poolCap = 0, ovfCap = 0; size_t nfeat = 0; };
+int size_pipe(mc_ctx* ctx, Pipe& P, uint32_t n, uint64_t numChars, bool wantFeatures, bool lanePath, uint64_t locs, uint64_t keys, PipeSizes& out);
+int enter_pipe(mc_ctx* ctx, Pipe& P, void* streamv, hipStream_t& st);
+int query_on_pipe(mc_ctx* ctx, Pipe& P, const mc_device_batch* in, int lowestRank, int flags, mc_device_results* out, void* streamv);
+int finish_on_pipe(mc_ctx* ctx, Pipe& P);
 
 // table_load.cpp: insert one chunk of a single-part database whose batch arrays already live in device memory
 // (between mc_load_begin and mc_load_end; used by mc_load_batch after its upload and by the builder directly)

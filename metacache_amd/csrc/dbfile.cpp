@@ -288,7 +288,7 @@ int mc_open_database(const char* name, const mc_config* cfgIn, mc_ctx** out)
             if (!rc) rc = mc_load_begin(ctx, p, h.nkeys, h.nvalues);
         }
         const double tb1 = now_s();
-        // the slot pipes' workspaces are allocated beside the file load (context.cpp size_pipe: allocations of memory that another process
+        // the slot pipes' workspaces are allocated beside the file load (query_pipe.cpp size_pipe: allocations of memory that another process
         // has just given back take 0.1-0.2 s apiece; inside the first batches they stall every stream)
         std::thread reserve;
         if (!rc && cfg.num_slots > 0 && !std::getenv("MC_NO_RESERVE")) {

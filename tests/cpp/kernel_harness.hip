@@ -166,7 +166,7 @@ struct SortedWork {
         ws.sideList = S.upload(side.data(), side.size());
         return S.failed ? KH_ERR_HIP : KH_OK;
     }
-    // the side list longest first (context.cpp run_sorted_tail: size query, then 3 n words + the order's own bytes)
+    // the side list longest first (query_pipe.cpp run_sorted_tail: size query, then 3 n words + the order's own bytes)
     int order(Scope& S, uint32_t n, uint32_t nseg, hipStream_t st)
     {
         size_t ordBytes = 0;

@@ -148,7 +148,7 @@ def test_part_groups_streamed_batch_by_batch_equal_classify(golden, resident, lo
 @pytest.mark.parametrize("big_min", [None, 0])
 def test_batch_sizes_around_the_small_batch_kernels_limits(golden, big_min):
     """Batches of up to 16 384 / 32 768 reads take other steps on the stream than larger ones (kernels.hip: scan_small_kernel, plan_scan_small_kernel,
-    flag_count_small_kernel; context.cpp: one host round trip for the sorted class and the wave tail): a read's candidates must not depend on
+    flag_count_small_kernel; query_pipe.cpp: one host round trip for the sorted class and the wave tail): a read's candidates must not depend on
     the size of the batch it came in.  big_min = 0 sends the toy table's lists through the filtered path and its counting kernels."""
     single, _, _ = golden.reads()
     rng = np.random.default_rng(4096)
