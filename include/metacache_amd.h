@@ -816,7 +816,7 @@ typedef struct {
     uint64_t  names_capacity;
     uint64_t* name_off;       /* [max_records + 1] */
     uint32_t* max_win;        /* [max_records] */
-    uint64_t* status;         /* [8] */
+    uint64_t* status;         /* [8]; mc_parse_mates: [10] */
     uint32_t  max_records;
 } mc_parse_output;
 extern const uint32_t mc_parse_tile;   /* bytes one block classifies: what lies in front of a tile comes from a scan over the tiles (for tests and tools) */
@@ -824,6 +824,32 @@ uint64_t mc_parse_scratch_bytes(uint64_t nbytes);
 int mc_parse_records(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags, uint64_t insert_size_max, const mc_parse_output* out,
                      void* workspace, uint64_t workspace_bytes, void* stream);
 int mc_parse_stats(mc_ctx* ctx, uint64_t stats[4]);
+
+/* ---- mates in two ranges: the two files of `-pairfiles` ("mates") ------
+ * THE MATES RULE (sequence_pair_reader::next for pairing_mode::files).  There are two ranges, B1[0, n1) and B2[0, n2).  Each is judged by
+ * the record rule above on its own and selects its own kind by its first byte (FASTA beside FASTQ is allowed: the reference's two
+ * readers are independent).  Query q is record q of B1 -- the first mate, and the query's name -- and record q of B2, the second mate.
+ * For accepted ranges qinfo, seq, names, name_off and max_win are, field by field and byte by byte, what mc_parse_records(...,
+ * MC_PARSE_PAIRS, ...) gives for a file in which the records of the two ranges alternate; hdr[2 * queries][2] holds in row 2q the header
+ * of query q's first mate as offset and length IN B1, in row 2q + 1 that of its second mate IN B2.  The ranges hold the same number of
+ * records, or the call refuses with MC_PARSE_UNEQUAL (the reference stops silently at the shorter file; this library never cuts an
+ * accepted input differently from what it was handed).
+ * status has 10 words: [0..6] as for mc_parse_records with [0] = the records of both ranges together, [1] = queries; [7] = the range
+ *   (0 or 1) in which the offence [5] lies with MC_PARSE_IRREGULAR, else 0 -- when both ranges are irregular, range 0's offence is the
+ *   one reported; [8], [9] = the records of B1 and of B2, meaningful with MC_PARSE_OK, MC_PARSE_OVERFLOW and MC_PARSE_UNEQUAL (so the
+ *   caller can cut the longer range).  MC_PARSE_OVERFLOW is as for mc_parse_records, max_records counted over both ranges; [0], [2] and
+ *   [3] then hold what a second call needs, and [6] is filled only where the records fit max_records (else 0).  With MC_PARSE_UNEQUAL
+ *   only [0], [4], [8] and [9] mean anything.  With a verdict other than MC_PARSE_OK NOTHING but status is written.
+ * mc_parse_mates: flags is 0 (DEVICE pointers; bytes1, bytes2, seq and workspace 16-byte aligned, the others as for mc_parse_records;
+ *   enqueued on `stream` without any synchronisation; the caller owns the workspace of mc_parse_mates_scratch_bytes(n1, n2,
+ *   out->max_records) bytes and the context keeps nothing per call, so calls on different streams may run at once; the same bytes give
+ *   the same outputs) or MC_PARSE_HOST (HOST arrays, staged through the context as mc_parse_records does).  MC_ERR_INVALID (checked
+ *   first, before any device call) as for mc_parse_records for either range, and: MC_PARSE_PAIRS or another flag, n1 + n2 > 2^31.
+ *   mc_parse_stats counts these calls too (bytes: n1 + n2). */
+#define MC_PARSE_UNEQUAL    3
+uint64_t mc_parse_mates_scratch_bytes(uint64_t n1, uint64_t n2, uint32_t max_records);
+int mc_parse_mates(mc_ctx* ctx, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, int flags, uint64_t insert_size_max,
+                   const mc_parse_output* out, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* raw bytes into a batch slot: the slot's reads are cut on the device
  * mc_batch_add_file_bytes fills an EMPTY slot with a byte range of a FASTA / FASTQ file (whole records; flags: 0 or MC_PARSE_PAIRS): one
@@ -847,6 +873,12 @@ typedef struct {
 } mc_batch_record_info;
 int mc_batch_add_file_bytes(mc_ctx* ctx, uint32_t slot, const char* bytes, uint64_t nbytes, int flags, uint64_t insert_size_max);
 int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out);
+/* mc_batch_add_file_mates fills an EMPTY slot with the two ranges of the mates rule: MC_BATCH_FULL, and nothing added, when n1 + n2
+ *   exceeds the slot's character capacity; otherwise as mc_batch_add_file_bytes.  mc_batch_submit uploads both ranges and runs
+ *   mc_parse_mates, then the unchanged query; it waits once for the device between the two, for the number of reads.  mc_batch_records
+ *   works unchanged: records = 2 * queries, half_pair = 0, hdr as mc_parse_mates leaves it (row 2q in bytes1, row 2q + 1 in bytes2);
+ *   a verdict other than MC_PARSE_OK (MC_PARSE_UNEQUAL among them) leaves mc_results.num_queries at 0. */
+int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insert_size_max);
 
 /* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
  * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the

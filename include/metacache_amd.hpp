@@ -267,6 +267,34 @@ public:
         return p;
     }
 
+    // the pairs of two mate files' byte ranges, cut on the device (mc_parse_mates on host arrays; the mates rule: metacache_amd.h):
+    // query q is record q of bytes1 and record q of bytes2.  As parse_records(pairs = true), except that hdr row 2q is a place in bytes1
+    // and row 2q + 1 a place in bytes2; records1 / records2 are set with MC_PARSE_OK and MC_PARSE_UNEQUAL, offenceRange with MC_PARSE_IRREGULAR.
+    struct parsed_mates : parsed_records { std::uint32_t records1 = 0, records2 = 0; int offenceRange = 0; };
+    parsed_mates parse_mates(const char* bytes1, std::size_t n1, const char* bytes2, std::size_t n2, std::uint64_t insertSizeMax = 0) const
+    {
+        parsed_mates p;
+        std::uint64_t status[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int pass = 0; pass < 2; ++pass) {                                   // (the first call reports what the second needs)
+            mc_parse_output o{};
+            const std::uint32_t mr = std::uint32_t(status[0]);
+            p.hdr.assign(std::size_t(mr) * 2 + 1, 0); p.qinfo.assign(std::size_t(mr) * 4 + 1, 0); p.maxWin.assign(std::size_t(mr) + 1, 0);
+            p.seq.assign(std::size_t(status[2]) + 1, 0); p.names.assign(std::size_t(status[3]) + 1, char(0)); p.nameOff.assign(std::size_t(mr) + 1, 0);
+            o.hdr = p.hdr.data(); o.qinfo = p.qinfo.data(); o.seq = p.seq.data(); o.seq_capacity = status[2]; o.names = &p.names[0];
+            o.names_capacity = status[3]; o.name_off = p.nameOff.data(); o.max_win = p.maxWin.data(); o.status = status; o.max_records = mr;
+            if (mc_parse_mates(ctx_, bytes1, n1, bytes2, n2, MC_PARSE_HOST, insertSizeMax, &o, nullptr, 0, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            if (status[4] != MC_PARSE_OVERFLOW) break;
+        }
+        p.verdict = int(status[4]); p.offence = status[5]; p.offenceRange = int(status[7]);
+        const bool ok = status[4] == MC_PARSE_OK;
+        p.records = ok ? std::uint32_t(status[0]) : 0; p.queries = ok ? std::uint32_t(status[1]) : 0;
+        p.records1 = std::uint32_t(status[8]); p.records2 = std::uint32_t(status[9]);
+        p.hdr.resize(std::size_t(p.records) * 2); p.qinfo.resize(std::size_t(p.queries) * 4); p.maxWin.resize(p.queries);
+        p.seq.resize(ok ? std::size_t(status[2]) : 0); p.names.resize(ok ? std::size_t(status[3]) : 0); p.nameOff.resize(ok ? std::size_t(p.queries) + 1 : 0);
+        return p;
+    }
+
     // -precision / -taxon-coverage after the last batch: what the batches' evaluate() calls have counted (mc_evaluate_tally; reset: the
     // counters start from zero again)
     classification_statistics evaluation(bool reset = false) const
@@ -502,6 +530,14 @@ public:
     bool add_file_bytes(unsigned hostId, const char* bytes, std::size_t nbytes, bool pairs = false, std::uint64_t insertSizeMax = 0)
     {
         const int rc = mc_batch_add_file_bytes(ctx_, hostId, bytes, nbytes, pairs ? MC_PARSE_PAIRS : 0, insertSizeMax);
+        if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
+        return rc == MC_OK;
+    }
+    // the byte ranges of two mate files (whole records; query q = record q of each) into an EMPTY batch (mc_batch_add_file_mates).
+    // Returns false if the two ranges together exceed the batch's character capacity.
+    bool add_file_mates(unsigned hostId, const char* bytes1, std::size_t n1, const char* bytes2, std::size_t n2, std::uint64_t insertSizeMax = 0)
+    {
+        const int rc = mc_batch_add_file_mates(ctx_, hostId, bytes1, n1, bytes2, n2, insertSizeMax);
         if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
         return rc == MC_OK;
     }

@@ -127,7 +127,12 @@ def parse_scratch_bytes(nbytes: int) -> int:
 
 
 PARSE_HOST, PARSE_PAIRS = 1, 2
-PARSE_OK, PARSE_IRREGULAR, PARSE_OVERFLOW = 0, 1, 2
+PARSE_OK, PARSE_IRREGULAR, PARSE_OVERFLOW, PARSE_UNEQUAL = 0, 1, 2, 3
+
+
+def parse_mates_scratch_bytes(n1: int, n2: int, max_records: int) -> int:
+    """the workspace a device call of mc_parse_mates needs for ranges of n1 and n2 bytes and outputs of max_records records"""
+    return int(lib().mc_parse_mates_scratch_bytes(n1, n2, max_records))
 
 
 class McParseOutput(C.Structure):
@@ -342,7 +347,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_format_set_text", "mc_format_mappings", "mc_format_stats",
            "mc_format_matches_set_text", "mc_format_matches", "mc_format_mappings_with", "mc_format_matches_stats",
            "mc_table_histogram", "mc_table_features", "mc_table_lookup",
-           "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records"]
+           "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records",
+           "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates"]
 
 _lib = None
 
@@ -433,6 +439,10 @@ def lib() -> C.CDLL:
         L.mc_parse_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.mc_batch_add_file_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64]
         L.mc_batch_records.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(McBatchRecordInfo)]
+        L.mc_parse_mates_scratch_bytes.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
+        L.mc_parse_mates_scratch_bytes.restype = C.c_uint64
+        L.mc_parse_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(McParseOutput), C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_batch_add_file_mates.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -877,6 +887,45 @@ class Database:
         out["raw"] = a
         return out
 
+    def parse_mates_device(self, bytes1_ptr: int, n1: int, bytes2_ptr: int, n2: int, *, hdr_ptr: int, qinfo_ptr: int, seq_ptr: int, seq_capacity: int,
+                           names_ptr: int, names_capacity: int, name_off_ptr: int, max_win_ptr: int, status_ptr: int, max_records: int,
+                           workspace_ptr: int, workspace_bytes: int, insert_max: int = 0, stream: int = 0, flags: int = 0):
+        """cuts two ranges of mates (device memory, 16-byte aligned; query q = record q of each) into pairs, as parse_device does one range;
+        status [10] uint64; workspace of parse_mates_scratch_bytes(n1, n2, max_records); asynchronous on `stream` (mc_parse_mates)"""
+        o = McParseOutput(hdr_ptr or None, qinfo_ptr or None, seq_ptr or None, seq_capacity, names_ptr or None, names_capacity,
+                          name_off_ptr or None, max_win_ptr or None, status_ptr or None, max_records)
+        self._check(lib().mc_parse_mates(self.h, bytes1_ptr or None, n1, bytes2_ptr or None, n2, flags, insert_max, C.byref(o),
+                                         workspace_ptr or None, workspace_bytes, stream or None))
+
+    def parse_mates(self, data1, data2, insert_max: int = 0, *, max_records=None, seq_capacity=None, names_capacity=None):
+        """the same on host memory: data1, data2 (bytes) -> dict(status uint64 [10], and with the verdict PARSE_OK the arrays of
+        parse_records(pairs=True), hdr rows 2q / 2q + 1 being places in data1 / data2).  Capacities that are left out are taken from a
+        first call's status.  "raw": the arrays as the last call left them."""
+        b1, b2 = np.frombuffer(bytes(data1), dtype=np.uint8), np.frombuffer(bytes(data2), dtype=np.uint8)
+        status = np.zeros(10, dtype=np.uint64)
+
+        def run(mr, sc, nc):
+            a = dict(hdr=np.zeros((max(mr, 1), 2), dtype=np.uint32), qinfo=np.zeros((max(mr, 1), 4), dtype=np.uint32), seq=np.zeros(max(sc, 1), dtype=np.uint8),
+                     names=np.zeros(max(nc, 1), dtype=np.uint8), name_off=np.zeros(mr + 1, dtype=np.uint64), max_win=np.zeros(max(mr, 1), dtype=np.uint32))
+            o = McParseOutput(a["hdr"].ctypes.data, a["qinfo"].ctypes.data, a["seq"].ctypes.data, sc, a["names"].ctypes.data, nc,
+                              a["name_off"].ctypes.data, a["max_win"].ctypes.data, status.ctypes.data, mr)
+            self._check(lib().mc_parse_mates(self.h, b1.ctypes.data if len(b1) else None, len(b1), b2.ctypes.data if len(b2) else None, len(b2),
+                                             PARSE_HOST, insert_max, C.byref(o), None, 0, None))
+            return a
+
+        sized = max_records is not None and seq_capacity is not None and names_capacity is not None
+        a = run(max_records or 0, seq_capacity or 0, names_capacity or 0)
+        if not sized and int(status[4]) == PARSE_OVERFLOW:
+            a = run(int(status[0]) if max_records is None else max_records, int(status[2]) if seq_capacity is None else seq_capacity,
+                    int(status[3]) if names_capacity is None else names_capacity)
+        out = dict(status=status.copy())
+        if int(status[4]) == PARSE_OK:
+            r, q = int(status[0]), int(status[1])
+            out.update(hdr=a["hdr"][:r].copy(), qinfo=a["qinfo"][:q].copy(), seq=a["seq"][:int(status[2])].tobytes(), names=a["names"][:int(status[3])].tobytes(),
+                       name_off=a["name_off"][:q + 1].copy(), max_win=a["max_win"][:q].copy())
+        out["raw"] = a
+        return out
+
     def batch_records(self, slot: int = 0) -> dict:
         """what the device made of a raw slot (mc_batch_records, after the wait): verdict, offence, records, queries, half_pair, and copies
         of hdr [records, 2] and qinfo [queries, 4] (empty with another verdict than PARSE_OK)"""
@@ -890,9 +939,19 @@ class Database:
         """one slot batch from a byte range of a FASTA / FASTQ file, cut into reads on the device (mc_batch_add_file_bytes)
         -> (cands[n, K], hit_counts[n], allhits list or None, records: batch_records()); n = 0 where the device refused the range
         (records["verdict"] says why) -- the caller then cuts that batch itself.  Raises McError("... does not fit ...") on MC_BATCH_FULL."""
-        L = lib()
         buf = np.frombuffer(bytes(data), dtype=np.uint8)
-        rc = self._check(L.mc_batch_add_file_bytes(self.h, slot, buf.ctypes.data if len(buf) else None, len(buf), PARSE_PAIRS if pairs else 0, insert_max))
+        rc = self._check(lib().mc_batch_add_file_bytes(self.h, slot, buf.ctypes.data if len(buf) else None, len(buf), PARSE_PAIRS if pairs else 0, insert_max))
+        return self._query_raw_slot(rc, lowest, slot)
+
+    def query_file_mates(self, data1, data2, lowest: int = 0, insert_max: int = 0, slot: int = 0):
+        """one slot batch from the byte ranges of two mate files (query q = record q of each), cut on the device (mc_batch_add_file_mates)
+        -> as query_file_bytes; records["hdr"] rows 2q / 2q + 1 are places in data1 / data2"""
+        b1, b2 = np.frombuffer(bytes(data1), dtype=np.uint8), np.frombuffer(bytes(data2), dtype=np.uint8)
+        rc = self._check(lib().mc_batch_add_file_mates(self.h, slot, b1.ctypes.data if len(b1) else None, len(b1), b2.ctypes.data if len(b2) else None, len(b2), insert_max))
+        return self._query_raw_slot(rc, lowest, slot)
+
+    def _query_raw_slot(self, rc: int, lowest: int, slot: int):
+        L = lib()
         if rc == MC_BATCH_FULL:
             raise McError("the byte range does not fit the slot's character capacity")
         K = self.cfg.max_candidates

@@ -302,7 +302,7 @@ void mc_destroy(mc_ctx* ctx)
     for (auto& s : ctx->slots) {
         if (s.hseq) (void)hipHostFree(s.hseq); if (s.hqinfo) (void)hipHostFree(s.hqinfo); if (s.hmaxwin) (void)hipHostFree(s.hmaxwin);
         if (s.dseq) (void)hipFree(s.dseq); if (s.dqinfo) (void)hipFree(s.dqinfo); if (s.dmaxwin) (void)hipFree(s.dmaxwin);
-        for (void* p : {(void*)s.draw, s.dparseWs, (void*)s.dhdr, (void*)s.dnames, (void*)s.dnameoff, (void*)s.dstatus}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)s.draw, s.dparseWs, s.dmatesWs, (void*)s.dhdr, (void*)s.dnames, (void*)s.dnameoff, (void*)s.dstatus}) if (p) (void)hipFree(p);
         if (s.hhdr) (void)hipHostFree(s.hhdr); if (s.hstatus) (void)hipHostFree(s.hstatus);
         if (s.hcands) (void)hipHostFree(s.hcands); if (s.hqstat) (void)hipHostFree(s.hqstat);
         if (s.hhitcounts) (void)hipHostFree(s.hhitcounts); if (s.hhitoff) (void)hipHostFree(s.hhitoff);
@@ -521,7 +521,21 @@ int mc_batch_add_file_bytes(mc_ctx* ctx, uint32_t slot, const char* bytes, uint6
     if (S.nq || S.raw) return fail(ctx, MC_ERR_STATE, "mc_batch_add_file_bytes: the slot already holds reads");
     if (nbytes > ctx->cfg.slot_max_chars) return MC_BATCH_FULL;
     std::memcpy(S.hseq, bytes, nbytes);
-    S.raw = true; S.rawBytes = nbytes; S.rawFlags = flags; S.rawInsertMax = insertMax;
+    S.raw = true; S.rawBytes = nbytes; S.rawBytes2 = 0; S.rawFlags = flags; S.rawInsertMax = insertMax;
+    return MC_OK;
+}
+
+int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insertMax)
+{
+    if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
+    if (!bytes1 || !bytes2 || n1 == 0 || n2 == 0) return fail(ctx, MC_ERR_INVALID, "mc_batch_add_file_mates: no bytes");
+    Slot& S = ctx->slots[slot];
+    if (S.submitted) return fail(ctx, MC_ERR_STATE, "mc_batch_add_file_mates: slot is in flight, call mc_batch_wait + mc_batch_clear");
+    if (S.nq || S.raw) return fail(ctx, MC_ERR_STATE, "mc_batch_add_file_mates: the slot already holds reads");
+    if (n1 > ctx->cfg.slot_max_chars || n2 > ctx->cfg.slot_max_chars || n1 + n2 > ctx->cfg.slot_max_chars) return MC_BATCH_FULL;
+    std::memcpy(S.hseq, bytes1, n1);
+    std::memcpy(S.hseq + n1, bytes2, n2);
+    S.raw = true; S.rawBytes = n1; S.rawBytes2 = n2; S.rawFlags = 0; S.rawInsertMax = insertMax;
     return MC_OK;
 }
 
@@ -537,16 +551,23 @@ static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
         HIP_TRY(ctx, hipMalloc((void**)&S.dhdr, nq * 16));
         HIP_TRY(ctx, hipMalloc((void**)&S.dnames, nc));
         HIP_TRY(ctx, hipMalloc((void**)&S.dnameoff, (nq + 1) * 8));
-        HIP_TRY(ctx, hipMalloc((void**)&S.dstatus, 64));
+        HIP_TRY(ctx, hipMalloc((void**)&S.dstatus, 128));
         HIP_TRY(ctx, hipHostMalloc((void**)&S.hhdr, nq * 16));
-        HIP_TRY(ctx, hipHostMalloc((void**)&S.hstatus, 64));
+        HIP_TRY(ctx, hipHostMalloc((void**)&S.hstatus, 128));
     }
-    const bool pairs = (S.rawFlags & MC_PARSE_PAIRS) != 0;
+    const bool mates = S.rawBytes2 != 0, pairs = mates || (S.rawFlags & MC_PARSE_PAIRS) != 0;
+    const uint64_t at2 = (S.rawBytes + 15) / 16 * 16;                     // (the second range on the device: behind the first, at a multiple of 16; draw has 16 bytes to spare)
+    const uint64_t matesWs = 2 * mc_parse_scratch_bytes(ctx->cfg.slot_max_chars) + mc_parse_mates_scratch_bytes(1, 1, (uint32_t)(2 * nq));   // (enough for every split of a slot's characters)
+    if (mates && !S.dmatesWs) HIP_TRY(ctx, hipMalloc(&S.dmatesWs, matesWs));
     HIP_TRY(ctx, hipMemcpyAsync(S.draw, S.hseq, S.rawBytes, hipMemcpyHostToDevice, st));
+    if (mates) HIP_TRY(ctx, hipMemcpyAsync(S.draw + at2, S.hseq + S.rawBytes, S.rawBytes2, hipMemcpyHostToDevice, st));
     mc_parse_output o{};
     o.hdr = S.dhdr; o.qinfo = S.dqinfo; o.seq = S.dseq; o.seq_capacity = nc; o.names = (char*)S.dnames; o.names_capacity = nc;
     o.name_off = S.dnameoff; o.max_win = S.dmaxwin; o.status = S.dstatus;
     o.max_records = (uint32_t)(pairs ? 2 * nq : nq);             // (qinfo, name_off and max_win take a row per QUERY)
+    if (mates) {
+        if (const int rc = mc_parse_mates(ctx, (const char*)S.draw, S.rawBytes, (const char*)S.draw + at2, S.rawBytes2, 0, S.rawInsertMax, &o, S.dmatesWs, matesWs, st)) return rc;
+    } else
     if (const int rc = mc_parse_records(ctx, (const char*)S.draw, S.rawBytes, S.rawFlags, S.rawInsertMax, &o, S.dparseWs, mc_parse_scratch_bytes(ctx->cfg.slot_max_chars), st)) return rc;
     HIP_TRY(ctx, hipMemcpyAsync(S.hstatus, S.dstatus, 64, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));
@@ -897,7 +918,7 @@ int mc_batch_clear(mc_ctx* ctx, uint32_t slot)
     } else if (S.submitted) (void)hipEventSynchronize(S.done);
     release_pipe(ctx, S);
     S.submitted = false; S.nq = 0; S.nchars = 0; S.maxSingle = 0;
-    S.raw = false; S.rawBytes = 0;
+    S.raw = false; S.rawBytes = 0; S.rawBytes2 = 0;
     return MC_OK;
 }
 

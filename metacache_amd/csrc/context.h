@@ -94,6 +94,9 @@ struct Slot {
     // raw input (mc_batch_add_file_bytes): hseq holds a byte range of a FASTA / FASTQ file; mc_batch_submit uploads it to draw and has
     // mc_parse_records cut it into dseq / dqinfo / dmaxwin -- the buffers of its own are made by the slot's first raw batch
     bool raw = false; uint64_t rawBytes = 0, rawInsertMax = 0; int rawFlags = 0;
+    // two raw ranges (mc_batch_add_file_mates): hseq holds the first range and, right behind it, rawBytes2 bytes of the second; they go
+    // through mc_parse_mates, whose workspace is dmatesWs
+    uint64_t rawBytes2 = 0; void* dmatesWs = nullptr;
     uint8_t* draw = nullptr; void* dparseWs = nullptr; uint32_t* dhdr = nullptr; uint8_t* dnames = nullptr; uint64_t* dnameoff = nullptr; uint64_t* dstatus = nullptr;
     uint32_t* hhdr = nullptr; uint64_t* hstatus = nullptr;   // pinned: the headers' places in the range, mc_parse_records' status
     hipEvent_t done = nullptr;

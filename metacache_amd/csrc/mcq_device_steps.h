@@ -332,7 +332,8 @@ struct FormatClient {                        // a worker's batch as the library 
 };
 
 // ---- parse (mc_batch_add_file_bytes): a batch's reads cut out of the file's bytes on the device ---------------------------
-// MCQ_PARSE_DEVICE=1.  The host index (SeqFile) stays: it numbers the queries, cuts the batches and hands irregular files to its exact
+// MCQ_PARSE_DEVICE=1; =2 means the same, and -pairfiles batches too, as two ranges through mc_batch_add_file_mates (7h.1).
+// The host index (SeqFile) stays: it numbers the queries, cuts the batches and hands irregular files to its exact
 // reader.  A batch whose records all come from the fast scan of a plain mapped file goes to its slot as ONE byte range; the library cuts
 // it, and the step takes the headers' places and the reads' lengths from mc_batch_records.  Whatever the device refuses, a record count
 // that differs from the index's, or a range the slot cannot take leaves the WHOLE batch to the host loop (SlotStep).
@@ -353,7 +354,7 @@ struct ParseStep : DeviceStep {
         const char* sw = std::getenv("MCQ_PARSE_DEVICE");
         if (!sw || std::atoi(sw) == 0) return;
         const bool selects = o.minReadLen > 0 || o.maxReadLen < std::numeric_limits<uint64_t>::max() || o.queryLimit < ((int64_t)1 << 62);
-        const char* first = o.pairing == Options::files ? "-pairfiles: a query's two reads lie in two files"
+        const char* first = (o.pairing == Options::files && std::atoi(sw) < 2) ? "-pairfiles: a query's two reads lie in two files"
                           : selects ? "length filters and -query-limit select the reads on the host"
                           : any_gzip(o) ? "gzip input is inflated on the host" : nullptr;
         off = shared_host_reason(S, merged, false, "", first);

@@ -440,6 +440,10 @@ struct Session {
         c.num_slots = (workers + nrep - 1) / nrep;                              // worker w: replica w % n, slot w / n
         c.slot_max_queries = o.batchSize;
         c.slot_max_chars = std::max<uint32_t>(1u << 24, o.batchSize * 320u);
+        // MCQ_PARSE_DEVICE=2 with -pairfiles: a slot takes the BYTES of a batch's records of both files, twice what one file's records take
+        if (const char* sw = std::getenv("MCQ_PARSE_DEVICE"))
+            if (std::atoi(sw) >= 2 && o.pairing == Options::files)
+                c.slot_max_chars = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(c.slot_max_chars, (uint64_t)o.batchSize * 640u), 0xFFFFFF00ull);
         c.max_load_factor = o.maxLoadFac;
         if (built) {
             if (built->opt.maxLoadFac > 0.4f && built->opt.maxLoadFac < 0.99f) c.max_load_factor = built->opt.maxLoadFac;
@@ -981,13 +985,16 @@ struct SlotStep {
     template <class Emit>
     bool parsed_on_device(Batch& B, Emit&& emit)
     {
+        const bool mates = o.pairing == Options::files;                       // (MCQ_PARSE_DEVICE=2: record q of each file, mc_batch_add_file_mates)
         const size_t per = o.pairing == Options::sequences ? 2 : 1;
         if (B.sel || B.qEnd <= B.qBeg) return false;
         const size_t r0 = B.qBeg * per, r1 = B.qEnd * per - (B.halfLast ? 1 : 0);
         const char* base = nullptr; size_t b = 0, e = 0;
-        if (!Q.files[B.f1]->byte_range(r0, r1, base, b, e)) { parse->note("its records come from the exact reader"); return false; }
+        const char* base2 = nullptr; size_t b2 = 0, e2 = 0;
+        if (!Q.files[B.f1]->byte_range(r0, r1, base, b, e) || (mates && !Q.files[B.f2]->byte_range(r0, r1, base2, b2, e2))) { parse->note("its records come from the exact reader"); return false; }
         const uint64_t tp0 = now_ns();
-        const int rc = mc_batch_add_file_bytes(ctx, slot, base + b, e - b, parse->flags, o.insertMax);
+        const int rc = mates ? mc_batch_add_file_mates(ctx, slot, base + b, e - b, base2 + b2, e2 - b2, o.insertMax)
+                             : mc_batch_add_file_bytes(ctx, slot, base + b, e - b, parse->flags, o.insertMax);
         if (rc == MC_BATCH_FULL) { parse->note("its bytes exceed the slot's character capacity"); return false; }
         if (rc < 0) { Q.fail(mc_last_error(ctx)); return false; }
         mc_results r;
@@ -998,13 +1005,15 @@ struct SlotStep {
         if (mc_batch_wait(ctx, slot, &r) != MC_OK || mc_batch_records(ctx, slot, &info) != MC_OK) { Q.fail(mc_last_error(ctx)); mc_batch_clear(ctx, slot); return false; }
         const uint64_t tp3 = now_ns();
         std::string why;
-        if (info.verdict == MC_PARSE_IRREGULAR) why = "irregular at byte " + std::to_string(b + info.offence);
+        const size_t indexed = mates ? 2 * (r1 - r0) : r1 - r0;
+        if (info.verdict == MC_PARSE_IRREGULAR) why = mates ? "irregular at byte " + std::to_string(info.offence) + " of one of the two ranges" : "irregular at byte " + std::to_string(b + info.offence);
+        else if (info.verdict == MC_PARSE_UNEQUAL) why = "the device counts different numbers of records in the two files' ranges";
         else if (info.verdict != MC_PARSE_OK) why = "more reads or characters than the slot takes";
-        else if (info.records != r1 - r0 || r.num_queries != B.qEnd - B.qBeg) why = "the device counts " + std::to_string(info.records) + " records, the index " + std::to_string(r1 - r0);
+        else if (info.records != indexed || r.num_queries != B.qEnd - B.qBeg) why = "the device counts " + std::to_string(info.records) + " records, the index " + std::to_string(indexed);
         if (!why.empty()) { mc_batch_clear(ctx, slot); parse->note(why); return false; }
         queries.clear();
         for (size_t q = B.qBeg; q < B.qEnd; ++q) {
-            const size_t i = q - B.qBeg, rr = i * per;
+            const size_t i = q - B.qBeg, rr = i * (mates ? 2 : per);          // (mates: row 2i is the first mate's header, a place in the first file's range)
             const bool halfPair = B.halfLast && q + 1 == B.qEnd;
             const View h{base + b + info.hdr[2 * rr], info.hdr[2 * rr + 1]};
             const uint64_t l1 = info.qinfo[4 * i + 1], l2 = info.qinfo[4 * i + 3];
@@ -1012,7 +1021,7 @@ struct SlotStep {
         }
         emit(queries, r);
         mc_batch_clear(ctx, slot);
-        parse->took(e - b, info.records);
+        parse->took((e - b) + (e2 - b2), info.records);
         if (P.on) { P.parse += tp1 - tp0; P.submit += tp2 - tp1; P.wait += tp3 - tp2; P.classify += now_ns() - tp3; }
         return true;
     }

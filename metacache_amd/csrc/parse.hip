@@ -15,6 +15,7 @@
 //   5. parse_queries_kernel  per query: max_win, the ends of name_off and seq
 // parse_scan_kernel is ONE block that turns the tile values into what lies in front of each tile.  No atomic decides a position: the same
 // bytes give the same outputs.  The five byte passes read the input once each: this is built to be right, not yet to be fast (7h).
+// mc_parse_mates (two ranges, query q = record q of each) runs layers 1 and 2 per range and adds a layer per RECORD: see "mates" below.
 // Plain HIP C++; no inline assembly.
 #include "rows_common.h"
 
@@ -436,6 +437,184 @@ __global__ __launch_bounds__(kBlock) void parse_scan_kernel(ParseArgs a)
 
 uint32_t tiles_of(uint64_t nbytes) { return (uint32_t)((nbytes + kTile - 1) / kTile); }
 
+// ---- mates: TWO ranges, query q = record q of the first + record q of the second (mc_parse_mates) --------------------------------------
+// Each range is classified on its own by the layers above (lines -> scan<1> -> classify -> scan<2>, no pairing), in a workspace of its
+// own.  A mate's place in seq depends on the lengths of all earlier records of BOTH ranges, which no prefix over one range's bytes
+// holds, so a layer per RECORD follows:
+//   a. mates_lengths_kernel per tile of either range: len[f][r] (the place is the record's number) and the tile's padding
+//   b. mates_sums_kernel    per kQBlock queries: the sum of pad4(len1) + pad4(len2), the longest len1 + len2
+//      mates_scan_kernel    ONE block: what lies in front of each such block, the verdict, status
+//   c. mates_place_kernel   per query: place[f][q], qinfo, max_win, the ends of name_off and seq
+//   d. mates_write_kernel   per tile of either range: sequence byte -> seq[place[f][r] + (S - S at the record's start)], hdr; names from range 0
+// A block of b./c. takes kQBlock = 256 queries (one a thread); ONE TRIP of mates_scan_kernel takes kBlock such blocks = 65 536 queries,
+// and it makes as many trips as the queries need.  No atomic decides a position.
+constexpr uint32_t kQBlock = kBlock, kMHead = 32;
+enum { mVerdict = 0, mQueries, mSeqEnd, mNames };
+enum { tLen0 = 0, tLen1, tPlace0, tPlace1 };
+
+struct MatesArgs {
+    ParseArgs f[2];                          // the two ranges (pairs = 0; the outputs, capacities and maxRecords are the call's in both)
+    uint32_t* m;                             // kMHead words, four tables of Q words (len, place by range), two of one word per kQBlock queries
+    uint32_t Q;                              // rows of a table: max_records / 2
+};
+
+__device__ __forceinline__ uint32_t* mtab(const MatesArgs& m, uint32_t which) { return m.m + kMHead + (uint64_t)which * m.Q; }
+__host__ __device__ __forceinline__ uint32_t qblocks_of(uint32_t queries) { return (queries + kQBlock - 1) / kQBlock; }
+__device__ __forceinline__ uint32_t* mblk(const MatesArgs& m, uint32_t which) { return m.m + kMHead + 4ull * m.Q + (uint64_t)which * qblocks_of(m.Q); }
+__device__ __forceinline__ uint32_t pad4(uint32_t len) { return (len + 3u) & ~3u; }
+
+// the verdict as far as the ranges' own layers give it: with MC_PARSE_OK the records of both ranges fit the tables
+__device__ __forceinline__ uint32_t mates_so_far(const MatesArgs& m)
+{
+    if (m.f[0].ws[hOffence] != kNone || m.f[1].ws[hOffence] != kNone) return MC_PARSE_IRREGULAR;
+    const uint32_t r0 = m.f[0].ws[hRecs], r1 = m.f[1].ws[hRecs];
+    if (r0 != r1) return MC_PARSE_UNEQUAL;
+    return (uint64_t)r0 + r1 > m.f[0].maxRecords ? MC_PARSE_OVERFLOW : MC_PARSE_OK;
+}
+
+struct LenSink {
+    uint32_t* len; uint32_t rows;
+    __device__ __forceinline__ void seq_byte(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void name_byte(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void query_start(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void header(uint32_t, uint32_t, uint32_t) {}
+    __device__ __forceinline__ void record(uint32_t r, uint32_t, uint32_t l, uint32_t, bool) { if (r < rows) len[r] = l; }
+};
+// (the walk hands S + P to seq_byte, P being the padding of the records that ended inside this thread's bytes: the walk started with P = 0)
+struct MatesSink {
+    const ParseArgs& a; const State& s; const uint32_t* place; uint32_t f, curRec, curPlace;
+    __device__ __forceinline__ uint32_t place_of(uint32_t r) { if (r != curRec) { curRec = r; curPlace = place[r]; } return curPlace; }
+    __device__ __forceinline__ void seq_byte(uint32_t at, uint32_t ch) { a.seq[place_of(s.recs - 1) + (at - s.P - s.recAt)] = (uint8_t)ch; }
+    __device__ __forceinline__ void name_byte(uint32_t at, uint32_t ch) { if (!f) a.names[at] = (uint8_t)ch; }
+    __device__ __forceinline__ void query_start(uint32_t q, uint32_t N) { if (!f) a.nameOff[q] = N; }
+    __device__ __forceinline__ void header(uint32_t r, uint32_t off, uint32_t len) { uint32_t* h = a.hdr + 2ull * (2ull * r + f); h[0] = off; h[1] = len; }
+    __device__ __forceinline__ void record(uint32_t r, uint32_t, uint32_t len, uint32_t pad, bool)
+    {
+        const uint32_t end = place_of(r) + len;
+        for (uint32_t k = 0; k < pad; ++k) a.seq[end + k] = 0;
+    }
+};
+
+__global__ __launch_bounds__(kBlock) void mates_lengths_kernel(MatesArgs m)
+{
+    __shared__ uint32_t lds[8 * kWaves];
+    const ParseArgs& a = m.f[blockIdx.y];
+    if (blockIdx.x >= a.tiles) return;
+    const uint32_t soFar = mates_so_far(m);
+    if (soFar == MC_PARSE_IRREGULAR || soFar == MC_PARSE_UNEQUAL) return;
+    const bool fastq = a.B[0] == '@';
+    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    State s;
+    layer1(a, c, s, lds);
+    layer2(a, c, fastq, s, lds);
+    Tally t = empty_tally();
+    LenSink sink{mtab(m, tLen0 + blockIdx.y), soFar == MC_PARSE_OK ? m.Q : 0u};
+    walk<true>(a, c, fastq, s, t, sink);
+    uint32_t sv[1] = {t.pads}, mv[1] = {0}, st[1], mt[1];
+    block_excl_scan<1, 1>(sv, mv, st, mt, lds);
+    if (threadIdx.x == 0) arr(a, aPads)[blockIdx.x] = st[0];
+}
+
+__global__ __launch_bounds__(kQBlock) void mates_sums_kernel(MatesArgs m)
+{
+    __shared__ uint32_t lds[2 * kWaves];
+    if (mates_so_far(m) != MC_PARSE_OK) return;
+    const uint32_t queries = m.f[0].ws[hRecs];
+    if (blockIdx.x * kQBlock >= queries) return;
+    const uint32_t q = blockIdx.x * kQBlock + threadIdx.x;
+    const uint32_t l0 = q < queries ? mtab(m, tLen0)[q] : 0u, l1 = q < queries ? mtab(m, tLen1)[q] : 0u;
+    uint32_t sv[1] = {pad4(l0) + pad4(l1)}, mv[1] = {l0 + l1}, st[1], mt[1];
+    block_excl_scan<1, 1>(sv, mv, st, mt, lds);
+    if (threadIdx.x == 0) { mblk(m, 0)[blockIdx.x] = st[0]; mblk(m, 1)[blockIdx.x] = mt[0]; }
+}
+
+// ONE block: the tiles' padding summed, the query blocks' sums turned into what lies in front of each, the verdict, status
+__global__ __launch_bounds__(kBlock) void mates_scan_kernel(MatesArgs m)
+{
+    __shared__ uint32_t lds[2 * kWaves];
+    const uint32_t t = threadIdx.x, soFar = mates_so_far(m);
+    const uint32_t r0 = m.f[0].ws[hRecs], r1 = m.f[1].ws[hRecs];
+    uint32_t pads = 0, longest = 0;
+    if (soFar == MC_PARSE_OK || soFar == MC_PARSE_OVERFLOW) {
+        uint32_t mine = 0;
+#pragma unroll
+        for (uint32_t f = 0; f < 2; ++f)
+            for (uint32_t j = t; j < m.f[f].tiles; j += kBlock) mine += arr(m.f[f], aPads)[j];
+        uint32_t sv[1] = {mine}, mv[1] = {0}, st[1], mt[1];
+        block_excl_scan<1, 1>(sv, mv, st, mt, lds);
+        pads = st[0];
+    }
+    if (soFar == MC_PARSE_OK) {
+        const uint32_t nb = qblocks_of(r0);
+        uint32_t inFront = 0;
+        for (uint32_t base = 0; base < nb; base += kBlock) {                      // (the same trips for every thread; a trip: kBlock * kQBlock queries)
+            const uint32_t j = base + t;
+            const bool in = j < nb;
+            uint32_t sv[1] = {in ? mblk(m, 0)[j] : 0u}, mv[1] = {in ? mblk(m, 1)[j] : 0u}, st[1], mt[1];
+            block_excl_scan<1, 1>(sv, mv, st, mt, lds);
+            if (in) mblk(m, 0)[j] = inFront + sv[0];
+            inFront += st[0]; longest = max(longest, mt[0]);
+        }
+    }
+    if (t == 0) {
+        const ParseArgs& a = m.f[0];
+        const uint32_t off0 = a.ws[hOffence], off1 = m.f[1].ws[hOffence];
+        const uint64_t seqNeed = (uint64_t)a.ws[hSeq] + m.f[1].ws[hSeq] + pads + 16, nameNeed = a.ws[hNames];
+        uint32_t verdict = soFar;
+        if (verdict == MC_PARSE_OK && (seqNeed > a.seqCap || nameNeed > a.namesCap)) verdict = MC_PARSE_OVERFLOW;
+        m.m[mVerdict] = verdict; m.m[mQueries] = r0; m.m[mSeqEnd] = (uint32_t)(seqNeed - 16); m.m[mNames] = (uint32_t)nameNeed;
+        const bool counted = verdict != MC_PARSE_IRREGULAR;
+        a.status[0] = counted ? (uint64_t)r0 + r1 : 0; a.status[1] = counted ? min(r0, r1) : 0;
+        a.status[2] = counted ? seqNeed : 0; a.status[3] = counted ? nameNeed : 0;
+        a.status[4] = verdict; a.status[5] = counted ? 0 : (off0 != kNone ? off0 : off1); a.status[6] = longest;
+        a.status[7] = (!counted && off0 == kNone) ? 1 : 0;
+        a.status[8] = counted ? r0 : 0; a.status[9] = counted ? r1 : 0;
+        if (verdict == MC_PARSE_OK) atomicAdd(&a.counters[0], (unsigned long long)r0 + r1);   // (statistics, no position)
+        else atomicAdd(&a.counters[1], 1ull);
+    }
+}
+
+__global__ __launch_bounds__(kQBlock) void mates_place_kernel(MatesArgs m)
+{
+    __shared__ uint32_t lds[2 * kWaves];
+    if (m.m[mVerdict] != MC_PARSE_OK) return;
+    const ParseArgs& a = m.f[0];
+    const uint32_t queries = m.m[mQueries];
+    if (blockIdx.x * kQBlock >= queries) return;
+    const uint32_t q = blockIdx.x * kQBlock + threadIdx.x;
+    const uint32_t l0 = q < queries ? mtab(m, tLen0)[q] : 0u, l1 = q < queries ? mtab(m, tLen1)[q] : 0u;
+    uint32_t sv[1] = {pad4(l0) + pad4(l1)}, mv[1] = {0}, st[1], mt[1];
+    block_excl_scan<1, 1>(sv, mv, st, mt, lds);
+    if (q == 0) {
+        a.nameOff[queries] = m.m[mNames];
+        const uint32_t end = m.m[mSeqEnd];
+        for (uint32_t k = 0; k < 16; ++k) a.seq[end + k] = 0;
+    }
+    if (q >= queries) return;
+    const uint32_t p0 = mblk(m, 0)[blockIdx.x] + sv[0], p1 = p0 + pad4(l0);
+    mtab(m, tPlace0)[q] = p0; mtab(m, tPlace1)[q] = p1;
+    uint32_t* qi = a.qinfo + 4ull * q;
+    qi[0] = p0; qi[1] = l0; qi[2] = p1; qi[3] = l1;
+    a.maxWin[q] = (uint32_t)(2 + max((uint64_t)l0 + l1, a.insertMax) / a.stride);
+}
+
+__global__ __launch_bounds__(kBlock) void mates_write_kernel(MatesArgs m)
+{
+    __shared__ uint32_t lds[8 * kWaves];
+    const ParseArgs& a = m.f[blockIdx.y];
+    if (blockIdx.x >= a.tiles || m.m[mVerdict] != MC_PARSE_OK) return;
+    const bool fastq = a.B[0] == '@';
+    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    State s;
+    layer1(a, c, s, lds);
+    layer2(a, c, fastq, s, lds);
+    Tally t = empty_tally();
+    MatesSink sink{a, s, mtab(m, tPlace0 + blockIdx.y), blockIdx.y, kNone, 0u};
+    walk<true>(a, c, fastq, s, t, sink);
+}
+
+uint64_t mates_words(uint32_t maxRecords) { const uint32_t Q = maxRecords / 2; return (uint64_t)kMHead + 4ull * Q + 2ull * qblocks_of(Q); }
+
 }  // namespace
 
 namespace mcamd {
@@ -445,7 +624,7 @@ struct ParseState {                      // what the context keeps for mc_parse_
     std::atomic<uint64_t> calls{0}, bytes{0};
     std::mutex stageMtx;                 // MC_PARSE_HOST callers take turns at the staging buffers
     DevBuf stageIn, stageWs, stageHdr, stageQinfo, stageSeq, stageNames, stageNameOff, stageMaxWin, stageStatus;
-    uint64_t* hStatus = nullptr;         // pinned [8]
+    uint64_t* hStatus = nullptr;         // pinned [16]: mc_parse_records reads 8 words, mc_parse_mates 10
 };
 
 void free_parse_state(mc_ctx* ctx)
@@ -474,7 +653,7 @@ int ensure_parse_state(mc_ctx* ctx, ParseState** out)
         HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, 16));
         HIP_TRY(ctx, hipMemset(S.dCounters, 0, 16));
     }
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 64));
+    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 128));
     return MC_OK;
 }
 
@@ -504,6 +683,49 @@ int enqueue_parse(mc_ctx* ctx, ParseState& S, const uint8_t* dBytes, uint32_t n,
     }
     HIP_TRY(ctx, hipGetLastError());
     ++S.calls; S.bytes += n;
+    return MC_OK;
+}
+
+// the device form for two ranges: each range's own layers, then the per-record layer; nothing waited for.  ws: range 0's workspace, range
+// 1's, the tables (mc_parse_mates_scratch_bytes)
+int enqueue_mates(mc_ctx* ctx, ParseState& S, const uint8_t* d1, uint32_t n1, const uint8_t* d2, uint32_t n2, uint64_t insertMax, const mc_parse_output& o, void* ws, hipStream_t st)
+{
+    MatesArgs m{};
+    const uint8_t* B[2] = {d1, d2};
+    const uint32_t n[2] = {n1, n2};
+    uint8_t* w = (uint8_t*)ws;
+    for (int f = 0; f < 2; ++f) {
+        ParseArgs& a = m.f[f];
+        a.B = B[f]; a.ws = (uint32_t*)w;
+        w += mc_parse_scratch_bytes(n[f]);
+        a.hdr = o.hdr; a.qinfo = o.qinfo; a.seq = o.seq; a.names = (uint8_t*)o.names; a.nameOff = o.name_off; a.maxWin = o.max_win; a.status = o.status;
+        a.counters = S.dCounters;
+        a.seqCap = o.seq_capacity; a.namesCap = o.names_capacity; a.insertMax = insertMax;
+        a.n = n[f]; a.tiles = tiles_of(n[f]); a.pairs = 0; a.maxRecords = o.max_records;
+        a.stride = ctx->targetSketch.stride ? ctx->targetSketch.stride : 1u;
+    }
+    m.m = (uint32_t*)w; m.Q = o.max_records / 2;
+    const dim3 both(std::max(m.f[0].tiles, m.f[1].tiles), 2);
+    {
+        ScopedTimer timer(ctx, "parse_classify", st);
+        for (int f = 0; f < 2; ++f) {
+            const ParseArgs& a = m.f[f];
+            hipLaunchKernelGGL(parse_lines_kernel, dim3(a.tiles), dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL(parse_scan_kernel<1>, dim3(1), dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL(parse_classify_kernel, dim3(a.tiles), dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL(parse_scan_kernel<2>, dim3(1), dim3(kBlock), 0, st, a);
+        }
+        hipLaunchKernelGGL(mates_lengths_kernel, both, dim3(kBlock), 0, st, m);
+        if (m.Q) hipLaunchKernelGGL(mates_sums_kernel, dim3(qblocks_of(m.Q)), dim3(kQBlock), 0, st, m);
+        hipLaunchKernelGGL(mates_scan_kernel, dim3(1), dim3(kBlock), 0, st, m);
+    }
+    if (m.Q) {
+        ScopedTimer timer(ctx, "parse_write", st);
+        hipLaunchKernelGGL(mates_place_kernel, dim3(qblocks_of(m.Q)), dim3(kQBlock), 0, st, m);
+        hipLaunchKernelGGL(mates_write_kernel, both, dim3(kBlock), 0, st, m);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    ++S.calls; S.bytes += (uint64_t)n1 + n2;
     return MC_OK;
 }
 
@@ -573,6 +795,73 @@ int mc_parse_records(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags,
         HIP_TRY(ctx, hipMemcpyAsync(out->max_win, d.max_win, queries * 4, hipMemcpyDeviceToHost, st));
     }
     if (out->max_records) HIP_TRY(ctx, hipMemcpyAsync(out->name_off, d.name_off, (queries + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out->seq, d.seq, out->status[2], hipMemcpyDeviceToHost, st));
+    if (out->status[3]) HIP_TRY(ctx, hipMemcpyAsync(out->names, d.names, out->status[3], hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return MC_OK;
+}
+
+uint64_t mc_parse_mates_scratch_bytes(uint64_t n1, uint64_t n2, uint32_t max_records)
+{
+    return mc_parse_scratch_bytes(n1) + mc_parse_scratch_bytes(n2) + (mates_words(max_records) * 4 + 255) / 256 * 256;
+}
+
+int mc_parse_mates(mc_ctx* ctx, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, int flags, uint64_t insert_size_max,
+                   const mc_parse_output* out, void* workspace, uint64_t workspace_bytes, void* streamv)
+{
+    // arguments first ...
+    if (!ctx) return MC_ERR_INVALID;
+    if (!out) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: no outputs");
+    if (flags & ~MC_PARSE_HOST) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: flags other than MC_PARSE_HOST (the ranges ARE the pairing)");
+    if (!bytes1 || !bytes2 || n1 == 0 || n2 == 0) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: no bytes");
+    if (n1 > (1ull << 31) || n2 > (1ull << 31) || n1 + n2 > (1ull << 31)) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: more than 2^31 bytes in the two ranges");
+    if (!out->status) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: no status");
+    if (out->max_records > 0 && (!out->hdr || !out->qinfo || !out->name_off || !out->max_win)) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: null array");
+    if ((out->seq_capacity > 0 && !out->seq) || (out->names_capacity > 0 && !out->names)) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: a capacity without its array");
+    if (out->seq_capacity > 0xFFFFFFFFull || out->names_capacity > 0xFFFFFFFFull) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: a capacity beyond 32-bit offsets");
+    const bool host = (flags & MC_PARSE_HOST) != 0;
+    const uint64_t wsNeed = mc_parse_mates_scratch_bytes(n1, n2, out->max_records);
+    if (host) {
+        if ((bytes1[0] != '>' && bytes1[0] != '@') || (bytes2[0] != '>' && bytes2[0] != '@')) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: a range does not begin with '>' or '@'");
+    } else {
+        if (!workspace || workspace_bytes < wsNeed) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: the workspace is smaller than mc_parse_mates_scratch_bytes");
+        if (((uintptr_t)bytes1 | (uintptr_t)bytes2 | (uintptr_t)out->seq | (uintptr_t)workspace) & 15u) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: device arrays must be aligned (bytes1, bytes2, seq, workspace: 16 bytes)");
+        if (((uintptr_t)out->name_off | (uintptr_t)out->status) & 7u) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: device arrays must be aligned (name_off, status: 8 bytes)");
+        if (((uintptr_t)out->hdr | (uintptr_t)out->qinfo | (uintptr_t)out->max_win) & 3u) return fail(ctx, MC_ERR_INVALID, "mc_parse_mates: device arrays must be aligned (hdr, qinfo, max_win: 4 bytes)");
+    }
+    // ... then state
+    if (!ctx->stream) return fail(ctx, MC_ERR_STATE, "mc_parse_mates: the context has no device (mc_open_metadata)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
+    ParseState* S = nullptr;
+    int rc = ensure_parse_state(ctx, &S);
+    if (rc) return rc;
+    if (!host) return enqueue_mates(ctx, *S, (const uint8_t*)bytes1, (uint32_t)n1, (const uint8_t*)bytes2, (uint32_t)n2, insert_size_max, *out, workspace, st);
+    // host arrays: through the staging buffers, one caller at a time (range 2 behind range 1, at a multiple of 16); outputs leave the
+    // device only with the verdict MC_PARSE_OK
+    std::lock_guard<std::mutex> lock(S->stageMtx);
+    const uint64_t mr = out->max_records, at2 = (n1 + 15) / 16 * 16;
+    if ((rc = grow(ctx, S->stageIn, at2 + (n2 + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, wsNeed)) != MC_OK ||
+        (rc = grow(ctx, S->stageHdr, std::max<uint64_t>(mr * 8, 16))) != MC_OK || (rc = grow(ctx, S->stageQinfo, std::max<uint64_t>(mr * 16, 16))) != MC_OK ||
+        (rc = grow(ctx, S->stageSeq, std::max<uint64_t>(out->seq_capacity, 16))) != MC_OK || (rc = grow(ctx, S->stageNames, std::max<uint64_t>(out->names_capacity, 16))) != MC_OK ||
+        (rc = grow(ctx, S->stageNameOff, (mr + 1) * 8)) != MC_OK || (rc = grow(ctx, S->stageMaxWin, std::max<uint64_t>(mr * 4, 16))) != MC_OK ||
+        (rc = grow(ctx, S->stageStatus, 128)) != MC_OK) return rc;
+    uint8_t* in = (uint8_t*)S->stageIn.p;
+    HIP_TRY(ctx, hipMemcpyAsync(in, bytes1, n1, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(in + at2, bytes2, n2, hipMemcpyHostToDevice, st));
+    mc_parse_output d = *out;
+    d.hdr = (uint32_t*)S->stageHdr.p; d.qinfo = (uint32_t*)S->stageQinfo.p; d.seq = (uint8_t*)S->stageSeq.p; d.names = (char*)S->stageNames.p;
+    d.name_off = (uint64_t*)S->stageNameOff.p; d.max_win = (uint32_t*)S->stageMaxWin.p; d.status = (uint64_t*)S->stageStatus.p;
+    if ((rc = enqueue_mates(ctx, *S, in, (uint32_t)n1, in + at2, (uint32_t)n2, insert_size_max, d, S->stageWs.p, st)) != MC_OK) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, d.status, 80, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(out->status, S->hStatus, 80);
+    if (out->status[4] != MC_PARSE_OK) return MC_OK;
+    const uint64_t recs = out->status[0], queries = out->status[1];
+    HIP_TRY(ctx, hipMemcpyAsync(out->hdr, d.hdr, recs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out->qinfo, d.qinfo, queries * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out->max_win, d.max_win, queries * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(out->name_off, d.name_off, (queries + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(out->seq, d.seq, out->status[2], hipMemcpyDeviceToHost, st));
     if (out->status[3]) HIP_TRY(ctx, hipMemcpyAsync(out->names, d.names, out->status[3], hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
