@@ -880,6 +880,89 @@ int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out);
  *   a verdict other than MC_PARSE_OK (MC_PARSE_UNEQUAL among them) leaves mc_results.num_queries at 0. */
 int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insert_size_max);
 
+/* ---- per-part result files merged on the device: what `metacache merge` reads ------
+ * The result files of queries against single database parts (docs/partitioning.md of the reference) are cut into one candidate list
+ * per query, and the vote runs over those lists.  (mc_merge_part_candidates above is something else: it merges candidate ARRAYS.)
+ * Terms: a RESULT LINE is a line that does not start with '#'; lines that start with '#' are comment lines.  A TAXON ENTRY x is taxon
+ * index + 1: row x - 1 of the taxon table (mc_set_taxon_table), 0 = none.  The LIST of query q is max_candidates pairs {taxon entry,
+ * hits}, hits descending, ending at the first pair with hits == 0.
+ * THE LINE RULE (read_results, mode_merge.cpp:158-238) -- narrower than what the reference's stream code tolerates: the device refuses
+ * more and never reads an accepted range differently.  A range is bytes[0, n), n <= 2^31; it begins at a line start and its last line
+ * may lack the '\n'.  A regular result line is, in order:
+ *   1. one or more decimal digits at the line's first byte, value id <= 2^32 - 1; the query is q = id > 0 ? id - 1 : 0;
+ *   2. any bytes up to the first '|';
+ *   3. blanks (' ' or '\t'), then the header token: a non-empty run of non-blank bytes that holds no '|';
+ *   4. from there tophits_column - 1 further '|', then the next '\t';
+ *   5. the list: empty when the next byte is '\t' or the line ends; else entry (',' entry)* followed by '\t' or the end of the line,
+ *      entry = an optional '-', 1-18 digits (the taxid), ':', 1-10 digits (hits, 1 .. 2^32 - 1).
+ *   An empty line, a '\r', '\v', '\f' or NUL byte anywhere in a result line, or any other deviation makes the range IRREGULAR; the offence is the
+ *   smallest line start of an offending line.  A second result line for the same q inside one file is an offending line too (found
+ *   for q below the store's capacity: beyond it the verdict is MC_MERGE_OVERFLOW first).
+ * TAXIDS: a taxid becomes a taxon entry through mc_merge_results_set_taxids; an entry whose taxid is not in the table is skipped and
+ *   counted (the reference's "Skipping hit").
+ * THE FILE RULE (the reference's resize, mode_merge.cpp:171-186): at the start of each file the number of lists is set to that file's
+ *   number of result lines, which empties the lists and header places of higher queries collected from earlier files; a line whose
+ *   q + 1 exceeds it grows it again.  Files are folded in the order of the calls, the entries of a line in their order.
+ * THE INSERT RULE is insert_taxon_candidate (candidate_generation.hpp:172-231) with max_candidates and merge_below: a full list whose
+ *   last entry has at least as many hits refuses the entry; with merge_below != 0 an entry whose taxon is in the list replaces that
+ *   one only with strictly more hits and moves up past entries with strictly fewer; otherwise it goes behind every entry with as
+ *   many hits (ties keep the earlier one in front) and the entry pushed out at the end is dropped.
+ * THE HEADER RULE: a query keeps the header token of the first line folded for it while it had none, as a place {call, offset,
+ *   length}: call = the number of the mc_merge_results_add call since mc_merge_results_begin (from 0, refused calls counted), offset
+ *   into that call's range.  length 0: no header.
+ * THE VOTE RULE is that of mc_classify_candidates for candidates that carry a taxon (classification.cpp:146-189): the lineage of a
+ *   candidate is its taxon's row of the taxon table, the walk starts at the top candidate's own taxon and at that taxon's rank (a taxon
+ *   without a rank starts at MC_NUM_RANKS and ends unclassified); threshold, voters, highest_rank, the final check and mc_assignment
+ *   are as there.  lowest_rank is checked and not used.
+ * mc_merge_results_set_taxids: id_of_row[x - 1] = the taxid of taxon entry x.  Needs mc_set_taxon_table first, with as many rows, and
+ *   again after a later mc_set_taxon_table; duplicate ids are MC_ERR_INVALID.  Waits for the device.
+ * mc_merge_results_begin: an empty store of capacity_queries lists (8 * max_candidates + 20 bytes per query); max_candidates beyond
+ *   mc_merge_results_max_candidates (32) is MC_ERR_UNSUPPORTED.  mc_merge_results_reserve grows the store and keeps its content; both
+ *   wait for the device.  mc_merge_results_end frees the store.
+ * mc_merge_results_add folds one range.  file_lines is ignored with MC_MERGE_CONTINUE (the range continues the file of the previous
+ *   call: no cut, duplicates are checked across the pieces); otherwise it is the file's number of result lines, 0 = "this range is the
+ *   whole file: count them".  status[8] = result lines, comment lines, lists after the call, entries folded, unknown taxids, verdict,
+ *   offence, capacity needed.  With a verdict other than MC_MERGE_OK NOTHING but status changes, and [3], [4] are 0; [7] is 0 with
+ *   MC_MERGE_IRREGULAR.  MC_MERGE_OVERFLOW: some q, or file_lines, is beyond the capacity; [7] says what to reserve.
+ *   Without MC_MERGE_HOST bytes, status and workspace are DEVICE pointers (bytes and workspace 16-byte, status 8-byte aligned; workspace
+ *   of mc_merge_results_scratch_bytes(nbytes) bytes) and the call is enqueued on `stream` (NULL: the context's) without any
+ *   synchronisation, neither between its passes nor between calls.  The calls on one context's store are ordered by the caller (one
+ *   stream, or events).  The same calls give the same bytes.  With MC_MERGE_HOST bytes and status are HOST arrays (workspace may be
+ *   NULL), staged through the context; the call returns when status is filled.
+ * mc_merge_results_lists copies lists [first, first + count) (count * max_candidates pairs) and their header places ([count][3]);
+ *   either array may be NULL; *num_queries (may be NULL) = the number of lists.  Lists beyond that number are empty.  flags: 0 (DEVICE
+ *   pointers, enqueued) or MC_MERGE_HOST (returns when filled).
+ * mc_merge_results_classify: out[i] = the assignment of query first + i.  flags as for mc_classify_candidates; MC_CLASSIFY_TALLY adds to
+ *   the counters mc_classify_tally reads.  Those are sized by the lineage table; a context WITHOUT lineages sizes them by the taxon table
+ *   (*num_counts = 1 + its rows, and mc_classify_tally then works without lineages), a context with lineages whose table names fewer
+ *   taxa than the taxon table has rows gets MC_ERR_UNSUPPORTED for the flag.
+ * mc_merge_results_stats: calls, bytes, result lines of accepted ranges, entries folded, unknown taxids, ranges refused; waits.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, bytes, status or options, nbytes == 0 or > 2^31,
+ *   tophits_column == 0, unknown flags, max_candidates == 0, misaligned device arrays, a workspace that is too small, NULL out with
+ *   count > 0; with a store: first + count beyond its capacity.  MC_ERR_STATE: no taxon table, no taxid table, no begin,
+ *   MC_MERGE_CONTINUE as the first call, or a context without a device (mc_open_metadata).  The calls work on a context without a
+ *   loaded table (mc_create).  mc_timing_get names: "merge_results_validate", "merge_results_fold", "merge_results_vote". */
+typedef struct { uint32_t taxon, hits; } mc_taxon_candidate;
+#define MC_MERGE_HOST      1         /* bytes is a HOST array, staged through the context; the call returns when done */
+#define MC_MERGE_CONTINUE  2         /* this range continues the file of the previous call */
+#define MC_MERGE_OK        0
+#define MC_MERGE_IRREGULAR 1
+#define MC_MERGE_OVERFLOW  2
+extern const uint32_t mc_merge_results_tile;             /* bytes one block owns the line starts of (for tests and tools) */
+extern const uint32_t mc_merge_results_max_candidates;
+int mc_merge_results_set_taxids(mc_ctx* ctx, const int64_t* id_of_row, uint64_t num_taxa);
+int mc_merge_results_begin(mc_ctx* ctx, uint64_t capacity_queries, uint32_t max_candidates, int32_t merge_below);
+int mc_merge_results_reserve(mc_ctx* ctx, uint64_t capacity_queries);
+uint64_t mc_merge_results_scratch_bytes(uint64_t nbytes);
+int mc_merge_results_add(mc_ctx* ctx, const char* bytes, uint64_t nbytes, uint32_t tophits_column, uint64_t file_lines, int flags,
+                         uint64_t status[8], void* workspace, uint64_t workspace_bytes, void* stream);
+int mc_merge_results_lists(mc_ctx* ctx, uint64_t first, uint64_t count, int flags, mc_taxon_candidate* lists, uint32_t* header_place,
+                           uint64_t* num_queries, void* stream);
+int mc_merge_results_classify(mc_ctx* ctx, const mc_classify_options* opt, int flags, uint64_t first, uint64_t count, mc_assignment* out,
+                              void* stream);
+int mc_merge_results_stats(mc_ctx* ctx, uint64_t stats[6]);
+void mc_merge_results_end(mc_ctx* ctx);
+
 /* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
  * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the
  * database -- how many features, how many locations, the distribution of the list sizes, which locations a feature has -- and here the

@@ -555,6 +555,97 @@ inline void database::query_gpu_async(query_batch& batch, unsigned hostId, taxon
     if (mc_batch_submit(ctx_, hostId, int(lowestRank)) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
 }
 
+// per-part result files merged on the device (mc_merge_results_*; the reference's mode_merge.cpp): a context of its own without a table.
+// set_taxa gives every taxon's ranked lineage (taxon index + 1, 0 = none), rank and taxid; begin makes the store; add folds one file (or
+// one piece of a file, in order); lists() / classify() read the store.  A range the device refuses leaves the store as it was.
+class result_merger {
+public:
+    struct status { std::uint64_t lines, comments, lists, entries, unknown, verdict, offence, needed; };
+    struct merged_lists {
+        std::uint32_t max_candidates = 0;
+        std::vector<mc_taxon_candidate> lists;       // [queries][max_candidates], a list ends at hits == 0
+        std::vector<std::uint32_t> header_place;     // [queries][3]: call, offset, length (0: none)
+        std::uint64_t queries = 0;
+    };
+
+    explicit result_merger(int device = 0)
+    {
+        mc_config c;
+        mc_config_default(&c);
+        c.device = device;
+        if (mc_create(&c, &ctx_) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
+    }
+    result_merger(const result_merger&) = delete;
+    result_merger& operator=(const result_merger&) = delete;
+    ~result_merger() { if (ctx_) { mc_merge_results_end(ctx_); mc_destroy(ctx_); } }
+    mc_ctx* handle() const noexcept { return ctx_; }
+
+    void set_taxa(const std::uint32_t* lin, const std::uint8_t* rank, const std::int64_t* ids, std::uint64_t numTaxa)
+    {
+        check(mc_set_taxon_table(ctx_, lin, rank, nullptr, numTaxa));
+        check(mc_merge_results_set_taxids(ctx_, ids, numTaxa));
+    }
+    void begin(std::uint64_t capacityQueries, std::uint32_t maxCandidates = 2, std::int32_t mergeBelow = 4)
+    {
+        check(mc_merge_results_begin(ctx_, capacityQueries, maxCandidates, mergeBelow));
+        capacity_ = capacityQueries; maxCand_ = maxCandidates;
+    }
+    void reserve(std::uint64_t capacityQueries) { check(mc_merge_results_reserve(ctx_, capacityQueries)); capacity_ = std::max(capacity_, capacityQueries); }
+    // host bytes; fileLines 0: the range is the whole file.  MC_MERGE_OVERFLOW is answered here by one reserve and a second call.
+    status add(const char* bytes, std::size_t nbytes, std::uint32_t tophitsColumn, std::uint64_t fileLines = 0, bool cont = false)
+    {
+        std::uint64_t st[8];
+        for (int attempt = 0;; ++attempt) {
+            check(mc_merge_results_add(ctx_, bytes, nbytes, tophitsColumn, fileLines, MC_MERGE_HOST | (cont ? MC_MERGE_CONTINUE : 0), st, nullptr, 0, nullptr));
+            ++calls_;
+            if (st[5] != MC_MERGE_OVERFLOW || attempt == 1) break;
+            reserve(st[7]);
+        }
+        return status{st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]};
+    }
+    std::uint32_t calls() const noexcept { return calls_; }      // add calls so far, the retries included: the next one's number in a header place
+    merged_lists lists() const
+    {
+        merged_lists m;
+        m.max_candidates = maxCand_;
+        check(mc_merge_results_lists(ctx_, 0, 0, MC_MERGE_HOST, nullptr, nullptr, &m.queries, nullptr));
+        m.lists.resize(m.queries * maxCand_);
+        m.header_place.resize(m.queries * 3);
+        if (m.queries) check(mc_merge_results_lists(ctx_, 0, m.queries, MC_MERGE_HOST, m.lists.data(), m.header_place.data(), nullptr, nullptr));
+        return m;
+    }
+    std::vector<mc_assignment> classify(const mc_classify_options& opt, bool tally = false) const
+    {
+        std::uint64_t n = 0;
+        check(mc_merge_results_lists(ctx_, 0, 0, MC_MERGE_HOST, nullptr, nullptr, &n, nullptr));
+        std::vector<mc_assignment> out(n);
+        if (n) check(mc_merge_results_classify(ctx_, &opt, MC_CLASSIFY_HOST | (tally ? MC_CLASSIFY_TALLY : 0), 0, n, out.data(), nullptr));
+        return out;
+    }
+    std::vector<std::uint64_t> stats() const
+    {
+        std::vector<std::uint64_t> s(6);
+        check(mc_merge_results_stats(ctx_, s.data()));
+        return s;
+    }
+    // the tallies of the classify(opt, true) calls (mc_classify_tally): assigned[r] = queries whose result has rank r ([MC_NUM_RANKS]:
+    // unclassified); returns the queries per taxon entry
+    std::vector<std::uint64_t> tally(std::uint64_t assigned[MC_NUM_RANKS + 1], bool reset = false) const
+    {
+        std::uint64_t n = 0;
+        check(mc_classify_tally(ctx_, nullptr, nullptr, 0, &n, 0));
+        std::vector<std::uint64_t> perTaxon(n);
+        check(mc_classify_tally(ctx_, assigned, perTaxon.data(), n, nullptr, reset ? 1 : 0));
+        return perTaxon;
+    }
+
+private:
+    void check(int rc) const { if (rc < 0) throw std::runtime_error(mc_last_error(ctx_)); }
+    mc_ctx* ctx_ = nullptr;
+    std::uint64_t capacity_ = 0;
+    std::uint32_t maxCand_ = 0, calls_ = 0;
+};
+
 }  // namespace mc_amd
 
 #endif

@@ -121,6 +121,16 @@ def parse_tile() -> int:
     return int(C.c_uint32.in_dll(lib(), "mc_parse_tile").value)
 
 
+def merge_results_tile() -> int:
+    """bytes one block of the merge kernels owns the line starts of (the library's mc_merge_results_tile)"""
+    return int(C.c_uint32.in_dll(lib(), "mc_merge_results_tile").value)
+
+
+def merge_results_scratch_bytes(nbytes: int) -> int:
+    """bytes of device workspace ResultMerger.add_device needs for a range of nbytes bytes"""
+    return int(lib().mc_merge_results_scratch_bytes(nbytes))
+
+
 def parse_scratch_bytes(nbytes: int) -> int:
     """the workspace a device call of mc_parse_records needs for a range of nbytes"""
     return int(lib().mc_parse_scratch_bytes(nbytes))
@@ -348,7 +358,9 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_format_matches_set_text", "mc_format_matches", "mc_format_mappings_with", "mc_format_matches_stats",
            "mc_table_histogram", "mc_table_features", "mc_table_lookup",
            "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records",
-           "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates"]
+           "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates",
+           "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
+           "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end"]
 
 _lib = None
 
@@ -443,6 +455,17 @@ def lib() -> C.CDLL:
         L.mc_parse_mates_scratch_bytes.restype = C.c_uint64
         L.mc_parse_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(McParseOutput), C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_batch_add_file_mates.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.mc_merge_results_set_taxids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_merge_results_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]
+        L.mc_merge_results_reserve.argtypes = [C.c_void_p, C.c_uint64]
+        L.mc_merge_results_scratch_bytes.argtypes = [C.c_uint64]
+        L.mc_merge_results_scratch_bytes.restype = C.c_uint64
+        L.mc_merge_results_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_merge_results_lists.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mc_merge_results_classify.argtypes = [C.c_void_p, C.POINTER(McClassifyOptions), C.c_int, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mc_merge_results_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_merge_results_end.argtypes = [C.c_void_p]
+        L.mc_merge_results_end.restype = None
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -1604,3 +1627,106 @@ def align_semiglobal(reads, subjects, mates=None, handle=None, scratch_mb=None):
         return A.align(reads, subjects, mates)
     finally:
         A.close()
+
+
+MERGE_HOST, MERGE_CONTINUE = 1, 2
+MERGE_OK, MERGE_IRREGULAR, MERGE_OVERFLOW = 0, 1, 2
+
+
+class ResultMerger:
+    """Per-part result files merged on the device (mc_merge_results_*): a context of its own, or any Database's handle.
+    set_taxa, begin, then add per file (or piece of a file) in order; lists() / classify() read the store."""
+
+    def __init__(self, handle=None, **kw):
+        self.own = handle is None
+        if self.own:
+            cfg = default_config(**kw)
+            h = C.c_void_p()
+            rc = lib().mc_create(C.byref(cfg), C.byref(h))
+            if rc != MC_OK:
+                raise McError(f"mc_create -> {rc}: {lib().mc_last_error(None).decode()}")
+            handle = h.value
+        self.h = C.c_void_p(handle)
+        self.capacity = self.max_candidates = 0
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise McError(f"{what} -> {rc}: {lib().mc_last_error(self.h).decode()}")
+        return rc
+
+    def close(self):
+        if self.h:
+            lib().mc_merge_results_end(self.h)
+            if self.own:
+                lib().mc_destroy(self.h)
+        self.h = None
+
+    def set_taxa(self, lin, rank, ids):
+        """the taxon table (lin[taxa, 21] taxon index + 1, rank[taxa] or None) and the taxid of every row"""
+        lin = np.ascontiguousarray(lin, dtype=np.uint32)
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        if lin.ndim != 2 or lin.shape[1] != NUM_RANKS or len(ids) != len(lin):
+            raise ValueError("set_taxa: lin must be [taxa, 21] with one id per row")
+        rank = None if rank is None else np.ascontiguousarray(rank, dtype=np.uint8)
+        self._check(lib().mc_set_taxon_table(self.h, lin.ctypes.data, None if rank is None else rank.ctypes.data, None, len(lin)), "mc_set_taxon_table")
+        self._check(lib().mc_merge_results_set_taxids(self.h, ids.ctypes.data, len(ids)), "mc_merge_results_set_taxids")
+
+    def begin(self, capacity: int, max_candidates: int = 2, merge_below: int = 4):
+        self._check(lib().mc_merge_results_begin(self.h, capacity, max_candidates, merge_below), "mc_merge_results_begin")
+        self.capacity, self.max_candidates = int(capacity), int(max_candidates)
+
+    def reserve(self, capacity: int):
+        self._check(lib().mc_merge_results_reserve(self.h, capacity), "mc_merge_results_reserve")
+        self.capacity = max(self.capacity, int(capacity))
+
+    def add(self, data, tophits_column: int, file_lines: int = 0, cont: bool = False):
+        """a host range (bytes) -> status[8]: result lines, comment lines, lists, entries folded, unknown taxids, verdict, offence, capacity needed"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        st = np.zeros(8, dtype=np.uint64)
+        self._check(lib().mc_merge_results_add(self.h, buf.ctypes.data, len(buf), tophits_column, file_lines, MERGE_HOST | (MERGE_CONTINUE if cont else 0),
+                                               st.ctypes.data, None, 0, None), "mc_merge_results_add")
+        return [int(x) for x in st]
+
+    def add_device(self, bytes_ptr: int, nbytes: int, tophits_column: int, *, status_ptr: int, workspace_ptr: int, workspace_bytes: int,
+                   file_lines: int = 0, cont: bool = False, stream: int = 0):
+        """device pointers; enqueued on `stream` (0: the context's), nothing is waited for"""
+        self._check(lib().mc_merge_results_add(self.h, bytes_ptr, nbytes, tophits_column, file_lines, MERGE_CONTINUE if cont else 0, status_ptr,
+                                               workspace_ptr, workspace_bytes, stream or None), "mc_merge_results_add")
+
+    def lists(self, first: int = 0, count=None):
+        """-> lists [count, max_candidates, 2] uint32 (taxon entry, hits), header places [count, 3] uint32 (call, offset, length), number of lists"""
+        count = self.capacity - first if count is None else count
+        lists = np.zeros((count, self.max_candidates, 2), dtype=np.uint32)
+        places = np.zeros((count, 3), dtype=np.uint32)
+        n = C.c_uint64(0)
+        self._check(lib().mc_merge_results_lists(self.h, first, count, MERGE_HOST, lists.ctypes.data, places.ctypes.data, C.addressof(n), None), "mc_merge_results_lists")
+        return lists, places, int(n.value)
+
+    def lists_device(self, first: int, count: int, *, lists_ptr: int, places_ptr: int, num_ptr: int = 0, stream: int = 0):
+        self._check(lib().mc_merge_results_lists(self.h, first, count, 0, lists_ptr or None, places_ptr or None, num_ptr or None, stream or None), "mc_merge_results_lists")
+
+    def classify(self, options: McClassifyOptions, tally: bool = False, first: int = 0, count=None):
+        """-> [count, 2] uint32: taxon entry, info (bits 0-7 rank, 8-15 voters) of the queries first .. first + count"""
+        count = self.capacity - first if count is None else count
+        out = np.zeros((count, 2), dtype=np.uint32)
+        self._check(lib().mc_merge_results_classify(self.h, C.byref(options), 1 | (2 if tally else 0), first, count, out.ctypes.data, None), "mc_merge_results_classify")
+        return out
+
+    def classify_device(self, options: McClassifyOptions, first: int, count: int, out_ptr: int, stream: int = 0, tally: bool = False):
+        self._check(lib().mc_merge_results_classify(self.h, C.byref(options), 2 if tally else 0, first, count, out_ptr, stream or None), "mc_merge_results_classify")
+
+    def tally(self, reset: bool = False):
+        """the tallies of the classify(..., tally=True) calls (mc_classify_tally) -> assigned [22] uint64 (reads per result rank, [21] =
+        unclassified), per_taxon [taxa + 1] uint64 (index = taxon entry)"""
+        n = C.c_uint64(0)
+        assigned = np.zeros(NUM_RANKS + 1, dtype=np.uint64)
+        self._check(lib().mc_classify_tally(self.h, assigned.ctypes.data, None, 0, C.byref(n), 0), "mc_classify_tally")
+        per_taxon = np.zeros(int(n.value), dtype=np.uint64)
+        self._check(lib().mc_classify_tally(self.h, assigned.ctypes.data, per_taxon.ctypes.data, len(per_taxon), None, 1 if reset else 0), "mc_classify_tally")
+        return assigned, per_taxon
+
+    def stats(self):
+        """[calls, bytes, result lines of accepted ranges, entries folded, unknown taxids, ranges refused]"""
+        st = np.zeros(6, dtype=np.uint64)
+        self._check(lib().mc_merge_results_stats(self.h, st.ctypes.data), "mc_merge_results_stats")
+        return [int(x) for x in st]

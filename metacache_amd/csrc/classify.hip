@@ -113,12 +113,24 @@ int mcamd::ensure_classify_state(mc_ctx* ctx, ClassifyState** out)
     if (!ctx->classify) ctx->classify = new ClassifyState;
     ClassifyState& S = *ctx->classify;
     *out = &S;
-    if (S.version == ctx->lineageVersion && S.dLin) return MC_OK;
+    // a context without lineages that has a taxon table (mc_merge_results_classify): no lineage planes, the tallies sized by the taxon table
+    const bool byTaxa = ctx->lineages.empty() && ctx->taxonTableSet;
+    if (byTaxa ? (S.byTaxonTable && S.taxonVersion == ctx->taxonTableVersion && S.dTally) : (!S.byTaxonTable && S.version == ctx->lineageVersion && S.dLin)) return MC_OK;
     if (S.dLin) {                                                  // (a new table: votes that still run finish with the old one)
         HIP_TRY(ctx, hipDeviceSynchronize());
         (void)hipFree(S.dLin); S.dLin = nullptr;
     }
     if (S.dTally) { (void)hipFree(S.dTally); S.dTally = nullptr; }
+    S.byTaxonTable = byTaxa;
+    if (byTaxa) {
+        S.numTargets = 0;
+        S.numCounts = (uint64_t)ctx->taxonRank.size() + 1;
+        HIP_TRY(ctx, hipMalloc((void**)&S.dTally, (kBins + S.numCounts) * 8));
+        HIP_TRY(ctx, hipMemset(S.dTally, 0, (kBins + S.numCounts) * 8));
+        S.taxonVersion = ctx->taxonTableVersion;
+        S.version = ~0ull;
+        return MC_OK;
+    }
     const uint64_t nt = ctx->lineages.size() / MC_NUM_RANKS;
     if (nt > 0xFFFFFFFFull) return fail(ctx, MC_ERR_UNSUPPORTED, "mc_classify: more than 2^32 targets");
     std::vector<uint32_t> planes(nt * MC_NUM_RANKS);
@@ -227,7 +239,7 @@ int mc_classify_tally(mc_ctx* ctx, uint64_t assigned[MC_NUM_RANKS + 1], uint64_t
 {
     if (!ctx) return MC_ERR_INVALID;
     if (capacity > 0 && !taxonCounts) return fail(ctx, MC_ERR_INVALID, "mc_classify_tally: capacity without an array");
-    if (ctx->lineages.empty()) return fail(ctx, MC_ERR_STATE, "mc_classify_tally: the context has no lineages (mc_set_lineages)");
+    if (ctx->lineages.empty() && !ctx->taxonTableSet) return fail(ctx, MC_ERR_STATE, "mc_classify_tally: the context has no lineages (mc_set_lineages)");
     if (!ctx->stream) return fail(ctx, MC_ERR_STATE, "mc_classify_tally: the context has no device (mc_open_metadata)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ClassifyState* S = nullptr;

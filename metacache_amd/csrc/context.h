@@ -183,6 +183,8 @@ struct ClassifyState {                   // what the context keeps on the device
     uint32_t numTargets = 0;
     unsigned long long* dTally = nullptr;   // [MC_NUM_RANKS + 1] reads per result rank | [numCounts] reads per taxon (index = taxon index + 1)
     uint64_t numCounts = 0;              // 1 + the largest entry of the lineage table
+    bool byTaxonTable = false;           // the context has no lineages: no dLin, numCounts = 1 + the rows of the taxon table (the tallies of mc_merge_results_classify)
+    uint64_t taxonVersion = ~0ull;       // ... and ctx->taxonTableVersion they were sized from
     std::mutex stageMtx;                 // MC_CLASSIFY_HOST callers take turns at the staging buffers
     DevBuf stageIn, stageOut;
 };
@@ -212,6 +214,11 @@ void free_format_state(mc_ctx* ctx);
 // parse.hip: the counters and the staging of mc_parse_* (made on first use), freed with the context
 struct ParseState;
 void free_parse_state(mc_ctx* ctx);
+
+// merge_results.hip: the taxid table, the store of merged candidate lists, the counters and the staging of mc_merge_results_* (made by
+// mc_merge_results_set_taxids), freed with the context
+struct MergeResultsState;
+void free_merge_results_state(mc_ctx* ctx);
 
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
@@ -273,6 +280,8 @@ struct mc_ctx {
 
     std::mutex parseMtx;
     mcamd::ParseState* parse = nullptr;    // made by the first mc_parse_records that reaches the device
+
+    mcamd::MergeResultsState* mergeResults = nullptr;   // made by mc_merge_results_set_taxids; its calls are ordered by the caller
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

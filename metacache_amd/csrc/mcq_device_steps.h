@@ -369,4 +369,120 @@ struct ParseStep : DeviceStep {
     }
 };
 
+// ---- merge (mc_merge_results_*): `mcq merge` hands its result files to the library -----------------------------------
+// MCQ_MERGE_DEVICE=1.  The host reads a file's leading comment block (results_head: its checks and errors, the column of the top hits),
+// the rest goes to mc_merge_results_add in ranges of at most 2^31 bytes cut at line starts; afterwards the lists, the header places and
+// the assignments come back and fill MergedInput.  Any verdict other than MC_MERGE_OK (after one reserve + retry for
+// MC_MERGE_OVERFLOW) and any library error leave the WHOLE merge to the host path; `why` says which file, verdict and offence.
+struct MergeFile { std::string name; const char* data = nullptr; size_t size = 0, body = 0; int tophitsColumn = 0; };   // body: the first byte behind the leading comment block
+struct MergeStep {
+    bool on = false;
+    std::string why;                         // on and not merged by the library: why
+    uint64_t files = 0, lines = 0, entries = 0, unknown = 0;
+    MergeStep() { const char* sw = std::getenv("MCQ_MERGE_DEVICE"); on = sw && std::atoi(sw) != 0; }
+
+    static uint64_t count_char(const char* p, size_t n, char c)
+    {
+        uint64_t k = 0;
+        for (const char* q = p, *e = p + n; (q = (const char*)memchr(q, c, (size_t)(e - q))) != nullptr; ++q) ++k;
+        return k;
+    }
+    static uint64_t count_result_lines(const char* p, size_t n)   // line starts that hold no '#'
+    {
+        uint64_t k = 0;
+        for (size_t s = 0; s < n;) {
+            if (p[s] != '#') ++k;
+            const char* nl = (const char*)memchr(p + s, '\n', n - s);
+            if (!nl) break;
+            s = (size_t)(nl - p) + 1;
+        }
+        return k;
+    }
+
+    bool run(const Options& o, const Taxonomy& tx, const std::vector<MergeFile>& in, size_t maxCand, MergedInput& M)
+    {
+        mc_config cfg;
+        mc_config_default(&cfg);
+        cfg.device = o.gpus.empty() ? 0 : o.gpus[0];
+        mc_ctx* ctx = nullptr;
+        if (mc_create(&cfg, &ctx) != MC_OK) { why = mc_last_error(nullptr); return false; }
+        struct Closer { mc_ctx* c; ~Closer() { mc_merge_results_end(c); mc_destroy(c); } } closer{ctx};
+        auto failed = [&](const std::string& what) { why = what; return false; };
+        auto lib_failed = [&] { return failed(mc_last_error(ctx)); };
+        // the taxonomy as arrays: every taxon's ranked lineage, rank, covers, and its taxid
+        const size_t nt = tx.taxa.size();
+        std::vector<uint32_t> lin(nt * kNumRanks);
+        std::vector<uint8_t> rank(nt), covered(nt);
+        std::vector<int64_t> ids(nt);
+        for (size_t i = 0; i < nt; ++i) {
+            const Lineage l = tx.ranks_of((uint32_t)i + 1);
+            std::copy(l.begin(), l.end(), lin.begin() + i * kNumRanks);
+            rank[i] = (uint8_t)std::min(tx.taxa[i].rank, kNumRanks);
+            covered[i] = tx.covers((uint32_t)i + 1) ? 1 : 0;
+            ids[i] = tx.taxa[i].id;
+        }
+        if (mc_set_taxon_table(ctx, lin.data(), rank.data(), covered.data(), nt) != MC_OK || mc_merge_results_set_taxids(ctx, ids.data(), nt) != MC_OK) return lib_failed();
+        uint64_t capacity = 1;
+        for (const MergeFile& f : in) capacity = std::max<uint64_t>(capacity, count_char(f.data + f.body, f.size - f.body, '\n') + 1);
+        if (mc_merge_results_begin(ctx, capacity, (uint32_t)maxCand, o.lowest) != MC_OK) return lib_failed();
+        struct Call { size_t file, base; };
+        std::vector<Call> calls;                                                // by call number: where the range lies
+        constexpr size_t kRange = (size_t)1 << 31;
+        for (size_t fi = 0; fi < in.size(); ++fi) {
+            const MergeFile& f = in[fi];
+            const char* p = f.data + f.body;
+            const size_t n = f.size - f.body;
+            if (n == 0) return failed(f.name + ": nothing behind the leading comment block");
+            const uint64_t fileLines = n <= kRange ? 0 : count_result_lines(p, n);
+            for (size_t pos = 0; pos < n;) {
+                size_t len = std::min(n - pos, kRange);
+                if (pos + len < n) {
+                    const void* nl = memrchr(p + pos, '\n', len);
+                    if (!nl) return failed(f.name + ": a line of more than 2^31 bytes");
+                    len = (size_t)((const char*)nl - (p + pos)) + 1;
+                }
+                uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (int attempt = 0;; ++attempt) {
+                    calls.push_back(Call{fi, f.body + pos});
+                    if (mc_merge_results_add(ctx, p + pos, len, (uint32_t)f.tophitsColumn, fileLines, MC_MERGE_HOST | (pos ? MC_MERGE_CONTINUE : 0), st, nullptr, 0, nullptr) != MC_OK) return lib_failed();
+                    if (st[5] != MC_MERGE_OVERFLOW || attempt == 1) break;
+                    if (mc_merge_results_reserve(ctx, st[7]) != MC_OK) return lib_failed();
+                    capacity = std::max<uint64_t>(capacity, st[7]);
+                }
+                if (st[5] != MC_MERGE_OK)
+                    return failed(f.name + ": " + (st[5] == MC_MERGE_IRREGULAR ? "irregular line at offset " + std::to_string(f.body + pos + st[6]) : "overflow, " + std::to_string(st[7]) + " lists needed"));
+                lines += st[0]; entries += st[3]; unknown += st[4];
+                pos += len;
+            }
+            ++files;
+        }
+        uint64_t nq = 0;
+        if (mc_merge_results_lists(ctx, 0, 0, MC_MERGE_HOST, nullptr, nullptr, &nq, nullptr) != MC_OK) return lib_failed();
+        std::vector<mc_taxon_candidate> lists(nq * maxCand);
+        std::vector<uint32_t> places(nq * 3);
+        std::vector<mc_assignment> assigned(nq);
+        mc_classify_options co;
+        co.hits_min = (uint32_t)o.hitsMin; co.hits_diff = o.hitsDiff; co.lowest_rank = o.lowest; co.highest_rank = o.highest;
+        if (nq && (mc_merge_results_lists(ctx, 0, nq, MC_MERGE_HOST, lists.data(), places.data(), nullptr, nullptr) != MC_OK ||
+                   mc_merge_results_classify(ctx, &co, MC_CLASSIFY_HOST, 0, nq, assigned.data(), nullptr) != MC_OK)) return lib_failed();
+        M.cands.assign(nq, {}); M.headers.assign(nq, std::string());
+        for (uint64_t q = 0; q < nq; ++q) {
+            for (size_t j = 0; j < maxCand && lists[q * maxCand + j].hits != 0; ++j)
+                M.cands[q].push_back(Cand{0xFFFFFFFFu, lists[q * maxCand + j].hits, 0, 0, lists[q * maxCand + j].taxon});
+            const uint32_t* h = &places[3 * q];
+            if (h[2]) { const Call& c = calls[h[0]]; M.headers[q].assign(in[c.file].data + c.base + h[1], h[2]); }
+        }
+        M.assigned = std::move(assigned);
+        return true;
+    }
+    // the device's line under MCQ_PROFILE; the fall-back's line also wherever the info level is not silent: the switch was set
+    void report(const Profile& P, bool done, bool info) const
+    {
+        if (!on || (done ? !P.on : !(P.on || info))) return;
+        if (done) std::cerr << "mcq profile: result files merged on the device: " << files << " files, " << lines << " lines, " << entries << " entries, " << unknown
+                            << " unknown taxids, 0 files left to the host\n";
+        else std::cerr << "mcq: result files merged on the host (" << why << ")\n";
+    }
+};
+
 #endif  // MCQ_DEVICE_STEPS_H_

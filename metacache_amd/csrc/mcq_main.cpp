@@ -519,7 +519,10 @@ struct Session {
 
 // process_input_files (querying.cpp:40-128): parameters, table layout, mappings of all given files, summary -> one output
 // merge mode (mode_merge.cpp): the candidates come from result files instead of the database
-struct MergedInput { std::vector<std::string> files, headers; std::vector<std::vector<Cand>> cands; };
+struct MergedInput {
+    std::vector<std::string> files, headers; std::vector<std::vector<Cand>> cands;
+    std::vector<mc_assignment> assigned;     // MCQ_MERGE_DEVICE: the library's vote over cands (empty: the host classifies)
+};
 
 // ---- per-query statistics: classification_statistics (classification_statistics.hpp), queries per taxon, matches per target ----------
 struct Cover { uint32_t tgt; uint64_t qid; uint32_t beg, end, hits; };
@@ -619,10 +622,11 @@ struct MappingWriter {
     }
 
     template <class OS>
-    void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits, size_t q = 0)
+    void operator()(OS& out, uint64_t id, View header, const std::vector<Cand>& cands, const mc_location* hits, uint64_t nhits, size_t q = 0, const mc_assignment* given = nullptr)
     {
-        bool isTarget; uint32_t tgt;
-        const uint32_t best = classify(o, tx, cands, isTarget, tgt);
+        bool isTarget = false; uint32_t tgt = 0;
+        // a merged query's assignment may come from the library; sequence-level results (rank 0) go through the host's rule for isTarget
+        const uint32_t best = (given && (given->info & 0xFFu) != 0) ? given->taxon : classify(o, tx, cands, isTarget, tgt);
         const int bestRank = best ? tx.taxon(best)->rank : kNumRanks;
         uint32_t truth = 0;
         if (o.determineGroundTruth) truth = ground_truth(tx, std::string(header.p, header.n));
@@ -1497,7 +1501,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     if (merged) {                                                           // map_candidates_to_targets, classification.cpp:891-911
         MappingWriter L{o, tx, S.dbStride, S.dbWinlen, false, T};
         std::ostringstream out;
-        for (size_t i = 0; i < merged->headers.size(); ++i) L(out, i + 1, View{merged->headers[i].data(), merged->headers[i].size()}, merged->cands[i], nullptr, 0);
+        for (size_t i = 0; i < merged->headers.size(); ++i) L(out, i + 1, View{merged->headers[i].data(), merged->headers[i].size()}, merged->cands[i], nullptr, 0, 0, merged->assigned.empty() ? nullptr : &merged->assigned[i]);
         os << out.str();
     }
     if (P.on)
@@ -1517,13 +1521,10 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
 // get_results_file_properties (mode_merge.cpp:79-150): no sequence-level results, the column of the top hits, number of result lines
 struct ResultsSource { std::string filename; size_t firstLine = 0, numQueries = 0; int tophitsColumn = 0; std::vector<std::string> lines; };
 
-ResultsSource results_file_properties(const std::string& filename)
+// the leading comment block of res.lines (which hold at least that block and the line behind it): its checks, tophitsColumn, firstLine
+void results_head(ResultsSource& res)
 {
-    ResultsSource res;
-    res.filename = filename;
-    std::ifstream is(filename);
-    if (!is.good()) throw std::runtime_error("could not open file " + filename);
-    for (std::string l; std::getline(is, l);) res.lines.push_back(std::move(l));
+    const std::string& filename = res.filename;
     size_t i = 0;
     for (;; ++i) {
         if (i >= res.lines.size() || res.lines[i].empty() || res.lines[i][0] != '#') throw std::runtime_error("classificaion ranks not found in file " + filename);
@@ -1552,9 +1553,53 @@ ResultsSource results_file_properties(const std::string& filename)
     if (res.tophitsColumn < 1) throw std::runtime_error("no top_hits in file " + filename);
     for (++i; i < res.lines.size() && !res.lines[i].empty() && res.lines[i][0] == '#'; ++i) {}
     res.firstLine = i;
-    for (; i < res.lines.size(); ++i) if (res.lines[i].empty() || res.lines[i][0] != '#') ++res.numQueries;
+}
+
+ResultsSource results_file_properties(const std::string& filename)
+{
+    ResultsSource res;
+    res.filename = filename;
+    std::ifstream is(filename);
+    if (!is.good()) throw std::runtime_error("could not open file " + filename);
+    for (std::string l; std::getline(is, l);) res.lines.push_back(std::move(l));
+    results_head(res);
+    for (size_t i = res.firstLine; i < res.lines.size(); ++i) if (res.lines[i].empty() || res.lines[i][0] != '#') ++res.numQueries;
     return res;
 }
+
+// MCQ_MERGE_DEVICE: a result file mapped into memory; only its leading comment block is read line by line
+struct MappedResults {
+    MergeFile file;
+    int fd = -1;
+    explicit MappedResults(const std::string& filename)
+    {
+        file.name = filename;
+        fd = ::open(filename.c_str(), O_RDONLY);
+        struct stat st;
+        if (fd < 0 || fstat(fd, &st) != 0) throw std::runtime_error("could not open file " + filename);
+        file.size = (size_t)st.st_size;
+        if (file.size) {
+            void* m = mmap(nullptr, file.size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) throw std::runtime_error("could not open file " + filename);
+            file.data = (const char*)m;
+        }
+        ResultsSource head;
+        head.filename = filename;
+        size_t s = 0;
+        while (s < file.size) {                                                 // the comment block and the line behind it
+            const char* nl = (const char*)memchr(file.data + s, '\n', file.size - s);
+            const size_t e = nl ? (size_t)(nl - file.data) : file.size;
+            head.lines.emplace_back(file.data + s, e - s);
+            if (head.lines.back().empty() || head.lines.back()[0] != '#') break;
+            s = nl ? e + 1 : file.size;
+        }
+        file.body = s;
+        results_head(head);
+        file.tophitsColumn = head.tophitsColumn;
+    }
+    ~MappedResults() { if (file.data) munmap((void*)file.data, file.size); if (fd >= 0) ::close(fd); }
+    MappedResults(const MappedResults&) = delete;
+};
 
 // best_distinct_matches_in_contiguous_window_ranges::insert for a candidate that names its taxon (candidate_generation.hpp:172-231)
 void insert_taxon_candidate(std::vector<Cand>& top, Cand c, int mergeBelow, size_t maxCand)
@@ -1668,7 +1713,19 @@ int merge_main(const std::vector<std::string>& args)
     MergedInput M;
     M.files = o.infiles;
     const size_t maxCand = o.maxCand > 0 ? (size_t)o.maxCand : 2;               // merge_result_files, mode_merge.cpp:254-258
-    for (const auto& f : o.infiles) read_results(results_file_properties(f), S.tx, o.lowest, maxCand, M, info != 0);
+    MergeStep mergeStep;                                                        // MCQ_MERGE_DEVICE (mcq_device_steps.h)
+    bool onDevice = false;
+    if (mergeStep.on) {
+        std::vector<std::unique_ptr<MappedResults>> maps;
+        std::vector<MergeFile> mfiles;
+        for (const auto& f : o.infiles) { maps.emplace_back(new MappedResults(f)); mfiles.push_back(maps.back()->file); }
+        onDevice = mergeStep.run(o, S.tx, mfiles, maxCand, M);
+        if (!onDevice) { M.cands.clear(); M.headers.clear(); M.assigned.clear(); }
+        else if (mergeStep.unknown && info)                                     // (the host path names every such hit; here they are only counted)
+            std::cerr << mergeStep.unknown << " hits name taxids that are not in the taxonomy. Skipping them.\n";
+        mergeStep.report(Profile(), onDevice, info != 0);
+    }
+    if (!onDevice) for (const auto& f : o.infiles) read_results(results_file_properties(f), S.tx, o.lowest, maxCand, M, info != 0);
     if (info) std::cerr << "Completed merge. Starting classification.\n";
     run_job(S, o, {}, o.outfile, "", o.abundanceFile, &M);
     return 0;
