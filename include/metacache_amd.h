@@ -880,6 +880,73 @@ int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out);
  *   a verdict other than MC_PARSE_OK (MC_PARSE_UNEQUAL among them) leaves mc_results.num_queries at 0. */
 int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insert_size_max);
 
+/* ---- BGZF input inflated on the device ---------------------------------------------
+ * BGZF (what bgzip and htslib write) is a sequence of independent gzip members of at most 64 KiB in and out.  gzread joins the members
+ * of such a file, so the specification of everything below is "the bytes zlib gives".
+ * A BGZF MEMBER at offset p of bytes[0, nbytes):
+ *   bytes[p .. p + 3] = 1f 8b 08 04 (deflate, FEXTRA and no other flag); MTIME, XFL and OS are anything; XLEN is the u16 at p + 10 (all
+ *   numbers little endian); the extra field is XLEN bytes of subfields {SI1, SI2, SLEN u16, SLEN bytes} that tile it exactly; exactly
+ *   one subfield has SI1 = 'B', SI2 = 'C', SLEN = 2: its u16 is BSIZE and the member is BSIZE + 1 bytes; the payload is
+ *   bytes[p + 12 + XLEN, p + BSIZE + 1 - 8); the trailer is CRC32 u32 and ISIZE u32 with ISIZE <= 65536; the member is at least
+ *   12 + XLEN + 8 bytes and ends at or before nbytes.
+ * A RANGE IS BGZF when members chain from offset 0 to exactly nbytes (an empty range is not).  Every other range is MC_BGZF_FOREIGN --
+ *   plain gzip, another FLG, a missing or doubled BC subfield, trailing bytes, a member cut short -- and the offence is the offset of
+ *   the member that broke the rule.  This refuses more than zlib does (zlib takes FNAME and ignores trailing garbage); it never accepts
+ *   a range and reads it differently.  The 28-byte end-of-file block (ISIZE 0) is an ordinary member.
+ * A BLOCK INFLATES CORRECTLY when its payload is a deflate stream (RFC 1951: stored, fixed and dynamic blocks, any number of them) that,
+ *   after its final block and the bits up to the next byte, ends exactly at the trailer; that produces exactly ISIZE bytes; in which no
+ *   match reaches in front of the block's own first output byte (a BGZF block has no history); and whose bytes have the trailer's
+ *   CRC-32.  Anything else is MC_INFLATE_CORRUPT.  Code sets are accepted as zlib accepts them: over-subscribed sets never, incomplete
+ *   sets only as a single 1-bit literal/length or distance code or no distance code at all, a dynamic block only with a code for 256.
+ *   Nothing that zlib's raw inflate refuses is accepted, and no other bytes are ever produced.
+ * mc_bgzf_index: HOST only -- no context, no device, no zlib.  info = members, out bytes (the sum of ISIZE), verdict, offence.  Row i is
+ *   member i: bytes[in_off, + in_len) -> out[out_off, + out_len), out_off the sum of the ISIZE in front.  With capacity too small (or
+ *   blocks == NULL) info is still complete and the first `capacity` rows are filled: size, then call again.  With MC_BGZF_FOREIGN
+ *   members and out bytes count the members in front of the offence.  MC_ERR_INVALID: info == NULL, bytes == NULL with nbytes > 0.
+ * mc_inflate_blocks inflates the members the rows name.  status = verdict, the lowest bad row, its reason (MC_INFLATE_R_*, 0 with
+ *   MC_INFLATE_OVERFLOW), the bytes of out the call covers (the largest out_off + out_len).  The lowest bad row decides the verdict:
+ *   MC_INFLATE_OVERFLOW where its out_off + out_len > out_capacity (such a row writes nothing), else MC_INFLATE_CORRUPT.  It is a
+ *   minimum over the rows, so the order in which the device takes them does not matter; the same input gives the same out and status.
+ *   With a verdict other than MC_INFLATE_OK out[0, out_capacity) is unspecified; nothing outside it is touched.  Each row stores only
+ *   inside its own [out_off, out_off + out_len) and uses only bytes of its own member; out_len bounds its stores, and a trailer whose
+ *   ISIZE differs from out_len is MC_INFLATE_R_SHORT or MC_INFLATE_R_OVER.
+ *   Without MC_INFLATE_HOST bytes, blocks, out and status are DEVICE pointers (bytes and out 16-byte, blocks and status 8-byte aligned;
+ *   bytes readable up to nbytes rounded up to 16); the call is enqueued on `stream` (NULL: the context's own) with no synchronisation
+ *   and no per-call state in the context, so calls on different streams may run at once, and mc_parse_records can take out behind it
+ *   on the same stream.
+ *   With MC_INFLATE_HOST they are HOST arrays, staged through buffers of the context in pieces of whole members (mc_set_tuning
+ *   "inflate_stage_bytes": compressed bytes per piece, 0 = 64 MiB), one caller at a time; the call returns when out is filled or the
+ *   verdict is known.  The rows are checked on the host first: in_off and out_off non-decreasing and the slices non-overlapping, inside
+ *   nbytes, out_len <= 65536 -- else MC_ERR_INVALID.
+ *   MC_ERR_INVALID (checked first, before any device call): NULL ctx or status; NULL bytes or blocks with num_blocks > 0; NULL out with
+ *   out_capacity > 0; unknown flags; misaligned device arrays; out overlapping bytes.  MC_ERR_STATE: a context without a device
+ *   (mc_open_metadata).  num_blocks == 0: MC_OK and an OK status.
+ * mc_inflate_stats: calls, bytes in (nbytes), bytes out of the accepted calls, calls refused; waits for the device.  mc_timing_get name:
+ *   "inflate_blocks" (the three launches of one enqueue; the host form enqueues once per staged piece). */
+typedef struct { uint64_t in_off, out_off; uint32_t in_len, out_len; } mc_bgzf_block;
+#define MC_BGZF_OK       0
+#define MC_BGZF_FOREIGN  1
+int mc_bgzf_index(const uint8_t* bytes, uint64_t nbytes, mc_bgzf_block* blocks, uint64_t capacity, uint64_t info[4]);
+
+#define MC_INFLATE_HOST      1
+#define MC_INFLATE_OK        0
+#define MC_INFLATE_CORRUPT   1
+#define MC_INFLATE_OVERFLOW  2
+#define MC_INFLATE_R_BTYPE     1   /* block type 3 */
+#define MC_INFLATE_R_STORED    2   /* LEN and NLEN of a stored block disagree */
+#define MC_INFLATE_R_LENGTHS   3   /* a dynamic block's code lengths: counts beyond 286 / 30, a bad code-length code, a repeat without a
+                                      predecessor or past HLIT + HDIST, no code for 256, an over-subscribed or incomplete set */
+#define MC_INFLATE_R_SYMBOL    4   /* a literal/length code that is no symbol, or symbol 286 / 287 */
+#define MC_INFLATE_R_DISTANCE  5   /* a distance code that is no symbol, code 30 / 31, or a distance beyond the block's output so far */
+#define MC_INFLATE_R_INPUT     6   /* the stream needs bits beyond its payload (or the row's member does not hold a payload) */
+#define MC_INFLATE_R_OVER      7   /* more than out_len / ISIZE bytes */
+#define MC_INFLATE_R_SHORT     8   /* fewer than ISIZE bytes */
+#define MC_INFLATE_R_LEFT      9   /* whole bytes left between the end of the stream and the trailer */
+#define MC_INFLATE_R_CRC      10
+int mc_inflate_blocks(mc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const mc_bgzf_block* blocks, uint64_t num_blocks, int flags,
+                      uint8_t* out, uint64_t out_capacity, uint64_t status[4], void* stream);
+int mc_inflate_stats(mc_ctx* ctx, uint64_t stats[4]);
+
 /* ---- per-part result files merged on the device: what `metacache merge` reads ------
  * The result files of queries against single database parts (docs/partitioning.md of the reference) are cut into one candidate list
  * per query, and the vote runs over those lists.  (mc_merge_part_candidates above is something else: it merges candidate ARRAYS.)

@@ -156,6 +156,20 @@ struct table_statistics {
     std::uint64_t buckets(float loadFactor = 0.8f) const noexcept { return std::uint64_t(1.0f + float(features + dead) / loadFactor); }
 };
 
+// the members of a BGZF range (mc_bgzf_index; host code: no device, no zlib).  verdict MC_BGZF_OK: blocks[i] is member i and outBytes the
+// sum of their ISIZE.  MC_BGZF_FOREIGN: the range is something else from byte `offence` on -- the caller reads it through zlib.
+struct bgzf_members { int verdict = MC_BGZF_FOREIGN; std::uint64_t offence = 0, outBytes = 0; std::vector<mc_bgzf_block> blocks; };
+inline bgzf_members bgzf_index(const void* bytes, std::size_t nbytes)
+{
+    bgzf_members m;
+    std::uint64_t info[4] = {0, 0, 0, 0};
+    if (mc_bgzf_index(static_cast<const std::uint8_t*>(bytes), nbytes, nullptr, 0, info) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
+    m.blocks.resize(std::size_t(info[0]));
+    if (mc_bgzf_index(static_cast<const std::uint8_t*>(bytes), nbytes, m.blocks.data(), m.blocks.size(), info) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
+    m.verdict = int(info[2]); m.offence = info[3]; m.outBytes = info[1];
+    return m;
+}
+
 class query_batch;
 
 class database {
@@ -265,6 +279,23 @@ public:
         p.hdr.resize(std::size_t(p.records) * 2); p.qinfo.resize(std::size_t(p.queries) * 4); p.maxWin.resize(p.queries);
         p.seq.resize(ok ? std::size_t(status[2]) : 0); p.names.resize(ok ? std::size_t(status[3]) : 0); p.nameOff.resize(ok ? std::size_t(p.queries) + 1 : 0);
         return p;
+    }
+
+    // the members of a BGZF range inflated on the device (mc_inflate_blocks on host arrays; the block rule: metacache_amd.h).  verdict
+    // MC_INFLATE_OK: bytes is what zlib gives for the range.  Another verdict: bytes is empty, block is the lowest member the device
+    // refused and reason says why (MC_INFLATE_R_*) -- the caller reads the range through zlib.
+    struct inflated { int verdict = MC_INFLATE_CORRUPT; std::uint64_t block = 0; int reason = 0; std::string bytes; };
+    inflated inflate(const void* bytes, std::size_t nbytes, const bgzf_members& members) const
+    {
+        inflated r;
+        std::uint64_t status[4] = {0, 0, 0, 0};
+        r.bytes.assign(std::size_t(members.outBytes) + 1, char(0));
+        if (mc_inflate_blocks(ctx_, static_cast<const std::uint8_t*>(bytes), nbytes, members.blocks.data(), members.blocks.size(), MC_INFLATE_HOST,
+                              reinterpret_cast<std::uint8_t*>(&r.bytes[0]), members.outBytes, status, nullptr) != MC_OK)
+            throw std::runtime_error(mc_last_error(ctx_));
+        r.verdict = int(status[0]); r.block = status[1]; r.reason = int(status[2]);
+        r.bytes.resize(r.verdict == MC_INFLATE_OK ? std::size_t(members.outBytes) : 0);
+        return r;
     }
 
     // the pairs of two mate files' byte ranges, cut on the device (mc_parse_mates on host arrays; the mates rule: metacache_amd.h):

@@ -140,6 +140,34 @@ PARSE_HOST, PARSE_PAIRS = 1, 2
 PARSE_OK, PARSE_IRREGULAR, PARSE_OVERFLOW, PARSE_UNEQUAL = 0, 1, 2, 3
 
 
+BGZF_OK, BGZF_FOREIGN = 0, 1
+INFLATE_HOST = 1
+INFLATE_OK, INFLATE_CORRUPT, INFLATE_OVERFLOW = 0, 1, 2
+(INFLATE_R_BTYPE, INFLATE_R_STORED, INFLATE_R_LENGTHS, INFLATE_R_SYMBOL, INFLATE_R_DISTANCE, INFLATE_R_INPUT, INFLATE_R_OVER, INFLATE_R_SHORT,
+ INFLATE_R_LEFT, INFLATE_R_CRC) = range(1, 11)
+bgzf_block_dtype = np.dtype([("in_off", np.uint64), ("out_off", np.uint64), ("in_len", np.uint32), ("out_len", np.uint32)])   # mc_bgzf_block
+
+
+def bgzf_index(data, capacity=None):
+    """the members of a BGZF range (mc_bgzf_index; host code, no device): -> (blocks bgzf_block_dtype [members], out_bytes, verdict,
+    offence).  With BGZF_FOREIGN the blocks are the members in front of the offence.  capacity: room for that many rows only (the
+    counts stay complete)."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = np.zeros(4, dtype=np.uint64)
+
+    def run(blocks):
+        rc = lib().mc_bgzf_index(buf.ctypes.data if len(buf) else None, len(buf), blocks.ctypes.data if len(blocks) else None, len(blocks), info.ctypes.data)
+        if rc < 0:
+            raise McError(f"mc_bgzf_index -> {rc}: {lib().mc_last_error(None).decode()}")
+
+    blocks = np.zeros(0 if capacity is None else capacity, dtype=bgzf_block_dtype)
+    run(blocks)
+    if capacity is None and int(info[0]):
+        blocks = np.zeros(int(info[0]), dtype=bgzf_block_dtype)
+        run(blocks)
+    return blocks[:min(len(blocks), int(info[0]))], int(info[1]), int(info[2]), int(info[3])
+
+
 def parse_mates_scratch_bytes(n1: int, n2: int, max_records: int) -> int:
     """the workspace a device call of mc_parse_mates needs for ranges of n1 and n2 bytes and outputs of max_records records"""
     return int(lib().mc_parse_mates_scratch_bytes(n1, n2, max_records))
@@ -360,7 +388,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records",
            "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates",
            "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
-           "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end"]
+           "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end",
+           "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats"]
 
 _lib = None
 
@@ -466,6 +495,9 @@ def lib() -> C.CDLL:
         L.mc_merge_results_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.mc_merge_results_end.argtypes = [C.c_void_p]
         L.mc_merge_results_end.restype = None
+        L.mc_bgzf_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_inflate_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        L.mc_inflate_stats.argtypes = [C.c_void_p, C.c_void_p]
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -999,6 +1031,46 @@ class Database:
         """-> [mc_parse_records calls, bytes handed over, records of the accepted ranges, ranges refused]"""
         st = np.zeros(4, dtype=np.uint64)
         self._check(lib().mc_parse_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    # ---- BGZF members inflated on the device (mc_inflate_*) ------------------------------------------------
+    def inflate_device(self, bytes_ptr: int, nbytes: int, blocks_ptr: int, num_blocks: int, out_ptr: int, out_capacity: int, status_ptr: int, stream: int = 0):
+        """inflates the members that the rows at blocks_ptr (bgzf_block_dtype) name out of the range at bytes_ptr into out -- all device
+        memory (bytes, out: 16-byte aligned; blocks, status [4] uint64: 8-byte); asynchronous on `stream`.  status = verdict, lowest bad
+        row, its reason, bytes of out covered"""
+        self._check(lib().mc_inflate_blocks(self.h, bytes_ptr or None, nbytes, blocks_ptr or None, num_blocks, 0, out_ptr or None, out_capacity,
+                                            status_ptr or None, stream or None))
+
+    def inflate_raw(self, data, blocks, out_capacity=None):
+        """the host form as it is: -> (out uint8 [out_capacity], status uint64 [4]); out_capacity defaults to the end of the last slice"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        rows = np.ascontiguousarray(blocks, dtype=bgzf_block_dtype)
+        if out_capacity is None:
+            out_capacity = int((rows["out_off"] + rows["out_len"]).max()) if len(rows) else 0
+        out = np.zeros(max(out_capacity, 1), dtype=np.uint8)
+        status = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_inflate_blocks(self.h, buf.ctypes.data if len(buf) else None, len(buf), rows.ctypes.data if len(rows) else None, len(rows),
+                                            INFLATE_HOST, out.ctypes.data, out_capacity, status.ctypes.data, None))
+        return out[:out_capacity], status
+
+    def inflate(self, data, blocks=None):
+        """a BGZF range -> the bytes gzip.decompress gives (host form; indexes first where blocks is None).  None for a range that is
+        not BGZF; McError with .verdict, .block and .reason where the device refuses a member"""
+        if blocks is None:
+            blocks, _, verdict, _ = bgzf_index(data)
+            if verdict != BGZF_OK:
+                return None
+        out, status = self.inflate_raw(data, blocks)
+        if int(status[0]) != INFLATE_OK:
+            e = McError(f"mc_inflate_blocks: verdict {int(status[0])}, block {int(status[1])}, reason {int(status[2])}")
+            e.verdict, e.block, e.reason = int(status[0]), int(status[1]), int(status[2])
+            raise e
+        return out.tobytes()
+
+    def inflate_stats(self):
+        """-> [mc_inflate_blocks calls, bytes in, bytes out of the accepted calls, calls refused]"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_inflate_stats(self.h, st.ctypes.data))
         return [int(x) for x in st]
 
     # ---- the all-hits column: location lists, run-length encoded (mc_format_matches*) ----------------

@@ -280,6 +280,7 @@ void mc_destroy(mc_ctx* ctx)
     free_format_state(ctx);
     free_parse_state(ctx);
     free_merge_results_state(ctx);
+    free_inflate_state(ctx);
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);
@@ -418,6 +419,7 @@ int mc_set_tuning(mc_ctx* ctx, const char* name, int64_t value)
     else if (n == "format_stage_rows") ctx->formatStageRows = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 26));   // mc_format_mappings(MC_FORMAT_HOST): reads per staged piece (0 = default)
     else if (n == "format_stage_hits") ctx->formatStageHits = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 30));   // mc_format_matches(MC_FORMAT_HOST): locations per staged piece (0 = default)
     else if (n == "evaluate_stage_rows") ctx->evaluateStageRows = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 26));   // mc_evaluate_assignments(MC_EVALUATE_HOST): reads per staged piece (0 = default)
+    else if (n == "inflate_stage_bytes") ctx->inflateStageBytes = (uint64_t)std::max<int64_t>(0, std::min<int64_t>(value, 1ll << 32));   // mc_inflate_blocks(MC_INFLATE_HOST): compressed bytes per staged piece (0 = default)
     else return fail(ctx, MC_ERR_INVALID, "mc_set_tuning: unknown switch '" + n + "'");
     return MC_OK;
 }

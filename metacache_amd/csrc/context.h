@@ -220,6 +220,10 @@ void free_parse_state(mc_ctx* ctx);
 struct MergeResultsState;
 void free_merge_results_state(mc_ctx* ctx);
 
+// inflate.hip: the counters and the staging of mc_inflate_* (made on first use), freed with the context
+struct InflateState;
+void free_inflate_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -282,6 +286,10 @@ struct mc_ctx {
     mcamd::ParseState* parse = nullptr;    // made by the first mc_parse_records that reaches the device
 
     mcamd::MergeResultsState* mergeResults = nullptr;   // made by mc_merge_results_set_taxids; its calls are ordered by the caller
+
+    std::mutex inflateMtx;
+    mcamd::InflateState* inflate = nullptr;   // made by the first mc_inflate_blocks that reaches the device
+    uint64_t inflateStageBytes = 0;        // MC_INFLATE_HOST: compressed bytes per staged piece (mc_set_tuning "inflate_stage_bytes"; 0 = 64 MiB)
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

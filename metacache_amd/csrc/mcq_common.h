@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <cmath>
 #include <iomanip>
@@ -167,15 +168,29 @@ inline std::vector<std::string> files_in_directory(std::string dirName, int recu
 // ---- sequence files (FASTA / 4-line FASTQ; plain = memory-mapped, gzip = inflated into memory) ---------------------------------------------
 struct View { const char* p = nullptr; size_t n = 0; bool empty() const { return n == 0; } };
 
+// What a SeqFile may hand a compressed file to before its own gzread loop: (file name, the file's bytes, their number, the buffer, the number
+// of inflated bytes) -> true: the buffer holds the inflated file; false: the file stays with the loop, the buffer is empty.  SeqFile knows
+// nothing about who inflates (mcq_device_steps.h: InflateStep).
+using GzInflater = std::function<bool(const std::string&, const unsigned char*, size_t, std::vector<char>&, size_t&)>;
+
 class SeqFile {
 public:
-    explicit SeqFile(const std::string& fn)
+    explicit SeqFile(const std::string& fn, const GzInflater* inflater = nullptr)
     {
         fd_ = ::open(fn.c_str(), O_RDONLY);
         struct stat st;
         if (fd_ < 0 || fstat(fd_, &st) != 0) throw std::runtime_error("file '" + fn + "' could not be opened");
         unsigned char magic[2] = {0, 0};
         const bool gz = st.st_size >= 2 && pread(fd_, magic, 2, 0) == 2 && magic[0] == 0x1f && magic[1] == 0x8b;
+        if (gz && inflater && *inflater) {
+            void* m = mmap(nullptr, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd_, 0);
+            if (m != MAP_FAILED) {
+                const bool done = (*inflater)(fn, (const unsigned char*)m, (size_t)st.st_size, own_, size_);
+                munmap(m, (size_t)st.st_size);
+                if (done) { data_ = own_.data(); return; }
+                own_.clear(); size_ = 0;
+            }
+        }
         if (gz) {
             // compressed input (the reference reads it through zlib as well): inflated into memory, then handled like a mapped file
             gzFile g = gzdopen(dup(fd_), "rb");

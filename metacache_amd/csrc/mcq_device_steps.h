@@ -369,6 +369,52 @@ struct ParseStep : DeviceStep {
     }
 };
 
+// ---- inflate (mc_bgzf_index + mc_inflate_blocks): BGZF input inflated on the device ---------------------------------
+// MCQ_INFLATE_DEVICE=1.  A compressed input file is mapped and indexed on the host; a BGZF file goes to mc_inflate_blocks(MC_INFLATE_HOST)
+// and into a buffer sized once from the index.  A file that is not BGZF, a verdict other than MC_INFLATE_OK and any library error leave
+// the file to SeqFile's gzread loop; the step keeps every such file with its reason.  Everything behind the bytes is unchanged -- inflated
+// input still does not take the device parse (SeqFile::byte_range).  build, modify and the reference files of -align never ask.
+struct InflateStep : DeviceStep {
+    uint64_t files = 0, blocks = 0, bytesIn = 0, bytesOut = 0;
+    std::vector<std::string> left;           // the files left to the host, each with its reason
+    GzInflater inflater;                     // empty: SeqFile inflates
+    static bool wanted() { const char* sw = std::getenv("MCQ_INFLATE_DEVICE"); return sw && std::atoi(sw) != 0; }
+    void open(const Session& S, bool merged)
+    {
+        if (!wanted()) return;
+        off = shared_host_reason(S, merged, false, "", S.built ? "build+query" : nullptr);
+        if (!off.empty()) return;
+        ctx = S.ctx;
+        inflater = [this](const std::string& fn, const unsigned char* bytes, size_t n, std::vector<char>& out, size_t& size) { return run(fn, bytes, n, out, size); };
+    }
+    bool leave(const std::string& fn, const std::string& why) { std::lock_guard<std::mutex> g(mtx); left.push_back(fn + ": " + why); return false; }
+    bool run(const std::string& fn, const unsigned char* bytes, size_t n, std::vector<char>& out, size_t& size)
+    {
+        uint64_t info[4] = {0, 0, 0, 0}, status[4] = {0, 0, 0, 0};
+        if (mc_bgzf_index(bytes, n, nullptr, 0, info) != MC_OK) return leave(fn, mc_last_error(nullptr));
+        if (info[2] != MC_BGZF_OK) return leave(fn, "not BGZF at byte " + std::to_string(info[3]));
+        std::vector<mc_bgzf_block> rows(info[0]);
+        if (mc_bgzf_index(bytes, n, rows.data(), rows.size(), info) != MC_OK) return leave(fn, mc_last_error(nullptr));
+        out.resize(std::max<uint64_t>(info[1], 1));
+        if (mc_inflate_blocks(ctx, bytes, n, rows.data(), rows.size(), MC_INFLATE_HOST, (uint8_t*)out.data(), info[1], status, nullptr) != MC_OK) return leave(fn, mc_last_error(ctx));
+        if (status[0] != MC_INFLATE_OK) return leave(fn, "the device refused block " + std::to_string(status[1]) + " (verdict " + std::to_string(status[0]) + ", reason " + std::to_string(status[2]) + ")");
+        size = (size_t)info[1];
+        std::lock_guard<std::mutex> g(mtx);
+        ++files; blocks += rows.size(); bytesIn += n; bytesOut += info[1];
+        return true;
+    }
+    void report(const Profile& P) const
+    {
+        if (!P.on) return;
+        if (ctx) {
+            std::cerr << "mcq profile: gzip input inflated on the device: " << files << " files, " << blocks << " blocks, " << bytesIn << " bytes in, " << bytesOut << " bytes out, "
+                      << left.size() << " files left to the host";
+            for (size_t i = 0; i < left.size(); ++i) std::cerr << (i ? "; " : " (") << left[i];
+            std::cerr << (left.empty() ? "\n" : ")\n");
+        } else if (!off.empty()) std::cerr << "mcq: gzip input inflated on the host (" << off << ")\n";
+    }
+};
+
 // ---- merge (mc_merge_results_*): `mcq merge` hands its result files to the library -----------------------------------
 // MCQ_MERGE_DEVICE=1.  The host reads a file's leading comment block (results_head: its checks and errors, the column of the top hits),
 // the rest goes to mc_merge_results_add in ranges of at most 2^31 bytes cut at line starts; afterwards the lists, the header places and

@@ -676,6 +676,7 @@ struct Records { View h1, s1, h2, s2; std::string scratch1, scratch2; };    // o
 struct BatchQueue {
     const Options& o; const unsigned workers; const std::chrono::steady_clock::time_point t0;
     std::vector<std::unique_ptr<SeqFile>> files;
+    const GzInflater* inflater = nullptr;                                   // MCQ_INFLATE_DEVICE: who takes a compressed query file before SeqFile's own loop
     std::vector<std::unique_ptr<std::vector<uint64_t>>> selections;
     std::deque<Batch> batches;                                              // grows at the back only: references stay valid
     std::mutex mu; std::condition_variable cv;
@@ -739,7 +740,7 @@ struct BatchQueue {
                 prefix += '\n';
                 size_t nq = 0, f1 = files.size(), f2 = files.size();
                 try {
-                    files.emplace_back(new SeqFile(o.infiles[fi]));
+                    files.emplace_back(new SeqFile(o.infiles[fi], inflater));
                     SeqFile& F = *files.back();
                     if (F.can_stream() && o.pairing != Options::files && !lengthFilter && o.queryLimit >= (int64_t)1 << 62 && !std::getenv("MCQ_NO_STREAM")) {
                         // streaming: batches of this file go out while its later chunks are still being indexed
@@ -772,7 +773,7 @@ struct BatchQueue {
                     if (o.pairing == Options::sequences) nq = (nq + 1) / 2;
                     if (o.pairing == Options::files) {
                         f2 = files.size();
-                        files.emplace_back(new SeqFile(o.infiles[fi + 1]));
+                        files.emplace_back(new SeqFile(o.infiles[fi + 1], inflater));
                         files.back()->index(workers);
                         nq = std::min(nq, files.back()->records());
                     }
@@ -1457,7 +1458,9 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     std::vector<Tally> tallies(S.workers);
     TargetCache targets(o.showErrors);                                      // -align: the target records of this job
     const bool aligning = o.align && !merged;
-    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep; ParseStep parseStep;   // the hand-offs to the library (mcq_device_steps.h)
+    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep; ParseStep parseStep; InflateStep inflateStep;   // the hand-offs to the library (mcq_device_steps.h)
+    inflateStep.open(S, merged != nullptr);
+    if (inflateStep.ctx) Q.inflater = &inflateStep.inflater;
     parseStep.open(S, o, merged != nullptr);
     hitsStep.open(S, o, merged != nullptr, covMode);
     evalStep.open(S, o, merged != nullptr, covMode);
@@ -1508,6 +1511,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    inflateStep.report(P);
     parseStep.report(P);
     fmtStep.report(P);
     evalStep.report(P);
@@ -1947,6 +1951,7 @@ int main(int argc, char** argv)
             using clock = std::chrono::steady_clock;
             std::vector<std::string> none;
             const BuildOptions bo = parse_build(args, false, none);
+            if (InflateStep::wanted() && std::getenv("MCQ_PROFILE")) std::cerr << "mcq: gzip input inflated on the host (build)\n";
             const bool info = bo.info != BuildOptions::silent;
             if (info) std::cout << "Building new database '" << bo.dbfile << "' from reference sequences." << std::endl;
             const auto t0 = clock::now();
@@ -1965,6 +1970,7 @@ int main(int argc, char** argv)
         if (mode == "modify") {                                                 // main_mode_modify, mode_build.cpp:74-88
             std::vector<std::string> none;
             BuildOptions bo = parse_build(args, false, none);
+            if (InflateStep::wanted() && std::getenv("MCQ_PROFILE")) std::cerr << "mcq: gzip input inflated on the host (modify)\n";
             std::cout << "Modify database " << bo.dbfile << std::endl;
             {   // get_modify_options (options.cpp:765-795): sketching and limits of the database file are the defaults
                 mc_ctx* meta = nullptr;
