@@ -249,7 +249,7 @@ uint32_t big_filter_grid(uint32_t n, bool compact, int bpcOverride = 0);     // 
 void launch_mid_cands(WorkList list, const BatchView& b, const DeviceTable& tab, const Workspace& ws, uint32_t maxCand,
                       const uint32_t* taxkey, void* cands, hipStream_t st);
 void launch_cands_from_hits(const BatchView& b, const DeviceTable& tab, const Workspace& ws, const uint32_t* taxkey, uint32_t maxCand,
-                            void* cands, hipStream_t st);
+                            void* cands, hipStream_t st, bool keepStat = false);   // (keepStat: ws.qstat is the caller's, left as it is)
 // Mode K owner side: per-source partial lists -> one list per read (hitOff[m + 1], out); tot[m], srcStart[sources * (m + 1)] scratch
 void launch_union_partial(const uint32_t* counts, uint32_t sources, uint32_t m, const uint64_t* hits, uint32_t* tot, uint64_t* srcStart, uint64_t* hitOff,
                           uint64_t* out, void* scanTmp, hipStream_t st);

@@ -604,8 +604,10 @@ __global__ __launch_bounds__(256) void sort_candidates_kernel(
 
 // rows 8-10 on lists that are already gathered (Mode K: the union of the key shards' partial lists): ws.hits[hitOff[q] ..
 // hitOff[q+1]) in any order; sorted in place (LDS copy for short lists), the sorted list is written back.
+// keepStat: the caller has written the reads' statistics (owner_entries_kernel: every read's locations and sources, whichever kernel
+// finishes it -- a read beyond kMaxHitsPerQuery has no list here, and its count must not become the empty list's)
 __global__ __launch_bounds__(256) void cands_from_hits_kernel(BatchView b, DeviceTable tab, Workspace ws, const uint32_t* __restrict__ taxkey,
-                                                              uint32_t K, mc_candidate_dev* __restrict__ cands)
+                                                              uint32_t K, mc_candidate_dev* __restrict__ cands, bool keepStat)
 {
     __shared__ SortLds lds[4];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -616,7 +618,7 @@ __global__ __launch_bounds__(256) void cands_from_hits_kernel(BatchView b, Devic
     mc_candidate_dev* out = cands + (size_t)q * K;
     const uint64_t hoff = ws.hitOff[q];
     const uint64_t H64 = ws.hitOff[q + 1] - hoff;
-    if (lane == 0) { QueryStat qs; qs.hits = (uint32_t)min(H64, (uint64_t)0xFFFFFFFFu); qs.nfeat = 0; qs.nfound = 0; qs.nsteps = 0; ws.qstat[q] = qs; }
+    if (lane == 0 && !keepStat) { QueryStat qs; qs.hits = (uint32_t)min(H64, (uint64_t)0xFFFFFFFFu); qs.nfeat = 0; qs.nfound = 0; qs.nsteps = 0; ws.qstat[q] = qs; }
     if (H64 == 0 || H64 > kMaxHitsPerQuery) { emit_empty(out, 0, K, lane); return; }
     const uint32_t H = (uint32_t)H64;
     const uint32_t maxWin = b.max_win(q);
@@ -633,10 +635,10 @@ __global__ __launch_bounds__(256) void cands_from_hits_kernel(BatchView b, Devic
 }
 
 void launch_cands_from_hits(const BatchView& b, const DeviceTable& tab, const Workspace& ws, const uint32_t* taxkey, uint32_t maxCand,
-                            void* cands, hipStream_t st)
+                            void* cands, hipStream_t st, bool keepStat)
 {
     if (b.n == 0) return;
-    hipLaunchKernelGGL(cands_from_hits_kernel, dim3((b.n + 3) / 4), dim3(256), 0, st, b, tab, ws, taxkey, maxCand, (mc_candidate_dev*)cands);
+    hipLaunchKernelGGL(cands_from_hits_kernel, dim3((b.n + 3) / 4), dim3(256), 0, st, b, tab, ws, taxkey, maxCand, (mc_candidate_dev*)cands, keepStat);
 }
 
 // Mode K, owner side: the partial location lists of `sources` key shards (counts[s * m + i] locations of read i from source s; the

@@ -664,7 +664,8 @@ int mc_candidates_from_partial_numbers_on(mc_ctx* ctx, const mc_device_partial_n
     if ((rc = ensure_sort_space(ctx, P, *P.hTotal, taxkey, ws))) return rc;
     { ScopedTimer t(ctx, "decode_union", st); launch_decode_union(b, tab, ws, in->counts, srcStart, bases, S, st); }
     const DeviceTable none = no_table();
-    { ScopedTimer t(ctx, "cands_from_hits", st); launch_cands_from_hits(b, none, ws, taxkey, K, P.bCands.p, st); }
+    // (owner_entries_kernel wrote every read's statistics: locations and sources whichever kernel finishes the read, a read beyond kMaxHitsPerQuery included)
+    { ScopedTimer t(ctx, "cands_from_hits", st); launch_cands_from_hits(b, none, ws, taxkey, K, P.bCands.p, st, true); }
     HIP_TRY(ctx, hipGetLastError());
     P.lastN = 0;
     publish_results(out, P, ws, false);

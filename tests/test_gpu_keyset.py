@@ -53,6 +53,40 @@ def test_key_shards_against_the_oracle(golden, shards, lowest, K):
     ks.close(); odb.close()
 
 
+@pytest.mark.parametrize("batch", [1, 63, 64, 65])
+@pytest.mark.parametrize("shards,lowest,K", [(63, 0, 2), (64, 4, 4)])
+def test_most_key_shards_and_batches_around_their_count(golden, shards, lowest, K, batch):
+    """63 and 64 shards (the most mc_candidates_from_partial_numbers takes sources from) with batches of 1, 63, 64 and 65 reads: owners
+    without a read of their own, shards that hold no feature of a read, read shards of one and two reads -- singles and pairs against the oracle"""
+    single, p1, p2 = golden.reads()
+    name = golden.db_path("toy32")
+    odb = cpuref.oracle().open(name)
+    ks = api.KeySet(name, shards=shards, max_candidates=K, slot_max_queries=batch, slot_max_chars=1 << 16)
+    try:
+        info = ks.info()
+        assert info["shards"] == shards and info["devices"] == 1 and not info["rccl"]
+        n = 2 * batch + 3                                             # three batches, the last one short (batch 1: five of one read)
+        reads = [r for r in single if len(r) > 0][:n]
+        got = ks.classify(reads, lowest=lowest)
+        for i, s in enumerate(reads):
+            _, c = odb.query(s, b"", K, lowest, 0)
+            _eq(got[i], c, K, ("single", i))
+        m = batch + 2
+        gp = ks.classify(p1[:m], p2[:m], lowest=lowest, insert_max=700)
+        for i, (a, b) in enumerate(zip(p1[:m], p2[:m])):
+            _, c = odb.query(a, b, K, lowest, 700)
+            _eq(gp[i], c, K, ("pair", i))
+        info = ks.info()
+        assert info["batches"] == 3 + 2 + (batch == 1) * 3 and info["numbers_sent"] > 0, info
+    finally:
+        ks.close(); odb.close()
+
+
+def test_more_than_64_key_shards_are_refused(golden):
+    with pytest.raises(api.McError, match="more than 64 key shards"):
+        api.KeySet(golden.db_path("toy32"), shards=65, max_candidates=2)
+
+
 def test_key_shard_exchange_over_rccl_single_rank(golden, monkeypatch):
     """the ncclSend / ncclRecv round of the exchange with one rank (it sends to itself) -- what several devices run between each other"""
     monkeypatch.setenv("MC_KEYSET_RCCL", "1")
