@@ -1030,6 +1030,63 @@ int mc_merge_results_classify(mc_ctx* ctx, const mc_classify_options* opt, int f
 int mc_merge_results_stats(mc_ctx* ctx, uint64_t stats[6]);
 void mc_merge_results_end(mc_ctx* ctx);
 
+/* ---- targets ranked from accession2taxid tables on the device: the ranking pass of build / modify ------
+ * try_to_rank_unranked_targets (building.cpp:85-149, :196-229): every row "accession accession.version taxid gi" of a table names at
+ * most one target, and a target that still has no parent takes the taxid of the FIRST row that names it.
+ * THE NAMES are the target names (taxonomy_cache::name2tax_): `count` byte strings, name i = names[name_off[i] .. name_off[i + 1]),
+ *   strictly ascending in unsigned byte order, a shorter prefix first (std::string::compare).  wanted[i] != 0: the name takes a taxid
+ *   (an unranked target; under -reset-taxa every target).
+ * THE TARGET OF A ROW `acc accver taxid gi` (building.cpp:122-130, taxonomy.hpp:1108-1127) is
+ *   1. the name equal to accver;
+ *   2. else the smallest name strictly greater than acc, if acc is a prefix of it (a name EQUAL to acc is thus skipped for the next
+ *      longer one, or for none: the reference's upper_bound, kept);
+ *   3. else the name equal to gi;
+ *   4. else none.
+ *   A row whose target is not wanted does nothing: it does not fall through to another name.
+ * THE WINNER: each wanted name takes the taxid of the first row, in the order of the calls and then of the bytes, whose target it is.
+ *   A taxid of 0 counts as found.  The position of the winner is call * 2^32 + line start, call = the number of the mc_taxmap_add call
+ *   since mc_taxmap_begin (from 0, refused calls counted), line start = the offset into that call's range.
+ * THE LINE RULE -- narrower than the reference's token stream `is >> acc >> accver >> taxid >> gi`: the device refuses more and never
+ *   reads an accepted range differently.  A range is bytes[0, n), n <= 2^31; it begins at a line start, holds whole lines, and its last
+ *   line may lack the '\n'.  The file's first line is not part of it (the reference drops it unread; so does the caller).  A regular
+ *   line is: optional blanks (' ' or '\t'), four non-empty tokens of non-blank bytes separated by runs of blanks, optional blanks; its
+ *   third token is 1-18 decimal digits; it has at most mc_taxmap_max_line (1 024) bytes, the '\n' not counted.  An empty or blank-only
+ *   line, a '\r', '\v', '\f' or NUL byte, a line that is too long or any other deviation (fewer or more tokens, a third token that is
+ *   not all digits or has 19 and more) makes the range MC_TAXMAP_IRREGULAR; the offence is the smallest line start of an offending
+ *   line.  With any verdict but MC_TAXMAP_OK NOTHING but status changes.
+ * mc_taxmap_begin: the names and their flags (HOST arrays, copied); every name is unfound afterwards.  Names that do not ascend
+ *   strictly, descending offsets, count >= 2^31 or more than 2^32 - 1 bytes of names are MC_ERR_INVALID; count == 0 is allowed.  Waits
+ *   for the device.  mc_taxmap_end frees the names.
+ * mc_taxmap_add matches one range.  status[8] = lines, rows with a target, rows with a wanted target (wanted as mc_taxmap_begin
+ *   flagged it), names this call ranked, names still wanted after it, verdict, offence, 0.  With MC_TAXMAP_IRREGULAR [1] - [3] are 0.
+ *   Without MC_TAXMAP_HOST bytes, status and workspace are DEVICE pointers (bytes and workspace 16-byte, status 8-byte aligned; workspace
+ *   of mc_taxmap_scratch_bytes(nbytes) bytes) and the call is enqueued on `stream` (NULL: the context's) without any synchronisation,
+ *   neither between its passes nor between calls: a name's winner is a minimum over {call, line start}, so earlier calls win by
+ *   themselves.  The calls on one context are ordered by the caller (one stream, or events), which is what makes [3] and [4] those of
+ *   the call order.  The same calls give the same bytes.  With MC_TAXMAP_HOST bytes and status are HOST arrays (workspace may be NULL),
+ *   staged through the context; the call returns when status is filled.
+ * mc_taxmap_result: taxid[i] / position[i] of name i (either may be NULL); position all ones = not found, taxid 0 then.  flags: 0
+ *   (DEVICE pointers, 8-byte aligned, enqueued on `stream`; remaining must be NULL) or MC_TAXMAP_HOST (returns when filled; *remaining,
+ *   may be NULL, = the wanted names not found).
+ * mc_taxmap_stats: calls, bytes, then of the accepted ranges lines, rows with a target, rows with a wanted target, names ranked; ranges
+ *   refused; 0.  Waits for the device.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, offsets, flags array (count > 0), bytes or status, nbytes == 0 or
+ *   > 2^31, unknown flags, misaligned device arrays, a workspace that is too small.  MC_ERR_STATE: no mc_taxmap_begin, or a context
+ *   without a device (mc_open_metadata).  The calls work on a context without a loaded table (mc_create).  mc_timing_get names:
+ *   "taxmap_validate", "taxmap_match" (the match, finish and status launches). */
+#define MC_TAXMAP_HOST      1        /* the arrays are HOST arrays, staged through the context; the call returns when done */
+#define MC_TAXMAP_OK        0
+#define MC_TAXMAP_IRREGULAR 1
+extern const uint32_t mc_taxmap_tile;                    /* bytes one block owns the line starts of (for tests and tools) */
+extern const uint32_t mc_taxmap_max_line;                /* bytes of the longest regular line, its '\n' not counted */
+int mc_taxmap_begin(mc_ctx* ctx, const char* names, const uint64_t* name_off, uint64_t count, const uint8_t* wanted);
+uint64_t mc_taxmap_scratch_bytes(uint64_t nbytes);
+int mc_taxmap_add(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags, uint64_t status[8], void* workspace, uint64_t workspace_bytes,
+                  void* stream);
+int mc_taxmap_result(mc_ctx* ctx, int64_t* taxid, uint64_t* position, uint64_t* remaining, int flags, void* stream);
+int mc_taxmap_stats(mc_ctx* ctx, uint64_t stats[8]);
+void mc_taxmap_end(mc_ctx* ctx);
+
 /* ---- table content: what `metacache info <db> statistics | featurecounts | featuremap` asks for ------
  * The reference answers these from its hash table (host_hashmap.hpp:376-445, printing.cpp:662-696).  They describe the CONTENT of the
  * database -- how many features, how many locations, the distribution of the list sizes, which locations a feature has -- and here the

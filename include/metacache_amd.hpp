@@ -677,6 +677,69 @@ private:
     std::uint32_t maxCand_ = 0, calls_ = 0;
 };
 
+// targets ranked from accession2taxid tables on the device (mc_taxmap_*; the reference's try_to_rank_unranked_targets): a context of its
+// own without a table.  begin takes the target names in ascending order (a std::map's order) with a flag per name; add matches one
+// piece of a table (whole lines, the file's first line dropped, in order); result() gives every name's taxid and where its row was.
+// A range the device refuses changes nothing.
+class accession_mapper {
+public:
+    struct status { std::uint64_t lines, targeted, wanted, ranked, remaining, verdict, offence; };
+    struct ranking {
+        std::vector<std::int64_t> taxid;             // per name; 0 where not found
+        std::vector<std::uint64_t> position;         // call * 2^32 + line start; not_found: no row named the name
+        std::uint64_t remaining = 0;                 // wanted names without a row
+    };
+    static constexpr std::uint64_t not_found = ~std::uint64_t(0);
+
+    explicit accession_mapper(int device = 0)
+    {
+        mc_config c;
+        mc_config_default(&c);
+        c.device = device;
+        if (mc_create(&c, &ctx_) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
+    }
+    accession_mapper(const accession_mapper&) = delete;
+    accession_mapper& operator=(const accession_mapper&) = delete;
+    ~accession_mapper() { if (ctx_) { mc_taxmap_end(ctx_); mc_destroy(ctx_); } }
+    mc_ctx* handle() const noexcept { return ctx_; }
+
+    // names strictly ascending (std::string's order); wanted: a flag per name, empty = all
+    void begin(const std::vector<std::string>& names, const std::vector<std::uint8_t>& wanted = {})
+    {
+        std::string text;
+        std::vector<std::uint64_t> off(1, 0);
+        for (const std::string& n : names) { text += n; off.push_back(text.size()); }
+        const std::vector<std::uint8_t> all(names.size(), 1);
+        if (!wanted.empty() && wanted.size() != names.size()) throw std::invalid_argument("accession_mapper::begin: one flag per name");
+        check(mc_taxmap_begin(ctx_, text.data(), off.data(), names.size(), (wanted.empty() ? all : wanted).data()));
+        count_ = names.size();
+    }
+    status add(const char* bytes, std::size_t nbytes)
+    {
+        std::uint64_t st[8];
+        check(mc_taxmap_add(ctx_, bytes, nbytes, MC_TAXMAP_HOST, st, nullptr, 0, nullptr));
+        return status{st[0], st[1], st[2], st[3], st[4], st[5], st[6]};
+    }
+    ranking result() const
+    {
+        ranking r;
+        r.taxid.resize(count_); r.position.resize(count_);
+        check(mc_taxmap_result(ctx_, r.taxid.data(), r.position.data(), &r.remaining, MC_TAXMAP_HOST, nullptr));
+        return r;
+    }
+    std::vector<std::uint64_t> stats() const
+    {
+        std::vector<std::uint64_t> s(8);
+        check(mc_taxmap_stats(ctx_, s.data()));
+        return s;
+    }
+
+private:
+    void check(int rc) const { if (rc < 0) throw std::runtime_error(mc_last_error(ctx_)); }
+    mc_ctx* ctx_ = nullptr;
+    std::uint64_t count_ = 0;
+};
+
 }  // namespace mc_amd
 
 #endif

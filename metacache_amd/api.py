@@ -126,6 +126,21 @@ def merge_results_tile() -> int:
     return int(C.c_uint32.in_dll(lib(), "mc_merge_results_tile").value)
 
 
+def taxmap_tile() -> int:
+    """bytes one block of the taxmap kernels owns the line starts of (the library's mc_taxmap_tile)"""
+    return int(C.c_uint32.in_dll(lib(), "mc_taxmap_tile").value)
+
+
+def taxmap_max_line() -> int:
+    """bytes of the longest line mc_taxmap_add accepts, its line end not counted (the library's mc_taxmap_max_line)"""
+    return int(C.c_uint32.in_dll(lib(), "mc_taxmap_max_line").value)
+
+
+def taxmap_scratch_bytes(nbytes: int) -> int:
+    """bytes of the device workspace of mc_taxmap_add for a range of nbytes bytes"""
+    return int(lib().mc_taxmap_scratch_bytes(nbytes))
+
+
 def merge_results_scratch_bytes(nbytes: int) -> int:
     """bytes of device workspace ResultMerger.add_device needs for a range of nbytes bytes"""
     return int(lib().mc_merge_results_scratch_bytes(nbytes))
@@ -389,7 +404,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates",
            "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
            "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end",
-           "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats"]
+           "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats",
+           "mc_taxmap_begin", "mc_taxmap_scratch_bytes", "mc_taxmap_add", "mc_taxmap_result", "mc_taxmap_stats", "mc_taxmap_end"]
 
 _lib = None
 
@@ -498,6 +514,14 @@ def lib() -> C.CDLL:
         L.mc_bgzf_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_inflate_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mc_inflate_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_taxmap_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_taxmap_scratch_bytes.argtypes = [C.c_uint64]
+        L.mc_taxmap_scratch_bytes.restype = C.c_uint64
+        L.mc_taxmap_add.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_taxmap_result.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.mc_taxmap_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_taxmap_end.argtypes = [C.c_void_p]
+        L.mc_taxmap_end.restype = None
         if hasattr(L, "mc_build_begin"):
             L.mc_build_begin.argtypes = [C.POINTER(McConfig), C.POINTER(C.c_void_p)]
             L.mc_build_add_target.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p]
@@ -1801,4 +1825,103 @@ class ResultMerger:
         """[calls, bytes, result lines of accepted ranges, entries folded, unknown taxids, ranges refused]"""
         st = np.zeros(6, dtype=np.uint64)
         self._check(lib().mc_merge_results_stats(self.h, st.ctypes.data), "mc_merge_results_stats")
+        return [int(x) for x in st]
+
+
+TAXMAP_HOST = 1
+TAXMAP_OK, TAXMAP_IRREGULAR = 0, 1
+TAXMAP_NOT_FOUND = 0xFFFFFFFFFFFFFFFF
+
+
+class TaxonMapper:
+    """Targets ranked from accession2taxid tables on the device (mc_taxmap_*): a context of its own, or any Database's handle.
+    begin with the target names, then add per piece of a table in order; result() reads every name's taxid and the place of its row."""
+
+    def __init__(self, handle=None, **kw):
+        self.own = handle is None
+        if self.own:
+            cfg = default_config(**kw)
+            h = C.c_void_p()
+            rc = lib().mc_create(C.byref(cfg), C.byref(h))
+            if rc != MC_OK:
+                raise McError(f"mc_create -> {rc}: {lib().mc_last_error(None).decode()}")
+            handle = h.value
+        self.h = C.c_void_p(handle)
+        self.count = 0
+
+    def _check(self, rc, what):
+        if rc < 0:
+            raise McError(f"{what} -> {rc}: {lib().mc_last_error(self.h).decode()}")
+        return rc
+
+    def close(self):
+        if self.h:
+            lib().mc_taxmap_end(self.h)
+            if self.own:
+                lib().mc_destroy(self.h)
+        self.h = None
+
+    def begin(self, names, wanted=None):
+        """names: byte strings, strictly ascending; wanted: a flag per name (None: all)"""
+        names = [bytes(n) for n in names]
+        flags = np.ones(len(names), dtype=np.uint8) if wanted is None else np.ascontiguousarray(np.asarray(wanted) != 0, dtype=np.uint8)
+        if len(flags) != len(names):
+            raise ValueError("begin: one flag per name")
+        text = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        off = np.zeros(len(names) + 1, dtype=np.uint64)
+        if names:
+            off[1:] = np.cumsum([len(n) for n in names], dtype=np.uint64)
+        self._check(lib().mc_taxmap_begin(self.h, text.ctypes.data, off.ctypes.data, len(names), flags.ctypes.data if len(names) else None), "mc_taxmap_begin")
+        self.count = len(names)
+
+    def add(self, data):
+        """a host range (bytes) -> status[8]: lines, rows with a target, rows with a wanted target, names newly ranked, names still wanted,
+        verdict, offence, 0"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        st = np.zeros(8, dtype=np.uint64)
+        self._check(lib().mc_taxmap_add(self.h, buf.ctypes.data if len(buf) else None, len(buf), TAXMAP_HOST, st.ctypes.data, None, 0, None), "mc_taxmap_add")
+        return [int(x) for x in st]
+
+    def add_device(self, bytes_ptr: int, nbytes: int, *, status_ptr: int, workspace_ptr: int, workspace_bytes: int, stream: int = 0):
+        """device pointers; enqueued on `stream` (0: the context's), nothing is waited for"""
+        self._check(lib().mc_taxmap_add(self.h, bytes_ptr or None, nbytes, 0, status_ptr or None, workspace_ptr or None, workspace_bytes, stream or None), "mc_taxmap_add")
+
+    def add_file(self, path, piece_bytes: int = 256 << 20):
+        """a whole table: the first line is dropped, the rest goes through add() in pieces of at most piece_bytes cut at line ends, until
+        no name is wanted -> the statuses of the calls (the last one's verdict is not TAXMAP_OK where the device refused a piece)"""
+        with open(path, "rb") as f:
+            data = f.read()
+        nl = data.find(b"\n")
+        pos = len(data) if nl < 0 else nl + 1
+        out = []
+        while pos < len(data):
+            end = min(len(data), pos + piece_bytes)
+            if end < len(data):
+                cut = data.rfind(b"\n", pos, end)
+                if cut < 0:
+                    cut = data.find(b"\n", end)
+                end = len(data) if cut < 0 else cut + 1
+            st = self.add(data[pos:end])
+            out.append(st)
+            if st[5] != TAXMAP_OK or st[4] == 0:
+                break
+            pos = end
+        return out
+
+    def result(self):
+        """-> taxid [count] int64, position [count] uint64 (call * 2^32 + line start; TAXMAP_NOT_FOUND: none), wanted names not found"""
+        taxid = np.zeros(self.count, dtype=np.int64)
+        position = np.zeros(self.count, dtype=np.uint64)
+        remaining = C.c_uint64(0)
+        self._check(lib().mc_taxmap_result(self.h, taxid.ctypes.data if self.count else None, position.ctypes.data if self.count else None,
+                                           C.addressof(remaining), TAXMAP_HOST, None), "mc_taxmap_result")
+        return taxid, position, int(remaining.value)
+
+    def result_device(self, *, taxid_ptr: int, position_ptr: int, stream: int = 0):
+        self._check(lib().mc_taxmap_result(self.h, taxid_ptr or None, position_ptr or None, None, 0, stream or None), "mc_taxmap_result")
+
+    def stats(self):
+        """[calls, bytes, lines / rows with a target / rows with a wanted target / names ranked of the accepted ranges, ranges refused, 0]"""
+        st = np.zeros(8, dtype=np.uint64)
+        self._check(lib().mc_taxmap_stats(self.h, st.ctypes.data), "mc_taxmap_stats")
         return [int(x) for x in st]

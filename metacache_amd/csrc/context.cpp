@@ -281,6 +281,7 @@ void mc_destroy(mc_ctx* ctx)
     free_parse_state(ctx);
     free_merge_results_state(ctx);
     free_inflate_state(ctx);
+    free_taxmap_state(ctx);
     for (auto& kv : ctx->taxkeyDev) (void)hipFree(kv.second);
     if (ctx->dGwBase) (void)hipFree(ctx->dGwBase);
     if (ctx->dGwDir) (void)hipFree(ctx->dGwDir);

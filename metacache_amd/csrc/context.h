@@ -224,6 +224,11 @@ void free_merge_results_state(mc_ctx* ctx);
 struct InflateState;
 void free_inflate_state(mc_ctx* ctx);
 
+// taxmap.hip: the target names, their keys and taxids, the counters and the staging of mc_taxmap_* (made by mc_taxmap_begin), freed
+// with the context
+struct TaxmapState;
+void free_taxmap_state(mc_ctx* ctx);
+
 struct TimedKernel { double ms = 0; uint64_t launches = 0; std::vector<std::pair<hipEvent_t, hipEvent_t>> pending; };
 
 }  // namespace mcamd
@@ -290,6 +295,8 @@ struct mc_ctx {
     std::mutex inflateMtx;
     mcamd::InflateState* inflate = nullptr;   // made by the first mc_inflate_blocks that reaches the device
     uint64_t inflateStageBytes = 0;        // MC_INFLATE_HOST: compressed bytes per staged piece (mc_set_tuning "inflate_stage_bytes"; 0 = 64 MiB)
+
+    mcamd::TaxmapState* taxmap = nullptr;     // made by mc_taxmap_begin; its calls are ordered by the caller
 
     std::mutex targetHitsMtx;
     mcamd::TargetHitsState* targetHits = nullptr;

@@ -343,6 +343,95 @@ struct BuiltDatabase {
     }
 };
 
+// ---- taxmap (mc_taxmap_*): the ranking pass hands its accession2taxid tables to the library ---------------------------
+// MCQ_TAXMAP_DEVICE=1 (build, modify, build+query).  Shaped as the hand-offs of mcq_device_steps.h: the switch, run, report.  Every file
+// the host loop would open is mapped, its first line dropped, and the rest goes to mc_taxmap_add(MC_TAXMAP_HOST) in pieces cut at line
+// ends (MCQ_TAXMAP_PIECE bytes each, 256 MiB by default), until no name is wanted -- where the host loop breaks.  Nothing is applied
+// before the last piece is through: any verdict other than MC_TAXMAP_OK and any library error leave the WHOLE pass to the host loop;
+// `why` says which file, verdict and offence.
+struct TaxmapStep {
+    bool on = false;
+    std::string why;                         // on and not ranked by the library: why
+    uint64_t calls = 0, bytes = 0, rows = 0, files = 0, ranked = 0;
+    double validateMs = 0, matchMs = 0;      // under MCQ_PROFILE: the kernels' time (mc_timing_get)
+    std::vector<std::string> tried;          // the files the pass opened, in order (the host loop's "Try to map" lines)
+    std::vector<int64_t> taxid; std::vector<uint64_t> position;   // per name in the map's order; position all ones: not found
+    size_t piece = (size_t)256 << 20;
+    TaxmapStep()
+    {
+        const char* sw = std::getenv("MCQ_TAXMAP_DEVICE"); on = sw && std::atoi(sw) != 0;
+        if (const char* p = std::getenv("MCQ_TAXMAP_PIECE")) piece = std::min<size_t>(std::max<long long>(1, std::atoll(p)), (size_t)1 << 31);
+    }
+
+    bool run(const std::vector<std::string>& mapFiles, const std::map<std::string, uint32_t>& name2tgt, const std::set<uint32_t>& unranked)
+    {
+        mc_config cfg;
+        mc_config_default(&cfg);
+        mc_ctx* ctx = nullptr;
+        if (mc_create(&cfg, &ctx) != MC_OK) { why = mc_last_error(nullptr); return false; }
+        struct Closer { mc_ctx* c; ~Closer() { mc_taxmap_end(c); mc_destroy(c); } } closer{ctx};
+        auto failed = [&](const std::string& what) { why = what; return false; };
+        auto lib_failed = [&] { return failed(mc_last_error(ctx)); };
+        const bool profile = std::getenv("MCQ_PROFILE") != nullptr;
+        if (profile) mc_timing_enable(ctx, 1);
+        std::string names;
+        std::vector<uint64_t> off(1, 0);
+        std::vector<uint8_t> wanted;
+        for (const auto& kv : name2tgt) { names += kv.first; off.push_back(names.size()); wanted.push_back(unranked.count(kv.second) ? 1 : 0); }
+        if (mc_taxmap_begin(ctx, names.data(), off.data(), wanted.size(), wanted.data()) != MC_OK) return lib_failed();
+        uint64_t remaining = unranked.size();
+        for (const std::string& file : mapFiles) {
+            if (remaining == 0) break;
+            const int fd = open(file.c_str(), O_RDONLY);
+            if (fd < 0) continue;                                              // (the host loop's `!is.good()`)
+            struct FdCloser { int fd; ~FdCloser() { close(fd); } } fdc{fd};
+            struct stat sb;
+            if (fstat(fd, &sb) != 0 || !S_ISREG(sb.st_mode)) return failed(file + ": not a regular file");
+            tried.push_back(file);
+            const size_t size = (size_t)sb.st_size;
+            if (size == 0) { ++files; continue; }
+            void* m = mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
+            if (m == MAP_FAILED) return failed(file + ": cannot be mapped");
+            struct Unmapper { void* p; size_t n; ~Unmapper() { munmap(p, n); } } um{m, size};
+            const char* data = (const char*)m;
+            const void* nl0 = memchr(data, '\n', size);
+            const size_t body = nl0 ? (size_t)((const char*)nl0 - data) + 1 : size;   // the first line is dropped unread
+            for (size_t pos = body; pos < size && remaining != 0;) {
+                size_t len = std::min(size - pos, piece);
+                if (pos + len < size) {
+                    const void* nl = memrchr(data + pos, '\n', len);
+                    if (!nl) {                                                 // no line end in a piece: up to the next one, if that is a range
+                        const void* nx = memchr(data + pos + len, '\n', size - pos - len);
+                        len = nx ? (size_t)((const char*)nx - (data + pos)) + 1 : size - pos;
+                        if (len > ((size_t)1 << 31)) return failed(file + ": a line of more than 2^31 bytes");
+                    }
+                    else len = (size_t)((const char*)nl - (data + pos)) + 1;
+                }
+                uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                if (mc_taxmap_add(ctx, data + pos, len, MC_TAXMAP_HOST, st, nullptr, 0, nullptr) != MC_OK) return lib_failed();
+                if (st[5] != MC_TAXMAP_OK) return failed(file + ": verdict " + std::to_string(st[5]) + " (irregular line) at offset " + std::to_string(pos + st[6]));
+                ++calls; bytes += len; rows += st[0]; ranked += st[3];
+                remaining = st[4];
+                pos += len;
+            }
+            ++files;
+        }
+        taxid.assign(wanted.size(), 0); position.assign(wanted.size(), ~0ull);
+        if (mc_taxmap_result(ctx, taxid.data(), position.data(), nullptr, MC_TAXMAP_HOST, nullptr) != MC_OK) return lib_failed();
+        if (profile) { uint64_t n = 0; mc_timing_get(ctx, "taxmap_validate", &validateMs, &n); mc_timing_get(ctx, "taxmap_match", &matchMs, &n); }
+        return true;
+    }
+    // the device's line under MCQ_PROFILE; the fall-back's line also wherever the info level is not silent: the switch was set
+    void report(bool done, bool info) const
+    {
+        const bool profile = std::getenv("MCQ_PROFILE") != nullptr;
+        if (!on || (done ? !profile : !(profile || info))) return;
+        if (done) std::cerr << "mcq profile: targets ranked on the device: " << calls << " mc_taxmap_add calls, " << bytes << " bytes, " << rows << " rows, " << ranked
+                            << " targets ranked, kernels " << validateMs << " + " << matchMs << " ms, " << files << " files, 0 files left to the host\n";
+        else std::cerr << "mcq: targets ranked on the host (" << why << ")\n";
+    }
+};
+
 inline void build_database(const BuildOptions& o, BuiltDatabase& db)
 {
     using clock = std::chrono::steady_clock;
@@ -522,7 +611,24 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
         for (uint32_t t = 0; t < db.targets.size(); ++t) if (o.resetParents || db.targets[t].parent == 0) unranked.insert(t);
         if (!unranked.empty()) {
             if (info) std::cout << unranked.size() << " targets are unranked (no taxon was assigned)." << std::endl;
-            for (const auto& file : o.mapPost) {
+            // MCQ_TAXMAP_DEVICE=1: the library finds every name's first row; what it found is applied as the loop below applies it
+            TaxmapStep step;
+            const auto r0 = clock::now();
+            const bool onDevice = step.on && step.run(o.mapPost, name2tgt, unranked);
+            step.report(onDevice, info);
+            if (onDevice) {
+                if (info) for (const auto& file : step.tried) std::cout << "Try to map sequences to taxa using '" << file << "'" << std::endl;
+                size_t i = 0;
+                for (const auto& kv : name2tgt) {
+                    const uint32_t t = kv.second;
+                    if (step.position[i] != ~0ull && unranked.count(t)) {
+                        db.targets[t].parent = step.taxid[i];
+                        for (mc_builder* b : db.bs) mc_build_set_parent(b, (uint64_t)t, step.taxid[i]);
+                    }
+                    ++i;
+                }
+            }
+            else for (const auto& file : o.mapPost) {
                 // rank_targets_with_mapping_file (building.cpp:80-150): rows "accession accession.version taxid gi" after one header line
                 std::ifstream is(file);
                 if (!is.good()) continue;
@@ -550,6 +656,8 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
                 }
                 if (unranked.empty()) break;
             }
+            if (std::getenv("MCQ_PROFILE"))
+                std::cerr << "mcq profile: ranking pass " << std::chrono::duration<double>(clock::now() - r0).count() << " s on the " << (onDevice ? "device" : "host") << "\n";
         }
         size_t still = 0;
         for (const auto& t : db.targets) if (t.parent == 0) ++still;
