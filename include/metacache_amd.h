@@ -851,6 +851,53 @@ uint64_t mc_parse_mates_scratch_bytes(uint64_t n1, uint64_t n2, uint32_t max_rec
 int mc_parse_mates(mc_ctx* ctx, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, int flags, uint64_t insert_size_max,
                    const mc_parse_output* out, void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* ---- batch borders of a FASTA / FASTQ range: what the host index did ------
+ * THE CUT RULE.  The range is B[0, n), n = nbytes, R = records_per_batch; B[0] selects the kind.  Line starts, record starts (FASTA: a
+ * line start that holds '>'; FASTQ: the start of every line 4k) and offences are those of THE RECORD RULE above.  What this call adds is
+ * where the range is taken to END:
+ *   closed (no MC_CUT_OPEN): consumed = n, whole = the number of record starts; verdict and offence are exactly those of
+ *          mc_parse_records for B[0, n) -- a first byte that is no marker (offence 0) and an incomplete last FASTQ group (offence n) included.
+ *   open (MC_CUT_OPEN): the last record may be cut short, and the next call starts at consumed.
+ *          FASTA: whole = the record starts - 1, consumed = the line start of the last record (one record: whole = 0, consumed = 0).
+ *          FASTQ: a group is whole when all four of its lines end in a '\n' inside the range: whole = (number of '\n') / 4, consumed = the
+ *          byte behind the (4 * whole)-th '\n'.
+ *          MC_PARSE_PAIRS: whole is rounded down to an even number and consumed moves back with it.
+ *          The verdict covers B[0, consumed) only -- an offence at or behind consumed is none, the next call judges it -- and for
+ *          consumed > 0 verdict and offence are those of mc_parse_records for B[0, consumed).  consumed = 0 is MC_PARSE_OK with no batch,
+ *          unless B[0] is no marker.
+ *   batches: nb = ceil(whole / R); cuts[i] = the line start of record i * R for i < nb, cuts[nb] = consumed.  Every B[cuts[i], cuts[i + 1])
+ *          is a range of whole records that mc_parse_records accepts: R records, the last batch the rest.  MC_PARSE_PAIRS wants an even R.
+ * status[8] = whole, nb, consumed, the record starts seen in the range, verdict, offence, the largest cuts[i + 1] - cuts[i] (what a slot
+ *   must hold; filled with MC_PARSE_OK only, else 0), 1 when the last batch ends in a half pair (closed, pairs, odd whole).
+ *   MC_PARSE_OVERFLOW: nb + 1 > capacity (the entries of cuts); status holds what a second call needs.  With a verdict other than
+ *   MC_PARSE_OK NOTHING but status is written; with MC_PARSE_IRREGULAR only verdict and offence mean anything.
+ * mc_parse_cut: as mc_parse_records -- without MC_PARSE_HOST bytes, cuts, status and workspace are DEVICE pointers (cuts and status
+ *   8-byte, workspace 16-byte aligned) and the call is enqueued on `stream` (NULL: the context's) without any synchronisation; the caller
+ *   owns the workspace (mc_parse_cut_scratch_bytes(nbytes) bytes), the context keeps nothing per call, the same bytes give the same
+ *   outputs.  Unlike mc_parse_records it accepts bytes at ANY address: a piece starts where the last one ended.  With MC_PARSE_HOST all
+ *   arrays are HOST arrays (workspace may be NULL), staged through the context, one caller at a time.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, bytes, cuts or status, nbytes == 0 or > 2^31, records_per_batch == 0
+ *   (or odd with MC_PARSE_PAIRS), unknown flags; device form: a workspace that is too small, misaligned cuts, status or workspace.
+ *   MC_ERR_STATE: a context without a device.  mc_parse_stats does not count these calls.  mc_timing_get name: "parse_cut".
+ * mc_parse_headers packs the headers of a range that mc_parse_records has cut: hdr and parse_status are what that call left for bytes
+ *   (device arrays, or host arrays with MC_PARSE_HOST).  The record count is read ON THE DEVICE from parse_status[0], so the call sits
+ *   behind the parse on one stream without any synchronisation.  out_off[r] = the sum of the header lengths in front of record r
+ *   (out_off[records] = all of them), out = the trimmed headers back to back.  status[4] = records, bytes of out needed, verdict, 0; the
+ *   verdict is MC_PARSE_OK, MC_PARSE_OVERFLOW (out_capacity too small; or more records than max_records, then the bytes needed are not
+ *   known and [1] = 0), or the parse's own verdict passed through ([0] = [1] = 0).  With a verdict other than MC_PARSE_OK NOTHING but
+ *   status is written.  Device form: hdr 4-byte, parse_status, out_off and status 8-byte, workspace 16-byte aligned
+ *   (mc_parse_headers_scratch_bytes(max_records) bytes); bytes and out at any address.  MC_ERR_INVALID as above; flags other than
+ *   MC_PARSE_HOST.  mc_timing_get name: "parse_headers". */
+#define MC_CUT_OPEN         4      /* beside MC_PARSE_HOST (1) and MC_PARSE_PAIRS (2) */
+uint64_t mc_parse_cut_scratch_bytes(uint64_t nbytes);
+int mc_parse_cut(mc_ctx* ctx, const char* bytes, uint64_t nbytes, uint32_t records_per_batch, int flags,
+                 uint64_t* cuts, uint64_t capacity, uint64_t status[8],
+                 void* workspace, uint64_t workspace_bytes, void* stream);
+uint64_t mc_parse_headers_scratch_bytes(uint32_t max_records);
+int mc_parse_headers(mc_ctx* ctx, const char* bytes, uint64_t nbytes, const uint32_t* hdr, const uint64_t* parse_status,
+                     uint32_t max_records, int flags, char* out, uint64_t out_capacity, uint64_t* out_off /* [max_records + 1] */,
+                     uint64_t status[4], void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* raw bytes into a batch slot: the slot's reads are cut on the device
  * mc_batch_add_file_bytes fills an EMPTY slot with a byte range of a FASTA / FASTQ file (whole records; flags: 0 or MC_PARSE_PAIRS): one
  *   copy into the slot's pinned input.  MC_BATCH_FULL, and nothing added, when nbytes exceeds the slot's character capacity; MC_ERR_STATE
@@ -879,6 +926,51 @@ int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out);
  *   works unchanged: records = 2 * queries, half_pair = 0, hdr as mc_parse_mates leaves it (row 2q in bytes1, row 2q + 1 in bytes2);
  *   a verdict other than MC_PARSE_OK (MC_PARSE_UNEQUAL among them) leaves mc_results.num_queries at 0. */
 int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insert_size_max);
+/* mc_batch_add_device_bytes is mc_batch_add_file_bytes for a range that lies in DEVICE memory already (a batch of mc_parse_cut, DESIGN.md
+ *   7l): any alignment; the memory stays untouched until mc_batch_wait returns; the same MC_BATCH_FULL / MC_ERR_STATE answers; never
+ *   united with other slots.  mc_batch_submit copies the range once on the device instead of uploading it, and has mc_parse_headers pack
+ *   the headers behind the parse; they travel back with the results.  mc_batch_records works unchanged.
+ * mc_batch_headers, after mc_batch_wait: host views of the headers back to back and of off[records + 1] (header r is bytes[off[r],
+ *   off[r + 1])), valid until mc_batch_clear; NULL views and 0 records with a verdict other than MC_PARSE_OK.  MC_ERR_STATE: a slot that
+ *   was not filled by mc_batch_add_device_bytes and submitted. */
+int mc_batch_add_device_bytes(mc_ctx* ctx, uint32_t slot, const void* dbytes, uint64_t nbytes, int flags, uint64_t insert_size_max);
+int mc_batch_headers(mc_ctx* ctx, uint32_t slot, const char** bytes, const uint64_t** off, uint64_t* records);
+
+/* ---- a query file resident on the device: for callers that own no device memory (`mcq query`, MCQ_INPUT_DEVICE) ------
+ * mc_input_open takes a file's bytes as they lie on the HOST (its mapping) and makes them resident: a plain file is uploaded; a file that
+ *   begins with the gzip magic goes through mc_bgzf_index and the DEVICE form of mc_inflate_blocks into a buffer sized from the index, so
+ *   the plain bytes never exist on the host.  The resident bytes are then cut with mc_parse_cut in pieces of at most piece_bytes (<= 2^31):
+ *   every piece but the last with MC_CUT_OPEN, the next one starting at `consumed`; an open piece with consumed = 0 is doubled up to 2^31.
+ *   A batch of records_per_batch records (flags: 0 or MC_PARSE_PAIRS, then an even number) whose bytes exceed slot_bytes is cut again with
+ *   half the records (kept even for pairs), down to one query; one query that still does not fit is kept with too_big = 1.  The call waits
+ *   for the device; it uses the context's own stream.
+ *   info[8] = verdict, detail, plain bytes, pieces, batches, records, 1 where the bytes were inflated on the device, second detail.
+ *   MC_INPUT_OK: *out is the handle.  MC_INPUT_NOT_BGZF (gzip that is no BGZF; detail: the offending member's offset), MC_INPUT_REFUSED
+ *   (a member the device refused; detail: the row, second detail: its MC_INFLATE_R_* reason), MC_INPUT_TOO_LARGE (plain bytes >
+ *   max_resident_bytes), MC_INPUT_NO_MEMORY, MC_INPUT_EMPTY: nothing is resident, *out is NULL.  MC_INPUT_IRREGULAR (detail: the offence,
+ *   an offset into the plain bytes) and MC_INPUT_RECORD_TOO_LARGE (a record that does not fit the largest piece): no batches; *out is
+ *   NULL for a plain file and a handle WITHOUT batches for an inflated one, so that mc_input_download can copy the plain bytes back once.
+ *   MC_ERR_INVALID: NULL arguments, nbytes == 0, unknown flags, records_per_batch == 0 or odd with pairs, piece_bytes == 0 or > 2^31,
+ *   slot_bytes == 0.  MC_ERR_STATE: a context without a device.
+ * mc_input_batches: the batches in file order ({offset into the plain bytes, bytes, records, queries, half_pair: the file's last query has
+ *   no second mate, too_big}; the first `capacity` of them), the device address of the plain bytes -- batch i goes to a slot as
+ *   mc_batch_add_device_bytes(ctx, slot, device_bytes + offset, nbytes, flags, ...) -- and their number.  mc_input_download copies the plain
+ *   bytes to the host.  mc_input_close frees the handle and its device memory; no batch of it may be in flight. */
+typedef struct mc_input mc_input;
+typedef struct { uint64_t offset, nbytes; uint32_t records, queries, half_pair, too_big; } mc_input_batch;
+#define MC_INPUT_OK                0
+#define MC_INPUT_NOT_BGZF          1
+#define MC_INPUT_REFUSED           2
+#define MC_INPUT_TOO_LARGE         3
+#define MC_INPUT_NO_MEMORY         4
+#define MC_INPUT_EMPTY             5
+#define MC_INPUT_IRREGULAR         6
+#define MC_INPUT_RECORD_TOO_LARGE  7
+int mc_input_open(mc_ctx* ctx, const void* file_bytes, uint64_t nbytes, int flags, uint32_t records_per_batch, uint64_t piece_bytes, uint64_t slot_bytes,
+                  uint64_t max_resident_bytes, mc_input** out, uint64_t info[8]);
+int mc_input_batches(const mc_input* in, mc_input_batch* batches, uint64_t capacity, const void** device_bytes, uint64_t* nbytes);
+int mc_input_download(const mc_input* in, void* host_bytes, uint64_t capacity);
+void mc_input_close(mc_input* in);
 
 /* ---- BGZF input inflated on the device ---------------------------------------------
  * BGZF (what bgzip and htslib write) is a sequence of independent gzip members of at most 64 KiB in and out.  gzread joins the members

@@ -281,6 +281,31 @@ public:
         return p;
     }
 
+    // the batch borders of a FASTA / FASTQ byte range, found on the device (mc_parse_cut on host arrays; the cut rule: metacache_amd.h).
+    // verdict MC_PARSE_OK: batch i is bytes[cuts[i] .. cuts[i + 1]), recordsPerBatch whole records (the last batch: the rest); open: the
+    // last record may be cut short and the next range starts at consumed.  Another verdict: cuts is empty and offence says where the
+    // range broke the rule.
+    struct cut_batches {
+        int verdict = MC_PARSE_IRREGULAR; std::uint64_t offence = 0, whole = 0, consumed = 0, seen = 0, longest = 0; bool halfPair = false;
+        std::vector<std::uint64_t> cuts;
+    };
+    cut_batches parse_cut(const char* bytes, std::size_t nbytes, std::uint32_t recordsPerBatch, bool pairs = false, bool open = false) const
+    {
+        cut_batches c;
+        std::uint64_t status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int pass = 0; pass < 2; ++pass) {                                   // (the first call reports what the second needs)
+            c.cuts.assign(std::size_t(status[1]) + 1, 0);
+            if (mc_parse_cut(ctx_, bytes, nbytes, recordsPerBatch, MC_PARSE_HOST | (pairs ? MC_PARSE_PAIRS : 0) | (open ? MC_CUT_OPEN : 0), c.cuts.data(),
+                             c.cuts.size(), status, nullptr, 0, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            if (status[4] != MC_PARSE_OVERFLOW) break;
+        }
+        c.verdict = int(status[4]); c.offence = status[5]; c.whole = status[0]; c.consumed = status[2]; c.seen = status[3]; c.longest = status[6];
+        c.halfPair = status[7] != 0;
+        if (status[4] != MC_PARSE_OK) c.cuts.clear();
+        return c;
+    }
+
     // the members of a BGZF range inflated on the device (mc_inflate_blocks on host arrays; the block rule: metacache_amd.h).  verdict
     // MC_INFLATE_OK: bytes is what zlib gives for the range.  Another verdict: bytes is empty, block is the lowest member the device
     // refused and reason says why (MC_INFLATE_R_*) -- the caller reads the range through zlib.
@@ -529,6 +554,15 @@ public:
             if (mc_batch_records(ctx_, slot_, &info) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
             return info;
         }
+        // the headers of a batch filled by add_device_bytes (after wait_for_results; mc_batch_headers): header r is bytes[off[r] ..
+        // off[r + 1]), views that are valid until clear(); null views with another verdict than MC_PARSE_OK
+        struct header_views { const char* bytes = nullptr; const std::uint64_t* off = nullptr; std::uint64_t records = 0; };
+        header_views headers() const
+        {
+            header_views h;
+            if (mc_batch_headers(ctx_, slot_, &h.bytes, &h.off, &h.records) != MC_OK) throw std::runtime_error(mc_last_error(ctx_));
+            return h;
+        }
         void clear() { mc_batch_clear(ctx_, slot_); res_ = mc_results{}; assigned_.clear(); kept_.clear(); verdicts_.clear(); lineOff_.clear(); pieceOff_.clear(); }   // query_batch.cuh:255-259
     private:
         friend class query_batch;
@@ -561,6 +595,14 @@ public:
     bool add_file_bytes(unsigned hostId, const char* bytes, std::size_t nbytes, bool pairs = false, std::uint64_t insertSizeMax = 0)
     {
         const int rc = mc_batch_add_file_bytes(ctx_, hostId, bytes, nbytes, pairs ? MC_PARSE_PAIRS : 0, insertSizeMax);
+        if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
+        return rc == MC_OK;
+    }
+    // the same for a range that lies in DEVICE memory already (any address; untouched until wait_for_results returns): one copy on the
+    // device instead of the upload, and the headers come back with the results -- host_data(hostId).headers() (mc_batch_add_device_bytes)
+    bool add_device_bytes(unsigned hostId, const void* deviceBytes, std::size_t nbytes, bool pairs = false, std::uint64_t insertSizeMax = 0)
+    {
+        const int rc = mc_batch_add_device_bytes(ctx_, hostId, deviceBytes, nbytes, pairs ? MC_PARSE_PAIRS : 0, insertSizeMax);
         if (rc < 0) throw std::runtime_error(mc_last_error(ctx_));
         return rc == MC_OK;
     }

@@ -151,7 +151,9 @@ def parse_scratch_bytes(nbytes: int) -> int:
     return int(lib().mc_parse_scratch_bytes(nbytes))
 
 
-PARSE_HOST, PARSE_PAIRS = 1, 2
+PARSE_HOST, PARSE_PAIRS, CUT_OPEN = 1, 2, 4
+INPUT_OK, INPUT_NOT_BGZF, INPUT_REFUSED, INPUT_TOO_LARGE, INPUT_NO_MEMORY, INPUT_EMPTY, INPUT_IRREGULAR, INPUT_RECORD_TOO_LARGE = range(8)
+input_batch_dtype = np.dtype([("offset", "<u8"), ("nbytes", "<u8"), ("records", "<u4"), ("queries", "<u4"), ("half_pair", "<u4"), ("too_big", "<u4")])
 PARSE_OK, PARSE_IRREGULAR, PARSE_OVERFLOW, PARSE_UNEQUAL = 0, 1, 2, 3
 
 
@@ -181,6 +183,16 @@ def bgzf_index(data, capacity=None):
         blocks = np.zeros(int(info[0]), dtype=bgzf_block_dtype)
         run(blocks)
     return blocks[:min(len(blocks), int(info[0]))], int(info[1]), int(info[2]), int(info[3])
+
+
+def parse_cut_scratch_bytes(nbytes: int) -> int:
+    """the workspace a device call of mc_parse_cut needs for a range of nbytes"""
+    return int(lib().mc_parse_cut_scratch_bytes(nbytes))
+
+
+def parse_headers_scratch_bytes(max_records: int) -> int:
+    """the workspace a device call of mc_parse_headers needs for outputs of max_records records"""
+    return int(lib().mc_parse_headers_scratch_bytes(max_records))
 
 
 def parse_mates_scratch_bytes(n1: int, n2: int, max_records: int) -> int:
@@ -402,6 +414,8 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_table_histogram", "mc_table_features", "mc_table_lookup",
            "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records",
            "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates",
+           "mc_parse_cut", "mc_parse_cut_scratch_bytes", "mc_parse_headers", "mc_parse_headers_scratch_bytes", "mc_batch_add_device_bytes", "mc_batch_headers",
+           "mc_input_open", "mc_input_batches", "mc_input_download", "mc_input_close",
            "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
            "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end",
            "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats",
@@ -500,6 +514,20 @@ def lib() -> C.CDLL:
         L.mc_parse_mates_scratch_bytes.restype = C.c_uint64
         L.mc_parse_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.POINTER(McParseOutput), C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_batch_add_file_mates.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64]
+        L.mc_parse_cut_scratch_bytes.argtypes = [C.c_uint64]
+        L.mc_parse_cut_scratch_bytes.restype = C.c_uint64
+        L.mc_parse_cut.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_parse_headers_scratch_bytes.argtypes = [C.c_uint32]
+        L.mc_parse_headers_scratch_bytes.restype = C.c_uint64
+        L.mc_parse_headers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_batch_add_device_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64]
+        L.mc_batch_headers.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.mc_input_open.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]
+        L.mc_input_batches.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.mc_input_download.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.mc_input_close.argtypes = [C.c_void_p]
+        L.mc_input_close.restype = None
         L.mc_merge_results_set_taxids.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.mc_merge_results_begin.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int32]
         L.mc_merge_results_reserve.argtypes = [C.c_void_p, C.c_uint64]
@@ -1029,7 +1057,7 @@ class Database:
         rc = self._check(lib().mc_batch_add_file_mates(self.h, slot, b1.ctypes.data if len(b1) else None, len(b1), b2.ctypes.data if len(b2) else None, len(b2), insert_max))
         return self._query_raw_slot(rc, lowest, slot)
 
-    def _query_raw_slot(self, rc: int, lowest: int, slot: int):
+    def _query_raw_slot(self, rc: int, lowest: int, slot: int, headers: bool = False):
         L = lib()
         if rc == MC_BATCH_FULL:
             raise McError("the byte range does not fit the slot's character capacity")
@@ -1047,9 +1075,111 @@ class Database:
                 hits = _view(res.hits, int(off[m]), loc_dtype)
                 allhits = [hits[int(off[i]):int(off[i + 1])].copy() for i in range(m)]
             records = self.batch_records(slot)
+            if headers:
+                records["headers"] = self.batch_headers(slot)
         finally:
             self._check(L.mc_batch_clear(self.h, slot))
         return cands, counts, allhits, records
+
+    # ---- batch borders of a FASTA / FASTQ range, the headers of a parsed one, slots that take device bytes -----------
+    def parse_cut_device(self, bytes_ptr: int, nbytes: int, records_per_batch: int, *, cuts_ptr: int, capacity: int, status_ptr: int, workspace_ptr: int,
+                         workspace_bytes: int, pairs: bool = False, open: bool = False, stream: int = 0):
+        """the batch borders of the range at bytes_ptr (device memory, ANY address): cuts [capacity] uint64, status [8] uint64 -- device memory;
+        workspace of parse_cut_scratch_bytes(nbytes); asynchronous on `stream` (mc_parse_cut).  status[4] is the verdict"""
+        flags = (PARSE_PAIRS if pairs else 0) | (CUT_OPEN if open else 0)
+        self._check(lib().mc_parse_cut(self.h, bytes_ptr or None, nbytes, records_per_batch, flags, cuts_ptr or None, capacity, status_ptr or None,
+                                       workspace_ptr or None, workspace_bytes, stream or None))
+
+    def parse_cut(self, data, records_per_batch: int, pairs: bool = False, open: bool = False, capacity=None):
+        """the same on host memory: data (bytes) -> dict(status uint64 [8] = whole, nb, consumed, record starts seen, verdict, offence, the
+        largest batch in bytes, half pair; and with the verdict PARSE_OK: cuts uint64 [nb + 1]).  A capacity that is left out is taken from a
+        first call's status (PARSE_OVERFLOW reports nb).  "raw": cuts as the last call left it, at its capacity."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        status = np.zeros(8, dtype=np.uint64)
+        flags = PARSE_HOST | (PARSE_PAIRS if pairs else 0) | (CUT_OPEN if open else 0)
+
+        def run(cap):
+            cuts = np.zeros(max(cap, 1), dtype=np.uint64)
+            self._check(lib().mc_parse_cut(self.h, buf.ctypes.data if len(buf) else None, len(buf), records_per_batch, flags, cuts.ctypes.data, cap,
+                                           status.ctypes.data, None, 0, None))
+            return cuts
+
+        cuts = run(1 if capacity is None else capacity)
+        if capacity is None and int(status[4]) == PARSE_OVERFLOW:
+            cuts = run(int(status[1]) + 1)
+        out = dict(status=status.copy(), raw=cuts)
+        if int(status[4]) == PARSE_OK:
+            out["cuts"] = cuts[:int(status[1]) + 1].copy()
+        return out
+
+    def parse_headers_device(self, bytes_ptr: int, nbytes: int, *, hdr_ptr: int, parse_status_ptr: int, max_records: int, out_ptr: int, out_capacity: int,
+                             out_off_ptr: int, status_ptr: int, workspace_ptr: int, workspace_bytes: int, stream: int = 0):
+        """packs the headers of the range at bytes_ptr that parse_device has cut (hdr, parse_status: what it left) into out, with out_off
+        [max_records + 1] uint64 and status [4] uint64 -- all device memory; workspace of parse_headers_scratch_bytes(max_records);
+        asynchronous on `stream`, behind the parse (mc_parse_headers).  status[2] is the verdict"""
+        self._check(lib().mc_parse_headers(self.h, bytes_ptr or None, nbytes, hdr_ptr or None, parse_status_ptr or None, max_records, 0, out_ptr or None,
+                                           out_capacity, out_off_ptr or None, status_ptr or None, workspace_ptr or None, workspace_bytes, stream or None))
+
+    def parse_headers(self, data, hdr, parse_status, *, max_records=None, out_capacity=None):
+        """the same on host memory: data (bytes), hdr [records, 2] uint32 and parse_status [8] uint64 as parse_records gives them -> dict(status
+        uint64 [4] = records, bytes needed, verdict, 0; and with the verdict PARSE_OK: out (bytes), out_off uint64 [records + 1]).  "raw":
+        (out, out_off) as the call left them, at their capacities."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        hdr = np.ascontiguousarray(hdr, dtype=np.uint32).reshape(-1, 2)
+        ps = np.ascontiguousarray(parse_status, dtype=np.uint64)
+        mr = len(hdr) if max_records is None else max_records
+        cap = len(buf) if out_capacity is None else out_capacity
+        out, off, status = np.zeros(max(cap, 1), dtype=np.uint8), np.zeros(mr + 1, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_parse_headers(self.h, buf.ctypes.data if len(buf) else None, len(buf), hdr.ctypes.data if mr else None, ps.ctypes.data, mr, PARSE_HOST,
+                                           out.ctypes.data if cap else None, cap, off.ctypes.data, status.ctypes.data, None, 0, None))
+        res = dict(status=status, raw=(out, off))
+        if int(status[2]) == PARSE_OK:
+            res.update(out=out[:int(status[1])].tobytes(), out_off=off[:int(status[0]) + 1].copy())
+        return res
+
+    def batch_headers(self, slot: int = 0):
+        """the headers of a slot that was filled with device bytes (mc_batch_headers, after the wait) -> [bytes] per record; None with another
+        verdict than PARSE_OK"""
+        text, off, n = C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self._check(lib().mc_batch_headers(self.h, slot, C.byref(text), C.byref(off), C.byref(n)))
+        if not off.value:
+            return None
+        o = _view(off.value, n.value + 1, np.dtype("<u8"))
+        total = int(o[n.value])
+        t = _view(text.value, total, np.dtype("u1")).tobytes()
+        return [t[int(o[r]):int(o[r + 1])] for r in range(n.value)]
+
+    def query_device_bytes(self, ptr: int, nbytes: int, pairs: bool = False, lowest: int = 0, insert_max: int = 0, slot: int = 0):
+        """one slot batch from a byte range of a FASTA / FASTQ file that lies in device memory at ptr (any address; mc_batch_add_device_bytes)
+        -> (cands, hit_counts, allhits, records) as query_file_bytes, records["headers"] being batch_headers().  The memory stays untouched
+        until this returns."""
+        rc = self._check(lib().mc_batch_add_device_bytes(self.h, slot, ptr or None, nbytes, PARSE_PAIRS if pairs else 0, insert_max))
+        return self._query_raw_slot(rc, lowest, slot, headers=True)
+
+    def resident_input(self, file_bytes, records_per_batch: int, pairs: bool = False, piece_bytes: int = 1 << 31, slot_bytes=None, max_resident_bytes: int = 1 << 62):
+        """a query file's bytes (plain or BGZF) made resident and cut into batches (mc_input_open) -> dict(info uint64 [8] = verdict, detail,
+        plain bytes, pieces, batches, records, inflated, second detail; handle (None where nothing is resident), ptr: the device address of
+        the plain bytes, nbytes, batches: input_batch_dtype rows).  close_input(handle) frees it."""
+        buf = np.frombuffer(bytes(file_bytes), dtype=np.uint8)
+        info, h = np.zeros(8, dtype=np.uint64), C.c_void_p()
+        self._check(lib().mc_input_open(self.h, buf.ctypes.data if len(buf) else None, len(buf), PARSE_PAIRS if pairs else 0, records_per_batch, piece_bytes,
+                                        self.cfg.slot_max_chars if slot_bytes is None else slot_bytes, max_resident_bytes, C.byref(h), info.ctypes.data))
+        out = dict(info=info, handle=h.value, ptr=0, nbytes=0, batches=np.zeros(0, dtype=input_batch_dtype))
+        if h.value:
+            rows, ptr, n = np.zeros(int(info[4]), dtype=input_batch_dtype), C.c_void_p(), C.c_uint64()
+            self._check(lib().mc_input_batches(h, rows.ctypes.data if len(rows) else None, len(rows), C.byref(ptr), C.byref(n)))
+            out.update(ptr=ptr.value or 0, nbytes=n.value, batches=rows)
+        return out
+
+    def download_input(self, handle: int, nbytes: int) -> bytes:
+        """the plain bytes of a resident file, copied back (mc_input_download)"""
+        buf = np.zeros(max(nbytes, 1), dtype=np.uint8)
+        self._check(lib().mc_input_download(handle, buf.ctypes.data, nbytes))
+        return buf[:nbytes].tobytes()
+
+    def close_input(self, handle):
+        if handle:
+            lib().mc_input_close(handle)
 
     def parse_stats(self):
         """-> [mc_parse_records calls, bytes handed over, records of the accepted ranges, ranges refused]"""

@@ -279,6 +279,7 @@ void mc_destroy(mc_ctx* ctx)
     free_evaluate_state(ctx);
     free_format_state(ctx);
     free_parse_state(ctx);
+    free_cut_state(ctx);
     free_merge_results_state(ctx);
     free_inflate_state(ctx);
     free_taxmap_state(ctx);
@@ -307,6 +308,8 @@ void mc_destroy(mc_ctx* ctx)
         if (s.dseq) (void)hipFree(s.dseq); if (s.dqinfo) (void)hipFree(s.dqinfo); if (s.dmaxwin) (void)hipFree(s.dmaxwin);
         for (void* p : {(void*)s.draw, s.dparseWs, s.dmatesWs, (void*)s.dhdr, (void*)s.dnames, (void*)s.dnameoff, (void*)s.dstatus}) if (p) (void)hipFree(p);
         if (s.hhdr) (void)hipHostFree(s.hhdr); if (s.hstatus) (void)hipHostFree(s.hstatus);
+        for (void* p : {s.dhdrWs, (void*)s.dhdrText, (void*)s.dhdrOff}) if (p) (void)hipFree(p);
+        if (s.hhdrText) (void)hipHostFree(s.hhdrText); if (s.hhdrOff) (void)hipHostFree(s.hhdrOff);
         if (s.hcands) (void)hipHostFree(s.hcands); if (s.hqstat) (void)hipHostFree(s.hqstat);
         if (s.hhitcounts) (void)hipHostFree(s.hhitcounts); if (s.hhitoff) (void)hipHostFree(s.hhitoff);
         if (s.hhits) (void)hipHostFree(s.hhits); if (s.done) (void)hipEventDestroy(s.done);
@@ -529,6 +532,19 @@ int mc_batch_add_file_bytes(mc_ctx* ctx, uint32_t slot, const char* bytes, uint6
     return MC_OK;
 }
 
+int mc_batch_add_device_bytes(mc_ctx* ctx, uint32_t slot, const void* dbytes, uint64_t nbytes, int flags, uint64_t insertMax)
+{
+    if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
+    if (!dbytes || nbytes == 0) return fail(ctx, MC_ERR_INVALID, "mc_batch_add_device_bytes: no bytes");
+    if (flags & ~MC_PARSE_PAIRS) return fail(ctx, MC_ERR_INVALID, "mc_batch_add_device_bytes: unknown flag");
+    Slot& S = ctx->slots[slot];
+    if (S.submitted) return fail(ctx, MC_ERR_STATE, "mc_batch_add_device_bytes: slot is in flight, call mc_batch_wait + mc_batch_clear");
+    if (S.nq || S.raw) return fail(ctx, MC_ERR_STATE, "mc_batch_add_device_bytes: the slot already holds reads");
+    if (nbytes > ctx->cfg.slot_max_chars) return MC_BATCH_FULL;
+    S.raw = true; S.rawDev = (const uint8_t*)dbytes; S.rawBytes = nbytes; S.rawBytes2 = 0; S.rawFlags = flags; S.rawInsertMax = insertMax;
+    return MC_OK;
+}
+
 int mc_batch_add_file_mates(mc_ctx* ctx, uint32_t slot, const char* bytes1, uint64_t n1, const char* bytes2, uint64_t n2, uint64_t insertMax)
 {
     if (!ctx || slot >= ctx->slots.size()) return MC_ERR_INVALID;
@@ -563,7 +579,16 @@ static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
     const uint64_t at2 = (S.rawBytes + 15) / 16 * 16;                     // (the second range on the device: behind the first, at a multiple of 16; draw has 16 bytes to spare)
     const uint64_t matesWs = 2 * mc_parse_scratch_bytes(ctx->cfg.slot_max_chars) + mc_parse_mates_scratch_bytes(1, 1, (uint32_t)(2 * nq));   // (enough for every split of a slot's characters)
     if (mates && !S.dmatesWs) HIP_TRY(ctx, hipMalloc(&S.dmatesWs, matesWs));
-    HIP_TRY(ctx, hipMemcpyAsync(S.draw, S.hseq, S.rawBytes, hipMemcpyHostToDevice, st));
+    const uint32_t hdrRows = (uint32_t)(2 * nq);                           // (rows of dhdr)
+    if (S.rawDev) {                                                        // (each on its own: a failed allocation is tried again by the next batch)
+        if (!S.dhdrWs) HIP_TRY(ctx, hipMalloc(&S.dhdrWs, mc_parse_headers_scratch_bytes(hdrRows)));
+        if (!S.dhdrText) HIP_TRY(ctx, hipMalloc((void**)&S.dhdrText, nc));
+        if (!S.dhdrOff) HIP_TRY(ctx, hipMalloc((void**)&S.dhdrOff, ((uint64_t)hdrRows + 1) * 8));
+        if (!S.hhdrText) HIP_TRY(ctx, hipHostMalloc((void**)&S.hhdrText, nc));   // (the headers are bytes of the range: the slot's character capacity holds them)
+        if (!S.hhdrOff) HIP_TRY(ctx, hipHostMalloc((void**)&S.hhdrOff, ((uint64_t)hdrRows + 1) * 8));
+    }
+    if (S.rawDev) HIP_TRY(ctx, hipMemcpyAsync(S.draw, S.rawDev, S.rawBytes, hipMemcpyDeviceToDevice, st));
+    else HIP_TRY(ctx, hipMemcpyAsync(S.draw, S.hseq, S.rawBytes, hipMemcpyHostToDevice, st));
     if (mates) HIP_TRY(ctx, hipMemcpyAsync(S.draw + at2, S.hseq + S.rawBytes, S.rawBytes2, hipMemcpyHostToDevice, st));
     mc_parse_output o{};
     o.hdr = S.dhdr; o.qinfo = S.dqinfo; o.seq = S.dseq; o.seq_capacity = nc; o.names = (char*)S.dnames; o.names_capacity = nc;
@@ -573,7 +598,9 @@ static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
         if (const int rc = mc_parse_mates(ctx, (const char*)S.draw, S.rawBytes, (const char*)S.draw + at2, S.rawBytes2, 0, S.rawInsertMax, &o, S.dmatesWs, matesWs, st)) return rc;
     } else
     if (const int rc = mc_parse_records(ctx, (const char*)S.draw, S.rawBytes, S.rawFlags, S.rawInsertMax, &o, S.dparseWs, mc_parse_scratch_bytes(ctx->cfg.slot_max_chars), st)) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S.hstatus, S.dstatus, 64, hipMemcpyDeviceToHost, st));
+    // (the headers' status: words 12 .. 15 of the slot's status, behind the 10 words that mc_parse_mates fills)
+    if (S.rawDev) { if (const int rc = mcamd::enqueue_parse_headers(ctx, S.draw, (uint32_t)S.rawBytes, S.dhdr, S.dstatus, o.max_records, S.dhdrText, nc, S.dhdrOff, S.dstatus + 12, S.dhdrWs, st)) return rc; }
+    HIP_TRY(ctx, hipMemcpyAsync(S.hstatus, S.dstatus, S.rawDev ? 128 : 64, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, traced_sync(st));
     uint64_t* status = S.hstatus;
     if (status[4] == MC_PARSE_OK && status[6] + 8 > ctx->cfg.slot_max_chars) status[4] = MC_PARSE_OVERFLOW;   // (a read the slot's loop would have refused)
@@ -583,6 +610,10 @@ static int raw_parse(mc_ctx* ctx, Slot& S, hipStream_t st)
     S.maxSingle = (uint32_t)std::min<uint64_t>(status[6], 0xFFFFFFFFull);   // (pairs: an upper bound of the half pair's length)
     HIP_TRY(ctx, hipMemcpyAsync(S.hhdr, S.dhdr, status[0] * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipMemcpyAsync(S.hqinfo, S.dqinfo, (size_t)S.nq * 16, hipMemcpyDeviceToHost, st));
+    if (S.rawDev && status[14] == MC_PARSE_OK) {
+        HIP_TRY(ctx, hipMemcpyAsync(S.hhdrOff, S.dhdrOff, (status[12] + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (status[13]) HIP_TRY(ctx, hipMemcpyAsync(S.hhdrText, S.dhdrText, status[13], hipMemcpyDeviceToHost, st));
+    }
     return MC_OK;
 }
 
@@ -607,6 +638,16 @@ int mc_batch_records(mc_ctx* ctx, uint32_t slot, mc_batch_record_info* out)
     out->verdict = (uint32_t)S.hstatus[4]; out->offence = S.hstatus[5];
     out->records = ok ? (uint32_t)S.hstatus[0] : 0; out->queries = ok ? (uint32_t)S.hstatus[1] : 0; out->half_pair = ok ? (uint32_t)S.hstatus[7] : 0;
     out->hdr = ok ? S.hhdr : nullptr; out->qinfo = ok ? S.hqinfo : nullptr;
+    return MC_OK;
+}
+
+int mc_batch_headers(mc_ctx* ctx, uint32_t slot, const char** bytes, const uint64_t** off, uint64_t* records)
+{
+    if (!ctx || slot >= ctx->slots.size() || !bytes || !off || !records) return MC_ERR_INVALID;
+    Slot& S = ctx->slots[slot];
+    if (!S.raw || !S.submitted || !S.rawDev || !S.hstatus) return fail(ctx, MC_ERR_STATE, "mc_batch_headers: the slot holds no submitted device range (mc_batch_add_device_bytes, mc_batch_submit, mc_batch_wait)");
+    const bool ok = S.hstatus[4] == MC_PARSE_OK && S.hstatus[14] == MC_PARSE_OK;
+    *bytes = ok ? S.hhdrText : nullptr; *off = ok ? S.hhdrOff : nullptr; *records = ok ? S.hstatus[12] : 0;
     return MC_OK;
 }
 
@@ -922,7 +963,7 @@ int mc_batch_clear(mc_ctx* ctx, uint32_t slot)
     } else if (S.submitted) (void)hipEventSynchronize(S.done);
     release_pipe(ctx, S);
     S.submitted = false; S.nq = 0; S.nchars = 0; S.maxSingle = 0;
-    S.raw = false; S.rawBytes = 0; S.rawBytes2 = 0;
+    S.raw = false; S.rawBytes = 0; S.rawBytes2 = 0; S.rawDev = nullptr;
     return MC_OK;
 }
 

@@ -99,6 +99,11 @@ struct Slot {
     uint64_t rawBytes2 = 0; void* dmatesWs = nullptr;
     uint8_t* draw = nullptr; void* dparseWs = nullptr; uint32_t* dhdr = nullptr; uint8_t* dnames = nullptr; uint64_t* dnameoff = nullptr; uint64_t* dstatus = nullptr;
     uint32_t* hhdr = nullptr; uint64_t* hstatus = nullptr;   // pinned: the headers' places in the range, mc_parse_records' status
+    // a raw range that lies in DEVICE memory already (mc_batch_add_device_bytes): one copy on the device into draw replaces the upload, and
+    // mc_parse_headers packs the headers behind the parse; they travel back into hhdrText / hhdrOff (made by the slot's first such batch)
+    const uint8_t* rawDev = nullptr;
+    void* dhdrWs = nullptr; uint8_t* dhdrText = nullptr; uint64_t* dhdrOff = nullptr;
+    char* hhdrText = nullptr; uint64_t* hhdrOff = nullptr;
     hipEvent_t done = nullptr;
     bool submitted = false;
     uint32_t submittedQueries = 0;
@@ -215,6 +220,13 @@ void free_format_state(mc_ctx* ctx);
 struct ParseState;
 void free_parse_state(mc_ctx* ctx);
 
+// parse_cut.hip: the staging of the MC_PARSE_HOST forms of mc_parse_cut and mc_parse_headers (made on first use), freed with the context
+struct CutState;
+void free_cut_state(mc_ctx* ctx);
+// ... and mc_parse_headers' device form for the slots (raw_parse): enqueued on st, nothing waited for
+int enqueue_parse_headers(mc_ctx* ctx, const uint8_t* dBytes, uint32_t nbytes, const uint32_t* hdr, const uint64_t* parseStatus, uint32_t maxRecords, uint8_t* out, uint64_t outCap,
+                          uint64_t* outOff, uint64_t* status, void* ws, hipStream_t st);
+
 // merge_results.hip: the taxid table, the store of merged candidate lists, the counters and the staging of mc_merge_results_* (made by
 // mc_merge_results_set_taxids), freed with the context
 struct MergeResultsState;
@@ -289,6 +301,9 @@ struct mc_ctx {
 
     std::mutex parseMtx;
     mcamd::ParseState* parse = nullptr;    // made by the first mc_parse_records that reaches the device
+
+    std::mutex cutMtx;
+    mcamd::CutState* cut = nullptr;        // made by the first MC_PARSE_HOST call of mc_parse_cut / mc_parse_headers
 
     mcamd::MergeResultsState* mergeResults = nullptr;   // made by mc_merge_results_set_taxids; its calls are ordered by the caller
 

@@ -415,6 +415,119 @@ struct InflateStep : DeviceStep {
     }
 };
 
+// ---- input (mc_input_*): a query file resident on the device, its batches cut there -----------------------------------
+// MCQ_INPUT_DEVICE=1.  The producer hands every input file to take(): the file is mapped, the library makes it resident (a plain file is
+// uploaded, a BGZF file inflated on the device), cuts it in pieces of at most MCQ_INPUT_DEVICE_PIECE bytes and gives the batches; the
+// workers feed them to their slots as device ranges (SlotStep::resident), and a file's buffer is freed when its last batch has been
+// cleared.  All resident input alive at once stays below MCQ_INPUT_DEVICE_MB (default 8192): the producer waits for earlier files'
+// batches instead.  A file that does not go resident takes the old path unchanged and is named with its reason; one that was inflated
+// on the device and then refused (irregular) is copied back once and handed to SeqFile as InflateStep hands its files over.
+struct ResidentFile { mc_input* in = nullptr; const char* dev = nullptr; uint64_t bytes = 0; std::atomic<size_t> left{0}; };
+
+struct InputStep : DeviceStep {
+    uint64_t files = 0, pieces = 0, batches = 0, bytes = 0, records = 0;
+    std::vector<std::string> leftFiles;      // the files left to the host, each with its reason
+    uint64_t capBytes = 0, pieceBytes = 0, slotBytes = 0; int flags = 0; uint32_t perBatch = 0;
+    std::mutex resMu; std::condition_variable resCv; uint64_t residentBytes = 0;   // (under resMu)
+    std::deque<std::unique_ptr<ResidentFile>> residents;                            // (the producer appends; addresses stay)
+
+    static uint64_t env_u64(const char* name, uint64_t dflt) { const char* v = std::getenv(name); return v && *v ? std::strtoull(v, nullptr, 10) : dflt; }
+    void open(const Session& S, const Options& o, bool merged, bool covMode, bool aligning)
+    {
+        const char* sw = std::getenv("MCQ_INPUT_DEVICE");
+        if (!sw || std::atoi(sw) == 0) return;
+        const bool selects = o.minReadLen > 0 || o.maxReadLen < std::numeric_limits<uint64_t>::max() || o.queryLimit < ((int64_t)1 << 62);
+        const char* first = o.pairing == Options::files ? "-pairfiles: a query's two reads lie in two files"
+                          : selects ? "length filters and -query-limit select the reads on the host"
+                          : aligning ? "-align needs the reads' characters on the host"
+                          : S.built ? "build+query" : nullptr;
+        off = shared_host_reason(S, merged, covMode, "-cov-percentile keeps the reads' headers beyond their batches", first);
+        if (!off.empty()) return;
+        ctx = S.ctx;
+        flags = o.pairing == Options::sequences ? MC_PARSE_PAIRS : 0;
+        perBatch = (uint32_t)(o.batchSize * (flags ? 2 : 1));
+        capBytes = env_u64("MCQ_INPUT_DEVICE_MB", 8192) << 20;
+        pieceBytes = std::max<uint64_t>(1, std::min<uint64_t>(env_u64("MCQ_INPUT_DEVICE_PIECE", 1ull << 31), 1ull << 31));
+        slotBytes = S.cfg.slot_max_chars;
+    }
+    bool leave(const std::string& fn, const std::string& why) { std::lock_guard<std::mutex> g(mtx); leftFiles.push_back(fn + ": " + why); return false; }
+
+    // true: the file is resident (rf, rows).  false: it takes the old path -- with `plain` filled where the device inflated it already
+    bool take(const std::string& fn, const std::atomic<bool>& stopped, ResidentFile*& rf, std::vector<mc_input_batch>& rows, std::vector<char>& plain)
+    {
+        const int fd = ::open(fn.c_str(), O_RDONLY);
+        struct stat st;
+        if (fd < 0 || fstat(fd, &st) != 0) { if (fd >= 0) ::close(fd); return false; }          // (SeqFile reports it)
+        struct Mapping { int fd; void* m; size_t n; ~Mapping() { if (m != MAP_FAILED) munmap(m, n); ::close(fd); } } map{fd, MAP_FAILED, (size_t)st.st_size};
+        if (map.n == 0) return leave(fn, "no bytes");
+        map.m = mmap(nullptr, map.n, PROT_READ, MAP_PRIVATE, fd, 0);
+        if (map.m == MAP_FAILED) return leave(fn, "cannot be mapped");
+        const unsigned char* B = (const unsigned char*)map.m;
+        uint64_t need = map.n;
+        if (map.n >= 2 && B[0] == 0x1f && B[1] == 0x8b) {
+            uint64_t bi[4] = {0, 0, 0, 0};
+            if (mc_bgzf_index(B, map.n, nullptr, 0, bi) != MC_OK) return leave(fn, mc_last_error(nullptr));
+            if (bi[2] != MC_BGZF_OK) return leave(fn, "plain gzip: not BGZF at byte " + std::to_string(bi[3]));
+            need = bi[1];
+        }
+        if (need > capBytes) return leave(fn, "larger than the cap of " + std::to_string(capBytes >> 20) + " MiB (MCQ_INPUT_DEVICE_MB)");
+        {   // the producer waits for earlier files' batches instead of exceeding the cap
+            std::unique_lock<std::mutex> l(resMu);
+            while (residentBytes && residentBytes + need > capBytes && !stopped) resCv.wait_for(l, std::chrono::milliseconds(20));
+            if (stopped) return false;
+        }
+        uint64_t info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        mc_input* in = nullptr;
+        if (mc_input_open(ctx, B, map.n, flags, perBatch, pieceBytes, slotBytes, capBytes, &in, info) != MC_OK) return leave(fn, mc_last_error(ctx));
+        if (info[0] != MC_INPUT_OK) {
+            if (in) {                                                     // inflated on the device, then refused: copied back once
+                plain.resize(info[2]);
+                if (mc_input_download(in, plain.data(), plain.size()) != MC_OK) plain.clear();
+                mc_input_close(in);
+            }
+            switch (info[0]) {
+            case MC_INPUT_NOT_BGZF: return leave(fn, "plain gzip: not BGZF at byte " + std::to_string(info[1]));
+            case MC_INPUT_REFUSED: return leave(fn, "the device refused block " + std::to_string(info[1]) + " (verdict " + std::to_string(info[6]) + ", reason " + std::to_string(info[7]) + ")");
+            case MC_INPUT_TOO_LARGE: return leave(fn, "larger than the cap of " + std::to_string(capBytes >> 20) + " MiB (MCQ_INPUT_DEVICE_MB)");
+            case MC_INPUT_NO_MEMORY: return leave(fn, "no device memory for " + std::to_string(info[1]) + " bytes");
+            case MC_INPUT_IRREGULAR: return leave(fn, "irregular at byte " + std::to_string(info[1]));
+            case MC_INPUT_RECORD_TOO_LARGE: return leave(fn, "a record does not fit the largest piece");
+            default: return leave(fn, "no bytes");
+            }
+        }
+        rows.resize(info[4]);
+        const void* dev = nullptr; uint64_t n = 0;
+        if (mc_input_batches(in, rows.data(), rows.size(), &dev, &n) != MC_OK || rows.empty()) { mc_input_close(in); return leave(fn, "no records"); }
+        residents.emplace_back(new ResidentFile);
+        rf = residents.back().get();
+        rf->in = in; rf->dev = (const char*)dev; rf->bytes = n; rf->left = rows.size();
+        { std::lock_guard<std::mutex> l(resMu); residentBytes += n; }
+        std::lock_guard<std::mutex> g(mtx);
+        ++files; pieces += info[3]; batches += rows.size(); bytes += n; records += info[5];
+        return true;
+    }
+    // a batch of rf has been cleared (or will never be submitted): the last one frees the file's buffer
+    void done(ResidentFile* rf)
+    {
+        if (rf->left.fetch_sub(1) != 1) return;
+        mc_input_close(rf->in);
+        rf->in = nullptr;
+        { std::lock_guard<std::mutex> l(resMu); residentBytes -= rf->bytes; }
+        resCv.notify_all();
+    }
+    ~InputStep() { for (auto& r : residents) if (r->in) mc_input_close(r->in); }   // (a job that failed: batches that were never taken)
+    void report(const Profile& P) const
+    {
+        if (!P.on) return;
+        if (ctx) {
+            std::cerr << "mcq profile: input resident on the device: " << files << " files, " << pieces << " pieces, " << batches << " batches, " << bytes << " bytes, " << records
+                      << " records, " << leftFiles.size() << " files left to the host";
+            for (size_t i = 0; i < leftFiles.size(); ++i) std::cerr << (i ? "; " : " (") << leftFiles[i];
+            std::cerr << (leftFiles.empty() ? "\n" : ")\n");
+        } else if (!off.empty()) std::cerr << "mcq: query input read on the host (" << off << ")\n";
+    }
+};
+
 // ---- merge (mc_merge_results_*): `mcq merge` hands its result files to the library -----------------------------------
 // MCQ_MERGE_DEVICE=1.  The host reads a file's leading comment block (results_head: its checks and errors, the column of the top hits),
 // the rest goes to mc_merge_results_add in ranges of at most 2^31 bytes cut at line starts; afterwards the lists, the header places and

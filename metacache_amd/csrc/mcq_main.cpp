@@ -546,10 +546,13 @@ struct Tally {
 };
 
 struct Deferred { uint64_t id; View header; std::vector<Cand> cands; size_t q; };   // (q: the query's place in its batch, BatchQueue::read)
+struct ResidentFile;
 struct Batch {
     size_t f1, f2; size_t qBeg, qEnd; uint64_t idBase; std::string prefix; const std::vector<uint64_t>* sel; bool halfLast;
     std::vector<Deferred> deferred;                                         // -cov-percentile: its reads' candidates
     std::vector<mc_candidate> carried;                                      // part groups: its reads' candidate lists from the groups so far
+    // MCQ_INPUT_DEVICE: the batch is a range of a file that is resident on the device (no SeqFile behind f1); records: what the cut counted
+    ResidentFile* res = nullptr; const char* dev = nullptr; uint64_t devBytes = 0; uint32_t devRecords = 0; bool tooBig = false;
 };
 struct Profile {                                                            // MCQ_PROFILE: phase times on stderr (development aid)
     const bool on = std::getenv("MCQ_PROFILE") != nullptr;
@@ -677,6 +680,7 @@ struct BatchQueue {
     const Options& o; const unsigned workers; const std::chrono::steady_clock::time_point t0;
     std::vector<std::unique_ptr<SeqFile>> files;
     const GzInflater* inflater = nullptr;                                   // MCQ_INFLATE_DEVICE: who takes a compressed query file before SeqFile's own loop
+    InputStep* input = nullptr;                                             // MCQ_INPUT_DEVICE: who makes a query file resident on the device before anything else looks at it
     std::vector<std::unique_ptr<std::vector<uint64_t>>> selections;
     std::deque<Batch> batches;                                              // grows at the back only: references stay valid
     std::mutex mu; std::condition_variable cv;
@@ -739,6 +743,30 @@ struct BatchQueue {
                 if (o.pairing == Options::files) prefix += " + " + o.infiles[fi + 1];
                 prefix += '\n';
                 size_t nq = 0, f1 = files.size(), f2 = files.size();
+                std::vector<char> inflated;                                      // MCQ_INPUT_DEVICE: the file's bytes where the device inflated it and then refused it
+                if (input && input->ctx) {
+                    ResidentFile* rf = nullptr;
+                    std::vector<mc_input_batch> rows;
+                    if (input->take(o.infiles[fi], stopped, rf, rows, inflated)) {
+                        files.emplace_back(nullptr);                             // (the file's place: its batches need no SeqFile)
+                        const size_t per = o.pairing == Options::sequences ? 2 : 1;
+                        size_t q = 0; uint64_t recs = 0;
+                        for (size_t i = 0; i < rows.size(); ++i) {
+                            Batch B{f1, f2, q, q + rows[i].queries, idOffset, i == 0 ? prefix : std::string(), nullptr, rows[i].half_pair != 0, {}, {}};
+                            B.res = rf; B.dev = rf->dev + rows[i].offset; B.devBytes = rows[i].nbytes; B.devRecords = rows[i].records; B.tooBig = rows[i].too_big != 0;
+                            { std::lock_guard<std::mutex> l(mu); batches.push_back(std::move(B)); }
+                            cv.notify_all();
+                            q += rows[i].queries; recs += rows[i].records;
+                        }
+                        size_t nread = q;
+                        if (per == 2 && q > 0 && (recs & 1u)) --nread;           // (the half pair did not count)
+                        idOffset += nread;
+                        continue;
+                    }
+                    if (stopped) break;
+                }
+                const GzInflater once = [&inflated](const std::string&, const unsigned char*, size_t, std::vector<char>& out, size_t& size) { out.swap(inflated); size = out.size(); return true; };
+                const GzInflater* const inflater = inflated.empty() ? this->inflater : &once;
                 try {
                     files.emplace_back(new SeqFile(o.infiles[fi], inflater));
                     SeqFile& F = *files.back();
@@ -985,6 +1013,52 @@ struct SlotStep {
     const bool prints = true;
     std::vector<Query> queries = {}; Records rec = {};
     ParseStep* parse = nullptr;                                             // MCQ_PARSE_DEVICE: the batch's byte range goes to the slot, the library cuts it
+    InputStep* input = nullptr;                                             // MCQ_INPUT_DEVICE: batches of resident files are device ranges already
+
+    // a batch of a resident file: mc_batch_add_device_bytes -> submit -> wait -> mc_batch_records + mc_batch_headers -> emit -> clear.  A record
+    // count that differs from the cut's is an error of the run, not a fall-back.  false: the job has failed
+    template <class Emit>
+    bool resident(Batch& B, Emit&& emit)
+    {
+        struct Done { InputStep* in; ResidentFile* r; ~Done() { in->done(r); } } done{input, B.res};   // (behind the clear: the range stays untouched until then)
+        if (B.tooBig) { std::cerr << "query batch is too small for a single read!\n"; return true; }    // database_query.hpp:103
+        const size_t per = o.pairing == Options::sequences ? 2 : 1;
+        const uint64_t tp0 = now_ns();
+        const int rc = mc_batch_add_device_bytes(ctx, slot, B.dev, B.devBytes, input->flags, o.insertMax);
+        if (rc != MC_OK) { Q.fail(rc == MC_BATCH_FULL ? "resident input: a batch exceeds the slot it was cut for" : mc_last_error(ctx)); return false; }
+        mc_results r;
+        mc_batch_record_info info;
+        const char* text = nullptr; const uint64_t* off = nullptr; uint64_t nheaders = 0;
+        const uint64_t tp1 = now_ns();
+        if (mc_batch_submit(ctx, slot, o.lowest) != MC_OK) { Q.fail(mc_last_error(ctx)); mc_batch_clear(ctx, slot); return false; }
+        const uint64_t tp2 = now_ns();
+        if (mc_batch_wait(ctx, slot, &r) != MC_OK || mc_batch_records(ctx, slot, &info) != MC_OK || mc_batch_headers(ctx, slot, &text, &off, &nheaders) != MC_OK) {
+            Q.fail(mc_last_error(ctx)); mc_batch_clear(ctx, slot); return false;
+        }
+        const uint64_t tp3 = now_ns();
+        if (info.verdict == MC_PARSE_OVERFLOW && B.qEnd - B.qBeg == 1) {      // one read (pair) beyond what a slot's kernels take
+            mc_batch_clear(ctx, slot);
+            std::cerr << "query batch is too small for a single read!\n";
+            return true;
+        }
+        if (info.verdict != MC_PARSE_OK || info.records != B.devRecords || r.num_queries != B.qEnd - B.qBeg || nheaders != info.records || !off) {
+            Q.fail("resident input: the device parse gives verdict " + std::to_string(info.verdict) + " and " + std::to_string(info.records) + " records, the cut " + std::to_string(B.devRecords));
+            mc_batch_clear(ctx, slot);
+            return false;
+        }
+        queries.clear();
+        for (size_t q = B.qBeg; q < B.qEnd; ++q) {
+            const size_t i = q - B.qBeg, rr = i * per;
+            const bool halfPair = B.halfLast && q + 1 == B.qEnd;
+            const View h{text + off[rr], (size_t)(off[rr + 1] - off[rr])};
+            const uint64_t l1 = info.qinfo[4 * i + 1], l2 = info.qinfo[4 * i + 3];
+            queries.push_back(Query{B.idBase + q + (halfPair ? 0 : 1), h, h.empty() || l1 == 0, l1 + l2, q});
+        }
+        emit(queries, r);
+        mc_batch_clear(ctx, slot);
+        if (P.on) { P.parse += tp1 - tp0; P.submit += tp2 - tp1; P.wait += tp3 - tp2; P.classify += now_ns() - tp3; }
+        return true;
+    }
 
     // the whole batch through mc_batch_add_file_bytes.  true: it was emitted; false: nothing was, and the host loop takes it (or the job has failed)
     template <class Emit>
@@ -1034,6 +1108,7 @@ struct SlotStep {
     template <class Emit>
     bool operator()(Batch& B, Emit&& emit)
     {
+        if (B.res) return resident(B, emit);
         if (parse && parse->ctx) {
             if (parsed_on_device(B, emit)) return true;
             if (Q.failed()) return false;
@@ -1458,10 +1533,12 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
     std::vector<Tally> tallies(S.workers);
     TargetCache targets(o.showErrors);                                      // -align: the target records of this job
     const bool aligning = o.align && !merged;
-    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep; ParseStep parseStep; InflateStep inflateStep;   // the hand-offs to the library (mcq_device_steps.h)
+    HitsStep hitsStep; EvalStep evalStep; FormatStep fmtStep; ParseStep parseStep; InflateStep inflateStep; InputStep inputStep;   // the hand-offs to the library (mcq_device_steps.h)
     inflateStep.open(S, merged != nullptr);
     if (inflateStep.ctx) Q.inflater = &inflateStep.inflater;
     parseStep.open(S, o, merged != nullptr);
+    inputStep.open(S, o, merged != nullptr, covMode, aligning);
+    if (inputStep.ctx) Q.input = &inputStep;
     hitsStep.open(S, o, merged != nullptr, covMode);
     evalStep.open(S, o, merged != nullptr, covMode);
     fmtStep.open(S, o, merged != nullptr, covMode, aligning);
@@ -1485,7 +1562,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
             Q.rewind();
             run_workers(S.workers, [&](unsigned w) { worker(w, SetStep{S, o, Q, g > 0, g + 1 == groups}); });
         }
-    } else run_workers(S.workers, [&](unsigned w) { worker(w, SlotStep{S, o, Q, P, S.replica(w % S.replication), w / S.replication, true, {}, {}, &parseStep}); });
+    } else run_workers(S.workers, [&](unsigned w) { worker(w, SlotStep{S, o, Q, P, S.replica(w % S.replication), w / S.replication, true, {}, {}, &parseStep, &inputStep}); });
     Q.finish();
     W.close();
     Q.rethrow();
@@ -1511,6 +1588,7 @@ void run_job(Session& S, Options o, const std::vector<std::string>& infiles, con
         std::cerr << "mcq profile: index " << Q.tIndexed * 1e3 << " ms, total " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() * 1e3
                   << " ms; summed over " << S.workers << " workers: parse+add " << P.parse / 1e6 << " ms, submit " << P.submit / 1e6 << " ms, wait "
                   << P.wait / 1e6 << " ms, classify+format " << P.classify / 1e6 << " ms; batches " << Q.batches.size() << "\n";
+    inputStep.report(P);
     inflateStep.report(P);
     parseStep.report(P);
     fmtStep.report(P);

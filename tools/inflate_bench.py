@@ -35,9 +35,11 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 PAYLOAD = 65280
 
 
-def piece(args):
-    """records [first, first + n) as BGZF members -> (compressed bytes, plain length, plain crc32, members)"""
-    import inflate_cases
+RECORD = 15 + 150 + 1 + 2 + 150 + 1                                  # bytes of one generated read
+
+
+def plain_records(args):
+    """records [first, first + n) of the seeded file, as FASTQ text (tools/input_device_bench.py measures on the same file)"""
     first, n, seed = args
     rng = np.random.default_rng([seed, first])
     L = 150
@@ -54,7 +56,13 @@ def piece(args):
     a[:, at + L + 2] = 10
     a[:, at + L + 3:at + 2 * L + 3] = np.frombuffer(b"FFFFFFFFFFFF:::,,#", dtype=np.uint8)[rng.integers(0, 18, (n, L), dtype=np.uint8)]
     a[:, -1] = 10
-    plain = a.tobytes()
+    return a.tobytes()
+
+
+def piece(args):
+    """records [first, first + n) as BGZF members -> (compressed bytes, plain length, plain crc32, members)"""
+    import inflate_cases
+    plain = plain_records(args)
     members = [inflate_cases.bgzf_block(plain[i:i + PAYLOAD], 6) for i in range(0, len(plain), PAYLOAD)]
     return b"".join(members), len(plain), zlib.crc32(plain), len(members)
 
