@@ -758,7 +758,7 @@ int mc_format_stats(mc_ctx* ctx, uint64_t stats[5]);
  *   errors and statistics as mc_format_mappings; MC_ERR_INVALID also for extra without extra_off and for out overlapping either.
  * mc_format_matches_stats: stats[0..4] = mc_format_matches calls that had reads, reads handed over, runs printed, bytes written, runs whose
  *   tgt lay beyond the table -- the last three counted by the calls whose pieces fitted.  Waits for the context's own streams.
- * mc_timing_get names: "matches_lengths" (matches_kernel<false> + format_scan_kernel), "matches_write" (matches_kernel<true>). */
+ * mc_timing_get names: "matches_lengths" (matches_kernel<false> + tile_scan_kernel), "matches_write" (matches_kernel<true>). */
 #define MC_MATCHES_WINDOWS    2      /* the window form: text '/' window ':' length ',' */
 int mc_format_matches_set_text(mc_ctx* ctx, const char* bytes, const uint64_t* offsets, uint64_t count);
 int mc_format_matches(mc_ctx* ctx, const mc_location* hits, const uint64_t* hit_off, uint32_t num_queries, int flags, char* out, uint64_t out_capacity,
@@ -1213,7 +1213,7 @@ int mc_table_lookup(mc_ctx* ctx, const uint32_t* keys, uint64_t n, uint64_t* off
  * "hash_cands_256", "hash_cands_512", "hash_cands_1024", the filtered path -- compact location store: "gw_filter_count" (gw_filter_count_kernel; "gw_filter" with
  * the tuning switch "gw_fuse" 0), "gw_filter2", "gw_compact" (+ the ordering of the stream filter's reads), "gw_filter_stream_fine" (the sixteen-wave instance), "gw_filter_stream" (+ the second gw_compact), "gw_count" (gw_count_kernel<9>), "gw_count_512" (<10>), "gw_count_1024" (<11>); 8-byte store:
  * "big_filter", "big_filter_2", "big_count", "big_count_2" --, "gw_sort", "gw_sorted_cands", "query_wave", "scan", "sort_candidates";
- * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect); "taxon_evaluate" (taxon_evaluate_kernel, mc_evaluate_assignments); "format_lengths" (format_lengths_kernel + format_scan_kernel) and "format_write" (format_write_kernel, mc_format_mappings).  Returns accumulated milliseconds and launch counts since the last reset. */
+ * Mode K: "mask_features", "gather_lists", "pack_numbers", "owner_entries", "decode_union"; "sketch_probe" (sketch_probe_lane_kernel: instead of "sketch_lane" + "probe_cands" where the two are one kernel, see "lane_fusion"); "cands_from_hits" (mc_candidates_from_hits); "coverage_count_kernel" (inside mc_coverage_counts); "target_hits_sort" (block sort + merge passes) and "target_hits_bounds" (inside mc_target_hits_collect); "taxon_evaluate" (taxon_evaluate_kernel, mc_evaluate_assignments); "format_lengths" (format_lengths_kernel + tile_scan_kernel) and "format_write" (format_write_kernel, mc_format_mappings).  Returns accumulated milliseconds and launch counts since the last reset. */
 int mc_timing_enable(mc_ctx* ctx, int on);
 int mc_timing_reset(mc_ctx* ctx);
 int mc_timing_get(mc_ctx* ctx, const char* kernel, double* total_ms, uint64_t* launches);

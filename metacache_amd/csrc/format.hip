@@ -6,7 +6,7 @@
 //   1. format_lengths_kernel: one lane per read walks the read's pieces and adds up their lengths (exact: digit counts, string lengths
 //      from the tables) into line_off[i]; block b owns TILE b, a run of consecutive reads, and leaves the tile's sum in the workspace
 //      behind line_off (MC_FORMAT_SCRATCH entries, so at most that many tiles: a tile grows with the batch instead of the grid).
-//   2. format_scan_kernel: ONE block turns the tile sums into tile offsets and stores the total in line_off[n].
+//   2. tile_scan_kernel (block_scan.h): ONE block turns the tile sums into tile offsets and stores the total in line_off[n].
 //   3. format_write_kernel: block b scans its tile's lengths into line_off (chunks of 256 reads, a running offset), and -- unless the
 //      total exceeds the capacity -- renders the chunk's lines.  Consecutive reads' lines are consecutive in `out`, so a chunk owns one
 //      byte range [c0, c1): the block walks it in WINDOWS of kStage bytes that begin at multiples of 16, every lane stores the part of
@@ -19,6 +19,7 @@
 // mc_format_matches_* (the -allhits column, show_matches, printing.cpp:315-365): a section of its own below, a wave or the block per read.
 // Plain HIP C++; no inline assembly.
 #include "rows_common.h"
+#include "block_scan.h"
 
 #include <algorithm>
 #include <atomic>
@@ -33,6 +34,7 @@ constexpr int kAllFlags = MC_FORMAT_HOST | MC_FORMAT_QUERY_IDS | MC_FORMAT_TRUTH
 constexpr uint32_t kCtrLines = 0, kCtrBytes = 1, kCtrOutOfTable = 2, kCtrMatchRuns = 3, kCtrMatchBytes = 4, kCtrMatchBeyond = 5, kCounters = 6;
 static_assert(sizeof(mc_candidate) == 16 && sizeof(mc_assignment) == 8, "ABI sizes");
 static_assert(kStage % 16 == 0, "windows begin at multiples of 16");
+static_assert(kBlock == kScanBlock, "the scans of block_scan.h are for blocks of 256 threads");
 
 struct Text {                            // one table of strings on the device: string k = bytes[off[k] .. off[k + 1])
     const uint8_t* bytes; const uint64_t* off; uint32_t count;
@@ -182,24 +184,6 @@ __device__ __forceinline__ void walk_line(const FmtArgs& a, uint64_t i, Sink<WRI
     s.ch('\n');
 }
 
-// exclusive scan of one 64-bit value per thread of the block; total = the block's sum.  sc: kBlock entries of LDS.
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* sc, uint64_t& total)
-{
-    const uint32_t t = threadIdx.x;
-    sc[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kBlock; d <<= 1) {
-        const uint64_t add = t >= d ? sc[t - d] : 0;
-        __syncthreads();
-        sc[t] += add;
-        __syncthreads();
-    }
-    total = sc[kBlock - 1];
-    const uint64_t incl = sc[t];
-    __syncthreads();
-    return incl - v;
-}
-
 template <bool EXTRA>
 __global__ __launch_bounds__(kBlock) void format_lengths_kernel(FmtArgs a)
 {
@@ -216,22 +200,6 @@ __global__ __launch_bounds__(kBlock) void format_lengths_kernel(FmtArgs a)
     uint64_t total;
     (void)block_excl_scan(mine, sc, total);
     if (threadIdx.x == 0) a.lineOff[(uint64_t)a.n + 1 + blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kBlock) void format_scan_kernel(FmtArgs a)
-{
-    __shared__ uint64_t sc[kBlock];
-    uint64_t* sums = a.lineOff + (uint64_t)a.n + 1;
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < a.tiles; base += kBlock) {                    // (the same trips for every lane)
-        const uint32_t j = base + threadIdx.x;
-        const uint64_t v = j < a.tiles ? sums[j] : 0;
-        uint64_t total;
-        const uint64_t excl = block_excl_scan(v, sc, total);
-        if (j < a.tiles) sums[j] = carry + excl;
-        carry += total;
-    }
-    if (threadIdx.x == 0) a.lineOff[a.n] = carry;
 }
 
 // EXTRA: the chunk's pieces of the extra column go into the window by the whole block -- a piece of any length costs every lane the same.
@@ -316,7 +284,7 @@ __global__ __launch_bounds__(kBlock) void format_write_kernel(FmtArgs a)
 // ---- the all-hits column (mc_format_matches): a read's location list, run-length encoded -------------------------------------------
 // show_matches (printing.cpp:315-365): a RUN is a maximal stretch of consecutive equal entries; it prints text '/' window ':' length ','
 // (MC_MATCHES_WINDOWS) or text ':' length ','.  The same three launches as the lines -- lengths, the scan of the tile sums
-// (format_scan_kernel itself), write -- but inside a read the work is a wave's, or for a list of more than kMatchBlockList entries the
+// (tile_scan_kernel itself), write -- but inside a read the work is a wave's, or for a list of more than kMatchBlockList entries the
 // block's: the lanes stride over the list in tiles of 64 (the block: of 256); the lane whose entry ENDS a run owns the run; it finds the
 // run's first entry from the ballots of the tile's run heads (head k = end k - 1), or, where the tile has none in front of it, from the
 // carry: the entries of the open run in front of the tile; a wave scan of the runs' byte lengths (the block: + the waves' sums through LDS)
@@ -592,7 +560,7 @@ void launch_lengths(mc_ctx* ctx, const FmtArgs& a, hipStream_t st)
     ScopedTimer timer(ctx, "format_lengths", st);
     if (a.extra) hipLaunchKernelGGL(format_lengths_kernel<true>, dim3(a.tiles), dim3(kBlock), 0, st, a);
     else hipLaunchKernelGGL(format_lengths_kernel<false>, dim3(a.tiles), dim3(kBlock), 0, st, a);
-    hipLaunchKernelGGL(format_scan_kernel, dim3(1), dim3(kBlock), 0, st, a);
+    hipLaunchKernelGGL(tile_scan_kernel<uint64_t>, dim3(1), dim3(kBlock), 0, st, a.lineOff + (uint64_t)a.n + 1, a.tiles, a.lineOff + a.n);
 }
 void launch_write(mc_ctx* ctx, const FmtArgs& a, hipStream_t st)
 {
@@ -616,9 +584,7 @@ void launch_match_lengths(mc_ctx* ctx, const MatchArgs& a, hipStream_t st)
 {
     ScopedTimer timer(ctx, "matches_lengths", st);
     hipLaunchKernelGGL(matches_kernel<false>, dim3(a.tiles), dim3(kBlock), 0, st, a);
-    FmtArgs scan{};
-    scan.lineOff = a.pieceOff; scan.n = a.n; scan.tiles = a.tiles;
-    hipLaunchKernelGGL(format_scan_kernel, dim3(1), dim3(kBlock), 0, st, scan);
+    hipLaunchKernelGGL(tile_scan_kernel<uint64_t>, dim3(1), dim3(kBlock), 0, st, a.pieceOff + (uint64_t)a.n + 1, a.tiles, a.pieceOff + a.n);
 }
 void launch_match_write(mc_ctx* ctx, const MatchArgs& a, hipStream_t st)
 {

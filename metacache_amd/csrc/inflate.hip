@@ -412,8 +412,8 @@ struct InflateState {                    // what the context keeps for mc_inflat
     unsigned long long* dCounters = nullptr;   // bytes out of accepted calls, calls refused
     std::atomic<uint64_t> calls{0}, bytesIn{0};
     std::mutex stageMtx;                 // MC_INFLATE_HOST callers take turns at the staging buffers
-    DevBuf stageIn, stageRows, stageOut, stageStatus;
-    uint64_t* hStatus = nullptr;         // pinned [4]
+    DevBuf stageIn, stageRows, stageOut;
+    StatusStage status;                  // [4]
 };
 
 void free_inflate_state(mc_ctx* ctx)
@@ -421,8 +421,8 @@ void free_inflate_state(mc_ctx* ctx)
     if (!ctx->inflate) return;
     InflateState& S = *ctx->inflate;
     if (S.dCounters) (void)hipFree(S.dCounters);
-    if (S.hStatus) (void)hipHostFree(S.hStatus);
-    for (DevBuf* b : {&S.stageIn, &S.stageRows, &S.stageOut, &S.stageStatus})
+    free_status_stage(S.status);
+    for (DevBuf* b : {&S.stageIn, &S.stageRows, &S.stageOut})
         if (b->p) (void)hipFree(b->p);
     delete ctx->inflate;
     ctx->inflate = nullptr;
@@ -442,8 +442,7 @@ int ensure_inflate_state(mc_ctx* ctx, InflateState** out)
         HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, kCounterPairBytes));
         HIP_TRY(ctx, hipMemset(S.dCounters, 0, kCounterPairBytes));
     }
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 32));
-    return MC_OK;
+    return make_status_stage(ctx, S.status, 4);
 }
 
 // the device form: three launches, nothing waited for
@@ -504,8 +503,7 @@ int mc_inflate_blocks(mc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const 
     std::lock_guard<std::mutex> lock(S->stageMtx);
     const uint64_t pieceIn = ctx->inflateStageBytes ? ctx->inflateStageBytes : kDefaultStageBytes, pieceOut = 4 * pieceIn;
     std::vector<mc_bgzf_block> rows;
-    uint64_t covered = 0;
-    if ((rc = grow(ctx, S->stageStatus, 32)) != MC_OK) return rc;
+    uint64_t covered = 0, piece[4];                                              // piece: the status of one piece
     for (uint64_t i = 0; i < num_blocks;) {
         const uint64_t inBase = blocks[i].in_off & ~15ull, outBase = blocks[i].out_off;
         uint64_t j = i, inEnd = inBase, outEnd = outBase;
@@ -523,12 +521,11 @@ int mc_inflate_blocks(mc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const 
         if (inSpan) HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes + inBase, inSpan, hipMemcpyHostToDevice, st));
         HIP_TRY(ctx, hipMemcpyAsync(S->stageRows.p, rows.data(), rows.size() * sizeof(mc_bgzf_block), hipMemcpyHostToDevice, st));
         if ((rc = enqueue_inflate(ctx, *S, (const uint8_t*)S->stageIn.p, inSpan, (const mc_bgzf_block*)S->stageRows.p, rows.size(), (uint8_t*)S->stageOut.p, cap,
-                                  (uint64_t*)S->stageStatus.p, st)) != MC_OK) return rc;
-        HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, S->stageStatus.p, 32, hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        covered = std::max(covered, outBase + S->hStatus[3]);
-        if (S->hStatus[0] != MC_INFLATE_OK) {
-            status[0] = S->hStatus[0]; status[1] = i + S->hStatus[1]; status[2] = S->hStatus[2]; status[3] = covered;
+                                  (uint64_t*)S->status.dev.p, st)) != MC_OK) return rc;
+        if ((rc = read_status(ctx, S->status, 4, piece, st)) != MC_OK) return rc;
+        covered = std::max(covered, outBase + piece[3]);
+        if (piece[0] != MC_INFLATE_OK) {
+            status[0] = piece[0]; status[1] = i + piece[1]; status[2] = piece[2]; status[3] = covered;
             return MC_OK;
         }
         // back: one copy per run of slices that touch (an indexed file is one run)

@@ -18,7 +18,7 @@
 // atomic decides a value of the lists, the header places or status.  This is built to be right, not yet to be fast (7i).
 // merge_vote_kernel (mc_merge_results_classify) is one lane per query over the store, the taxon table rank-major as classify.hip reads
 // the lineages.  Plain HIP C++; no inline assembly.
-#include "rows_common.h"
+#include "parse_scan.h"
 
 #include <atomic>
 #include <cmath>
@@ -26,10 +26,11 @@
 #include <numeric>
 
 using namespace mcamd;
+using namespace mcamd::parsek;
 
 namespace {
 
-constexpr uint32_t kBlock = 256, kTile = kBlock * 16, kNone = 0xFFFFFFFFu, kMaxBlocks = 2048;
+constexpr uint32_t kMaxBlocks = 2048;
 constexpr uint32_t kMaxCandidates = 32, kBins = MC_NUM_RANKS + 1;
 constexpr uint64_t kMaxCapacity = 0xFFFFFFFFull;         // a query is id - 1 with id <= 2^32 - 1
 constexpr uint64_t kScratchBytes = 256;
@@ -51,39 +52,12 @@ struct MergeArgs {
     int32_t mergeBelow;
 };
 
-__device__ __forceinline__ uint32_t byte_at(const MergeArgs& a, uint32_t p) { return p < a.n ? (uint32_t)a.B[p] : (uint32_t)'\n'; }
-__device__ __forceinline__ bool is_digit(uint32_t c) { return c - '0' < 10u; }
-__device__ __forceinline__ bool is_refused(uint32_t c) { return c == '\r' || c == '\v' || c == '\f' || c == 0; }   // (a NUL ends the host's C string)
-
-// bit k: byte p0 + k of the range is a line start (position 0 or the byte behind a '\n')
-__device__ __forceinline__ uint32_t line_starts(const MergeArgs& a, uint32_t p0)
-{
-    if (p0 >= a.n) return 0;
-    const uint32_t cnt = min(16u, a.n - p0);
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (cnt == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.B + p0);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16; ++k) if (k < cnt) w[k >> 2] |= (uint32_t)a.B[p0 + k] << ((k & 3u) * 8u);
-    }
-    uint32_t prev = p0 ? (uint32_t)a.B[p0 - 1] : (uint32_t)'\n', mask = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) {
-        if (k >= cnt) continue;
-        if (prev == '\n') mask |= 1u << k;
-        prev = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
-    }
-    return mask;
-}
-
 // clause 1 of the line rule: the digits at the line start -> the query
 __device__ __forceinline__ bool parse_id(const MergeArgs& a, uint32_t& p, uint32_t& q)
 {
     uint64_t id = 0;
     uint32_t digits = 0;
-    for (uint32_t c; is_digit(c = byte_at(a, p)); ++p) { id = min(id * 10 + (c - '0'), 1ull << 40); ++digits; }
+    for (uint32_t c; is_digit(c = byte_at(a.B, a.n, p)); ++p) { id = min(id * 10 + (c - '0'), 1ull << 40); ++digits; }
     if (!digits || id > 0xFFFFFFFFull) return false;
     q = id ? (uint32_t)id - 1 : 0u;
     return true;
@@ -93,7 +67,7 @@ __device__ __forceinline__ bool parse_id(const MergeArgs& a, uint32_t& p, uint32
 __device__ __forceinline__ bool skip_past(const MergeArgs& a, uint32_t& p, uint32_t stop)
 {
     for (;; ++p) {
-        const uint32_t c = byte_at(a, p);
+        const uint32_t c = byte_at(a.B, a.n, p);
         if (c == stop) { ++p; return true; }
         if (c == '\n' || is_refused(c)) return false;
     }
@@ -106,9 +80,9 @@ __device__ __forceinline__ bool parse_head(const MergeArgs& a, uint32_t s, uint3
     if (!parse_id(a, p, q)) return false;
     if (!skip_past(a, p, '|')) return false;
     uint32_t c;
-    while ((c = byte_at(a, p)) == ' ' || c == '\t') ++p;
+    while ((c = byte_at(a.B, a.n, p)) == ' ' || c == '\t') ++p;
     hdrOff = p;
-    for (; (c = byte_at(a, p)) != ' ' && c != '\t' && c != '\n'; ++p) if (c == '|' || is_refused(c)) return false;
+    for (; (c = byte_at(a.B, a.n, p)) != ' ' && c != '\t' && c != '\n'; ++p) if (c == '|' || is_refused(c)) return false;
     hdrLen = p - hdrOff;
     if (!hdrLen) return false;
     for (uint32_t k = 1; k < a.tophitsColumn; ++k) if (!skip_past(a, p, '|')) return false;
@@ -121,27 +95,27 @@ __device__ __forceinline__ bool parse_head(const MergeArgs& a, uint32_t s, uint3
 template <class Sink>
 __device__ __forceinline__ bool parse_list(const MergeArgs& a, uint32_t p, Sink&& sink)
 {
-    uint32_t c = byte_at(a, p);
+    uint32_t c = byte_at(a.B, a.n, p);
     if (c != '\t' && c != '\n') {
         for (;;) {
             const bool neg = c == '-';
             if (neg) ++p;
             int64_t taxid = 0;
             uint32_t digits = 0;
-            for (; is_digit(c = byte_at(a, p)); ++p) { if (++digits > 18) return false; taxid = taxid * 10 + (int64_t)(c - '0'); }
+            for (; is_digit(c = byte_at(a.B, a.n, p)); ++p) { if (++digits > 18) return false; taxid = taxid * 10 + (int64_t)(c - '0'); }
             if (!digits || c != ':') return false;
             ++p;
             uint64_t hits = 0;
             digits = 0;
-            for (; is_digit(c = byte_at(a, p)); ++p) { if (++digits > 10) return false; hits = hits * 10 + (c - '0'); }
+            for (; is_digit(c = byte_at(a.B, a.n, p)); ++p) { if (++digits > 10) return false; hits = hits * 10 + (c - '0'); }
             if (!digits || hits == 0 || hits > 0xFFFFFFFFull) return false;
             sink(neg ? -taxid : taxid, (uint32_t)hits);
             if (c == '\t' || c == '\n') break;
             if (c != ',') return false;
-            c = byte_at(a, ++p);
+            c = byte_at(a.B, a.n, ++p);
         }
     }
-    for (; (c = byte_at(a, p)) != '\n'; ++p) if (is_refused(c)) return false;
+    for (; (c = byte_at(a.B, a.n, p)) != '\n'; ++p) if (is_refused(c)) return false;
     return true;
 }
 
@@ -185,16 +159,15 @@ __global__ __launch_bounds__(kBlock) void merge_validate_kernel(MergeArgs a)
 {
     const uint32_t p0 = blockIdx.x * kTile + threadIdx.x * 16u;
     uint32_t lines = 0, comments = 0, offenceInv = 0, maxQ1 = 0;
-    for (uint32_t m = line_starts(a, p0); m; m &= m - 1) {
-        const uint32_t s = p0 + (uint32_t)__ffs((int)m) - 1u;
-        if (a.B[s] == '#') { ++comments; continue; }
+    for_each_line_start(a.B, a.n, p0, [&](uint32_t s) {
+        if (a.B[s] == '#') { ++comments; return; }
         ++lines;
         uint32_t q = 0, hdrOff, hdrLen, listAt;
         const bool ok = parse_head(a, s, q, hdrOff, hdrLen, listAt) && parse_list(a, listAt, [](int64_t, uint32_t) {});
-        if (!ok) { offenceInv = max(offenceInv, kNone - s); continue; }
+        if (!ok) { offenceInv = max(offenceInv, kNone - s); return; }
         maxQ1 = max(maxQ1, q + 1);
         if (q < a.capacity) atomicMin(&a.owner[q], s);
-    }
+    });
     lines = wave_sum_u32(lines); comments = wave_sum_u32(comments); offenceInv = wave_max_u32(offenceInv); maxQ1 = wave_max_u32(maxQ1);
     if ((threadIdx.x & 63u) == 0) {                            // (sums and maxima: the same whatever the order)
         if (lines) atomicAdd(&a.ws[wLines], lines);
@@ -208,13 +181,12 @@ __global__ __launch_bounds__(kBlock) void merge_dups_kernel(MergeArgs a)
 {
     const uint32_t p0 = blockIdx.x * kTile + threadIdx.x * 16u;
     uint32_t offenceInv = 0;
-    for (uint32_t m = line_starts(a, p0); m; m &= m - 1) {
-        const uint32_t s = p0 + (uint32_t)__ffs((int)m) - 1u;
-        if (a.B[s] == '#') continue;
+    for_each_line_start(a.B, a.n, p0, [&](uint32_t s) {
+        if (a.B[s] == '#') return;
         uint32_t p = s, q = 0;
-        if (!parse_id(a, p, q) || q >= a.capacity) continue;
+        if (!parse_id(a, p, q) || q >= a.capacity) return;
         if (a.owner[q] != s || (a.cont && a.epoch[q] == a.fileSeq)) offenceInv = max(offenceInv, kNone - s);
-    }
+    });
     offenceInv = wave_max_u32(offenceInv);
     if ((threadIdx.x & 63u) == 0 && offenceInv) atomicMax(&a.ws[wOffenceInv], offenceInv);
 }
@@ -253,17 +225,16 @@ __global__ __launch_bounds__(kBlock) void merge_fold_kernel(MergeArgs a)
     const uint32_t p0 = blockIdx.x * kTile + threadIdx.x * 16u;
     const bool fold = a.ws[wVerdict] == MC_MERGE_OK;
     uint32_t entries = 0, unknown = 0;
-    for (uint32_t m = line_starts(a, p0); m; m &= m - 1) {
-        const uint32_t s = p0 + (uint32_t)__ffs((int)m) - 1u;
-        if (a.B[s] == '#') continue;
+    for_each_line_start(a.B, a.n, p0, [&](uint32_t s) {
+        if (a.B[s] == '#') return;
         uint32_t q = 0;
         if (!fold) {                                           // nothing changes but the claims of pass 1 are given back
             uint32_t p = s;
             if (parse_id(a, p, q) && q < a.capacity) a.owner[q] = kNone;
-            continue;
+            return;
         }
         uint32_t hdrOff = 0, hdrLen = 0, listAt = 0;
-        if (!parse_head(a, s, q, hdrOff, hdrLen, listAt) || q >= a.capacity) continue;   // (cannot happen with the verdict OK)
+        if (!parse_head(a, s, q, hdrOff, hdrLen, listAt) || q >= a.capacity) return;     // (cannot happen with the verdict OK)
         a.owner[q] = kNone;
         a.epoch[q] = a.fileSeq;
         uint32_t* h = a.hdr + 3ull * q;
@@ -275,7 +246,7 @@ __global__ __launch_bounds__(kBlock) void merge_fold_kernel(MergeArgs a)
             ++entries;
             insert_candidate(L, a.maxCand, make_uint2(x, hits), a.mergeBelow);
         });
-    }
+    });
     entries = wave_sum_u32(entries); unknown = wave_sum_u32(unknown);
     if ((threadIdx.x & 63u) == 0) {                            // (sums: the same whatever the order)
         if (entries) { atomicAdd((unsigned long long*)&a.status[3], (unsigned long long)entries); atomicAdd(&a.counters[cEntries], (unsigned long long)entries); }
@@ -343,8 +314,6 @@ __global__ __launch_bounds__(kBlock) void merge_vote_kernel(MergeVoteArgs a)
     }
 }
 
-uint32_t tiles_of(uint64_t nbytes) { return (uint32_t)((nbytes + kTile - 1) / kTile); }
-
 }  // namespace
 
 namespace mcamd {
@@ -363,8 +332,8 @@ struct MergeResultsState {               // what the context keeps for mc_merge_
     bool begun = false;
     unsigned long long* dCounters = nullptr;
     uint64_t calls = 0, bytes = 0;
-    DevBuf stageIn, stageWs, stageStatus, stageOut;
-    uint64_t* hStatus = nullptr;         // pinned [8]
+    DevBuf stageIn, stageWs, stageOut;
+    StatusStage status;                  // [8]
 };
 
 void free_merge_results_state(mc_ctx* ctx)
@@ -372,9 +341,9 @@ void free_merge_results_state(mc_ctx* ctx)
     if (!ctx->mergeResults) return;
     MergeResultsState& S = *ctx->mergeResults;
     for (void* p : {(void*)S.dIds, (void*)S.dRows, (void*)S.dLin, (void*)S.dRank, (void*)S.dLists, (void*)S.dHdr, (void*)S.dOwner, (void*)S.dEpoch, (void*)S.dCount,
-                    (void*)S.dCounters, S.stageIn.p, S.stageWs.p, S.stageStatus.p, S.stageOut.p})
+                    (void*)S.dCounters, S.stageIn.p, S.stageWs.p, S.stageOut.p})
         if (p) (void)hipFree(p);
-    if (S.hStatus) (void)hipHostFree(S.hStatus);
+    free_status_stage(S.status);
     delete ctx->mergeResults;
     ctx->mergeResults = nullptr;
 }
@@ -396,8 +365,7 @@ int ensure_merge_state(mc_ctx* ctx, MergeResultsState** out)
         HIP_TRY(ctx, hipMalloc((void**)&S.dCount, 8));
         HIP_TRY(ctx, hipMemset(S.dCount, 0, 8));
     }
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 64));
-    return MC_OK;
+    return make_status_stage(ctx, S.status, 8);
 }
 
 void free_store(MergeResultsState& S)
@@ -581,13 +549,9 @@ int mc_merge_results_add(mc_ctx* ctx, const char* bytes, uint64_t nbytes, uint32
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
     if (!host) return enqueue_add(ctx, *S, (const uint8_t*)bytes, (uint32_t)nbytes, tophitsColumn, fileLines, cont, status, workspace, st);
-    if ((rc = grow(ctx, S->stageIn, (nbytes + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, kScratchBytes)) != MC_OK || (rc = grow(ctx, S->stageStatus, 64)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes, nbytes, hipMemcpyHostToDevice, st));
-    if ((rc = enqueue_add(ctx, *S, (const uint8_t*)S->stageIn.p, (uint32_t)nbytes, tophitsColumn, fileLines, cont, (uint64_t*)S->stageStatus.p, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, S->stageStatus.p, 64, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(status, S->hStatus, 64);
-    return MC_OK;
+    if ((rc = grow(ctx, S->stageWs, kScratchBytes)) != MC_OK || (rc = stage_bytes(ctx, S->stageIn, bytes, nbytes, st)) != MC_OK) return rc;
+    if ((rc = enqueue_add(ctx, *S, (const uint8_t*)S->stageIn.p, (uint32_t)nbytes, tophitsColumn, fileLines, cont, (uint64_t*)S->status.dev.p, S->stageWs.p, st)) != MC_OK) return rc;
+    return read_status(ctx, S->status, 8, status, st);
 }
 
 int mc_merge_results_lists(mc_ctx* ctx, uint64_t first, uint64_t count, int flags, mc_taxon_candidate* lists, uint32_t* headerPlace, uint64_t* numQueries, void* streamv)

@@ -44,28 +44,7 @@ struct ParseArgs {
 
 __device__ __forceinline__ uint32_t* arr(const ParseArgs& a, uint32_t which) { return a.ws + kHead + (uint64_t)which * a.tiles; }
 
-// ---- a thread's 16 bytes ------------------------------------------------------------------------------------------------------------
-struct Chunk { uint32_t w[4]; uint32_t p0, cnt, prev, next; };     // cnt bytes from p0 on; the byte in front of them and the one behind ('\n' where the range ends)
-
-__device__ __forceinline__ Chunk load_chunk(const ParseArgs& a, uint32_t p0)
-{
-    Chunk c;
-    c.p0 = p0;
-    c.cnt = p0 < a.n ? min(16u, a.n - p0) : 0u;
-    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
-    if (c.cnt == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.B + p0);
-        c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16; ++k) if (k < c.cnt) c.w[k >> 2] |= (uint32_t)a.B[p0 + k] << ((k & 3u) * 8u);
-    }
-    c.prev = (p0 > 0 && c.cnt) ? a.B[p0 - 1] : (uint32_t)'\n';
-    c.next = (c.cnt == 16 && p0 + 16u < a.n) ? a.B[p0 + 16u] : (uint32_t)'\n';
-    return c;
-}
-#define CHUNK_BYTE(c, k) (((c).w[(k) >> 2] >> (((k) & 3u) * 8u)) & 0xFFu)
-
+// ---- a thread's 16 bytes: the Chunk of parse_scan.h with shift 0 (g: the position of its first byte, hi: how many of them the range holds)
 // layer 1, which needs nothing in front of it: line starts, the last line start + 1, the last blank + 1 (0: none)
 __device__ __forceinline__ void chunk_lines(const Chunk& c, uint32_t& lines, uint32_t& lastLine, uint32_t& lastBlank)
 {
@@ -73,8 +52,8 @@ __device__ __forceinline__ void chunk_lines(const Chunk& c, uint32_t& lines, uin
     uint32_t prev = c.prev;
 #pragma unroll
     for (uint32_t k = 0; k < 16; ++k) {
-        if (k >= c.cnt) continue;
-        const uint32_t p = c.p0 + k, ch = CHUNK_BYTE(c, k);
+        if (k >= c.hi) continue;
+        const uint32_t p = c.g + k, ch = CHUNK_BYTE(c, k);
         if (p == 0 || prev == '\n') { ++lines; lastLine = p + 1; }
         if (ch == ' ') lastBlank = p + 1;
         prev = ch;
@@ -143,9 +122,9 @@ __device__ __forceinline__ void walk(const ParseArgs& a, const Chunk& c, bool fa
     uint32_t prev = c.prev;
 #pragma unroll
     for (uint32_t k = 0; k < 16; ++k) {
-        if (k >= c.cnt) continue;
-        const uint32_t p = c.p0 + k, ch = CHUNK_BYTE(c, k);
-        const uint32_t nx = k == 15 ? c.next : (k + 1 < c.cnt ? CHUNK_BYTE(c, (k + 1) & 15u) : (uint32_t)'\n');
+        if (k >= c.hi) continue;
+        const uint32_t p = c.g + k, ch = CHUNK_BYTE(c, k);
+        const uint32_t nx = k == 15 ? c.next : (k + 1 < c.hi ? CHUNK_BYTE(c, (k + 1) & 15u) : (uint32_t)'\n');
         if (p == 0 || prev == '\n') {
             ++s.lines; s.lastLine = p + 1;
             bool bad;
@@ -223,7 +202,7 @@ __device__ __forceinline__ void layer2(const ParseArgs& a, const Chunk& c, bool 
 __global__ __launch_bounds__(kBlock) void parse_lines_kernel(ParseArgs a)
 {
     __shared__ uint32_t lds[3 * kWaves];
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     uint32_t sv[1], mv[2], st[1], mt[2];
     chunk_lines(c, sv[0], mv[0], mv[1]);
     block_excl_scan<1, 2>(sv, mv, st, mt, lds);
@@ -234,7 +213,7 @@ __global__ __launch_bounds__(kBlock) void parse_classify_kernel(ParseArgs a)
 {
     __shared__ uint32_t lds[8 * kWaves];
     const bool fastq = a.B[0] == '@';
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     State s;
     layer1(a, c, s, lds);
     Tally t = empty_tally();
@@ -267,7 +246,7 @@ __global__ __launch_bounds__(kBlock) void parse_pads_kernel(ParseArgs a)
     __shared__ uint32_t lds[8 * kWaves];
     if (a.ws[hOffence] != kNone) return;
     const bool fastq = a.B[0] == '@';
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     State s;
     layer1(a, c, s, lds);
     layer2(a, c, fastq, s, lds);
@@ -284,7 +263,7 @@ __global__ __launch_bounds__(kBlock) void parse_write_kernel(ParseArgs a)
     __shared__ uint32_t lds[8 * kWaves];
     if (a.ws[hVerdict] != MC_PARSE_OK) return;
     const bool fastq = a.B[0] == '@';
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     State s;
     layer1(a, c, s, lds);
     layer2(a, c, fastq, s, lds);
@@ -392,8 +371,6 @@ __global__ __launch_bounds__(kBlock) void parse_scan_kernel(ParseArgs a)
     }
 }
 
-uint32_t tiles_of(uint64_t nbytes) { return (uint32_t)((nbytes + kTile - 1) / kTile); }
-
 // ---- mates: TWO ranges, query q = record q of the first + record q of the second (mc_parse_mates) --------------------------------------
 // Each range is classified on its own by the layers above (lines -> scan<1> -> classify -> scan<2>, no pairing), in a workspace of its
 // own.  A mate's place in seq depends on the lengths of all earlier records of BOTH ranges, which no prefix over one range's bytes
@@ -460,7 +437,7 @@ __global__ __launch_bounds__(kBlock) void mates_lengths_kernel(MatesArgs m)
     const uint32_t soFar = mates_so_far(m);
     if (soFar == MC_PARSE_IRREGULAR || soFar == MC_PARSE_UNEQUAL) return;
     const bool fastq = a.B[0] == '@';
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     State s;
     layer1(a, c, s, lds);
     layer2(a, c, fastq, s, lds);
@@ -561,7 +538,7 @@ __global__ __launch_bounds__(kBlock) void mates_write_kernel(MatesArgs m)
     const ParseArgs& a = m.f[blockIdx.y];
     if (blockIdx.x >= a.tiles || m.m[mVerdict] != MC_PARSE_OK) return;
     const bool fastq = a.B[0] == '@';
-    const Chunk c = load_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.B, a.n, 0, blockIdx.x * kTile + threadIdx.x * 16u);
     State s;
     layer1(a, c, s, lds);
     layer2(a, c, fastq, s, lds);
@@ -580,8 +557,8 @@ struct ParseState {                      // what the context keeps for mc_parse_
     unsigned long long* dCounters = nullptr;   // records parsed, ranges refused
     std::atomic<uint64_t> calls{0}, bytes{0};
     std::mutex stageMtx;                 // MC_PARSE_HOST callers take turns at the staging buffers
-    DevBuf stageIn, stageWs, stageHdr, stageQinfo, stageSeq, stageNames, stageNameOff, stageMaxWin, stageStatus;
-    uint64_t* hStatus = nullptr;         // pinned [16]: mc_parse_records reads 8 words, mc_parse_mates 10
+    DevBuf stageIn, stageWs, stageHdr, stageQinfo, stageSeq, stageNames, stageNameOff, stageMaxWin;
+    StatusStage status;                  // [16]: mc_parse_records reads 8 words, mc_parse_mates 10
 };
 
 void free_parse_state(mc_ctx* ctx)
@@ -589,8 +566,8 @@ void free_parse_state(mc_ctx* ctx)
     if (!ctx->parse) return;
     ParseState& S = *ctx->parse;
     if (S.dCounters) (void)hipFree(S.dCounters);
-    if (S.hStatus) (void)hipHostFree(S.hStatus);
-    for (DevBuf* b : {&S.stageIn, &S.stageWs, &S.stageHdr, &S.stageQinfo, &S.stageSeq, &S.stageNames, &S.stageNameOff, &S.stageMaxWin, &S.stageStatus})
+    free_status_stage(S.status);
+    for (DevBuf* b : {&S.stageIn, &S.stageWs, &S.stageHdr, &S.stageQinfo, &S.stageSeq, &S.stageNames, &S.stageNameOff, &S.stageMaxWin})
         if (b->p) (void)hipFree(b->p);
     delete ctx->parse;
     ctx->parse = nullptr;
@@ -610,8 +587,7 @@ int ensure_parse_state(mc_ctx* ctx, ParseState** out)
         HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, 16));
         HIP_TRY(ctx, hipMemset(S.dCounters, 0, 16));
     }
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 128));
-    return MC_OK;
+    return make_status_stage(ctx, S.status, 16);
 }
 
 // the device form: five byte passes, three scans, nothing waited for
@@ -731,19 +707,16 @@ int mc_parse_records(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags,
     // host arrays: through the staging buffers, one caller at a time; outputs leave the device only with the verdict MC_PARSE_OK
     std::lock_guard<std::mutex> lock(S->stageMtx);
     const uint64_t mr = out->max_records;
-    if ((rc = grow(ctx, S->stageIn, (nbytes + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, mc_parse_scratch_bytes(nbytes))) != MC_OK ||
+    if ((rc = grow(ctx, S->stageWs, mc_parse_scratch_bytes(nbytes))) != MC_OK ||
         (rc = grow(ctx, S->stageHdr, std::max<uint64_t>(mr * 8, 16))) != MC_OK || (rc = grow(ctx, S->stageQinfo, std::max<uint64_t>(mr * 16, 16))) != MC_OK ||
         (rc = grow(ctx, S->stageSeq, std::max<uint64_t>(out->seq_capacity, 16))) != MC_OK || (rc = grow(ctx, S->stageNames, std::max<uint64_t>(out->names_capacity, 16))) != MC_OK ||
         (rc = grow(ctx, S->stageNameOff, (mr + 1) * 8)) != MC_OK || (rc = grow(ctx, S->stageMaxWin, std::max<uint64_t>(mr * 4, 16))) != MC_OK ||
-        (rc = grow(ctx, S->stageStatus, 64)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes, nbytes, hipMemcpyHostToDevice, st));
+        (rc = stage_bytes(ctx, S->stageIn, bytes, nbytes, st)) != MC_OK) return rc;
     mc_parse_output d = *out;
     d.hdr = (uint32_t*)S->stageHdr.p; d.qinfo = (uint32_t*)S->stageQinfo.p; d.seq = (uint8_t*)S->stageSeq.p; d.names = (char*)S->stageNames.p;
-    d.name_off = (uint64_t*)S->stageNameOff.p; d.max_win = (uint32_t*)S->stageMaxWin.p; d.status = (uint64_t*)S->stageStatus.p;
+    d.name_off = (uint64_t*)S->stageNameOff.p; d.max_win = (uint32_t*)S->stageMaxWin.p; d.status = (uint64_t*)S->status.dev.p;
     if ((rc = enqueue_parse(ctx, *S, (const uint8_t*)S->stageIn.p, n, flags & ~MC_PARSE_HOST, insert_size_max, d, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, d.status, 64, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(out->status, S->hStatus, 64);
+    if ((rc = read_status(ctx, S->status, 8, out->status, st)) != MC_OK) return rc;
     if (out->status[4] != MC_PARSE_OK) return MC_OK;
     const uint64_t recs = out->status[0], queries = out->status[1];
     if (recs) HIP_TRY(ctx, hipMemcpyAsync(out->hdr, d.hdr, recs * 8, hipMemcpyDeviceToHost, st));
@@ -801,18 +774,15 @@ int mc_parse_mates(mc_ctx* ctx, const char* bytes1, uint64_t n1, const char* byt
     if ((rc = grow(ctx, S->stageIn, at2 + (n2 + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, wsNeed)) != MC_OK ||
         (rc = grow(ctx, S->stageHdr, std::max<uint64_t>(mr * 8, 16))) != MC_OK || (rc = grow(ctx, S->stageQinfo, std::max<uint64_t>(mr * 16, 16))) != MC_OK ||
         (rc = grow(ctx, S->stageSeq, std::max<uint64_t>(out->seq_capacity, 16))) != MC_OK || (rc = grow(ctx, S->stageNames, std::max<uint64_t>(out->names_capacity, 16))) != MC_OK ||
-        (rc = grow(ctx, S->stageNameOff, (mr + 1) * 8)) != MC_OK || (rc = grow(ctx, S->stageMaxWin, std::max<uint64_t>(mr * 4, 16))) != MC_OK ||
-        (rc = grow(ctx, S->stageStatus, 128)) != MC_OK) return rc;
+        (rc = grow(ctx, S->stageNameOff, (mr + 1) * 8)) != MC_OK || (rc = grow(ctx, S->stageMaxWin, std::max<uint64_t>(mr * 4, 16))) != MC_OK) return rc;
     uint8_t* in = (uint8_t*)S->stageIn.p;
     HIP_TRY(ctx, hipMemcpyAsync(in, bytes1, n1, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(in + at2, bytes2, n2, hipMemcpyHostToDevice, st));
     mc_parse_output d = *out;
     d.hdr = (uint32_t*)S->stageHdr.p; d.qinfo = (uint32_t*)S->stageQinfo.p; d.seq = (uint8_t*)S->stageSeq.p; d.names = (char*)S->stageNames.p;
-    d.name_off = (uint64_t*)S->stageNameOff.p; d.max_win = (uint32_t*)S->stageMaxWin.p; d.status = (uint64_t*)S->stageStatus.p;
+    d.name_off = (uint64_t*)S->stageNameOff.p; d.max_win = (uint32_t*)S->stageMaxWin.p; d.status = (uint64_t*)S->status.dev.p;
     if ((rc = enqueue_mates(ctx, *S, in, (uint32_t)n1, in + at2, (uint32_t)n2, insert_size_max, d, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, d.status, 80, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(out->status, S->hStatus, 80);
+    if ((rc = read_status(ctx, S->status, 10, out->status, st)) != MC_OK) return rc;
     if (out->status[4] != MC_PARSE_OK) return MC_OK;
     const uint64_t recs = out->status[0], queries = out->status[1];
     HIP_TRY(ctx, hipMemcpyAsync(out->hdr, d.hdr, recs * 8, hipMemcpyDeviceToHost, st));

@@ -37,40 +37,19 @@ struct CutArgs {
     uint32_t n, shift, tiles, R, pairs, open, spanBlocks;
 };
 
-__host__ __device__ __forceinline__ uint32_t cut_tiles_of(uint64_t nbytes, uint32_t shift) { return (uint32_t)((nbytes + shift + kTile - 1) / kTile); }
 __host__ __device__ __forceinline__ uint32_t span_blocks_of(uint64_t cuts) { return (uint32_t)((cuts + kSpan - 1) / kSpan); }
 __device__ __forceinline__ uint32_t* arr(const CutArgs& a, uint32_t which) { return a.ws + kHead + (uint64_t)which * a.tiles; }
 __device__ __forceinline__ uint32_t* spans(const CutArgs& a) { return a.ws + kHead + (uint64_t)kArrays * a.tiles; }
 
-// ---- a thread's 16 bytes of A: bytes k in [lo, hi) are positions g + k - shift of the range ------------------------------------------------
-struct CutChunk { uint32_t w[4]; uint32_t g, lo, hi, prev, next; };  // prev / next: the byte in front of position g + lo - shift, the one behind g + 15 - shift ('\n' outside the range)
-
-__device__ __forceinline__ CutChunk load_cut_chunk(const CutArgs& a, uint32_t g)
-{
-    CutChunk c;
-    const uint32_t end = a.n + a.shift;                                          // (n <= 2^31, shift < 16)
-    c.g = g;
-    c.lo = g < a.shift ? a.shift - g : 0u;
-    c.hi = g < end ? min(16u, end - g) : 0u;
-    c.w[0] = c.w[1] = c.w[2] = c.w[3] = 0;
-    c.prev = c.next = (uint32_t)'\n';
-    if (c.lo >= c.hi) { c.lo = c.hi = 0; return c; }
-    const uint4 v = *reinterpret_cast<const uint4*>(a.A + g);                    // (an aligned 16 bytes that hold a byte of the range: inside its pages)
-    c.w[0] = v.x; c.w[1] = v.y; c.w[2] = v.z; c.w[3] = v.w;
-    if (g + c.lo > a.shift) c.prev = a.A[g + c.lo - 1];
-    if (c.hi == 16 && g + 16u < end) c.next = a.A[g + 16u];
-    return c;
-}
-#define CUT_BYTE(c, k) (((c).w[(k) >> 2] >> (((k) & 3u) * 8u)) & 0xFFu)
-
-__device__ __forceinline__ uint32_t chunk_line_starts(const CutArgs& a, const CutChunk& c)
+// ---- a thread's 16 bytes of A: the Chunk of parse_scan.h with the range's shift ------------------------------------------------------------
+__device__ __forceinline__ uint32_t chunk_line_starts(const CutArgs& a, const Chunk& c)
 {
     uint32_t lines = 0, prev = c.prev;
 #pragma unroll
     for (uint32_t k = 0; k < 16; ++k) {
         if (k < c.lo || k >= c.hi) continue;
         if (c.g + k == a.shift || prev == '\n') ++lines;
-        prev = CUT_BYTE(c, k);
+        prev = CHUNK_BYTE(c, k);
     }
     return lines;
 }
@@ -80,14 +59,14 @@ struct CutTally { uint32_t recs, offence, last, second; };                      
 // the one walk over a thread's bytes: the line starts and record starts of the record rule and, with JUDGE, its offences (a range whose
 // verdict is known needs none).  lines: line starts in front.
 template <bool JUDGE, class OnRecord>
-__device__ __forceinline__ void walk_cut(const CutArgs& a, const CutChunk& c, bool fastq, uint32_t lines, CutTally& t, OnRecord on_record)
+__device__ __forceinline__ void walk_cut(const CutArgs& a, const Chunk& c, bool fastq, uint32_t lines, CutTally& t, OnRecord on_record)
 {
     uint32_t prev = c.prev;
 #pragma unroll
     for (uint32_t k = 0; k < 16; ++k) {
         if (k < c.lo || k >= c.hi) continue;
-        const uint32_t p = c.g + k - a.shift, ch = CUT_BYTE(c, k);
-        const uint32_t nx = k == 15 ? c.next : (k + 1 < c.hi ? CUT_BYTE(c, (k + 1) & 15u) : (uint32_t)'\n');
+        const uint32_t p = c.g + k - a.shift, ch = CHUNK_BYTE(c, k);
+        const uint32_t nx = k == 15 ? c.next : (k + 1 < c.hi ? CHUNK_BYTE(c, (k + 1) & 15u) : (uint32_t)'\n');
         if (p == 0 || prev == '\n') {
             bool rec, bad;
             if (fastq) {
@@ -106,7 +85,7 @@ __device__ __forceinline__ void walk_cut(const CutArgs& a, const CutChunk& c, bo
 struct NoRecord { __device__ __forceinline__ void operator()(uint32_t, uint32_t) const {} };
 
 // line starts in front of the thread (the tile's own come from cut_scan_kernel<1>)
-__device__ __forceinline__ uint32_t lines_in_front(const CutArgs& a, const CutChunk& c, uint32_t* lds)
+__device__ __forceinline__ uint32_t lines_in_front(const CutArgs& a, const Chunk& c, uint32_t* lds)
 {
     uint32_t sv[1] = {chunk_line_starts(a, c)}, m0[1] = {0}, st[1], mt[1];
     block_excl_scan<1, 1>(sv, m0, st, mt, lds);
@@ -116,7 +95,7 @@ __device__ __forceinline__ uint32_t lines_in_front(const CutArgs& a, const CutCh
 __global__ __launch_bounds__(kBlock) void cut_lines_kernel(CutArgs a)
 {
     __shared__ uint32_t lds[2 * kWaves];
-    const CutChunk c = load_cut_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.A, a.n, a.shift, blockIdx.x * kTile + threadIdx.x * 16u);
     uint32_t sv[1] = {chunk_line_starts(a, c)}, m0[1] = {0}, st[1], mt[1];
     block_excl_scan<1, 1>(sv, m0, st, mt, lds);
     if (threadIdx.x == 0) arr(a, aLines)[blockIdx.x] = st[0];
@@ -126,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void cut_classify_kernel(CutArgs a)
 {
     __shared__ uint32_t lds[2 * kWaves];
     const bool fastq = a.A[a.shift] == '@';
-    const CutChunk c = load_cut_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.A, a.n, a.shift, blockIdx.x * kTile + threadIdx.x * 16u);
     const uint32_t lines = lines_in_front(a, c, lds);
     CutTally t{0, kNone, 0, 0};
     walk_cut<true>(a, c, fastq, lines, t, NoRecord{});
@@ -218,7 +197,7 @@ __global__ __launch_bounds__(kBlock) void cut_select_kernel(CutArgs a)
     __shared__ uint32_t lds[2 * kWaves];
     if (a.ws[hVerdict] != MC_PARSE_OK) return;
     const bool fastq = a.A[a.shift] == '@';
-    const CutChunk c = load_cut_chunk(a, blockIdx.x * kTile + threadIdx.x * 16u);
+    const Chunk c = load_chunk(a.A, a.n, a.shift, blockIdx.x * kTile + threadIdx.x * 16u);
     const uint32_t lines = lines_in_front(a, c, lds);
     CutTally t{0, kNone, 0, 0};
     walk_cut<false>(a, c, fastq, lines, t, NoRecord{});                     // (the verdict is MC_PARSE_OK: only the record starts are counted)
@@ -347,16 +326,16 @@ namespace mcamd {
 
 struct CutState {                        // what the context keeps for the MC_PARSE_HOST forms of mc_parse_cut and mc_parse_headers
     std::mutex stageMtx;                 // callers take turns at the staging buffers
-    DevBuf stageIn, stageWs, stageCuts, stageStatus, stageHdr, stageOut, stageOff;
-    uint64_t* hStatus = nullptr;         // pinned [8]
+    DevBuf stageIn, stageWs, stageCuts, stageHdr, stageOut, stageOff;
+    StatusStage status;                  // [16]: mc_parse_cut reads 8 words; mc_parse_headers keeps the parse's 8 in front of its own 4
 };
 
 void free_cut_state(mc_ctx* ctx)
 {
     if (!ctx->cut) return;
     CutState& S = *ctx->cut;
-    if (S.hStatus) (void)hipHostFree(S.hStatus);
-    for (DevBuf* b : {&S.stageIn, &S.stageWs, &S.stageCuts, &S.stageStatus, &S.stageHdr, &S.stageOut, &S.stageOff})
+    free_status_stage(S.status);
+    for (DevBuf* b : {&S.stageIn, &S.stageWs, &S.stageCuts, &S.stageHdr, &S.stageOut, &S.stageOff})
         if (b->p) (void)hipFree(b->p);
     delete ctx->cut;
     ctx->cut = nullptr;
@@ -372,8 +351,7 @@ int ensure_cut_state(mc_ctx* ctx, CutState** out)
     if (!ctx->cut) ctx->cut = new CutState;
     CutState& S = *ctx->cut;
     *out = &S;
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 64));
-    return MC_OK;
+    return make_status_stage(ctx, S.status, 16);
 }
 
 // the device form: two byte passes and their scans, the selection, the spans; nothing waited for
@@ -382,7 +360,7 @@ int enqueue_cut(mc_ctx* ctx, const uint8_t* dBytes, uint32_t n, uint32_t R, int 
     CutArgs a{};
     a.shift = (uint32_t)((uintptr_t)dBytes & 15u);
     a.A = dBytes - a.shift; a.ws = (uint32_t*)ws; a.cuts = cuts; a.status = status; a.capacity = capacity;
-    a.n = n; a.tiles = cut_tiles_of(n, a.shift); a.R = R;
+    a.n = n; a.tiles = tiles_of((uint64_t)n + a.shift); a.R = R;
     a.pairs = (flags & MC_PARSE_PAIRS) ? 1u : 0u; a.open = (flags & MC_CUT_OPEN) ? 1u : 0u;
     a.spanBlocks = span_blocks_of(std::min<uint64_t>(capacity ? capacity - 1 : 0, most_batches(n)));
     ScopedTimer timer(ctx, "parse_cut", st);
@@ -424,7 +402,7 @@ extern "C" {
 
 uint64_t mc_parse_cut_scratch_bytes(uint64_t nbytes)
 {
-    const uint64_t words = (uint64_t)kHead + (uint64_t)kArrays * cut_tiles_of(nbytes, 15) + span_blocks_of(most_batches(nbytes));
+    const uint64_t words = (uint64_t)kHead + (uint64_t)kArrays * tiles_of(nbytes + 15) + span_blocks_of(most_batches(nbytes));
     return (words * 4 + 255) / 256 * 256;
 }
 
@@ -457,13 +435,10 @@ int mc_parse_cut(mc_ctx* ctx, const char* bytes, uint64_t nbytes, uint32_t recor
     if (rc) return rc;
     std::lock_guard<std::mutex> lock(S->stageMtx);
     const uint64_t room = std::min<uint64_t>(capacity, most_batches(nbytes) + 1);   // (no range needs more)
-    if ((rc = grow(ctx, S->stageIn, (nbytes + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, mc_parse_cut_scratch_bytes(nbytes))) != MC_OK ||
-        (rc = grow(ctx, S->stageCuts, std::max<uint64_t>(room * 8, 16))) != MC_OK || (rc = grow(ctx, S->stageStatus, 64)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes, nbytes, hipMemcpyHostToDevice, st));
-    if ((rc = enqueue_cut(ctx, (const uint8_t*)S->stageIn.p, n, records_per_batch, flags & ~MC_PARSE_HOST, (uint64_t*)S->stageCuts.p, room, (uint64_t*)S->stageStatus.p, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, S->stageStatus.p, 64, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(status, S->hStatus, 64);
+    if ((rc = grow(ctx, S->stageWs, mc_parse_cut_scratch_bytes(nbytes))) != MC_OK || (rc = grow(ctx, S->stageCuts, std::max<uint64_t>(room * 8, 16))) != MC_OK ||
+        (rc = stage_bytes(ctx, S->stageIn, bytes, nbytes, st)) != MC_OK) return rc;
+    if ((rc = enqueue_cut(ctx, (const uint8_t*)S->stageIn.p, n, records_per_batch, flags & ~MC_PARSE_HOST, (uint64_t*)S->stageCuts.p, room, (uint64_t*)S->status.dev.p, S->stageWs.p, st)) != MC_OK) return rc;
+    if ((rc = read_status(ctx, S->status, 8, status, st)) != MC_OK) return rc;
     if (status[4] != MC_PARSE_OK) return MC_OK;
     HIP_TRY(ctx, hipMemcpyAsync(cuts, S->stageCuts.p, (status[1] + 1) * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -506,17 +481,15 @@ int mc_parse_headers(mc_ctx* ctx, const char* bytes, uint64_t nbytes, const uint
     const uint64_t outRoom = std::min<uint64_t>(out_capacity, nbytes);           // (the headers are bytes of the range)
     if ((rc = grow(ctx, S->stageIn, nbytes)) != MC_OK || (rc = grow(ctx, S->stageWs, mc_parse_headers_scratch_bytes(max_records))) != MC_OK ||
         (rc = grow(ctx, S->stageHdr, std::max<uint64_t>((uint64_t)max_records * 8, 16))) != MC_OK || (rc = grow(ctx, S->stageOut, std::max<uint64_t>(outRoom, 16))) != MC_OK ||
-        (rc = grow(ctx, S->stageOff, ((uint64_t)max_records + 1) * 8)) != MC_OK || (rc = grow(ctx, S->stageStatus, 128)) != MC_OK) return rc;
-    uint64_t* dParse = (uint64_t*)S->stageStatus.p;                               // [8] the parse's status, [8] this call's
+        (rc = grow(ctx, S->stageOff, ((uint64_t)max_records + 1) * 8)) != MC_OK) return rc;
+    uint64_t* dParse = (uint64_t*)S->status.dev.p;                                // [8] the parse's status, [8] this call's
     HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes, nbytes, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(dParse, parse_status, 64, hipMemcpyHostToDevice, st));
     const uint64_t rows = (parse_status[4] == MC_PARSE_OK) ? std::min<uint64_t>(parse_status[0], max_records) : 0;
     if (rows) HIP_TRY(ctx, hipMemcpyAsync(S->stageHdr.p, hdr, rows * 8, hipMemcpyHostToDevice, st));
     if ((rc = enqueue_parse_headers(ctx, (const uint8_t*)S->stageIn.p, (uint32_t)nbytes, (const uint32_t*)S->stageHdr.p, dParse, max_records, (uint8_t*)S->stageOut.p, outRoom,
                               (uint64_t*)S->stageOff.p, dParse + 8, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, dParse + 8, 32, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(status, S->hStatus, 32);
+    if ((rc = read_status(ctx, S->status, 4, status, st, dParse + 8)) != MC_OK) return rc;
     if (status[2] != MC_PARSE_OK) return MC_OK;
     HIP_TRY(ctx, hipMemcpyAsync(out_off, S->stageOff.p, (status[0] + 1) * 8, hipMemcpyDeviceToHost, st));
     if (status[1]) HIP_TRY(ctx, hipMemcpyAsync(out, S->stageOut.p, status[1], hipMemcpyDeviceToHost, st));

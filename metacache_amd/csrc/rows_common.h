@@ -1,12 +1,14 @@
 // metacache_amd/csrc/rows_common.h -- what the consumers of candidate rows (classify.hip, coverage.hip, target_hits.hip) and of their
 // assignments (evaluate.hip) share with each other and with context.cpp: the staging of host arrays, the drain before a readback, the
 // kernel timer, and -- on the device -- the taxon-of-a-target rule and the per-key wave sum of the tallies.  The wave reductions they use are
-// device_common.h's.  Internal.
+// device_common.h's.  The MC_*_HOST forms of the byte passes and of inflate.hip take the staged input bytes (stage_bytes) and the staged
+// status (StatusStage, read_status) from here.  Internal.
 #pragma once
 
 #include "context.h"
 
 #include <algorithm>
+#include <cstring>
 
 #ifdef __HIPCC__
 #include "device_common.h"
@@ -28,6 +30,41 @@ inline int grow(mc_ctx* ctx, DevBuf& b, size_t bytes)
     if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
     HIP_TRY(ctx, hipMalloc(&b.p, bytes));
     b.cap = bytes;
+    return MC_OK;
+}
+
+// ---- the MC_*_HOST forms: the input bytes up, the status words back.  The caller holds whatever mutex guards its staging buffers -----------
+// the status of a call as its kernels write it (dev) and the pinned words the host reads it through
+struct StatusStage { DevBuf dev; uint64_t* pinned = nullptr; };
+
+// made once, for the largest status the owner reads (`words` 64-bit words); a second call changes nothing
+inline int make_status_stage(mc_ctx* ctx, StatusStage& s, size_t words)
+{
+    if (const int rc = grow(ctx, s.dev, words * 8)) return rc;
+    if (!s.pinned) HIP_TRY(ctx, hipHostMalloc((void**)&s.pinned, words * 8));
+    return MC_OK;
+}
+inline void free_status_stage(StatusStage& s)
+{
+    if (s.dev.p) (void)hipFree(s.dev.p);
+    if (s.pinned) (void)hipHostFree(s.pinned);
+    s = StatusStage{};
+}
+
+// what has been enqueued on st is waited for and `words` status words are left in out; from: where they lie on the device (null: s.dev)
+inline int read_status(mc_ctx* ctx, StatusStage& s, size_t words, uint64_t* out, hipStream_t st, const uint64_t* from = nullptr)
+{
+    HIP_TRY(ctx, hipMemcpyAsync(s.pinned, from ? from : s.dev.p, words * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    std::memcpy(out, s.pinned, words * 8);
+    return MC_OK;
+}
+
+// n host bytes into stageIn, which is grown to whole 16-byte loads; the copy is enqueued on st
+inline int stage_bytes(mc_ctx* ctx, DevBuf& stageIn, const void* bytes, uint64_t n, hipStream_t st)
+{
+    if (const int rc = grow(ctx, stageIn, (n + 15) / 16 * 16)) return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(stageIn.p, bytes, n, hipMemcpyHostToDevice, st));
     return MC_OK;
 }
 

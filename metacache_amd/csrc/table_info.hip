@@ -13,6 +13,7 @@
 //                            payload, the 8-byte store or the compact store (gw_widen).  Stores to the output are lane-consecutive.
 // All three work on the buckets alone (never the direct-address index), wait for their own work and keep nothing in the context.
 #include "rows_common.h"
+#include "block_scan.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 
@@ -24,29 +25,13 @@ using namespace mcamd;
 namespace {
 
 constexpr uint32_t kBlock = 256;
+static_assert(kBlock == kScanBlock, "the scans of block_scan.h are for blocks of 256 threads");
 constexpr uint32_t kMaxTiles = 2048;             // tiles of the count / scan / write sequences: one single-block scan reaches them all
 constexpr uint32_t kBins = 256;                  // hist[0 .. 255]; bin 256 collects what mc_table_* does not support (sizes above 255)
 constexpr uint32_t kPieceKeys = 1u << 22;        // mc_table_lookup: keys per staged piece
 constexpr uint64_t kPieceLocs = 1ull << 26;      // ... and locations per gather launch (512 MB of staging at the most)
 constexpr uint64_t kPieceWords = 1ull << 22;     // mc_table_features: words per copy to the host
 constexpr uint32_t kFlagSize = 1, kFlagStore = 2;
-
-__device__ __forceinline__ uint64_t block_excl_scan(uint64_t v, uint64_t* sc, uint64_t& total)
-{
-    const uint32_t t = threadIdx.x;
-    sc[t] = v;
-    __syncthreads();
-    for (uint32_t d = 1; d < kBlock; d <<= 1) {
-        const uint64_t add = t >= d ? sc[t - d] : 0;
-        __syncthreads();
-        sc[t] += add;
-        __syncthreads();
-    }
-    total = sc[kBlock - 1];
-    const uint64_t incl = sc[t];
-    __syncthreads();
-    return incl - v;
-}
 
 // the four u16 sizes of a bucket in one 8-byte load (0 = free slot)
 __device__ __forceinline__ uint64_t bucket_sizes(const TableBucket* buckets, uint64_t b) { return *reinterpret_cast<const uint64_t*>(buckets[b].size); }
@@ -83,22 +68,6 @@ __global__ __launch_bounds__(kBlock) void table_count_kernel(const TableBucket* 
     uint64_t total;
     (void)block_excl_scan(mine, sc, total);
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// sums[tiles] -> their exclusive scan in place, *total = the grand total (one block)
-__global__ __launch_bounds__(kBlock) void tile_scan_kernel(uint64_t* __restrict__ sums, uint32_t tiles, uint64_t* __restrict__ total)
-{
-    __shared__ uint64_t sc[kBlock];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < tiles; base += kBlock) {                      // (the same trips for every lane)
-        const uint32_t j = base + threadIdx.x;
-        const uint64_t v = j < tiles ? sums[j] : 0;
-        uint64_t chunk;
-        const uint64_t excl = block_excl_scan(v, sc, chunk);
-        if (j < tiles) sums[j] = carry + excl;
-        carry += chunk;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 
 __global__ __launch_bounds__(kBlock) void table_compact_kernel(const TableBucket* __restrict__ buckets, uint32_t nbuckets, uint32_t tileLen,
@@ -287,7 +256,7 @@ int mc_table_features(mc_ctx* ctx, uint32_t* keys, uint32_t* sizes, uint64_t cap
     HIP_TRY(ctx, hipMemsetAsync(sums, 0, ((uint64_t)tiles + 1) * 8, st));
     if (tiles) {
         hipLaunchKernelGGL(table_count_kernel, dim3(tiles), dim3(kBlock), 0, st, tab.buckets, tab.nbuckets, tileLen, sums);
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, sums, tiles, sums + tiles);
+        hipLaunchKernelGGL(tile_scan_kernel<uint64_t>, dim3(1), dim3(kBlock), 0, st, sums, tiles, sums + tiles);
     }
     HIP_TRY(ctx, hipGetLastError());
     uint64_t total = 0;
@@ -352,7 +321,7 @@ int mc_table_lookup(mc_ctx* ctx, const uint32_t* keys, uint64_t n, uint64_t* off
         ScopedTimer timer(ctx, "table_lookup", st);
         hipLaunchKernelGGL(table_lookup_sizes_kernel, dim3(tiles), dim3(kBlock), 0, st, tab, dKeys.as<uint32_t>(), m, tileLen, dSizes.as<uint32_t>(),
                            dPays.as<uint64_t>(), dSums.as<uint64_t>(), dFlag.as<unsigned int>());
-        hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(kBlock), 0, st, dSums.as<uint64_t>(), tiles, dOff.as<uint64_t>() + m);
+        hipLaunchKernelGGL(tile_scan_kernel<uint64_t>, dim3(1), dim3(kBlock), 0, st, dSums.as<uint64_t>(), tiles, dOff.as<uint64_t>() + m);
         hipLaunchKernelGGL(table_offsets_kernel, dim3(tiles), dim3(kBlock), 0, st, dSizes.as<uint32_t>(), m, tileLen, dSums.as<uint64_t>(), dOff.as<uint64_t>());
         HIP_TRY(ctx, hipGetLastError());
         return MC_OK;

@@ -14,15 +14,16 @@
 //                              names still wanted are counted
 //   4. taxmap_status_kernel    one thread: status and the context's counters
 // No atomic decides anything but a minimum, a maximum or a sum, so the same calls give the same bytes.  Plain HIP C++; no inline assembly.
-#include "rows_common.h"
+#include "parse_scan.h"
 
 #include <cstring>
 
 using namespace mcamd;
+using namespace mcamd::parsek;
 
 namespace {
 
-constexpr uint32_t kBlock = 256, kTile = kBlock * 16, kNone = 0xFFFFFFFFu, kMaxBlocks = 2048, kMaxLine = 1024, kMaxDigits = 18;
+constexpr uint32_t kMaxBlocks = 2048, kMaxLine = 1024, kMaxDigits = 18;
 constexpr uint64_t kScratchBytes = 256, kNoKey = ~0ull;
 constexpr uint64_t kMaxNames = 1ull << 31, kMaxNameBytes = 0xFFFFFFFFull;
 // the call's workspace, in 32-bit words (zeroed in front of pass 1)
@@ -40,50 +41,22 @@ struct TaxmapArgs {
     uint32_t n, count, callNo;
 };
 
-__device__ __forceinline__ uint32_t byte_at(const TaxmapArgs& a, uint32_t p) { return p < a.n ? (uint32_t)a.B[p] : (uint32_t)'\n'; }
-__device__ __forceinline__ bool is_digit(uint32_t c) { return c - '0' < 10u; }
-__device__ __forceinline__ bool is_blank(uint32_t c) { return c == ' ' || c == '\t'; }
-__device__ __forceinline__ bool is_refused(uint32_t c) { return c == '\r' || c == '\v' || c == '\f' || c == 0; }
-
-// bit k: byte p0 + k of the range is a line start (position 0 or the byte behind a '\n')
-__device__ __forceinline__ uint32_t line_starts(const TaxmapArgs& a, uint32_t p0)
-{
-    if (p0 >= a.n) return 0;
-    const uint32_t cnt = min(16u, a.n - p0);
-    uint32_t w[4] = {0, 0, 0, 0};
-    if (cnt == 16) {
-        const uint4 v = *reinterpret_cast<const uint4*>(a.B + p0);
-        w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < 16; ++k) if (k < cnt) w[k >> 2] |= (uint32_t)a.B[p0 + k] << ((k & 3u) * 8u);
-    }
-    uint32_t prev = p0 ? (uint32_t)a.B[p0 - 1] : (uint32_t)'\n', mask = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16; ++k) {
-        if (k >= cnt) continue;
-        if (prev == '\n') mask |= 1u << k;
-        prev = (w[k >> 2] >> ((k & 3u) * 8u)) & 0xFFu;
-    }
-    return mask;
-}
-
 // the line rule on the line that starts at s; tok[k] / len[k]: where token k begins and how long it is (filled as far as the line is regular)
 __device__ __forceinline__ bool cut_line(const TaxmapArgs& a, uint32_t s, uint32_t tok[4], uint32_t len[4])
 {
     const uint32_t limit = s + kMaxLine;                       // the line's last byte lies below this
     uint32_t p = s, c;
     for (int k = 0; k < 4; ++k) {
-        while (is_blank(c = byte_at(a, p))) if (++p > limit) return false;
+        while (is_blank(c = byte_at(a.B, a.n, p))) if (++p > limit) return false;
         tok[k] = p;
-        for (; (c = byte_at(a, p)) != '\n' && !is_blank(c); ++p) {
+        for (; (c = byte_at(a.B, a.n, p)) != '\n' && !is_blank(c); ++p) {
             if (is_refused(c) || p >= limit) return false;
             if (k == 2 && (!is_digit(c) || p - tok[k] >= kMaxDigits)) return false;
         }
         len[k] = p - tok[k];
         if (!len[k]) return false;                             // (an empty or blank-only line; fewer than four tokens)
     }
-    while (is_blank(c = byte_at(a, p))) if (++p > limit) return false;
+    while (is_blank(c = byte_at(a.B, a.n, p))) if (++p > limit) return false;
     return c == '\n';                                          // (anything else: a fifth token or a refused byte)
 }
 
@@ -144,12 +117,11 @@ __global__ __launch_bounds__(kBlock) void taxmap_validate_kernel(TaxmapArgs a)
 {
     const uint32_t p0 = blockIdx.x * kTile + threadIdx.x * 16u;
     uint32_t lines = 0, offenceInv = 0;
-    for (uint32_t m = line_starts(a, p0); m; m &= m - 1) {
-        const uint32_t s = p0 + (uint32_t)__ffs((int)m) - 1u;
+    for_each_line_start(a.B, a.n, p0, [&](uint32_t s) {
         uint32_t tok[4], len[4];
         ++lines;
         if (!cut_line(a, s, tok, len)) offenceInv = max(offenceInv, kNone - s);
-    }
+    });
     lines = wave_sum_u32(lines); offenceInv = wave_max_u32(offenceInv);
     if ((threadIdx.x & 63u) == 0) {                            // (a sum and a maximum: the same whatever the order)
         if (lines) atomicAdd(&a.ws[wLines], lines);
@@ -162,19 +134,18 @@ __global__ __launch_bounds__(kBlock) void taxmap_match_kernel(TaxmapArgs a)
     if (a.ws[wOffenceInv] != 0 || a.count == 0) return;        // (the same for every thread of the grid)
     const uint32_t p0 = blockIdx.x * kTile + threadIdx.x * 16u;
     uint32_t targeted = 0, wanted = 0;
-    for (uint32_t m = line_starts(a, p0); m; m &= m - 1) {
-        const uint32_t s = p0 + (uint32_t)__ffs((int)m) - 1u;
+    for_each_line_start(a.B, a.n, p0, [&](uint32_t s) {
         uint32_t tok[4], len[4];
-        if (!cut_line(a, s, tok, len)) continue;               // (cannot happen without an offence)
+        if (!cut_line(a, s, tok, len)) return;                 // (cannot happen without an offence)
         uint32_t t = name_equal_to(a, a.B + tok[1], len[1]);
         if (t == kNone) t = name_similar_to(a, a.B + tok[0], len[0]);
         if (t == kNone) t = name_equal_to(a, a.B + tok[3], len[3]);
-        if (t == kNone) continue;
+        if (t == kNone) return;
         ++targeted;
-        if (!a.wanted[t]) continue;
+        if (!a.wanted[t]) return;
         ++wanted;
         atomicMin(&a.key[t], ((unsigned long long)a.callNo << 32) | s);   // (a minimum: the same whatever the order)
-    }
+    });
     targeted = wave_sum_u32(targeted); wanted = wave_sum_u32(wanted);
     if ((threadIdx.x & 63u) == 0) {
         if (targeted) atomicAdd(&a.ws[wTargeted], targeted);
@@ -220,8 +191,6 @@ __global__ void taxmap_status_kernel(TaxmapArgs a)
     atomicAdd(&a.counters[cRanked], (unsigned long long)a.ws[wNewly]);
 }
 
-uint32_t tiles_of(uint64_t nbytes) { return (uint32_t)((nbytes + kTile - 1) / kTile); }
-
 }  // namespace
 
 namespace mcamd {
@@ -234,8 +203,8 @@ struct TaxmapState {                     // what the context keeps for mc_taxmap
     bool begun = false;
     unsigned long long* dCounters = nullptr;
     uint64_t calls = 0, bytes = 0;
-    DevBuf stageIn, stageWs, stageStatus;
-    uint64_t* hStatus = nullptr;         // pinned [8]
+    DevBuf stageIn, stageWs;
+    StatusStage status;                  // [8]
 };
 
 void free_taxmap_state(mc_ctx* ctx)
@@ -243,9 +212,9 @@ void free_taxmap_state(mc_ctx* ctx)
     if (!ctx->taxmap) return;
     TaxmapState& S = *ctx->taxmap;
     for (void* p : {(void*)S.dNames, (void*)S.dOff, (void*)S.dPrefix, (void*)S.dWanted, (void*)S.dKey, (void*)S.dTaxid, (void*)S.dCounters,
-                    S.stageIn.p, S.stageWs.p, S.stageStatus.p})
+                    S.stageIn.p, S.stageWs.p})
         if (p) (void)hipFree(p);
-    if (S.hStatus) (void)hipHostFree(S.hStatus);
+    free_status_stage(S.status);
     delete ctx->taxmap;
     ctx->taxmap = nullptr;
 }
@@ -334,7 +303,7 @@ int mc_taxmap_begin(mc_ctx* ctx, const char* names, const uint64_t* nameOff, uin
         HIP_TRY(ctx, hipMalloc((void**)&S.dCounters, cCounters * 8));
         HIP_TRY(ctx, hipMemset(S.dCounters, 0, cCounters * 8));
     }
-    if (!S.hStatus) HIP_TRY(ctx, hipHostMalloc((void**)&S.hStatus, 64));
+    if (const int rc = make_status_stage(ctx, S.status, 8)) return rc;
     const uint64_t rows = std::max<uint64_t>(count, 1);
     std::vector<uint32_t> off(count + 1);
     std::vector<uint64_t> prefix(rows, 0);
@@ -384,13 +353,9 @@ int mc_taxmap_add(mc_ctx* ctx, const char* bytes, uint64_t nbytes, int flags, ui
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = streamv ? (hipStream_t)streamv : ctx->stream;
     if (!host) return enqueue_add(ctx, *S, (const uint8_t*)bytes, (uint32_t)nbytes, status, workspace, st);
-    if ((rc = grow(ctx, S->stageIn, (nbytes + 15) / 16 * 16)) != MC_OK || (rc = grow(ctx, S->stageWs, kScratchBytes)) != MC_OK || (rc = grow(ctx, S->stageStatus, 64)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->stageIn.p, bytes, nbytes, hipMemcpyHostToDevice, st));
-    if ((rc = enqueue_add(ctx, *S, (const uint8_t*)S->stageIn.p, (uint32_t)nbytes, (uint64_t*)S->stageStatus.p, S->stageWs.p, st)) != MC_OK) return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(S->hStatus, S->stageStatus.p, 64, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    std::memcpy(status, S->hStatus, 64);
-    return MC_OK;
+    if ((rc = grow(ctx, S->stageWs, kScratchBytes)) != MC_OK || (rc = stage_bytes(ctx, S->stageIn, bytes, nbytes, st)) != MC_OK) return rc;
+    if ((rc = enqueue_add(ctx, *S, (const uint8_t*)S->stageIn.p, (uint32_t)nbytes, (uint64_t*)S->status.dev.p, S->stageWs.p, st)) != MC_OK) return rc;
+    return read_status(ctx, S->status, 8, status, st);
 }
 
 int mc_taxmap_result(mc_ctx* ctx, int64_t* taxid, uint64_t* position, uint64_t* remaining, int flags, void* streamv)

@@ -121,6 +121,11 @@ def generated_files(ids, rank):
     return files
 
 
+def sweep_zones(T: int):
+    """where the tail sweeps lie: lengths L .. L + 15 inside one tile, and with T - 8 <= L < T + 8 around the tile border"""
+    return (("one_tile", 208), ("tile_border", T - 8))
+
+
 def tile_files(T: int, ids, rank):
     """regular files laid out around the tile T -> {name: bytes}"""
     sp = [int(i) for i, r in zip(ids, rank) if r == 4]
@@ -148,6 +153,15 @@ def tile_files(T: int, ids, rank):
     out["many_tiles"] = b"".join(l + b"#" + b"p" * 400 + b"\n" for l in many)   # > 256 tiles of 4096 bytes
     out["no_final_newline"] = line(1, b"only", [(sp[0], 5), (sp[1], 4)])[:-1]
     out["comments_only"] = HEAD + b"# nothing\n"
+    # a range that ends inside a thread's 16 bytes: every length L .. L + 15 inside one tile and around the tile border, the last line whole
+    # and without its '\n', and a (comment) line that starts in the range's last byte
+    for zone, L in sweep_zones(T):
+        for i in range(16):
+            last = line(3 + i, b"s%d" % i, [(sp[i % len(sp)], 1 + i)])
+            out["sweep_%s_%02d" % (zone, i)] = first + pad_comment(L + i - len(first) - len(last)) + last
+            out["sweep_%s_%02d_cut" % (zone, i)] = first + pad_comment(L + i + 1 - len(first) - len(last)) + last[:-1]
+            out["sweep_%s_%02d_last_byte" % (zone, i)] = first + pad_comment(L + i - 1 - len(first)) + b"#"
+    assert all(len(out["sweep_%s_%02d%s" % (z, i, k)]) == L + i for z, L in sweep_zones(T) for i in range(16) for k in ("", "_cut", "_last_byte"))
     return out
 
 
@@ -178,4 +192,10 @@ def irregular_files(ids, rank):
         if name == "empty_header":
             b = b + b"\n"
         out[name] = (good + b + tail, len(good))
+    # a line that starts in the last byte of the range, at every residue of the length: an id without the rest of its line
+    for zone, L in sweep_zones(4096):
+        for i in range(16):
+            data = good + b"#" + b"c" * (L + i - len(good) - 3) + b"\n7"
+            assert len(data) == L + i
+            out["last_byte_%s_%02d" % (zone, i)] = (data, L + i - 1)
     return out

@@ -15,6 +15,9 @@ def golden_bytes(name):
         return f.read()
 
 
+TAIL_ZONES = ("one_tile", "tile_border")
+
+
 def dna(rng, n):
     return np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n)].tobytes()
 
@@ -111,10 +114,26 @@ def all_cases(T):
         out[f"marker_at_T_{'fq' if fq else 'fa'}_crlf2"] = a + crlf((fastq_record if fq else fasta_record)(b"atT", dna(rng, 70)))
     for name in REGULAR:
         out[name] = golden_bytes(name)
+    out.update(tail_sweep(T))
+    return out
+
+
+def tail_sweep(T):
+    """a range that ends inside a thread's 16 bytes: one FASTA file cut to every length L .. L + 15, inside one tile and with
+    T - 8 <= L < T + 8 around the tile border, its last line whole and without its final '\\n'"""
+    rng = np.random.default_rng(8)
+    last = fasta_record(b"last one", dna(rng, 21))
+    out = {}
+    for zone, L in zip(TAIL_ZONES, (208, T - 8)):
+        for i in range(16):
+            out[f"tail_{zone}_{i:02d}_fa"] = pad_to(0, L + i - len(last), rng, False) + last
+            out[f"tail_{zone}_{i:02d}_cut_fa"] = (pad_to(0, L + i + 1 - len(last), rng, False) + last)[:-1]
+            assert len(out[f"tail_{zone}_{i:02d}_fa"]) == len(out[f"tail_{zone}_{i:02d}_cut_fa"]) == L + i
     return out
 
 
 CASE_NAMES = sorted(["marker_at_T", "header_across", "blank_at_T", "single", "no_final_newline", "many_tiles", "long_record", "markers_inside"][i] + s
                     for i in range(8) for s in ("_fa", "_fq", "_fa_crlf", "_fq_crlf")) + \
     ["empty_sequence_fa", "empty_sequence_fa_crlf", "blank_lines_fa", "blank_lines_fa_crlf", "newline_before_T_fa", "newline_before_T_fa_crlf",
-     "cr_before_T_fa", "cr_before_T_fq", "marker_at_T_fa_crlf2", "marker_at_T_fq_crlf2"] + REGULAR
+     "cr_before_T_fa", "cr_before_T_fq", "marker_at_T_fa_crlf2", "marker_at_T_fq_crlf2"] + REGULAR + \
+    [f"tail_{zone}_{i:02d}{cut}_fa" for zone in TAIL_ZONES for i in range(16) for cut in ("", "_cut")]

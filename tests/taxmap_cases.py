@@ -158,6 +158,21 @@ def cases(T=4096, M=1024):
     out["irregular_last_line"] = (three, None, [good + b"P_000003 P_000003.1 3"])
     out["irregular_twice"] = (three, None, [fill_to(good, T + 3) + kinds["cr"] + fill_to(b"", 2 * T) + kinds["three_tokens"] + hit(2, 4)])
 
+    # a range that ends inside a thread's 16 bytes: every length L .. L + 15 inside one tile and around the tile border, the last line whole
+    # and without its '\n' (a call and a name each), and a line that starts in the range's last byte (refused there)
+    sweep = numbered(32)
+    for zone, L in (("one_tile", 208), ("tile_border", T - 8)):
+        ends, last_byte = [], []
+        for i in range(16):
+            for j, cut in ((2 * i, 0), (2 * i + 1, 1)):
+                last = row(sweep[j][:-2], sweep[j], 500 + j, b"9")
+                r = fill_to(b"", L + i + cut - len(last)) + last
+                ends.append(r[:len(r) - cut])
+            last_byte.append(fill_to(b"", L + i - 1) + b"x")
+        assert [len(r) for r in ends[0::2]] == [len(r) for r in ends[1::2]] == [len(r) for r in last_byte] == list(range(L, L + 16))
+        out["tail_sweep_" + zone] = (sweep, None, ends)
+        out["irregular_last_byte_" + zone] = (sweep, None, last_byte)
+
     # random rows
     rng = random.Random(20261021)
     names = sorted({b"R%05d" % rng.randrange(3000) + (b".%d" % rng.randrange(1, 4) if rng.randrange(5) else b"") for _ in range(340)})[:300]

@@ -1,4 +1,4 @@
-"""GPU: mc_format_mappings (format_lengths_kernel, format_scan_kernel, format_write_kernel) -- the mapping lines rendered on the device.
+"""GPU: mc_format_mappings (format_lengths_kernel, tile_scan_kernel, format_write_kernel) -- the mapping lines rendered on the device.
 
   * against the model (tests/format_ref.py, itself held to the reference's lines by test_format_witness_cpu.py): bytes and offsets, on
     synthetic tables of about 3 000 result texts and 500 targets (text lengths 0 .. 300, some candidate texts empty); the sizes around
@@ -22,7 +22,7 @@ from metacache_amd import api
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NUM_RANKS = 21
-SCAN_TILE, MAX_TILES, BLOCK = 256, api.FORMAT_SCRATCH, 256     # format_scan_kernel scans 256 tile sums per trip; at most MAX_TILES tiles, of whole blocks of reads
+SCAN_TILE, MAX_TILES, BLOCK = 256, api.FORMAT_SCRATCH, 256     # tile_scan_kernel scans 256 tile sums per trip; at most MAX_TILES tiles, of whole blocks of reads
 GUARD, FILL = 256, 0xA5
 ALL = format_ref.QUERY_IDS | format_ref.TRUTH | format_ref.TOPHITS | format_ref.LOCATIONS
 NUM_RESULT, NUM_TARGETS = 3000, 500

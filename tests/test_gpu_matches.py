@@ -1,4 +1,4 @@
-"""GPU: mc_format_matches (matches_kernel<false>, format_scan_kernel, matches_kernel<true>) -- the all-hits column rendered on the device --
+"""GPU: mc_format_matches (matches_kernel<false>, tile_scan_kernel, matches_kernel<true>) -- the all-hits column rendered on the device --
 and mc_format_mappings_with (format_lengths_kernel<true>, format_write_kernel<true>), which puts it into the mapping lines.
 
   * against the model (tests/matches_ref.py, itself held to the reference's lines by test_matches_witness_cpu.py), byte for byte, with

@@ -117,6 +117,11 @@ def test_the_cases_cover_what_they_are_there_for(all_cases, expected):
     assert expected["taxid_0_and_18_digits"][1][0][:3] == [0, 999999999999999999, 7] and expected["taxid_0_and_18_digits"][1][1][0] == 0
     assert expected["all_ranked_then_more"][0][1][3:5] == [0, 0]
     assert sum(1 for n in all_cases if n.startswith("irregular_")) >= 15
+    for zone, L in (("one_tile", 208), ("tile_border", T - 8)):                 # ranges that end at every place of a thread's 16 bytes
+        st, (taxid, key, _) = expected["tail_sweep_" + zone]
+        assert [s[5] for s in st] == [ref.OK] * 32 and taxid == [500 + j for j in range(32)]
+        assert [len(r) for r in all_cases["tail_sweep_" + zone][2]][0::2] == list(range(L, L + 16))
+        assert [s[5:7] for s in expected["irregular_last_byte_" + zone][0]] == [[ref.IRREGULAR, L + i - 1] for i in range(16)]
     assert expected["random_20000x300"][0][0][0] + expected["random_20000x300"][0][1][0] == 20000
 
 

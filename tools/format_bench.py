@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measures mc_format_mappings' three kernels (format_lengths_kernel, format_scan_kernel, format_write_kernel) on device-resident arrays
+"""Measures mc_format_mappings' three kernels (format_lengths_kernel, tile_scan_kernel, format_write_kernel) on device-resident arrays
 (a record, not a gate).
 
 No database: --reads (5 * 10^6) synthetic reads with names of 8 .. 24 bytes, candidate lists of stride 2 and 4 (a quarter of the lists

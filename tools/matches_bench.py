@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Measures the all-hits column on device-resident arrays: mc_format_matches (matches_kernel<false>, format_scan_kernel,
+"""Measures the all-hits column on device-resident arrays: mc_format_matches (matches_kernel<false>, tile_scan_kernel,
 matches_kernel<true>) and mc_format_mappings_with, which copies the column into the lines (a record, not a gate).
 
 No database: synthetic location lists of 100, 1 000 and 5 000 locations per read (--locations in all, 2 * 10^7, so 200 000, 20 000 and
