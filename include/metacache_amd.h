@@ -430,6 +430,13 @@ int mc_copy_results(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, int
  * kind 2 = host -> device: a caller whose reads lie in pinned host memory uploads batch i + 1 on the pipe it will run on while batch i's
  * kernels run on the other pipe (cudaMemcpyAsync of query_batch's host buffers, query_batch.cu:330-360) */
 int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, int kind, void* stream);
+/* device memory (kind 0) and pinned host memory (kind 1) on the context's device, for callers that do not link the HIP runtime themselves
+ * (mcq's build step): with mc_copy_results_on and mc_synchronize they fill and read the arrays of the device forms.  The
+ * memory is the caller's until mc_buffer_free (same kind; NULL, another kind or a context without a device: nothing happens); the context
+ * keeps no list of it, so the kind is the caller's word.  Device memory is 256-byte aligned.
+ * MC_ERR_INVALID: NULL ctx or out, bytes == 0, another kind; MC_ERR_STATE: a context without a device; MC_ERR_NOMEM. */
+int  mc_buffer_alloc(mc_ctx* ctx, uint64_t bytes, int kind, void** out);
+void mc_buffer_free(mc_ctx* ctx, void* p, int kind);
 
 /* tuning / test hook (not needed for normal use): the switches the MC_BIG_MIN / MC_QUAD_LOOKUP / MC_NO_LANE_PATH environment variables
  * set at mc_create, on a live context with no batch in flight.  names: "big_min" (location lists longer than this are filtered by
@@ -897,6 +904,52 @@ uint64_t mc_parse_headers_scratch_bytes(uint32_t max_records);
 int mc_parse_headers(mc_ctx* ctx, const char* bytes, uint64_t nbytes, const uint32_t* hdr, const uint64_t* parse_status,
                      uint32_t max_records, int flags, char* out, uint64_t out_capacity, uint64_t* out_off /* [max_records + 1] */,
                      uint64_t status[4], void* workspace, uint64_t workspace_bytes, void* stream);
+
+/* ---- targets out of MANY FASTA files in one byte range: the input side of a build on the device ------
+ * THE TARGET RULE.  The range is bytes[0, nbytes).  File f is bytes[file_off[f], file_off[f + 1]); file_off[0] = 0, the table ascends
+ * strictly and file_off[num_files] = nbytes.  Each file is judged by the FASTA part of THE RECORD RULE above ON ITS OWN:
+ *   a line start is the file's first byte, or the byte after a '\n' of the same file (a file need not end in '\n');
+ *   a file's first byte that is not '>' is IRREGULAR, the offence is that byte (FASTQ is not taken);
+ *   a line start that holds '+' is IRREGULAR; a '\r' that is not followed by '\n' or by the file's end is IRREGULAR.
+ *   A record starts at every line start that holds '>'; header and sequence are those of the record rule (the header ends with its line
+ *   or with the file).  So the files, each with a '\n' put behind it where it lacks one, give exactly the records of mc_parse_records.
+ *   The lowest offence of the range is reported and status[7] names its file.  A file table that breaks its own rule is found on the
+ *   device (one thread per row): MC_PARSE_IRREGULAR with offence nbytes and status[7] = the first bad row (row r > 0 is bad when it is
+ *   not above row r - 1, row 0 when it is not 0, row num_files also when it is not nbytes).  MC_PARSE_HOST refuses such a table with
+ *   MC_ERR_INVALID before any device call.
+ * mc_parse_targets fills, in range order and for ALL records, empty ones included: hdr[records][2] as mc_parse_records lays it out
+ *   (offset of the header in the range, without the marker; its trimmed length); targets[r] = seq_off (an offset into seq, a multiple
+ *   of 4), len (sequence bytes: all lines but the header, trimmed, empty lines add nothing), file, index (the record's number inside its
+ *   file, from 0, empty records counted), reserved = 0; seq = the sequences back to back, each at a multiple of 4, the padding bytes and
+ *   the 16 bytes behind the last sequence 0, a record with len == 0 takes no room (seq_off is then where the next sequence begins) --
+ *   what mc_build_add_target_device asks of its source.  status[8] = records, records with len > 0, bytes of seq needed (with the 16
+ *   behind), 0, verdict, offence, the longest len, the file of the offence.  status[0] and status[4] are the words mc_parse_headers
+ *   reads of a parse's status (the record count and the verdict; of hdr it reads rows [0, records)), so it packs the headers of a range
+ *   parsed here unchanged.  With MC_PARSE_OVERFLOW (more than max_records records, or seq_capacity too small) status[0..2] and [6] hold
+ *   what a second call needs; with MC_PARSE_IRREGULAR only [4], [5] and [7] mean anything (the others are 0).  With a verdict other than
+ *   MC_PARSE_OK NOTHING but status is written.
+ *   Without MC_PARSE_HOST all arrays, file_off included, are DEVICE pointers (bytes, seq and workspace 16-byte, targets, status and
+ *   file_off 8-byte, hdr 4-byte aligned) and the call is enqueued on `stream` (NULL: the context's) without any synchronisation.  The
+ *   caller owns the workspace (mc_parse_targets_scratch_bytes(nbytes, num_files, max_records) bytes); the context keeps nothing per call,
+ *   so calls on different streams may run at once.  The same bytes give the same outputs, byte for byte.
+ *   With MC_PARSE_HOST all arrays are HOST arrays (workspace may be NULL), staged through buffers of the context, one caller at a time;
+ *   the call returns when they are filled.
+ * MC_ERR_INVALID (checked first, before any device call): NULL ctx, out, bytes, file_off or status, nbytes == 0 or > 2^31, num_files == 0,
+ *   flags other than MC_PARSE_HOST, NULL arrays with max_records > 0, a capacity without its array; device form: a workspace that is too
+ *   small, misaligned arrays.  MC_ERR_STATE: a context without a device (mc_open_metadata).  mc_parse_stats counts these calls.
+ *   mc_timing_get names: "targets_classify" (the table pass, three byte passes, the record sums and the scans), "targets_write". */
+typedef struct { uint64_t seq_off; uint32_t len, file, index, reserved; } mc_parse_target;   /* 24 bytes */
+typedef struct {
+    uint32_t*        hdr;          /* [max_records][2]: offset and length of each header, as mc_parse_records leaves them */
+    mc_parse_target* targets;      /* [max_records] */
+    uint8_t*         seq;
+    uint64_t         seq_capacity;
+    uint64_t*        status;       /* [8] */
+    uint32_t         max_records;
+} mc_parse_targets_output;
+uint64_t mc_parse_targets_scratch_bytes(uint64_t nbytes, uint32_t num_files, uint32_t max_records);
+int mc_parse_targets(mc_ctx* ctx, const char* bytes, uint64_t nbytes, const uint64_t* file_off /* [num_files + 1] */, uint32_t num_files,
+                     int flags, const mc_parse_targets_output* out, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* raw bytes into a batch slot: the slot's reads are cut on the device
  * mc_batch_add_file_bytes fills an EMPTY slot with a byte range of a FASTA / FASTQ file (whole records; flags: 0 or MC_PARSE_PAIRS): one

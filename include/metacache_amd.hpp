@@ -172,6 +172,17 @@ inline bgzf_members bgzf_index(const void* bytes, std::size_t nbytes)
 
 class query_batch;
 
+// the targets of a range that holds many FASTA files back to back, cut on the device (mc_parse_targets on host arrays; the target rule:
+// metacache_amd.h).  verdict MC_PARSE_OK: record r's header is bytes[hdr[2r] .. + hdr[2r + 1]), its sequence seq[targets[r].seq_off .. +
+// targets[r].len), its file targets[r].file and its number inside that file targets[r].index; records counts ALL records, withSequence
+// those with len > 0 (what a build adds).  Another verdict: the arrays are empty, offence says where the range broke the rule and file in
+// which file (a file table that breaks its own rule: offence = the range's length, file = the first bad row).
+struct parsed_targets {
+    int verdict = MC_PARSE_IRREGULAR; std::uint64_t offence = 0, file = 0; std::uint32_t records = 0, withSequence = 0, longest = 0;
+    std::vector<std::uint32_t> hdr; std::vector<mc_parse_target> targets; std::vector<std::uint8_t> seq;
+    std::string header(const char* bytes, std::size_t r) const { return std::string(bytes + hdr[2 * r], hdr[2 * r + 1]); }
+};
+
 class database {
 public:
     database() = default;
@@ -191,6 +202,15 @@ public:
         sk_.kmerlen = std::uint32_t(info[0]); sk_.sketchlen = std::uint32_t(info[1]);
         sk_.winlen = std::uint32_t(info[2]); sk_.winstride = std::uint32_t(info[3]);
         targets_ = info[5]; parts_ = unsigned(info[6]);
+        maxCand_ = c.max_candidates; slots_ = c.num_slots; copyAllhits_ = c.copy_allhits != 0;
+    }
+    // a context on the device without a table: what the parse calls (parse_records, parse_cut, parse_targets, ...) need
+    void create(int device = 0)
+    {
+        mc_config c;
+        mc_config_default(&c);
+        c.device = device;
+        if (mc_create(&c, &ctx_) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
         maxCand_ = c.max_candidates; slots_ = c.num_slots; copyAllhits_ = c.copy_allhits != 0;
     }
     const sketching_opt& target_sketching() const noexcept { return sk_; }
@@ -278,6 +298,28 @@ public:
         p.records = ok ? std::uint32_t(status[0]) : 0; p.queries = ok ? std::uint32_t(status[1]) : 0; p.halfPair = ok && status[7] != 0;
         p.hdr.resize(std::size_t(p.records) * 2); p.qinfo.resize(std::size_t(p.queries) * 4); p.maxWin.resize(p.queries);
         p.seq.resize(ok ? std::size_t(status[2]) : 0); p.names.resize(ok ? std::size_t(status[3]) : 0); p.nameOff.resize(ok ? std::size_t(p.queries) + 1 : 0);
+        return p;
+    }
+
+    // files back to back in bytes[0, nbytes), file f = bytes[fileOff[f], fileOff[f + 1]) -> their targets (see parsed_targets)
+    parsed_targets parse_targets(const char* bytes, std::size_t nbytes, const std::vector<std::uint64_t>& fileOff) const
+    {
+        parsed_targets p;
+        if (fileOff.size() < 2) throw std::invalid_argument("database::parse_targets: a file table has two rows at least");
+        std::uint64_t status[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (int pass = 0; pass < 2; ++pass) {                                   // (the first call reports what the second needs)
+            mc_parse_targets_output o{};
+            const std::uint32_t mr = std::uint32_t(status[0]);
+            p.hdr.assign(std::size_t(mr) * 2 + 1, 0); p.targets.assign(std::size_t(mr) + 1, mc_parse_target{}); p.seq.assign(std::size_t(status[2]) + 1, 0);
+            o.hdr = p.hdr.data(); o.targets = p.targets.data(); o.seq = p.seq.data(); o.seq_capacity = status[2]; o.status = status; o.max_records = mr;
+            if (mc_parse_targets(ctx_, bytes, nbytes, fileOff.data(), std::uint32_t(fileOff.size() - 1), MC_PARSE_HOST, &o, nullptr, 0, nullptr) != MC_OK)
+                throw std::runtime_error(mc_last_error(ctx_));
+            if (status[4] != MC_PARSE_OVERFLOW) break;
+        }
+        p.verdict = int(status[4]); p.offence = status[5]; p.file = status[7];
+        const bool ok = status[4] == MC_PARSE_OK;
+        p.records = ok ? std::uint32_t(status[0]) : 0; p.withSequence = ok ? std::uint32_t(status[1]) : 0; p.longest = ok ? std::uint32_t(status[6]) : 0;
+        p.hdr.resize(std::size_t(p.records) * 2); p.targets.resize(p.records); p.seq.resize(ok ? std::size_t(status[2]) : 0);
         return p;
     }
 

@@ -205,6 +205,18 @@ class McParseOutput(C.Structure):
                 ("names_capacity", C.c_uint64), ("name_off", C.c_void_p), ("max_win", C.c_void_p), ("status", C.c_void_p), ("max_records", C.c_uint32)]
 
 
+class McParseTargetsOutput(C.Structure):
+    _fields_ = [("hdr", C.c_void_p), ("targets", C.c_void_p), ("seq", C.c_void_p), ("seq_capacity", C.c_uint64), ("status", C.c_void_p), ("max_records", C.c_uint32)]
+
+
+parse_target_dtype = np.dtype([("seq_off", "<u8"), ("len", "<u4"), ("file", "<u4"), ("index", "<u4"), ("reserved", "<u4")])   # mc_parse_target
+
+
+def parse_targets_scratch_bytes(nbytes: int, num_files: int, max_records: int) -> int:
+    """the workspace a device call of mc_parse_targets needs for a range of nbytes in num_files files and outputs of max_records records"""
+    return int(lib().mc_parse_targets_scratch_bytes(nbytes, num_files, max_records))
+
+
 class McBatchRecordInfo(C.Structure):
     _fields_ = [("verdict", C.c_uint32), ("records", C.c_uint32), ("queries", C.c_uint32), ("half_pair", C.c_uint32), ("offence", C.c_uint64),
                 ("hdr", C.c_void_p), ("qinfo", C.c_void_p)]
@@ -415,6 +427,7 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_parse_records", "mc_parse_scratch_bytes", "mc_parse_stats", "mc_batch_add_file_bytes", "mc_batch_records",
            "mc_parse_mates", "mc_parse_mates_scratch_bytes", "mc_batch_add_file_mates",
            "mc_parse_cut", "mc_parse_cut_scratch_bytes", "mc_parse_headers", "mc_parse_headers_scratch_bytes", "mc_batch_add_device_bytes", "mc_batch_headers",
+           "mc_parse_targets", "mc_parse_targets_scratch_bytes", "mc_buffer_alloc", "mc_buffer_free",
            "mc_input_open", "mc_input_batches", "mc_input_download", "mc_input_close",
            "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
            "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end",
@@ -521,6 +534,9 @@ def lib() -> C.CDLL:
         L.mc_parse_headers_scratch_bytes.restype = C.c_uint64
         L.mc_parse_headers.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_parse_targets_scratch_bytes.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32]
+        L.mc_parse_targets_scratch_bytes.restype = C.c_uint64
+        L.mc_parse_targets.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(McParseTargetsOutput), C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_batch_add_device_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64]
         L.mc_batch_headers.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.mc_input_open.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_void_p), C.c_void_p]
@@ -638,6 +654,16 @@ class Database:
     @classmethod
     def from_handle(cls, handle, cfg) -> "Database":
         return cls(handle, cfg)
+
+    @classmethod
+    def create(cls, **kw) -> "Database":
+        """a context on the device without a database (mc_create): what the calls that need no table run on -- the parse calls among them"""
+        cfg = default_config(**kw)
+        h = C.c_void_p()
+        rc = lib().mc_create(C.byref(cfg), C.byref(h))
+        if rc != MC_OK:
+            raise McError(f"mc_create -> {rc}: {lib().mc_last_error(None).decode()}")
+        return cls(h.value, cfg)
 
     def close(self):
         if self.h:
@@ -1136,6 +1162,44 @@ class Database:
         if int(status[2]) == PARSE_OK:
             res.update(out=out[:int(status[1])].tobytes(), out_off=off[:int(status[0]) + 1].copy())
         return res
+
+    # ---- targets out of many FASTA files in one range: the input side of a build -------------------------------------
+    def parse_targets_device(self, bytes_ptr: int, nbytes: int, file_off_ptr: int, num_files: int, *, hdr_ptr: int, targets_ptr: int, seq_ptr: int,
+                             seq_capacity: int, status_ptr: int, max_records: int, workspace_ptr: int, workspace_bytes: int, stream: int = 0):
+        """(device ADDRESSES as integers -- a torch tensor's data_ptr() --, as every *_device method of this class takes them)
+        cuts the range at bytes_ptr (device memory, 16-byte aligned), whose files begin at the uint64 offsets at file_off_ptr [num_files + 1],
+        into targets: hdr [max_records, 2] uint32, targets [max_records] parse_target_dtype, seq, status [8] uint64 -- all device memory;
+        workspace of parse_targets_scratch_bytes(nbytes, num_files, max_records); asynchronous on `stream` (mc_parse_targets).  status[4] is
+        the verdict (PARSE_OK: the arrays are filled)"""
+        o = McParseTargetsOutput(hdr_ptr or None, targets_ptr or None, seq_ptr or None, seq_capacity, status_ptr or None, max_records)
+        self._check(lib().mc_parse_targets(self.h, bytes_ptr or None, nbytes, file_off_ptr or None, num_files, 0, C.byref(o), workspace_ptr or None,
+                                           workspace_bytes, stream or None))
+
+    def parse_targets(self, data, file_off, *, max_records=None, seq_capacity=None):
+        """the same on host memory: data (bytes), file_off [files + 1] -> dict(status uint64 [8], and with the verdict PARSE_OK: hdr
+        [records, 2], targets [records] parse_target_dtype, seq (bytes, with the 16 behind the last sequence)).  Capacities that are left
+        out are taken from a first call's status (PARSE_OVERFLOW reports what is needed).  "raw": the arrays as the last call left them."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        off = np.ascontiguousarray(file_off, dtype=np.uint64)
+        status = np.zeros(8, dtype=np.uint64)
+
+        def run(mr, sc):
+            a = dict(hdr=np.zeros((max(mr, 1), 2), dtype=np.uint32), targets=np.zeros(max(mr, 1), dtype=parse_target_dtype), seq=np.zeros(max(sc, 1), dtype=np.uint8))
+            o = McParseTargetsOutput(a["hdr"].ctypes.data, a["targets"].ctypes.data, a["seq"].ctypes.data, sc, status.ctypes.data, mr)
+            self._check(lib().mc_parse_targets(self.h, buf.ctypes.data if len(buf) else None, len(buf), off.ctypes.data if len(off) else None, max(len(off), 1) - 1,
+                                               PARSE_HOST, C.byref(o), None, 0, None))
+            return a
+
+        sized = max_records is not None and seq_capacity is not None
+        a = run(max_records or 0, seq_capacity or 0)
+        if not sized and int(status[4]) == PARSE_OVERFLOW:
+            a = run(int(status[0]) if max_records is None else max_records, int(status[2]) if seq_capacity is None else seq_capacity)
+        out = dict(status=status.copy())
+        if int(status[4]) == PARSE_OK:
+            r = int(status[0])
+            out.update(hdr=a["hdr"][:r].copy(), targets=a["targets"][:r].copy(), seq=a["seq"][:int(status[2])].tobytes())
+        out["raw"] = a
+        return out
 
     def batch_headers(self, slot: int = 0):
         """the headers of a slot that was filled with device bytes (mc_batch_headers, after the wait) -> [bytes] per record; None with another
@@ -1641,6 +1705,19 @@ class Builder:
         L = lib()
         L.mc_build_add_target_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_int64, C.c_char_p, C.c_uint64]
         self._check(L.mc_build_add_target_device(self.h, ptr, length, name.encode(), parent_taxid, filename.encode(), file_index))
+
+    def add_parsed_targets(self, seq_ptr: int, targets, names, parents=None, filenames=None):
+        """the targets of a range that parse_targets_device has cut, in order: seq_ptr = the device address of its seq, targets = its rows
+        (host copy, parse_target_dtype), names[r] per record, parents[r] (None: 0), filenames[file] (None: "").  Records with len == 0 are
+        skipped, as the build loop skips them.  The memory stays valid until flush() / finish().  -> targets added"""
+        added = 0
+        for r, t in enumerate(targets):
+            if int(t["len"]) == 0:
+                continue
+            self.add_target_device(seq_ptr + int(t["seq_off"]), int(t["len"]), names[r], 0 if parents is None else int(parents[r]),
+                                   "" if filenames is None else filenames[int(t["file"])], int(t["index"]))
+            added += 1
+        return added
 
     def flush(self):
         lib().mc_build_flush.argtypes = [C.c_void_p]

@@ -280,6 +280,7 @@ void mc_destroy(mc_ctx* ctx)
     free_format_state(ctx);
     free_parse_state(ctx);
     free_cut_state(ctx);
+    free_targets_state(ctx);
     free_merge_results_state(ctx);
     free_inflate_state(ctx);
     free_taxmap_state(ctx);
@@ -456,6 +457,25 @@ int mc_copy_results_on(mc_ctx* ctx, void* dst, const void* src, uint64_t bytes, 
     const hipMemcpyKind how = (kind & 1) ? hipMemcpyDeviceToHost : (kind & 2) ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
     HIP_TRY(ctx, hipMemcpyAsync(dst, src, bytes, how, st));
     return MC_OK;
+}
+
+int mc_buffer_alloc(mc_ctx* ctx, uint64_t bytes, int kind, void** out)
+{
+    if (!ctx) return MC_ERR_INVALID;
+    if (!out || bytes == 0 || (kind != 0 && kind != 1)) return fail(ctx, MC_ERR_INVALID, "mc_buffer_alloc: no place for the pointer, no bytes or an unknown kind");
+    *out = nullptr;
+    if (!ctx->stream) return fail(ctx, MC_ERR_STATE, "mc_buffer_alloc: the context has no device (mc_open_metadata)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = kind == 0 ? hipMalloc(out, bytes) : hipHostMalloc(out, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return fail(ctx, MC_ERR_NOMEM, std::string("mc_buffer_alloc: ") + hipGetErrorString(e)); }
+    return MC_OK;
+}
+
+void mc_buffer_free(mc_ctx* ctx, void* p, int kind)
+{
+    if (!ctx || !p || (kind != 0 && kind != 1) || !ctx->stream) return;
+    (void)hipSetDevice(ctx->device);
+    if (kind == 0) (void)hipFree(p); else (void)hipHostFree(p);
 }
 
 int mc_timing_enable(mc_ctx* ctx, int on) { if (!ctx) return MC_ERR_INVALID; ctx->timing = on != 0; return MC_OK; }

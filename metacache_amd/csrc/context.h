@@ -219,6 +219,13 @@ void free_format_state(mc_ctx* ctx);
 // parse.hip: the counters and the staging of mc_parse_* (made on first use), freed with the context
 struct ParseState;
 void free_parse_state(mc_ctx* ctx);
+// ... and what mc_parse_targets (parse_targets.hip) takes from it: the call is counted for mc_parse_stats, counters = the device words its
+// scan adds records and refused ranges to
+int count_parse_call(mc_ctx* ctx, uint64_t bytes, unsigned long long** counters);
+
+// parse_targets.hip: the staging of the MC_PARSE_HOST form of mc_parse_targets (made on first use), freed with the context
+struct TargetsState;
+void free_targets_state(mc_ctx* ctx);
 
 // parse_cut.hip: the staging of the MC_PARSE_HOST forms of mc_parse_cut and mc_parse_headers (made on first use), freed with the context
 struct CutState;
@@ -301,6 +308,9 @@ struct mc_ctx {
 
     std::mutex parseMtx;
     mcamd::ParseState* parse = nullptr;    // made by the first mc_parse_records that reaches the device
+
+    std::mutex parseTargetsMtx;
+    mcamd::TargetsState* parseTargets = nullptr;   // made by the first MC_PARSE_HOST call of mc_parse_targets
 
     std::mutex cutMtx;
     mcamd::CutState* cut = nullptr;        // made by the first MC_PARSE_HOST call of mc_parse_cut / mc_parse_headers

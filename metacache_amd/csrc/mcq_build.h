@@ -432,6 +432,240 @@ struct TaxmapStep {
     }
 };
 
+// ---- target parse (mc_parse_targets): the file loop hands plain FASTA files to the library ------------------------------
+// MCQ_BUILD_PARSE_DEVICE=1 (build, modify, build+query).  Shaped as TaxmapStep: the switch, run, report.  The file loop of build_database
+// walks the input files in order; consecutive files the step takes (regular, not empty, no gzip magic, first byte '>') are gathered into one
+// PIECE of at most MCQ_BUILD_PARSE_PIECE bytes (256 MiB by default, within [4096, 2^31]): their bytes are copied from their mappings into
+// one pinned staging buffer, uploaded once and cut by mc_parse_targets (device form, on a context of the builders' device); status, targets
+// and hdr come back after ONE wait.  The headers are read from the staging buffer, which holds the bytes hdr points into -- no
+// mc_parse_headers call, nothing more to download.  Every record with len > 0 then goes through the loop's own body with
+// mc_build_add_target_device(seq + seq_off), every builder reading the same memory, and mc_build_flush precedes the buffers' reuse.
+// A file larger than a piece is cut on the host at record starts (the last "\n>" inside the room; the piece doubles up to 2^31 where there
+// is none) and ALL its ranges are judged (a call without room for a record: verdict and counts only) before its first target is added, so
+// a file is added entirely here or entirely by the host loop.  MC_PARSE_IRREGULAR leaves the piece's files to the host loop, in order;
+// MC_PARSE_OVERFLOW (more records than the tables hold) is answered by one second call with grown tables; a library error leaves the rest
+// of the pass to the host loop.
+struct TargetParseStep {
+    struct Mapped {
+        int fd = -1; const char* p = nullptr; size_t n = 0;
+        ~Mapped() { if (p) munmap((void*)p, n); if (fd >= 0) close(fd); }
+    };
+    struct Segment { size_t fi; const char* data; size_t n; uint64_t recordBase; bool first; };   // a file, or a range of a cut one
+    struct Buf { void* p = nullptr; size_t cap = 0; int kind = 0; };
+
+    bool on = false, dead = false;
+    std::string deadWhy;                     // a library error: why the rest of the pass is the host loop's
+    size_t piece = (size_t)256 << 20;
+    uint64_t calls = 0, bytes = 0, records = 0, targets = 0, files = 0;
+    std::vector<std::string> left;           // "file: reason" of every file that went to the host loop
+    mc_ctx* ctx = nullptr;
+    Buf hIn{nullptr, 0, 1}, hOff{nullptr, 0, 1}, hStatus{nullptr, 0, 1}, hHdr{nullptr, 0, 1}, hTargets{nullptr, 0, 1};
+    Buf dIn, dOff, dStatus, dHdr, dTargets, dSeq, dWs;
+    uint32_t recCap = 1u << 16;
+    std::vector<Segment> segs;               // the piece being gathered
+    std::vector<std::unique_ptr<Mapped>> maps;
+    size_t fill = 0;
+
+    TargetParseStep()
+    {
+        const char* sw = std::getenv("MCQ_BUILD_PARSE_DEVICE"); on = sw && std::atoi(sw) != 0;
+        if (const char* p = std::getenv("MCQ_BUILD_PARSE_PIECE")) piece = (size_t)std::min<long long>(std::max<long long>(4096, std::atoll(p)), 1ll << 31);
+    }
+    ~TargetParseStep()
+    {
+        if (!ctx) return;
+        for (Buf* b : {&hIn, &hOff, &hStatus, &hHdr, &hTargets, &dIn, &dOff, &dStatus, &dHdr, &dTargets, &dSeq, &dWs}) mc_buffer_free(ctx, b->p, b->kind);
+        mc_destroy(ctx);
+    }
+    TargetParseStep(const TargetParseStep&) = delete;
+
+    bool begin(int device)
+    {
+        mc_config cfg;
+        mc_config_default(&cfg);
+        cfg.device = device;
+        if (mc_create(&cfg, &ctx) != MC_OK) { ctx = nullptr; return die(mc_last_error(nullptr)); }
+        if (std::getenv("MCQ_PROFILE")) mc_timing_enable(ctx, 1);
+        return room(hStatus, 64) && room(dStatus, 64);
+    }
+    bool die(const std::string& why) { dead = true; deadWhy = why; return false; }
+    bool room(Buf& b, size_t need)
+    {
+        if (need <= b.cap) return true;
+        mc_buffer_free(ctx, b.p, b.kind); b.p = nullptr; b.cap = 0;
+        if (mc_buffer_alloc(ctx, need, b.kind, &b.p) != MC_OK) return die(mc_last_error(ctx));
+        b.cap = need;
+        return true;
+    }
+    bool copy(void* dst, const void* src, size_t n, int kind) { return mc_copy_results_on(ctx, dst, src, n, kind, nullptr) == MC_OK || die(mc_last_error(ctx)); }
+    bool wait() { return mc_synchronize(ctx) == MC_OK || die(mc_last_error(ctx)); }
+
+    // does the step take this file?  why: the reason where it does not
+    std::unique_ptr<Mapped> take(const std::string& file, std::string& why) const
+    {
+        std::unique_ptr<Mapped> m(new Mapped);
+        m->fd = open(file.c_str(), O_RDONLY);
+        struct stat sb;
+        if (m->fd < 0 || fstat(m->fd, &sb) != 0) { why = "unreadable"; return nullptr; }
+        if (!S_ISREG(sb.st_mode)) { why = "not a regular file"; return nullptr; }
+        if (sb.st_size == 0) { why = "empty"; return nullptr; }
+        unsigned char magic[2] = {0, 0};
+        if (pread(m->fd, magic, 2, 0) < 1) { why = "unreadable"; return nullptr; }
+        if (sb.st_size >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) { why = "gzip"; return nullptr; }
+        if (magic[0] == '@') { why = "FASTQ"; return nullptr; }
+        if (magic[0] != '>') { why = "does not begin with '>'"; return nullptr; }
+        void* p = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, m->fd, 0);
+        if (p == MAP_FAILED) { why = "cannot be mapped"; return nullptr; }
+        m->p = (const char*)p; m->n = (size_t)sb.st_size;
+        return m;
+    }
+
+    // a file cut at record starts into ranges of at most `cap` bytes, cap doubling up to 2^31 where a record does not fit: [begin, end) each
+    static bool cut_file(const char* data, size_t size, size_t cap, std::vector<std::pair<size_t, size_t>>& out)
+    {
+        for (size_t pos = 0; pos < size;) {
+            size_t len = std::min(size - pos, cap);
+            if (pos + len < size) {
+                const char* base = data + pos + 1;                             // (a cut at pos itself would be no cut)
+                const char* q = (const char*)memrchr(base, '>', len - 1);
+                while (q && q[-1] != '\n') q = (const char*)memrchr(base, '>', (size_t)(q - base));
+                if (!q) {
+                    if (cap >= ((size_t)1 << 31)) return false;
+                    cap = std::min(cap * 2, (size_t)1 << 31);
+                    continue;
+                }
+                len = (size_t)(q - (data + pos));
+            }
+            out.emplace_back(pos, pos + len);
+            pos += len;
+        }
+        return true;
+    }
+
+    void gather(size_t fi, std::unique_ptr<Mapped> m) { segs.push_back(Segment{fi, m->p, m->n, 0, true}); fill += m->n; maps.push_back(std::move(m)); }
+    void clear() { segs.clear(); maps.clear(); fill = 0; }
+
+    // what a range of n bytes in nf files needs of seq: a sequence's padding exceeds what its record's '>' and line ends give back only
+    // for a file's LAST record, whose final '\n' may be missing -- by one byte per file
+    static size_t seq_bound(size_t n, uint32_t nf) { return n + nf + 16; }
+    // every buffer of a call for n bytes in nf files with tables of maxRecords rows.  false: the step died
+    bool rooms(size_t n, uint32_t nf, uint32_t maxRecords)
+    {
+        const size_t rows = std::max<size_t>(maxRecords, 2);
+        return room(hIn, n) && room(hOff, ((size_t)nf + 1) * 8) && room(dIn, (n + 15) / 16 * 16 + 16) && room(dOff, ((size_t)nf + 1) * 8) &&
+               room(dWs, mc_parse_targets_scratch_bytes(n, nf, maxRecords)) && room(dSeq, seq_bound(n, nf) + 16) && room(dHdr, rows * 8) && room(dTargets, rows * sizeof(mc_parse_target)) &&
+               room(hHdr, rows * 8) && room(hTargets, rows * sizeof(mc_parse_target));
+    }
+
+    // the segments' bytes into the staging buffer and up; mc_parse_targets with tables of maxRecords rows; status, and with them hdr and
+    // targets at the tables' size, back after ONE wait.  false: the step died
+    bool parse(const std::vector<Segment>& ss, uint32_t maxRecords, uint64_t st[8])
+    {
+        size_t n = 0;
+        for (const Segment& s : ss) n += s.n;
+        const uint32_t nf = (uint32_t)ss.size();
+        const uint64_t wsBytes = mc_parse_targets_scratch_bytes(n, nf, maxRecords);
+        if (!rooms(n, nf, maxRecords)) return false;
+        uint64_t* off = (uint64_t*)hOff.p;
+        size_t at = 0;
+        for (uint32_t f = 0; f < nf; ++f) { off[f] = at; std::memcpy((char*)hIn.p + at, ss[f].data, ss[f].n); at += ss[f].n; }
+        off[nf] = at;
+        if (!copy(dIn.p, hIn.p, n, 2) || !copy(dOff.p, hOff.p, ((size_t)nf + 1) * 8, 2)) return false;
+        mc_parse_targets_output o{};
+        o.hdr = (uint32_t*)dHdr.p; o.targets = (mc_parse_target*)dTargets.p; o.seq = (uint8_t*)dSeq.p; o.seq_capacity = maxRecords ? seq_bound(n, nf) : 0;
+        o.status = (uint64_t*)dStatus.p; o.max_records = maxRecords;
+        if (mc_parse_targets(ctx, (const char*)dIn.p, n, (const uint64_t*)dOff.p, nf, 0, &o, dWs.p, wsBytes, nullptr) != MC_OK) return die(mc_last_error(ctx));
+        ++calls;
+        if (!copy(hStatus.p, dStatus.p, 64, 1)) return false;
+        if (maxRecords && (!copy(hHdr.p, dHdr.p, (size_t)maxRecords * 8, 1) || !copy(hTargets.p, dTargets.p, (size_t)maxRecords * sizeof(mc_parse_target), 1))) return false;
+        if (!wait()) return false;
+        std::memcpy(st, hStatus.p, 64);
+        return true;
+    }
+
+    // one piece: parsed (a second call where the tables were too small), then every record with len > 0 added through add_record(segment,
+    // record number in its file, header, length, device address).  false: nothing was added; why says so (the step may have died)
+    template <class Prologue, class AddRecord>
+    bool run(const std::vector<Segment>& ss, std::string& why, const std::vector<mc_builder*>& bs, Prologue&& prologue, AddRecord&& add_record)
+    {
+        uint64_t st[8];
+        if (!parse(ss, recCap, st)) { why = deadWhy; return false; }
+        if (st[4] == MC_PARSE_OVERFLOW && st[0] > recCap) {
+            recCap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(st[0], 2ull * recCap), 0xFFFFFFFFull);
+            if (!parse(ss, recCap, st)) { why = deadWhy; return false; }
+        }
+        if (st[4] == MC_PARSE_IRREGULAR) {
+            why = "irregular at byte " + std::to_string(st[5] - ((const uint64_t*)hOff.p)[std::min<uint64_t>(st[7], ss.size() - 1)]) + " of file " + std::to_string(st[7]) + " of its piece";
+            return false;
+        }
+        if (st[4] != MC_PARSE_OK) { why = "verdict " + std::to_string(st[4]); return false; }
+        const uint64_t recs = st[0];                                            // (<= recCap: rows [0, recs) of hdr and targets came back with status)
+        const uint32_t* hdr = (const uint32_t*)hHdr.p;
+        const mc_parse_target* tg = (const mc_parse_target*)hTargets.p;
+        uint64_t r = 0;
+        for (uint32_t f = 0; f < ss.size(); ++f) {
+            const int64_t fileTax = prologue(ss[f]);
+            for (; r < recs && tg[r].file == f; ++r) {
+                if (tg[r].len == 0) continue;                                   // building.cpp:295
+                add_record(ss[f], fileTax, ss[f].recordBase + tg[r].index, std::string((const char*)hIn.p + hdr[2 * r], hdr[2 * r + 1]), (size_t)tg[r].len,
+                           (const char*)dSeq.p + tg[r].seq_off);
+                ++targets;
+            }
+        }
+        for (mc_builder* b : bs) if (mc_build_flush(b) != MC_OK) throw std::runtime_error(mc_build_last_error(b));
+        size_t n = 0;
+        for (const Segment& s : ss) n += s.n;
+        bytes += n; records += recs;
+        return true;
+    }
+
+    // a file larger than a piece: cut, every range judged, the tables and buffers made for the largest range, then every range added.
+    // Nothing that can be refused is left for the adding phase: verdicts, record counts and memory are settled before the first target
+    // goes in.  What remains is a failing HIP call between two ranges, and that ends the build: the file's first targets cannot be taken back.
+    template <class Prologue, class AddRecord>
+    bool run_cut_file(size_t fi, const Mapped& m, std::string& why, const std::vector<mc_builder*>& bs, Prologue&& prologue, AddRecord&& add_record)
+    {
+        std::vector<std::pair<size_t, size_t>> cuts;
+        if (!cut_file(m.p, m.n, piece, cuts)) { why = "a record that does not fit the largest piece"; return false; }
+        std::vector<Segment> ranges;
+        uint64_t base = 0, mostRecords = 0;
+        size_t largest = 0;
+        for (const auto& c : cuts) {
+            std::vector<Segment> one(1, Segment{fi, m.p + c.first, c.second - c.first, base, c.first == 0});
+            uint64_t st[8];
+            if (!parse(one, 0, st)) { why = deadWhy; return false; }
+            if (st[4] == MC_PARSE_IRREGULAR) { why = "irregular at byte " + std::to_string(c.first + st[5]); return false; }
+            ranges.push_back(one[0]);
+            base += st[0]; mostRecords = std::max(mostRecords, st[0]); largest = std::max(largest, one[0].n);
+        }
+        recCap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(mostRecords, recCap), 0xFFFFFFFFull);
+        if (!rooms(largest, 1, recCap)) { why = deadWhy; return false; }
+        for (const Segment& s : ranges) {
+            std::vector<Segment> one(1, s);
+            if (!run(one, why, bs, prologue, add_record)) throw std::runtime_error("mcq build: the device parse failed inside a file whose first targets were added (" + why + ")");
+        }
+        return true;
+    }
+
+    // the device's line under MCQ_PROFILE; the fall-back's line also wherever the info level is not silent: the switch was set
+    void report(bool info)
+    {
+        const bool profile = std::getenv("MCQ_PROFILE") != nullptr;
+        if (!on) return;
+        std::string list;
+        for (const auto& l : left) list += (list.empty() ? " (" : "; ") + l;
+        if (!list.empty()) list += ")";
+        if (profile) {
+            double classifyMs = 0, writeMs = 0; uint64_t n = 0;
+            if (ctx) { mc_timing_get(ctx, "targets_classify", &classifyMs, &n); mc_timing_get(ctx, "targets_write", &writeMs, &n); }
+            std::cerr << "mcq profile: reference sequences parsed on the device: " << calls << " mc_parse_targets calls, " << bytes << " bytes, " << records << " records, "
+                      << targets << " targets, kernels " << classifyMs << " + " << writeMs << " ms, " << files << " files, " << left.size() << " files left to the host" << list << "\n";
+        }
+        if (!left.empty() && (profile || info))
+            std::cerr << "mcq: reference sequences of " << left.size() << " files parsed on the host" << list << (dead ? " [the device parse stopped: " + deadWhy + "]" : "") << "\n";
+    }
+};
+
 inline void build_database(const BuildOptions& o, BuiltDatabase& db)
 {
     using clock = std::chrono::steady_clock;
@@ -551,14 +785,50 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
         if (info) std::cout << "Database holds " << db.targets.size() << " reference sequences." << std::endl;
     }
     const size_t initTargets = db.targets.size();
-    for (size_t fi = 0; fi < o.infiles.size(); ++fi) {
+    // what both callers -- the host loop below and the device parse (TargetParseStep) -- do for a file and for a record of it
+    auto file_taxid = [&](size_t fi, bool say) -> int64_t {
         const std::string& filename = o.infiles[fi];
-        if (o.info == BuildOptions::verbose) std::cerr << "  (" << fi << '/' << o.infiles.size() << ") " << filename << std::endl;
+        std::string fileAcc = accession_string(filename, o.idType);
+        int64_t fileTax = find_taxon_id(seq2tax, fileAcc);
+        if (fileTax == 0 && o.idType == IdType::smart) { fileAcc = accession_string(filename, IdType::filename); fileTax = find_taxon_id(seq2tax, fileAcc); }
+        if (say && o.info == BuildOptions::verbose) std::cerr << "      accession '" << fileAcc << "' -> taxid " << fileTax << std::endl;
+        return fileTax;
+    };
+    // add(builder, name, parent): the mc_build_add_target_* call that hands the sequence over
+    auto add_record = [&](const std::string& filename, int64_t fileTax, uint64_t r, const std::string& header, size_t seqLen, const std::function<int(mc_builder*, const char*, int64_t)>& add) {
+        std::string seqId = accession_string(header, o.idType);
+        if (seqId.empty()) seqId = header;
+        int64_t parent = fileTax;
+        if (parent == 0) parent = find_taxon_id(seq2tax, seqId);
+        if (parent == 0) parent = taxon_id_in_header(header);
+        if (parent < 1) parent = 0;                                    // database.cpp:58
+        // a name that is already taken gets "!1", "!1!2", ... appended until it is new (taxonomy.hpp:1141-1146)
+        std::string sid = seqId;
+        int dupl = 0;
+        while (name2tgt.find(sid) != name2tgt.end()) { ++dupl; sid += "!" + std::to_string(dupl); }
+        const uint32_t tgt = (uint32_t)db.targets.size();
+        for (mc_builder* b : db.bs)
+            if (add(b, sid.c_str(), parent) != MC_OK)
+                throw BuilderError(mc_build_last_error(b));
+        if (dupl > 0 && info)
+            std::cerr << "Warning: duplicate sequence id! '" << seqId << "' already in database - '" << filename << "/" << r
+                      << "' inserted as '" << sid << "'\n";
+        name2tgt.emplace(sid, tgt);
+        Taxon t; t.id = -(int64_t)tgt - 1; t.parent = parent; t.rank = 0; t.name = sid; t.srcFile = filename; t.srcIndex = r;
+        mc_build_target_windows(db.bs[0], tgt, &t.windows);
+        db.targets.push_back(std::move(t));
+        if (o.info == BuildOptions::verbose) {
+            std::cerr << "    P0  [" << seqId;
+            if (parent > 0) std::cerr << ":" << parent;
+            std::cerr << "]  " << seqLen << " bp" << (dupl > 0 ? "  --  not added to database!\n" : "\n");
+        }
+    };
+    auto announce = [&](size_t fi) { if (o.info == BuildOptions::verbose) std::cerr << "  (" << fi << '/' << o.infiles.size() << ") " << o.infiles[fi] << std::endl; };
+    auto host_file = [&](size_t fi) {
+        const std::string& filename = o.infiles[fi];
+        announce(fi);
         try {
-            std::string fileAcc = accession_string(filename, o.idType);
-            int64_t fileTax = find_taxon_id(seq2tax, fileAcc);
-            if (fileTax == 0 && o.idType == IdType::smart) { fileAcc = accession_string(filename, IdType::filename); fileTax = find_taxon_id(seq2tax, fileAcc); }
-            if (o.info == BuildOptions::verbose) std::cerr << "      accession '" << fileAcc << "' -> taxid " << fileTax << std::endl;
+            const int64_t fileTax = file_taxid(fi, true);
             SeqFile file(filename);
             file.index(std::max(1u, std::thread::hardware_concurrency()));
             std::string scratch;
@@ -566,40 +836,49 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
                 View h, s;
                 file.record(r, h, s, scratch);
                 if (s.empty()) continue;                                       // building.cpp:295
-                const std::string header(h.p, h.n);
-                std::string seqId = accession_string(header, o.idType);
-                if (seqId.empty()) seqId = header;
-                int64_t parent = fileTax;
-                if (parent == 0) parent = find_taxon_id(seq2tax, seqId);
-                if (parent == 0) parent = taxon_id_in_header(header);
-                if (parent < 1) parent = 0;                                    // database.cpp:58
-                // a name that is already taken gets "!1", "!1!2", ... appended until it is new (taxonomy.hpp:1141-1146)
-                std::string sid = seqId;
-                int dupl = 0;
-                while (name2tgt.find(sid) != name2tgt.end()) { ++dupl; sid += "!" + std::to_string(dupl); }
-                const uint32_t tgt = (uint32_t)db.targets.size();
-                for (mc_builder* b : db.bs)
-                    if (mc_build_add_target_src(b, s.p, s.n, sid.c_str(), parent, filename.c_str(), r) != MC_OK)
-                        throw BuilderError(mc_build_last_error(b));
-                if (dupl > 0 && info)
-                    std::cerr << "Warning: duplicate sequence id! '" << seqId << "' already in database - '" << filename << "/" << r
-                              << "' inserted as '" << sid << "'\n";
-                name2tgt.emplace(sid, tgt);
-                Taxon t; t.id = -(int64_t)tgt - 1; t.parent = parent; t.rank = 0; t.name = sid; t.srcFile = filename; t.srcIndex = r;
-                mc_build_target_windows(db.bs[0], tgt, &t.windows);
-                db.targets.push_back(std::move(t));
-                if (o.info == BuildOptions::verbose) {
-                    std::cerr << "    P0  [" << seqId;
-                    if (parent > 0) std::cerr << ":" << parent;
-                    std::cerr << "]  " << s.n << " bp" << (dupl > 0 ? "  --  not added to database!\n" : "\n");
-                }
+                add_record(filename, fileTax, r, std::string(h.p, h.n), s.n,
+                           [&](mc_builder* b, const char* sid, int64_t parent) { return mc_build_add_target_src(b, s.p, s.n, sid, parent, filename.c_str(), r); });
             }
         } catch (BuilderError&) {
             throw;
         } catch (std::exception& e) {                                          // unreadable file: the reference reports it only with -verbose
             if (o.info == BuildOptions::verbose) std::cerr << "FAIL: " << e.what() << '\n';
         }
+    };
+    TargetParseStep parse;                                                     // MCQ_BUILD_PARSE_DEVICE=1: plain FASTA files are cut by the library, piece by piece
+    if (parse.on) parse.begin(c.device);
+    auto device_prologue = [&](const TargetParseStep::Segment& s) -> int64_t { if (s.first) announce(s.fi); return file_taxid(s.fi, s.first); };   // (a later range of a cut file: its lines are out)
+    auto device_record = [&](const TargetParseStep::Segment& s, int64_t fileTax, uint64_t r, const std::string& header, size_t len, const char* dseq) {
+        const std::string& filename = o.infiles[s.fi];
+        add_record(filename, fileTax, r, header, len,
+                   [&](mc_builder* b, const char* sid, int64_t parent) { return mc_build_add_target_device(b, dseq, len, sid, parent, filename.c_str(), r); });
+    };
+    // the gathered piece goes through the library; where it refuses, the piece's files go through the host loop, in order
+    auto drain = [&]() {
+        if (parse.segs.empty()) return;
+        std::string why;
+        const std::vector<TargetParseStep::Segment> ss = parse.segs;
+        if (parse.run(ss, why, db.bs, device_prologue, device_record)) parse.files += ss.size();
+        else for (const auto& s : ss) { parse.left.push_back(o.infiles[s.fi] + ": " + why); host_file(s.fi); }
+        parse.clear();
+    };
+    for (size_t fi = 0; fi < o.infiles.size(); ++fi) {
+        if (!parse.on) { host_file(fi); continue; }
+        std::string why = parse.deadWhy;
+        std::unique_ptr<TargetParseStep::Mapped> m = parse.dead ? nullptr : parse.take(o.infiles[fi], why);
+        if (m && m->n > parse.piece) {                                         // a file of several pieces: on its own
+            drain();
+            if (!parse.dead && parse.run_cut_file(fi, *m, why, db.bs, device_prologue, device_record)) { ++parse.files; continue; }
+            if (parse.dead) why = parse.deadWhy;
+            m.reset();
+        }
+        if (!m) { drain(); parse.left.push_back(o.infiles[fi] + ": " + why); host_file(fi); continue; }
+        if (parse.fill + m->n > parse.piece) drain();
+        if (parse.dead) { parse.left.push_back(o.infiles[fi] + ": " + parse.deadWhy); host_file(fi); continue; }
+        parse.gather(fi, std::move(m));
     }
+    drain();
+    parse.report(info);
     for (mc_builder* b : db.bs) if (mc_build_finish(b, nullptr) != MC_OK) throw std::runtime_error(mc_build_last_error(b));
     if (info)
         std::cout << "Added " << db.targets.size() - initTargets << " reference sequences in "

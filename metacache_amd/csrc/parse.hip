@@ -590,6 +590,23 @@ int ensure_parse_state(mc_ctx* ctx, ParseState** out)
     return make_status_stage(ctx, S.status, 16);
 }
 
+}  // namespace
+
+namespace mcamd {
+
+int count_parse_call(mc_ctx* ctx, uint64_t bytes, unsigned long long** counters)
+{
+    ParseState* S = nullptr;
+    if (const int rc = ensure_parse_state(ctx, &S)) return rc;
+    ++S->calls; S->bytes += bytes;
+    *counters = S->dCounters;
+    return MC_OK;
+}
+
+}  // namespace mcamd
+
+namespace {
+
 // the device form: five byte passes, three scans, nothing waited for
 int enqueue_parse(mc_ctx* ctx, ParseState& S, const uint8_t* dBytes, uint32_t n, int flags, uint64_t insertMax, const mc_parse_output& o, void* ws, hipStream_t st)
 {
