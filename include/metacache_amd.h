@@ -1092,6 +1092,58 @@ int mc_inflate_blocks(mc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const 
                       uint8_t* out, uint64_t out_capacity, uint64_t status[4], void* stream);
 int mc_inflate_stats(mc_ctx* ctx, uint64_t stats[4]);
 
+/* ---- whole gzip files inflated on the device ------------------------------------------
+ * Reference genomes are ordinary gzip files: one long member each, no BSIZE, no 64 KiB bound.  One such stream is a chain and gains
+ * nothing from a GPU; a build reads thousands of them, and there the FILE is the unit of parallelism as the member is above.
+ * THE STREAM RULE.  A ROW is one file's bytes[in_off, in_off + in_len) and a slice out[out_off, out_off + out_cap).  The row's bytes are
+ *   a CHAIN of one or more gzip members from in_off to exactly in_off + in_len.
+ * A MEMBER: 1f 8b 08 FLG, MTIME (4), XFL, OS; then, as FLG says and in this order, FEXTRA (bit 2: a u16 length and its bytes), FNAME
+ *   (bit 3: bytes up to and with a zero), FCOMMENT (bit 4: the same).  FTEXT (bit 0) is ignored.  FHCRC (bit 1) or a reserved bit (5, 6, 7)
+ *   is refused -- more than zlib refuses; as above, never an accepted range read differently.  Behind the header a raw deflate stream
+ *   whose length nothing states: the stream says where it ends, and what bounds its input is the row's end minus the 8 trailer bytes.
+ *   Behind the byte-aligned end of the stream the trailer: CRC-32, then ISIZE.  The member is correct when its output has that CRC-32,
+ *   its length mod 2^32 is ISIZE, and no match reaches in front of THIS member's first output byte: a second member starts with an
+ *   empty history, as zlib's reset between members gives it.  Deflate blocks and code sets are accepted exactly as by the block rule.
+ * Behind a trailer the row ends or the next member begins; bytes there that do not start with 1f 8b are MC_INFLATE_R_TRAILING (gzread
+ *   would ignore them; the caller's host path reads such a file as it always did).  A row is ACCEPTED when its chain ends exactly at the
+ *   row's end and the total output fits out_cap; `produced` is that total and may be less than out_cap.  A refused row reports
+ *   produced 0, the members it finished and the reason.
+ * LIMITS of a row: 18 <= in_len <= 2^28 and out_cap <= 2^31.  The decoder counts a member's unread input in bits and its output in
+ *   bytes, both in 32-bit registers; these limits keep the counters valid.  The host form checks them before any device call
+ *   (MC_ERR_INVALID), the kernel refuses such a row with MC_INFLATE_R_INPUT.
+ * REASONS: the MC_INFLATE_R_* above with their numbers (MC_INFLATE_R_LEFT has no meaning here), and MC_INFLATE_R_HEADER (bad magic in the
+ *   first member, CM != 8, FHCRC or a reserved flag, a header field that runs past the row), MC_INFLATE_R_TRAILING.  MC_INFLATE_R_INPUT
+ *   also covers a stream or a trailer that runs past the row, MC_INFLATE_R_OVER more than out_cap and a slice outside out_capacity,
+ *   MC_INFLATE_R_SHORT / _OVER an ISIZE that differs from the member's own count.
+ * mc_gzip_hint: HOST only -- no context, no device, no zlib; every access checked against nbytes.  info = verdict (MC_GZIP_OK: the first
+ *   member's header is one the device takes, and a trailer fits behind it), the offset of the first member's deflate stream, the
+ *   trailing ISIZE (the last four bytes; 0 below 4 bytes), the offence (the MC_INFLATE_R_* reason, 0 with MC_GZIP_OK).  The trailing
+ *   ISIZE is the size of a single-member file below 4 GiB.  For a chain it is too small: a row sized by it ends in MC_INFLATE_R_OVER and
+ *   the caller falls back.  MC_ERR_INVALID: info == NULL, bytes == NULL with nbytes > 0.
+ * mc_inflate_streams inflates the rows.  It follows mc_inflate_blocks in form -- flags, pointers, alignment (rows, results and status
+ *   8-byte), stream, staging ("inflate_stage_bytes", the same buffers and mutex), the argument checks and their order -- and differs
+ *   where it says so here:
+ *   A ROW'S VERDICT IS ITS OWN.  results[i] is written for every row.  An accepted row's out[out_off, out_off + produced) holds zlib's
+ *   bytes whatever the other rows are.  A refused row may write anywhere inside its OWN slice and nowhere else; a row whose slice does
+ *   not lie inside out_capacity writes nothing.  The host form checks that the slices are pairwise disjoint (MC_ERR_INVALID); in the
+ *   device form disjoint slices are the CALLER'S CONTRACT -- the kernel cannot see the other rows.
+ *   status = verdict, the lowest refused row, its reason, the number of accepted rows.  MC_INFLATE_OK only if every row is accepted;
+ *   else the lowest refused row decides: MC_INFLATE_OVERFLOW where its reason is MC_INFLATE_R_OVER (a matter of room), else
+ *   MC_INFLATE_CORRUPT.  The lowest row is an atomic minimum: the same input gives the same status.  No synchronisation between the
+ *   launches, no host step before the verdict.  num_rows <= 2^30.
+ * mc_inflate_streams_stats: calls, bytes in (nbytes), bytes out of the accepted rows, rows refused; waits for the device.  mc_inflate_stats
+ *   does not count these calls.  mc_timing_get name: "inflate_streams". */
+typedef struct { uint64_t in_off, in_len, out_off, out_cap; } mc_gzip_stream;
+typedef struct { uint64_t produced; uint32_t members, reason; } mc_gzip_result;   /* reason 0 = accepted */
+#define MC_GZIP_OK       0
+#define MC_GZIP_FOREIGN  1
+#define MC_INFLATE_R_HEADER   11
+#define MC_INFLATE_R_TRAILING 12
+int mc_gzip_hint(const uint8_t* bytes, uint64_t nbytes, uint64_t info[4]);
+int mc_inflate_streams(mc_ctx* ctx, const uint8_t* bytes, uint64_t nbytes, const mc_gzip_stream* rows, uint64_t num_rows, int flags,
+                       uint8_t* out, uint64_t out_capacity, mc_gzip_result* results, uint64_t status[4], void* stream);
+int mc_inflate_streams_stats(mc_ctx* ctx, uint64_t stats[4]);
+
 /* ---- per-part result files merged on the device: what `metacache merge` reads ------
  * The result files of queries against single database parts (docs/partitioning.md of the reference) are cut into one candidate list
  * per query, and the vote runs over those lists.  (mc_merge_part_candidates above is something else: it merges candidate ARRAYS.)

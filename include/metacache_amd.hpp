@@ -170,6 +170,19 @@ inline bgzf_members bgzf_index(const void* bytes, std::size_t nbytes)
     return m;
 }
 
+// what a gzip file's first header and last four bytes say (mc_gzip_hint; host code: no device, no zlib).  verdict MC_GZIP_OK: the device
+// takes the first member's header, whose deflate stream begins at `payload`; isize is the trailing ISIZE -- the plain size of a file of
+// one member below 4 GiB, too small for a chain of members.  MC_GZIP_FOREIGN: offence says why (MC_INFLATE_R_*).
+struct gzip_file_hint { int verdict = MC_GZIP_FOREIGN; std::uint64_t payload = 0, isize = 0; int offence = 0; };
+inline gzip_file_hint gzip_hint(const void* bytes, std::size_t nbytes)
+{
+    gzip_file_hint h;
+    std::uint64_t info[4] = {0, 0, 0, 0};
+    if (mc_gzip_hint(static_cast<const std::uint8_t*>(bytes), nbytes, info) != MC_OK) throw std::runtime_error(mc_last_error(nullptr));
+    h.verdict = int(info[0]); h.payload = info[1]; h.isize = info[2]; h.offence = int(info[3]);
+    return h;
+}
+
 class query_batch;
 
 // the targets of a range that holds many FASTA files back to back, cut on the device (mc_parse_targets on host arrays; the target rule:
@@ -362,6 +375,37 @@ public:
             throw std::runtime_error(mc_last_error(ctx_));
         r.verdict = int(status[0]); r.block = status[1]; r.reason = int(status[2]);
         r.bytes.resize(r.verdict == MC_INFLATE_OK ? std::size_t(members.outBytes) : 0);
+        return r;
+    }
+
+    // whole gzip files inflated on the device, a wave per file (mc_inflate_streams on host arrays; the stream rule: metacache_amd.h).
+    // files[i] is one file's bytes, room[i] the bytes its output may take (gzip_hint's isize for a file of one member).  Every file has
+    // its own verdict: results[i].reason == 0 and plain[i] what zlib gives for it, or the reason (MC_INFLATE_R_*) and an empty plain[i] --
+    // the caller reads that file through zlib.  verdict, row and reason are the call's: those of the lowest refused file.
+    struct inflated_files { int verdict = MC_INFLATE_CORRUPT; std::uint64_t row = 0, accepted = 0; int reason = 0; std::vector<mc_gzip_result> results; std::vector<std::string> plain; };
+    inflated_files inflate_streams(const std::vector<std::string>& files, const std::vector<std::uint64_t>& room) const
+    {
+        if (files.size() != room.size()) throw std::invalid_argument("inflate_streams: one room per file");
+        inflated_files r;
+        std::vector<mc_gzip_stream> rows(files.size());
+        std::string in;
+        std::uint64_t outAt = 0;
+        for (std::size_t i = 0; i < files.size(); ++i) {
+            in.resize((in.size() + 15) / 16 * 16, char(0));
+            rows[i] = mc_gzip_stream{in.size(), files[i].size(), outAt, room[i]};
+            in += files[i];
+            outAt += room[i];
+        }
+        std::string out(std::size_t(outAt) + 1, char(0));
+        std::uint64_t status[4] = {0, 0, 0, 0};
+        r.results.resize(files.size());
+        if (mc_inflate_streams(ctx_, reinterpret_cast<const std::uint8_t*>(in.data()), in.size(), rows.data(), rows.size(), MC_INFLATE_HOST,
+                               reinterpret_cast<std::uint8_t*>(&out[0]), outAt, r.results.data(), status, nullptr) != MC_OK)
+            throw std::runtime_error(mc_last_error(ctx_));
+        r.verdict = int(status[0]); r.row = status[1]; r.reason = int(status[2]); r.accepted = status[3];
+        r.plain.resize(files.size());
+        for (std::size_t i = 0; i < files.size(); ++i)
+            if (!r.results[i].reason) r.plain[i].assign(out, std::size_t(rows[i].out_off), std::size_t(r.results[i].produced));
         return r;
     }
 

@@ -185,6 +185,23 @@ def bgzf_index(data, capacity=None):
     return blocks[:min(len(blocks), int(info[0]))], int(info[1]), int(info[2]), int(info[3])
 
 
+GZIP_OK, GZIP_FOREIGN = 0, 1
+INFLATE_R_HEADER, INFLATE_R_TRAILING = 11, 12
+gzip_stream_dtype = np.dtype([("in_off", np.uint64), ("in_len", np.uint64), ("out_off", np.uint64), ("out_cap", np.uint64)])   # mc_gzip_stream
+gzip_result_dtype = np.dtype([("produced", np.uint64), ("members", np.uint32), ("reason", np.uint32)])                       # mc_gzip_result
+
+
+def gzip_hint(data):
+    """what a gzip file's first header and last four bytes say (mc_gzip_hint; host code, no device): -> (verdict GZIP_OK / GZIP_FOREIGN,
+    the offset of the first member's deflate stream, the trailing ISIZE, the offence: an INFLATE_R_* reason)"""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    info = np.zeros(4, dtype=np.uint64)
+    rc = lib().mc_gzip_hint(buf.ctypes.data if len(buf) else None, len(buf), info.ctypes.data)
+    if rc < 0:
+        raise McError(f"mc_gzip_hint -> {rc}: {lib().mc_last_error(None).decode()}")
+    return int(info[0]), int(info[1]), int(info[2]), int(info[3])
+
+
 def parse_cut_scratch_bytes(nbytes: int) -> int:
     """the workspace a device call of mc_parse_cut needs for a range of nbytes"""
     return int(lib().mc_parse_cut_scratch_bytes(nbytes))
@@ -431,7 +448,7 @@ EXPORTS = ["mc_candidates_from_partial_numbers_on", "mc_runtime_warning", "mc_sl
            "mc_input_open", "mc_input_batches", "mc_input_download", "mc_input_close",
            "mc_merge_results_set_taxids", "mc_merge_results_begin", "mc_merge_results_reserve", "mc_merge_results_scratch_bytes", "mc_merge_results_add",
            "mc_merge_results_lists", "mc_merge_results_classify", "mc_merge_results_stats", "mc_merge_results_end",
-           "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats",
+           "mc_bgzf_index", "mc_inflate_blocks", "mc_inflate_stats", "mc_gzip_hint", "mc_inflate_streams", "mc_inflate_streams_stats",
            "mc_taxmap_begin", "mc_taxmap_scratch_bytes", "mc_taxmap_add", "mc_taxmap_result", "mc_taxmap_stats", "mc_taxmap_end"]
 
 _lib = None
@@ -558,6 +575,9 @@ def lib() -> C.CDLL:
         L.mc_bgzf_index.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_inflate_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         L.mc_inflate_stats.argtypes = [C.c_void_p, C.c_void_p]
+        L.mc_gzip_hint.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
+        L.mc_inflate_streams.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.mc_inflate_streams_stats.argtypes = [C.c_void_p, C.c_void_p]
         L.mc_taxmap_begin.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.mc_taxmap_scratch_bytes.argtypes = [C.c_uint64]
         L.mc_taxmap_scratch_bytes.restype = C.c_uint64
@@ -1289,6 +1309,52 @@ class Database:
         """-> [mc_inflate_blocks calls, bytes in, bytes out of the accepted calls, calls refused]"""
         st = np.zeros(4, dtype=np.uint64)
         self._check(lib().mc_inflate_stats(self.h, st.ctypes.data))
+        return [int(x) for x in st]
+
+    # ---- whole gzip files inflated on the device (mc_inflate_streams) ----------------------------------------
+    def inflate_streams_device(self, bytes_ptr: int, nbytes: int, rows_ptr: int, num_rows: int, out_ptr: int, out_capacity: int, results_ptr: int,
+                               status_ptr: int, stream: int = 0):
+        """inflates the gzip files that the rows at rows_ptr (gzip_stream_dtype) name out of the range at bytes_ptr, each into its own slice
+        of out -- all device memory (bytes, out: 16-byte aligned; rows, results gzip_result_dtype [num_rows], status [4] uint64: 8-byte);
+        asynchronous on `stream`.  The slices must be disjoint.  status = verdict, lowest refused row, its reason, accepted rows"""
+        self._check(lib().mc_inflate_streams(self.h, bytes_ptr or None, nbytes, rows_ptr or None, num_rows, 0, out_ptr or None, out_capacity,
+                                             results_ptr or None, status_ptr or None, stream or None))
+
+    def inflate_streams_raw(self, data, rows, out_capacity=None):
+        """the host form as it is: -> (out uint8 [out_capacity], results gzip_result_dtype [rows], status uint64 [4]); out_capacity defaults
+        to the end of the last slice"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
+        rows = np.ascontiguousarray(rows, dtype=gzip_stream_dtype)
+        if out_capacity is None:
+            out_capacity = int((rows["out_off"] + rows["out_cap"]).max()) if len(rows) else 0
+        out = np.zeros(max(out_capacity, 1), dtype=np.uint8)
+        results = np.zeros(max(len(rows), 1), dtype=gzip_result_dtype)
+        status = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_inflate_streams(self.h, buf.ctypes.data if len(buf) else None, len(buf), rows.ctypes.data if len(rows) else None, len(rows),
+                                             INFLATE_HOST, out.ctypes.data, out_capacity, results.ctypes.data, status.ctypes.data, None))
+        return out[:out_capacity], results[:len(rows)], status
+
+    def inflate_streams(self, files, out_caps=None):
+        """gzip files (a list of bytes) -> (a list with each accepted file's plain bytes and None for a refused one, results
+        gzip_result_dtype [files]).  Host form.  out_caps: room per file; default: each file's trailing ISIZE (gzip_hint)"""
+        files = [bytes(f) for f in files]
+        if out_caps is None:
+            out_caps = [gzip_hint(f)[2] for f in files]
+        rows = np.zeros(len(files), dtype=gzip_stream_dtype)
+        in_at = out_at = 0
+        for i, (f, cap) in enumerate(zip(files, out_caps)):
+            rows[i] = (in_at, len(f), out_at, cap)
+            in_at += (len(f) + 15) // 16 * 16
+            out_at += cap
+        data = b"".join(f + bytes(-len(f) % 16) for f in files)
+        out, results, _ = self.inflate_streams_raw(data, rows, out_at)
+        plain = [None if int(r["reason"]) else out[int(w["out_off"]):int(w["out_off"]) + int(r["produced"])].tobytes() for w, r in zip(rows, results)]
+        return plain, results
+
+    def inflate_streams_stats(self):
+        """-> [mc_inflate_streams calls, bytes in, bytes out of the accepted rows, rows refused]"""
+        st = np.zeros(4, dtype=np.uint64)
+        self._check(lib().mc_inflate_streams_stats(self.h, st.ctypes.data))
         return [int(x) for x in st]
 
     # ---- the all-hits column: location lists, run-length encoded (mc_format_matches*) ----------------

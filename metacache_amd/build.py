@@ -18,8 +18,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIBDIR = os.path.join(PKG, "lib")
 LIB = os.path.join(LIBDIR, "libmetacache_amd.so")
-SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "query_pipe.cpp", "table_load.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip", "evaluate.hip", "format.hip", "table_info.hip", "parse.hip", "parse_cut.hip", "input_device.hip", "merge_results.hip", "inflate.hip", "taxmap.hip", "parse_targets.hip"]
-HEADERS = ["kernels.h", "table_rules.h", "read_class.h", "query_rules.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", "rows_common.h", "parse_scan.h", "block_scan.h", "bgzf_rules.h", os.path.join(ROOT, "include", "metacache_amd.h")]
+SOURCES = ["kernels.hip", "gw_kernels.hip", "gw_sort.hip", "table_build.hip", "context.cpp", "query_pipe.cpp", "table_load.cpp", "dbfile.cpp", "dbload.cpp", "builder.hip", "partset.cpp", "keyshard.hip", "keyset.cpp", "devcache.cpp", "align.hip", "classify.hip", "coverage.hip", "target_hits.hip", "evaluate.hip", "format.hip", "table_info.hip", "parse.hip", "parse_cut.hip", "input_device.hip", "merge_results.hip", "inflate.hip", "inflate_streams.hip", "taxmap.hip", "parse_targets.hip"]
+HEADERS = ["kernels.h", "table_rules.h", "read_class.h", "query_rules.h", "device_common.h", "context.h", "rccl_dl.h", "devcache.h", "rows_common.h", "parse_scan.h", "block_scan.h", "bgzf_rules.h", "gzip_rules.h", "inflate_wave.h", os.path.join(ROOT, "include", "metacache_amd.h")]
 ARCH = "gfx950"
 BINDIR = os.path.join(PKG, "bin")
 MCQ = os.path.join(BINDIR, "mcq")

@@ -445,12 +445,22 @@ struct TaxmapStep {
 // a file is added entirely here or entirely by the host loop.  MC_PARSE_IRREGULAR leaves the piece's files to the host loop, in order;
 // MC_PARSE_OVERFLOW (more records than the tables hold) is answered by one second call with grown tables; a library error leaves the rest
 // of the pass to the host loop.
+// MCQ_BUILD_INFLATE_DEVICE=1 beside it: a file with the gzip magic is no longer refused outright.  mc_gzip_hint on its
+// mapping decides; a file whose header the device takes and whose trailing ISIZE is at most MCQ_BUILD_INFLATE_MAX_MB (and a piece) joins
+// the piece as COMPRESSED bytes, counted with its trailing ISIZE.  The piece's gzip files go up in a second pinned buffer and ONE
+// mc_inflate_streams call (device form) writes each at its offset of dIn with out_cap = its trailing ISIZE; one wait brings the results
+// back.  All rows accepted with produced == out_cap: mc_parse_targets runs on the piece as before, and the headers come from
+// mc_parse_headers (the staging buffer does not hold those files' bytes).  The FIRST row that is not ends the piece: the files in front
+// of it are parsed and added, it goes through the host loop named "gzip: <reason>", the files behind it are a piece of their own.
 struct TargetParseStep {
     struct Mapped {
         int fd = -1; const char* p = nullptr; size_t n = 0;
+        bool gz = false; size_t plain = 0;                                        // a gzip file the step inflates: its trailing ISIZE
+        size_t size() const { return gz ? plain : n; }                            // the bytes it takes of a piece
         ~Mapped() { if (p) munmap((void*)p, n); if (fd >= 0) close(fd); }
     };
-    struct Segment { size_t fi; const char* data; size_t n; uint64_t recordBase; bool first; };   // a file, or a range of a cut one
+    // a file, or a range of a cut one: n plain bytes of the piece.  gz: data is the file's zn COMPRESSED bytes, n its trailing ISIZE
+    struct Segment { size_t fi; const char* data; size_t n; uint64_t recordBase; bool first; bool gz; size_t zn; };
     struct Buf { void* p = nullptr; size_t cap = 0; int kind = 0; };
 
     bool on = false, dead = false;
@@ -461,6 +471,15 @@ struct TargetParseStep {
     mc_ctx* ctx = nullptr;
     Buf hIn{nullptr, 0, 1}, hOff{nullptr, 0, 1}, hStatus{nullptr, 0, 1}, hHdr{nullptr, 0, 1}, hTargets{nullptr, 0, 1};
     Buf dIn, dOff, dStatus, dHdr, dTargets, dSeq, dWs;
+    // MCQ_BUILD_INFLATE_DEVICE=1: gzip files join a piece as compressed bytes and mc_inflate_streams writes them into dIn
+    bool inflateOn = false, inflateAlone = false;
+    // MCQ_BUILD_INFLATE_MAX_MB: plain bytes per gzip file.  A row is one wave's serial work and the piece waits for its longest row; 4 is
+    // where one row takes the device as long as gzread takes for a whole piece of 256 MiB on one host thread (measured: DESIGN.md 7n)
+    size_t inflateMax = (size_t)4 << 20;
+    uint64_t zCalls = 0, zFiles = 0, zBytesIn = 0, zBytesOut = 0;
+    std::vector<std::string> zLeft;          // "file: gzip: reason" of every gzip file that went to the host loop
+    Buf hZ{nullptr, 0, 1}, hRows{nullptr, 0, 1}, hResults{nullptr, 0, 1}, hText{nullptr, 0, 1}, hTextOff{nullptr, 0, 1};
+    Buf dZ, dRows, dResults, dZStatus, dText, dTextOff, dTextStatus, dTextWs;
     uint32_t recCap = 1u << 16;
     std::vector<Segment> segs;               // the piece being gathered
     std::vector<std::unique_ptr<Mapped>> maps;
@@ -470,11 +489,16 @@ struct TargetParseStep {
     {
         const char* sw = std::getenv("MCQ_BUILD_PARSE_DEVICE"); on = sw && std::atoi(sw) != 0;
         if (const char* p = std::getenv("MCQ_BUILD_PARSE_PIECE")) piece = (size_t)std::min<long long>(std::max<long long>(4096, std::atoll(p)), 1ll << 31);
+        const char* zw = std::getenv("MCQ_BUILD_INFLATE_DEVICE");
+        const bool zset = zw && std::atoi(zw) != 0;
+        inflateOn = zset && on; inflateAlone = zset && !on;
+        if (const char* p = std::getenv("MCQ_BUILD_INFLATE_MAX_MB")) inflateMax = (size_t)std::min<long long>(std::max<long long>(1, std::atoll(p)), 2048) << 20;
     }
     ~TargetParseStep()
     {
         if (!ctx) return;
         for (Buf* b : {&hIn, &hOff, &hStatus, &hHdr, &hTargets, &dIn, &dOff, &dStatus, &dHdr, &dTargets, &dSeq, &dWs}) mc_buffer_free(ctx, b->p, b->kind);
+        for (Buf* b : {&hZ, &hRows, &hResults, &hText, &hTextOff, &dZ, &dRows, &dResults, &dZStatus, &dText, &dTextOff, &dTextStatus, &dTextWs}) mc_buffer_free(ctx, b->p, b->kind);
         mc_destroy(ctx);
     }
     TargetParseStep(const TargetParseStep&) = delete;
@@ -500,6 +524,13 @@ struct TargetParseStep {
     bool copy(void* dst, const void* src, size_t n, int kind) { return mc_copy_results_on(ctx, dst, src, n, kind, nullptr) == MC_OK || die(mc_last_error(ctx)); }
     bool wait() { return mc_synchronize(ctx) == MC_OK || die(mc_last_error(ctx)); }
 
+    static const char* reason_word(uint32_t r)
+    {
+        static const char* const words[] = {"accepted", "block type", "stored lengths", "code lengths", "symbol", "distance", "input ends early", "more bytes than its trailing size",
+                                            "fewer bytes than its trailing size", "bytes left", "crc", "header", "trailing bytes"};
+        return r < sizeof words / sizeof words[0] ? words[r] : "unknown reason";
+    }
+
     // does the step take this file?  why: the reason where it does not
     std::unique_ptr<Mapped> take(const std::string& file, std::string& why) const
     {
@@ -511,7 +542,22 @@ struct TargetParseStep {
         if (sb.st_size == 0) { why = "empty"; return nullptr; }
         unsigned char magic[2] = {0, 0};
         if (pread(m->fd, magic, 2, 0) < 1) { why = "unreadable"; return nullptr; }
-        if (sb.st_size >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) { why = "gzip"; return nullptr; }
+        if (sb.st_size >= 2 && magic[0] == 0x1f && magic[1] == 0x8b) {
+            if (!inflateOn) { why = "gzip"; return nullptr; }
+            // the hint on the file's mapping decides: a header the device takes, and a trailing ISIZE within the cap and a piece
+            void* z = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, m->fd, 0);
+            if (z == MAP_FAILED) { why = "cannot be mapped"; return nullptr; }
+            m->p = (const char*)z; m->n = (size_t)sb.st_size;
+            uint64_t hint[4] = {0, 0, 0, 0};
+            if (mc_gzip_hint((const uint8_t*)m->p, m->n, hint) != MC_OK) { why = "gzip: no hint"; return nullptr; }
+            if (hint[0] != MC_GZIP_OK) { why = std::string("gzip: ") + reason_word((uint32_t)hint[3]); return nullptr; }
+            if (m->n > ((size_t)1 << 28)) { why = "gzip: more than 2^28 compressed bytes"; return nullptr; }
+            if (hint[2] == 0) { why = "gzip: a trailing size of 0"; return nullptr; }
+            if (hint[2] > inflateMax) { why = "gzip: larger than MCQ_BUILD_INFLATE_MAX_MB"; return nullptr; }
+            if (hint[2] > piece) { why = "gzip: larger than a piece"; return nullptr; }
+            m->gz = true; m->plain = (size_t)hint[2];
+            return m;
+        }
         if (magic[0] == '@') { why = "FASTQ"; return nullptr; }
         if (magic[0] != '>') { why = "does not begin with '>'"; return nullptr; }
         void* p = mmap(nullptr, (size_t)sb.st_size, PROT_READ, MAP_PRIVATE, m->fd, 0);
@@ -542,7 +588,7 @@ struct TargetParseStep {
         return true;
     }
 
-    void gather(size_t fi, std::unique_ptr<Mapped> m) { segs.push_back(Segment{fi, m->p, m->n, 0, true}); fill += m->n; maps.push_back(std::move(m)); }
+    void gather(size_t fi, std::unique_ptr<Mapped> m) { segs.push_back(Segment{fi, m->p, m->size(), 0, true, m->gz, m->n}); fill += m->size(); maps.push_back(std::move(m)); }
     void clear() { segs.clear(); maps.clear(); fill = 0; }
 
     // what a range of n bytes in nf files needs of seq: a sequence's padding exceeds what its record's '>' and line ends give back only
@@ -568,9 +614,18 @@ struct TargetParseStep {
         if (!rooms(n, nf, maxRecords)) return false;
         uint64_t* off = (uint64_t*)hOff.p;
         size_t at = 0;
-        for (uint32_t f = 0; f < nf; ++f) { off[f] = at; std::memcpy((char*)hIn.p + at, ss[f].data, ss[f].n); at += ss[f].n; }
+        bool anyGz = false;
+        for (uint32_t f = 0; f < nf; ++f) { off[f] = at; if (ss[f].gz) anyGz = true; else std::memcpy((char*)hIn.p + at, ss[f].data, ss[f].n); at += ss[f].n; }
         off[nf] = at;
-        if (!copy(dIn.p, hIn.p, n, 2) || !copy(dOff.p, hOff.p, ((size_t)nf + 1) * 8, 2)) return false;
+        if (!anyGz) { if (!copy(dIn.p, hIn.p, n, 2)) return false; }
+        else                                                                    // (the gzip files' ranges of dIn hold what inflate() wrote: only the runs of plain files go up)
+            for (uint32_t f = 0; f < nf;) {
+                uint32_t e = f;
+                while (e < nf && ss[e].gz == ss[f].gz) ++e;
+                if (!ss[f].gz && !copy((char*)dIn.p + off[f], (char*)hIn.p + off[f], off[e] - off[f], 2)) return false;
+                f = e;
+            }
+        if (!copy(dOff.p, hOff.p, ((size_t)nf + 1) * 8, 2)) return false;
         mc_parse_targets_output o{};
         o.hdr = (uint32_t*)dHdr.p; o.targets = (mc_parse_target*)dTargets.p; o.seq = (uint8_t*)dSeq.p; o.seq_capacity = maxRecords ? seq_bound(n, nf) : 0;
         o.status = (uint64_t*)dStatus.p; o.max_records = maxRecords;
@@ -580,6 +635,65 @@ struct TargetParseStep {
         if (maxRecords && (!copy(hHdr.p, dHdr.p, (size_t)maxRecords * 8, 1) || !copy(hTargets.p, dTargets.p, (size_t)maxRecords * sizeof(mc_parse_target), 1))) return false;
         if (!wait()) return false;
         std::memcpy(st, hStatus.p, 64);
+        return true;
+    }
+
+    // the piece's gzip files, uploaded as they are and inflated into dIn at their offsets by ONE mc_inflate_streams call (device form,
+    // out_cap = the trailing ISIZE); ONE wait brings the results back.  -1: every row was accepted with produced == out_cap (or there is
+    // no gzip file); >= 0: the first segment that was not, `word` says why; -2: the step died.  The bytes of the segments in front of
+    // a refused one are in dIn, contiguous from 0
+    int inflate(const std::vector<Segment>& ss, std::string& word)
+    {
+        size_t n = 0, zbytes = 0;
+        uint32_t nz = 0;
+        for (const Segment& s : ss) { if (s.gz) { zbytes = (zbytes + 15) / 16 * 16 + s.zn; ++nz; } n += s.n; }
+        if (!nz) return -1;
+        if (!(room(hZ, zbytes) && room(dZ, (zbytes + 15) / 16 * 16 + 16) && room(hRows, nz * sizeof(mc_gzip_stream)) && room(dRows, nz * sizeof(mc_gzip_stream)) &&
+              room(hResults, nz * sizeof(mc_gzip_result)) && room(dResults, nz * sizeof(mc_gzip_result)) && room(dZStatus, 32) && room(dIn, (n + 15) / 16 * 16 + 16))) return -2;
+        mc_gzip_stream* rows = (mc_gzip_stream*)hRows.p;
+        size_t at = 0, z = 0;
+        uint32_t k = 0;
+        for (const Segment& s : ss) {
+            if (s.gz) {
+                z = (z + 15) / 16 * 16;
+                std::memcpy((char*)hZ.p + z, s.data, s.zn);
+                rows[k++] = mc_gzip_stream{z, s.zn, at, s.n};
+                z += s.zn;
+            }
+            at += s.n;
+        }
+        if (!copy(dZ.p, hZ.p, zbytes, 2) || !copy(dRows.p, hRows.p, nz * sizeof(mc_gzip_stream), 2)) return -2;
+        if (mc_inflate_streams(ctx, (const uint8_t*)dZ.p, zbytes, (const mc_gzip_stream*)dRows.p, nz, 0, (uint8_t*)dIn.p, n, (mc_gzip_result*)dResults.p, (uint64_t*)dZStatus.p,
+                               nullptr) != MC_OK) { die(mc_last_error(ctx)); return -2; }
+        ++zCalls;
+        if (!copy(hResults.p, dResults.p, nz * sizeof(mc_gzip_result), 1) || !wait()) return -2;
+        const mc_gzip_result* res = (const mc_gzip_result*)hResults.p;
+        k = 0;
+        for (size_t f = 0; f < ss.size(); ++f) {
+            if (!ss[f].gz) continue;
+            const mc_gzip_result& r = res[k++];
+            if (r.reason) { word = reason_word(r.reason); return (int)f; }
+            if (r.produced != ss[f].n) { word = "fewer bytes than its trailing size"; return (int)f; }
+            ++zFiles; zBytesIn += ss[f].zn; zBytesOut += r.produced;
+        }
+        return -1;
+    }
+
+    // the headers of a parsed piece that holds gzip files, packed by mc_parse_headers from dIn (the staging buffer does not hold those
+    // files' bytes) and downloaded: hText, hTextOff.  false: why says so
+    bool headers(size_t n, uint64_t recs, std::string& why)
+    {
+        const uint32_t* hdr = (const uint32_t*)hHdr.p;
+        size_t total = 0;
+        for (uint64_t r = 0; r < recs; ++r) total += hdr[2 * r + 1];
+        const uint64_t wsBytes = mc_parse_headers_scratch_bytes((uint32_t)recs);
+        if (!(room(dText, total + 16) && room(hText, total + 16) && room(dTextOff, (recs + 1) * 8) && room(hTextOff, (recs + 1) * 8) && room(dTextStatus, 32) &&
+              room(dTextWs, wsBytes + 16))) { why = deadWhy; return false; }
+        if (mc_parse_headers(ctx, (const char*)dIn.p, n, (const uint32_t*)dHdr.p, (const uint64_t*)dStatus.p, (uint32_t)recs, 0, (char*)dText.p, total, (uint64_t*)dTextOff.p,
+                             (uint64_t*)dTextStatus.p, dTextWs.p, wsBytes, nullptr) != MC_OK) { die(mc_last_error(ctx)); why = deadWhy; return false; }
+        if ((total && !copy(hText.p, dText.p, total, 1)) || !copy(hTextOff.p, dTextOff.p, (recs + 1) * 8, 1) || !copy(hStatus.p, dTextStatus.p, 32, 1) || !wait()) { why = deadWhy; return false; }
+        const uint64_t* st = (const uint64_t*)hStatus.p;
+        if (st[2] != MC_PARSE_OK || st[0] != recs || st[1] != total) { why = "headers: verdict " + std::to_string(st[2]); return false; }
         return true;
     }
 
@@ -600,6 +714,11 @@ struct TargetParseStep {
         }
         if (st[4] != MC_PARSE_OK) { why = "verdict " + std::to_string(st[4]); return false; }
         const uint64_t recs = st[0];                                            // (<= recCap: rows [0, recs) of hdr and targets came back with status)
+        bool anyGz = false;
+        size_t pieceBytes = 0;
+        for (const Segment& s : ss) { anyGz = anyGz || s.gz; pieceBytes += s.n; }
+        if (anyGz && recs && !headers(pieceBytes, recs, why)) return false;
+        const uint64_t* textOff = (const uint64_t*)hTextOff.p;
         const uint32_t* hdr = (const uint32_t*)hHdr.p;
         const mc_parse_target* tg = (const mc_parse_target*)hTargets.p;
         uint64_t r = 0;
@@ -607,7 +726,8 @@ struct TargetParseStep {
             const int64_t fileTax = prologue(ss[f]);
             for (; r < recs && tg[r].file == f; ++r) {
                 if (tg[r].len == 0) continue;                                   // building.cpp:295
-                add_record(ss[f], fileTax, ss[f].recordBase + tg[r].index, std::string((const char*)hIn.p + hdr[2 * r], hdr[2 * r + 1]), (size_t)tg[r].len,
+                add_record(ss[f], fileTax, ss[f].recordBase + tg[r].index,
+                           anyGz ? std::string((const char*)hText.p + textOff[r], textOff[r + 1] - textOff[r]) : std::string((const char*)hIn.p + hdr[2 * r], hdr[2 * r + 1]), (size_t)tg[r].len,
                            (const char*)dSeq.p + tg[r].seq_off);
                 ++targets;
             }
@@ -660,6 +780,15 @@ struct TargetParseStep {
             if (ctx) { mc_timing_get(ctx, "targets_classify", &classifyMs, &n); mc_timing_get(ctx, "targets_write", &writeMs, &n); }
             std::cerr << "mcq profile: reference sequences parsed on the device: " << calls << " mc_parse_targets calls, " << bytes << " bytes, " << records << " records, "
                       << targets << " targets, kernels " << classifyMs << " + " << writeMs << " ms, " << files << " files, " << left.size() << " files left to the host" << list << "\n";
+        }
+        if (profile && inflateOn) {
+            double ms = 0; uint64_t n = 0;
+            if (ctx) mc_timing_get(ctx, "inflate_streams", &ms, &n);
+            std::string zlist;
+            for (const auto& l : zLeft) zlist += (zlist.empty() ? " (" : "; ") + l;
+            if (!zlist.empty()) zlist += ")";
+            std::cerr << "mcq profile: gzip references inflated on the device: " << zFiles << " files, " << zBytesIn << " bytes in, " << zBytesOut << " bytes out, " << zCalls
+                      << " mc_inflate_streams calls, kernels " << ms << " ms, " << zLeft.size() << " gzip files left to the host" << zlist << "\n";
         }
         if (!left.empty() && (profile || info))
             std::cerr << "mcq: reference sequences of " << left.size() << " files parsed on the host" << list << (dead ? " [the device parse stopped: " + deadWhy + "]" : "") << "\n";
@@ -847,6 +976,7 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
     };
     TargetParseStep parse;                                                     // MCQ_BUILD_PARSE_DEVICE=1: plain FASTA files are cut by the library, piece by piece
     if (parse.on) parse.begin(c.device);
+    if (parse.inflateAlone && info) std::cerr << "mcq: MCQ_BUILD_INFLATE_DEVICE=1 has no effect without MCQ_BUILD_PARSE_DEVICE=1\n";
     auto device_prologue = [&](const TargetParseStep::Segment& s) -> int64_t { if (s.first) announce(s.fi); return file_taxid(s.fi, s.first); };   // (a later range of a cut file: its lines are out)
     auto device_record = [&](const TargetParseStep::Segment& s, int64_t fileTax, uint64_t r, const std::string& header, size_t len, const char* dseq) {
         const std::string& filename = o.infiles[s.fi];
@@ -854,26 +984,43 @@ inline void build_database(const BuildOptions& o, BuiltDatabase& db)
                    [&](mc_builder* b, const char* sid, int64_t parent) { return mc_build_add_target_device(b, dseq, len, sid, parent, filename.c_str(), r); });
     };
     // the gathered piece goes through the library; where it refuses, the piece's files go through the host loop, in order
+    // Its gzip files are inflated first; the first one the device refuses ends the piece: the files in front of it are parsed and added (their
+    // bytes lie in the piece from 0), that file goes through the host loop, the files behind it are a piece of their own.  Order stays
     auto drain = [&]() {
         if (parse.segs.empty()) return;
-        std::string why;
-        const std::vector<TargetParseStep::Segment> ss = parse.segs;
-        if (parse.run(ss, why, db.bs, device_prologue, device_record)) parse.files += ss.size();
-        else for (const auto& s : ss) { parse.left.push_back(o.infiles[s.fi] + ": " + why); host_file(s.fi); }
+        std::vector<TargetParseStep::Segment> ss = parse.segs;
+        while (!ss.empty()) {
+            std::string why, word;
+            const int bad = parse.dead ? -2 : parse.inflate(ss, word);
+            if (bad == -2) {
+                for (const auto& s : ss) { parse.left.push_back(o.infiles[s.fi] + ": " + parse.deadWhy); host_file(s.fi); }
+                break;
+            }
+            const std::vector<TargetParseStep::Segment> head(ss.begin(), bad < 0 ? ss.end() : ss.begin() + bad);
+            if (!head.empty()) {
+                if (parse.run(head, why, db.bs, device_prologue, device_record)) parse.files += head.size();
+                else for (const auto& s : head) { parse.left.push_back(o.infiles[s.fi] + ": " + why); host_file(s.fi); }
+            }
+            if (bad < 0) break;
+            parse.left.push_back(o.infiles[ss[bad].fi] + ": gzip: " + word);
+            parse.zLeft.push_back(parse.left.back());
+            host_file(ss[bad].fi);
+            ss.erase(ss.begin(), ss.begin() + bad + 1);
+        }
         parse.clear();
     };
     for (size_t fi = 0; fi < o.infiles.size(); ++fi) {
         if (!parse.on) { host_file(fi); continue; }
         std::string why = parse.deadWhy;
         std::unique_ptr<TargetParseStep::Mapped> m = parse.dead ? nullptr : parse.take(o.infiles[fi], why);
-        if (m && m->n > parse.piece) {                                         // a file of several pieces: on its own
+        if (m && m->size() > parse.piece) {                                    // a file of several pieces: on its own (never a gzip file: take leaves those to the host)
             drain();
             if (!parse.dead && parse.run_cut_file(fi, *m, why, db.bs, device_prologue, device_record)) { ++parse.files; continue; }
             if (parse.dead) why = parse.deadWhy;
             m.reset();
         }
-        if (!m) { drain(); parse.left.push_back(o.infiles[fi] + ": " + why); host_file(fi); continue; }
-        if (parse.fill + m->n > parse.piece) drain();
+        if (!m) { drain(); parse.left.push_back(o.infiles[fi] + ": " + why); if (why.compare(0, 5, "gzip:") == 0) parse.zLeft.push_back(parse.left.back()); host_file(fi); continue; }
+        if (parse.fill + m->size() > parse.piece) drain();
         if (parse.dead) { parse.left.push_back(o.infiles[fi] + ": " + parse.deadWhy); host_file(fi); continue; }
         parse.gather(fi, std::move(m));
     }
