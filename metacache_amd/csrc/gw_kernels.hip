@@ -18,9 +18,11 @@
 // locations per lane, the read's whole list held in registers between the filter's two phases (no second pass over the fabric),
 // 24-bit multiplies (full rate; v_mul_lo_u32 is a quarter-rate instruction), one LDS operation per location and phase.
 #include "device_common.h"
+#include "query_rules.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace mcamd {
 
@@ -151,6 +153,18 @@ struct GwFrame {
     }
 };
 
+// The frame of a kernel instance whose window range is a template parameter (gw_filter_count_kernel<.., MAXWIN>: one range of 2 or 3 windows for
+// all reads, so 64 D <= 128 and the blocks are the smallest ones, 2^8): every field is a constant of the instruction stream -- no
+// scalar registers carried through the read, no vector register for the shift.
+template <uint32_t MAXWIN>
+struct GwFrameFixed {
+    static_assert(MAXWIN >= 2 && 64u * (MAXWIN - 1u) <= 256u, "gw_block_shift(MAXWIN) == 8");
+    static constexpr uint32_t D = MAXWIN - 1u, A = 8u, blockMask = (1u << A) - 1u, inner = (1u << A) - 2u * D;
+    static constexpr uint32_t sh = 32u - A, Dsh = D << sh, twoDsh = (2u * D) << sh;
+    __device__ __forceinline__ explicit GwFrameFixed(uint32_t) {}
+    __device__ __forceinline__ bool edge(uint32_t v) const { return (v << sh) + Dsh < twoDsh; }
+};
+
 // round table of the batch [r0, r0 + kGwRounds) of an entry chunk's rounds: first index | numbers << 40.  start / myR: the lane's entry
 // begins at round 'start' of the chunk and has myR rounds.
 __device__ __forceinline__ void gw_fill_rounds(uint64_t* T, uint32_t lane, uint32_t r0, uint32_t Rc, uint32_t start, uint32_t myR, uint32_t sz, uint64_t pay)
@@ -224,21 +238,27 @@ __device__ __forceinline__ uint4 gw_left_as_is()
 // value -- and masks the result): one move per load made instead of four.  The registers of a load NOT made keep the four constants,
 // though the three loops behind the loads leave at nl and never read them: left as they are they stayed live across both phases, and
 // the last load's four were spilled (13 registers instead of 2; docs/LAB_NOTEBOOK_r10.md section 2).
-template <bool BARE = false>
-__device__ __forceinline__ void gw_load_rounds(const uint64_t* T, const uint32_t* __restrict__ values32, uint32_t grp, uint32_t sub4, uint4 (&x)[kGwLoads],
-                                               uint32_t nl = kGwLoads)   // nl: loads of this batch that have rounds at all (wave-uniform: the others are skipped)
+// PACK (the shape-fixed instances of gw_filter_count_kernel): the lane's places per load, three bits each as gw_pack_rems makes them, are
+// put together HERE, from the round-table word that is in a register for the `sub4 < count` test anyway -- gw_pack_rems reads the table
+// from LDS a second time.  Returns them (0 without PACK).
+template <bool BARE = false, bool PACK = false>
+__device__ __forceinline__ uint32_t gw_load_rounds(const uint64_t* T, const uint32_t* __restrict__ values32, uint32_t grp, uint32_t sub4, uint4 (&x)[kGwLoads],
+                                                   uint32_t nl = kGwLoads)   // nl: loads of this batch that have rounds at all (wave-uniform: the others are skipped)
 {
+    uint32_t packed = 0;
 #pragma unroll
     for (uint32_t u = 0; u < kGwLoads; ++u) {
         x[u] = make_uint4(kGwNone, kGwNone, kGwNone, kGwNone);
         if (u >= nl) continue;
         if constexpr (BARE) { x[u] = gw_left_as_is(); x[u].x = kGwNone; }
         const uint64_t rd = T[u * 16 + grp];
+        if constexpr (PACK) { const uint32_t cnt = (uint32_t)(rd >> 40); packed |= (cnt > sub4 ? min(cnt - sub4, 4u) : 0u) << (3u * u); }
         if (sub4 < (uint32_t)(rd >> 40)) {
             const U4 t = *reinterpret_cast<const U4*>(values32 + (rd & 0xFFFFFFFFFFull) + sub4);
             x[u] = make_uint4(t.x, t.y, t.z, t.w);
         }
     }
+    return packed;
 }
 // LEAVE (the three loops below that follow the loads; gw_filter_count_kernel<LOOKUP>): the unrolled loop is left at the first load without
 // rounds -- a scalar compare and a branch per load -- instead of skipping every such load under a condition of its own: the compiler kept
@@ -268,8 +288,8 @@ __device__ __forceinline__ uint32_t gw_reserve(uint32_t* shared, uint32_t tot)
 // FINE: the filter's blocks hold 2^A >= D numbers only -- a neighbour lies in the same block (marked twice) or in one of the two next to
 // it (seen): three lookups instead of one and an edge rule, for reads whose tens of thousands of locations leave no block of 64 D
 // numbers without a second one (gw_filter_stream_kernel<.., FINE>)
-template <class Bloom, bool FINE = false>
-__device__ __forceinline__ void gw_take(const uint32_t* bits, const GwFrame& F, GwSink& S, uint32_t v, bool valid)
+template <class Bloom, bool FINE = false, class Frame>
+__device__ __forceinline__ void gw_take(const uint32_t* bits, const Frame& F, GwSink& S, uint32_t v, bool valid)
 {
     const uint32_t key = v >> F.A;
     const bool keep = valid & (FINE ? (Bloom::twice(bits, key) | Bloom::seen(bits, key - 1u) | Bloom::seen(bits, key + 1u)) : (Bloom::twice(bits, key) | F.edge(v)));
@@ -291,8 +311,8 @@ __device__ __forceinline__ void gw_take(const uint32_t* bits, const GwFrame& F, 
 //                is valid only while n2 <= S.room: for sinks whose list is dropped when n2 passes the room (gw_filter_count_kernel<LOOKUP>'s
 //                kept numbers in LDS; a compare per store, and either form in the instances without LOOKUP, cost registers: notebook r10).
 constexpr int kGwFits = 0, kGwLaneRoom = 1, kGwWaveRoom = 2;
-template <class Bloom, int CHECK, bool FINE = false>
-__device__ __forceinline__ void gw_take4(const uint32_t* bits, const GwFrame& F, GwSink& S, const uint4 x, const int32_t rem)
+template <class Bloom, int CHECK, bool FINE = false, class Frame>
+__device__ __forceinline__ void gw_take4(const uint32_t* bits, const Frame& F, GwSink& S, const uint4 x, const int32_t rem)
 {
     const uint32_t v[4] = {x.x, x.y, x.z, x.w};
     uint32_t m[4], wd[4];
@@ -354,8 +374,8 @@ __device__ __forceinline__ void gw_take4(const uint32_t* bits, const GwFrame& F,
     }
     S.n2 = n2;
 }
-template <class Bloom, int CHECK, bool FINE = false>
-__device__ __forceinline__ void gw_take_rounds(const uint32_t* bits, const uint64_t* T, const GwFrame& F, GwSink& S, uint32_t grp, uint32_t sub4,
+template <class Bloom, int CHECK, bool FINE = false, class Frame>
+__device__ __forceinline__ void gw_take_rounds(const uint32_t* bits, const uint64_t* T, const Frame& F, GwSink& S, uint32_t grp, uint32_t sub4,
                                                const uint4 (&x)[kGwLoads], uint32_t nl = kGwLoads)
 {
 #pragma unroll
@@ -380,8 +400,8 @@ __device__ __forceinline__ uint32_t gw_pack_rems(const uint64_t* T, uint32_t grp
     }
     return packed;
 }
-template <class Bloom, int CHECK, bool LEAVE = false>
-__device__ __forceinline__ void gw_take_rounds_packed(const uint32_t* bits, const uint32_t packed, const GwFrame& F, GwSink& S, const uint4 (&x)[kGwLoads], uint32_t nl)
+template <class Bloom, int CHECK, bool LEAVE = false, class Frame>
+__device__ __forceinline__ void gw_take_rounds_packed(const uint32_t* bits, const uint32_t packed, const Frame& F, GwSink& S, const uint4 (&x)[kGwLoads], uint32_t nl)
 {
 #pragma unroll
     for (uint32_t u = 0; u < kGwLoads; ++u) {
@@ -910,21 +930,22 @@ __device__ __forceinline__ uint32_t gw_pick(const uint32_t* ck, const uint32_t C
 // The K winners of a read (lane i: number, hits, end - begin; target wt with its numbers [wlo, whi) looked up by the caller) -> the
 // candidates.  Returns true when two winners are one target (region striking met another region of a picked target): the caller hands
 // the read to the exact wave kernel.
-template <bool TAX>
+// KN: the most winners there can be (kLaneK; gw_filter_count_kernel<.., KFIX>: the instance's K)
+template <bool TAX, uint32_t KN = kLaneK>
 __device__ __forceinline__ bool gw_winners_out(const uint32_t lane, const uint32_t K, const uint32_t wv, const uint32_t wh, const uint32_t wd,
                                                const uint32_t wt, const uint32_t wlo, const uint32_t whi, mc_candidate_dev* __restrict__ out,
-                                               uint32_t (&pickLo)[kLaneK], uint32_t (&pickHi)[kLaneK])
+                                               uint32_t (&pickLo)[KN], uint32_t (&pickHi)[KN])
 {
     bool again = false;
     if constexpr (!TAX) {
 #pragma unroll
-        for (uint32_t i = 0; i + 1 < kLaneK; ++i) {
+        for (uint32_t i = 0; i + 1 < KN; ++i) {
             const uint32_t ti = rdlane(wt, i);
             again = again || (__ballot(lane > i && lane < K && wt == ti && ti != 0xFFFFFFFFu) != 0);
         }
     }
 #pragma unroll
-    for (uint32_t i = 0; i < kLaneK; ++i) { pickLo[i] = rdlane(wlo, i); pickHi[i] = rdlane(whi, i); }
+    for (uint32_t i = 0; i < KN; ++i) { pickLo[i] = rdlane(wlo, i); pickHi[i] = rdlane(whi, i); }
     if (lane < K) {
         mc_candidate_dev e; e.tgt = wt; e.hits = wh; e.end = wv - wlo; e.beg = e.end - wd;
         if (wv == kGwNone) { e.tgt = 0xFFFFFFFFu; e.hits = 0; e.beg = 0; e.end = 0; }
@@ -1015,7 +1036,7 @@ struct GwPend {
         b0 = b1 = b2 = 0u;                                         // (set on every way through: nothing of them is carried from read to read)
         if (pend && wv != kGwNone) { b0 = tab.gwBase[dir]; b1 = tab.gwBase[dir + 1]; b2 = tab.gwBase[min(dir + 2, tab.gwTargets)]; }
     }
-    template <bool TAX, class Ent>
+    template <bool TAX, uint32_t KN = kLaneK, class Ent>
     __device__ __forceinline__ void finish(const uint32_t lane, const uint32_t K, const DeviceTable& tab, const Workspace& ws, mc_candidate_dev* __restrict__ cands, const Ent& ent)   // stage 2
     {
         if (!pend) return;
@@ -1025,8 +1046,8 @@ struct GwPend {
             if (wv >= b1) { ++t; lo = b1; hi = b2; }
             while (wv >= hi) { ++t; lo = hi; hi = tab.gwBase[t + 1]; }
         }
-        uint32_t plo[kLaneK], phi[kLaneK];
-        const bool again = gw_winners_out<TAX>(lane, K, wv, whd & 0xFFFFu, whd >> 16, t, lo, hi, cands + (size_t)q * K, plo, phi);
+        uint32_t plo[KN], phi[KN];
+        const bool again = gw_winners_out<TAX, KN>(lane, K, wv, whd & 0xFFFFu, whd >> 16, t, lo, hi, cands + (size_t)q * K, plo, phi);
         if (again) ent.leave(ws, tab, q, lane);                    // (the read BEFORE the one the caller is at)
         if (lane == 0) {
             if (again) { ws.hitScan[q] = ws.qstat[q].hits; ws.qflag[q] = kFlagCands; }
@@ -1043,7 +1064,8 @@ struct GwPend {
 // LONG (first instance's table only): the list may hold up to 2^LOG2S numbers as long as no more than half of them are DISTINCT (a filtered
 // list of 400 numbers has about 100 distinct ones); a list with more goes to the exact wave kernel.
 // ent: where the read's hand-over entries are (GwEntRecord / GwEntLookup)
-template <uint32_t LOG2S, bool TAX, bool DEFER, bool LONG = false, class GetV, class Ent>
+// KN: the lanes' lists of step D and the winners' bounds hold this many (kLaneK; gw_filter_count_kernel<.., KFIX>: K itself, a constant there)
+template <uint32_t LOG2S, bool TAX, bool DEFER, bool LONG = false, uint32_t KN = kLaneK, class GetV, class Ent>
 __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, const uint32_t n2, const uint32_t maxWin, GetV&& getv,
                                               uint2* slots, uint32_t* ck, uint64_t* T, const uint32_t lane, const uint32_t grp, const uint32_t sub4,
                                               const uint32_t K, const uint32_t* __restrict__ taxkey, const DeviceTable& tab, const Workspace& ws,
@@ -1056,9 +1078,9 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
         for (uint32_t i = 0; i < kSlots * 8 / 16 / 64; ++i) k4[i * 64 + lane] = make_uint4(kGwNone, 0u, kGwNone, 0u);
     }
     wave_lds_sync();
-    uint32_t pickLo[kLaneK], pickHi[kLaneK];
+    uint32_t pickLo[KN], pickHi[KN];
 #pragma unroll
-    for (uint32_t i = 0; i < kLaneK; ++i) { pickLo[i] = 0; pickHi[i] = 0; }
+    for (uint32_t i = 0; i < KN; ++i) { pickLo[i] = 0; pickHi[i] = 0; }
     uint32_t strong = 0, wv = kGwNone, wh = 0, wd = 0;
     bool again = false;
     mc_candidate_dev* out = cands + (size_t)q * K;
@@ -1093,7 +1115,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
     wave_lds_sync();
     if constexpr (LONG) {
         if (C > kList) {                                           // more distinct numbers than the table is made for (the neighbour lookups need free slots):
-            if constexpr (DEFER) P.template finish<TAX>(lane, K, tab, ws, cands, ent);   // the caller sends the list on (false)
+            if constexpr (DEFER) P.template finish<TAX, KN>(lane, K, tab, ws, cands, ent);   // the caller sends the list on (false)
             wave_lds_sync();
             return false;
         }
@@ -1111,7 +1133,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
     }
     strong = __builtin_amdgcn_readfirstlane(strong);
     if constexpr (DEFER) {
-        P.template finish<TAX>(lane, K, tab, ws, cands, ent);      // the previous read's candidates
+        P.template finish<TAX, KN>(lane, K, tab, ws, cands, ent);      // the previous read's candidates
         if (strong >= K) {                                         // this read's: later
             P.pend = true; P.q = q; P.wv = wv; P.whd = wh | (wd << 16);
             P.dir = wv != kGwNone ? tab.gwDir[wv >> tab.gwDirShift] : 0u;
@@ -1122,7 +1144,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
     {
         uint32_t wt = 0xFFFFFFFFu, wlo = 0, whi = 0;
         if (wv != kGwNone) tab.gw_target_bounds(wv, wt, wlo, whi);
-        again = gw_winners_out<TAX>(lane, K, wv, wh, wd, wt, wlo, whi, out, pickLo, pickHi);
+        again = gw_winners_out<TAX, KN>(lane, K, wv, wh, wd, wt, wlo, whi, out, pickLo, pickHi);
     }
     bool done = true;
     if (again) {                                                   // two winners of one target: the exact wave kernel
@@ -1146,22 +1168,22 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
             ent.load(ws, tab, q, fbase, nent, lane, sz, pay);
             const uint32_t myR = sz > 1 ? (sz + 15u) >> 4 : 0u;
             const uint32_t incl = wave_incl_scan_u32(myR, lane), Rc = rdlane(incl, 63), start = incl - myR;
-            // every lane keeps the kLaneK smallest numbers it sees (several may be one target's: the rounds below strike whole
+            // every lane keeps the KN (kLaneK) smallest numbers it sees (several may be one target's: the rounds below strike whole
             // targets, and a lane that had to drop numbers and is left with none cannot vouch for its minimum any more)
-            uint32_t best[kLaneK];
+            uint32_t best[KN];
 #pragma unroll
-            for (uint32_t i = 0; i < kLaneK; ++i) best[i] = kGwNone;
+            for (uint32_t i = 0; i < KN; ++i) best[i] = kGwNone;
             uint32_t seen = 0;
             auto visit = [&](uint32_t g, bool valid) {
                 if (!valid) return;
                 bool skip = false;
 #pragma unroll
-                for (uint32_t i = 0; i < kLaneK; ++i) skip = skip || (i < strong && g - pickLo[i] < pickHi[i] - pickLo[i]);
+                for (uint32_t i = 0; i < KN; ++i) skip = skip || (i < strong && g - pickLo[i] < pickHi[i] - pickLo[i]);
                 if (skip) return;
                 ++seen;
                 uint32_t c = g;                                     // sorted insert, the largest falls out
 #pragma unroll
-                for (uint32_t i = 0; i < kLaneK; ++i) { const uint32_t lo = min(best[i], c); c = max(best[i], c); best[i] = lo; }
+                for (uint32_t i = 0; i < KN; ++i) { const uint32_t lo = min(best[i], c); c = max(best[i], c); best[i] = lo; }
             };
             visit(sz == 1 ? tab.gw_of(pay) : kGwNone, sz == 1);
             for (uint32_t r0 = 0; r0 < Rc; r0 += kGwRounds) {
@@ -1180,7 +1202,7 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
                 }
                 wave_lds_sync();
             }
-            const bool dropped = seen > kLaneK;
+            const bool dropped = seen > KN;
             bool unsure = false;
             for (uint32_t rnd = strong; rnd < K; ++rnd) {
                 if (__ballot(dropped && best[0] == kGwNone)) { unsure = true; break; }
@@ -1190,19 +1212,19 @@ __device__ __forceinline__ bool gw_count_read(const uint32_t q, const Ent& ent, 
                     const uint32_t t = tab.gw_target(m), lo = tab.gwBase[t], hi = tab.gwBase[t + 1];
                     e.tgt = t; e.hits = 1; e.beg = e.end = m - lo;
                     // that target leaves every lane's list (its numbers are neighbours in the sorted list: compact the rest)
-                    uint32_t kept[kLaneK];
+                    uint32_t kept[KN];
 #pragma unroll
-                    for (uint32_t i = 0; i < kLaneK; ++i) kept[i] = kGwNone;
+                    for (uint32_t i = 0; i < KN; ++i) kept[i] = kGwNone;
                     uint32_t n = 0;
 #pragma unroll
-                    for (uint32_t i = 0; i < kLaneK; ++i) {
+                    for (uint32_t i = 0; i < KN; ++i) {
                         const bool stay = best[i] != kGwNone && !(best[i] - lo < hi - lo);
 #pragma unroll
-                        for (uint32_t j = 0; j < kLaneK; ++j) if (stay && j == n) kept[j] = best[i];
+                        for (uint32_t j = 0; j < KN; ++j) if (stay && j == n) kept[j] = best[i];
                         n += stay ? 1u : 0u;
                     }
 #pragma unroll
-                    for (uint32_t i = 0; i < kLaneK; ++i) best[i] = kept[i];
+                    for (uint32_t i = 0; i < KN; ++i) best[i] = kept[i];
                 }
                 if (lane == 0) out[rnd] = e;
             }
@@ -1317,10 +1339,22 @@ constexpr uint32_t kGwCounted = 0x80000000u;      // record of kListFiltered: th
 // atomic each, they are few).  The hand-over entries (found features only, singletons first; the slots up to nf cleared) are written
 // for those two kinds of reads ONLY (round 8: lk_store_entries) -- a read the kernel finishes, 59 in 60 at RefSeq scale,
 // is never visited again (what the stores' share of the kernel's write requests was: docs/LAB_NOTEBOOK_r08.md).
-template <uint32_t WAVES, uint32_t TLOG2, bool TAX, uint32_t WPE = MC_GW_FILTER_WPE, bool LOOKUP = false>
-__global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchView b, DeviceTable tab, Workspace ws, uint32_t K, const uint32_t* __restrict__ taxkey,
+//
+// MAXWIN, KFIX (round 11, LOOKUP only; 0, 0: any batch): the instance of a batch whose reads all have ONE window range of MAXWIN = 2 or 3 windows
+// (no range per read) and whose candidate count is KFIX = 1 or 2 -- the host's rule is lookup_shape (query_rules.h).  What the other instance
+// carries in registers through every read is a constant of the instruction stream here: the frame (GwFrameFixed: blocks of 2^8 numbers, no
+// shift register), the one or two neighbour windows of gw_pick, the K rounds, and the winners' bounds, GwPend and step D are sized by KFIX
+// instead of kLaneK.  The range is at most kHashWin, so a read's kept numbers always go to LDS first (`here`).
+template <uint32_t WAVES, uint32_t TLOG2, bool TAX, uint32_t WPE = MC_GW_FILTER_WPE, bool LOOKUP = false, uint32_t MAXWIN = 0, uint32_t KFIX = 0>
+__global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchView b, DeviceTable tab, Workspace ws, uint32_t Kany, const uint32_t* __restrict__ taxkey,
                                                                                  mc_candidate_dev* __restrict__ cands, const uint32_t s)
 {
+    static_assert((MAXWIN == 0) == (KFIX == 0) && (MAXWIN == 0 || LOOKUP), "shape-fixed instances: LOOKUP, both the window range and the candidate count");
+    static_assert(MAXWIN <= kHashWin && KFIX <= kLaneK, "a fixed range is counted in LDS, a fixed K fits the lanes' lists");
+    constexpr bool kFixed = MAXWIN != 0;
+    constexpr uint32_t KN = kFixed ? KFIX : kLaneK;
+    const uint32_t K = kFixed ? KFIX : Kany;
+    using Frame = std::conditional_t<kFixed, GwFrameFixed<kFixed ? MAXWIN : 2u>, GwFrame>;
     using Bloom = GwBloom<TLOG2, TLOG2>;
     constexpr uint32_t kKeep = WPE >= 6 ? 384 : 512;               // numbers kept in LDS: the counting takes them when at most 256 are distinct
                                                                    // (WPE >= 6: 384 -- 26 KB of LDS per block, six blocks per CU, 80 registers: six waves per SIMD, "gw_fuse" 6)
@@ -1426,7 +1460,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             const uint32_t n1 = (uint32_t)__popcll(sm), lsz = sz > 1u ? sz : 0u;
             const uint32_t lincl = wave_incl_scan_u32(lsz, lane);
             H = n1 + rdlane(lincl, 63);
-            maxWin = b.max_win(q);
+            maxWin = kFixed ? MAXWIN : b.max_win(q);
             if (lane == 0) { QueryStat qs; qs.hits = H; qs.nfeat = nfeat; qs.nfound = nent; qs.nsteps = nfeat; ws.qstat[q] = qs; }
             if (H == 0) {                                          // nothing found: empty candidates, as the lane kernel leaves them
                 if (lane < K) { mc_candidate_dev ev; ev.tgt = 0xFFFFFFFFu; ev.hits = 0; ev.beg = 0; ev.end = 0; cands[(size_t)q * K + lane] = ev; }
@@ -1477,18 +1511,17 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         if constexpr (!kSeven) clear_bits();
         gw_fill_rounds_scan(T, kept, lane, Rc, incl - myR, myR, sz, pay);   // (kept: free until phase B)
         wave_lds_sync();
-        const GwFrame F(maxWin);
+        const Frame F(maxWin);
         const uint32_t nl = (Rc + 15u) >> 4;
         // the singleton's gwBase word is requested in front of the list loads and taken behind them (tab.gw_of in two halves: no wait
         // between its load and the list loads; lanes without a singleton: kGwNone + 0)
         const uint32_t svLow = sz == 1 ? (uint32_t)pay : 0u;
         const uint32_t svBase = sz == 1 ? tab.gwBase[(uint32_t)(pay >> 32)] : kGwNone;
         uint4 x[kGwLoads];
-        gw_load_rounds<LOOKUP>(T, tab.values32, grp, sub4, x, nl);
+        uint32_t rems = gw_load_rounds<LOOKUP, kFixed>(T, tab.values32, grp, sub4, x, nl);   // (kFixed: with the places per load, else 0)
         uint32_t svTop = svBase;
-        uint32_t rems = 0;
         if constexpr (kSeven) {                                    // the table has been read: its place is the filter's now
-            rems = gw_pack_rems<LOOKUP>(T, grp, sub4, nl);
+            if constexpr (!kFixed) rems = gw_pack_rems<LOOKUP>(T, grp, sub4, nl);
             hide_lane();
             wave_lds_sync();
             clear_bits();
@@ -1507,7 +1540,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
         gw_mark_rounds<Bloom, LOOKUP>(bits, x, F.A, nl);
         hide_lane();
         wave_lds_sync();
-        const bool here = maxWin <= kHashWin;
+        const bool here = kFixed || maxWin <= kHashWin;            // (a fixed range: always, the pool form of phase B below is only the repeat of a list beyond kKeep)
         uint32_t n2;
         if (here) {
             GwSink S{kept, kKeep, 0u};
@@ -1526,7 +1559,7 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
             if constexpr (!LOOKUP) { if (lane == 0) outRec[w] = make_uint4(q, 0u, kGwCounted | n2, maxWin); }   // (LOOKUP: a read finished here has no record)
             wave_lds_sync();
             auto count = [&](const auto& ent) {
-                return gw_count_read<9, TAX, true, true>(q, ent, n2, maxWin,
+                return gw_count_read<9, TAX, true, true, KN>(q, ent, n2, maxWin,
                                         [&](uint32_t r) -> uint32_t { return r * 64 + lane < n2 ? kept[r * 64 + lane] : kGwNone; },
                                         reinterpret_cast<uint2*>(bits), kSeven ? kept : reinterpret_cast<uint32_t*>(T), kSeven ? reinterpret_cast<uint64_t*>(kept) : T,
                                         lane, grp, sub4, K, taxkey, tab, ws, cands, P);
@@ -1575,8 +1608,8 @@ __global__ __launch_bounds__(WAVES * 64, WPE) void gw_filter_count_kernel(BatchV
       if (!advanced) advance();
     }
     P.bases(tab);
-    if constexpr (LOOKUP) P.template finish<TAX>(lane, K, tab, ws, cands, GwEntLookup{0u, 0u, s});
-    else P.template finish<TAX>(lane, K, tab, ws, cands, GwEntRecord{work});
+    if constexpr (LOOKUP) P.template finish<TAX, KN>(lane, K, tab, ws, cands, GwEntLookup{0u, 0u, s});
+    else P.template finish<TAX, KN>(lane, K, tab, ws, cands, GwEntRecord{work});
     if (lane == 0) {
         if (ws.sliceFill) ws.sliceFill[w0] = (uint32_t)sliceUsed;
         if (deferred) atomicAdd(&ws.midCount[kCntSecond], deferred);
@@ -1828,8 +1861,19 @@ void launch_gw_cands(FilterStep step, const BatchView& b, const SketchParams& sp
         else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
     } else if (step == FilterStep::FilterLookup) {
         // the seven-wave instance walking the reads, the direct-index lookups inside ("filter_lookup"; behind the launch over kListFilter)
-        if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7, true>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
-        else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7, true>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        // (round 11: the shape-fixed instance where the batch has one -- lookup_shape, query_rules.h)
+        const LookupShape fx = lookup_shape(b.maxWin != nullptr, b.maxWinUniform, maxCand);
+        auto go = [&](auto win, auto k) {
+            constexpr uint32_t MW = decltype(win)::value, KF = decltype(k)::value;
+            if (taxkey) hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, true, 7, true, MW, KF>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+            else hipLaunchKernelGGL((gw_filter_count_kernel<4, 14, false, 7, true, MW, KF>), dim3(fgrid), dim3(256), 0, st, b, tab, ws, maxCand, taxkey, c, sp.s);
+        };
+        using U = std::integral_constant<uint32_t, 0>;
+        if (fx.maxWin == 3 && fx.k == 2) go(std::integral_constant<uint32_t, 3>{}, std::integral_constant<uint32_t, 2>{});
+        else if (fx.maxWin == 2 && fx.k == 2) go(std::integral_constant<uint32_t, 2>{}, std::integral_constant<uint32_t, 2>{});
+        else if (fx.maxWin == 3 && fx.k == 1) go(std::integral_constant<uint32_t, 3>{}, std::integral_constant<uint32_t, 1>{});
+        else if (fx.maxWin == 2 && fx.k == 1) go(std::integral_constant<uint32_t, 2>{}, std::integral_constant<uint32_t, 1>{});
+        else go(U{}, U{});
     } else if (step == FilterStep::PairFilter) {
         // reads of up to 2 x kGwRounds rounds (read pairs): two register batches
         // ("gw_fuse" 5 also brings back the pair filter of rounds 3-5: both filter halves of 2^15 bits, 38 KB per block, four waves per SIMD)

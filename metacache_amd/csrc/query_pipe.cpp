@@ -122,7 +122,13 @@ static void run_filter_step(mc_ctx* ctx, BatchRun& r)
 {
     ScopedTimer t(ctx, r.compact ? (r.ws.gwFuse ? "gw_filter_count" : "gw_filter") : "big_filter", r.st);
     launch_big_cands(FilterStep::Filter, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
-    if (r.compact && r.ws.filterLookup) launch_big_cands(FilterStep::FilterLookup, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
+    if (r.compact && r.ws.filterLookup) {
+        launch_big_cands(FilterStep::FilterLookup, r.b, r.sp, r.tab, r.ws, r.K, r.taxkey, r.cands, r.st);
+        if (ctx->timing) {                                         // which LOOKUP instance the launcher's rule picked: a launch count, no events
+            std::lock_guard<std::mutex> l(ctx->timerMtx);
+            ++ctx->timers[lookup_shape_name(lookup_shape(r.b.maxWin != nullptr, r.b.maxWinUniform, r.K))].launches;
+        }
+    }
 }
 
 static int run_filtered_path(mc_ctx* ctx, Pipe& P, BatchRun& r, bool second, bool deferSorted = false, bool filterDone = false)

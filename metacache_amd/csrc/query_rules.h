@@ -72,6 +72,24 @@ constexpr LaneStage lane_stage(QueryWants w, LaneSwitches sw, LaneTable t, Batch
     return LaneStage{filterLookup ? LaneOrder::FilterLookup : fuseSketch ? LaneOrder::Fused : LaneOrder::Apart, maskFeatures};
 }
 
+// ---- which instance of gw_filter_count_kernel<LOOKUP> walks the batch's reads ----
+// The kernel has instances compiled for ONE window range and ONE candidate count (round 11: the frame, the neighbour windows and the K
+// rounds are constants of their code).  A batch gets one when its reads share a window range (no range per read) of 2 or 3 windows and it
+// asks for 1 or 2 candidates per read -- the reference's defaults for single reads of up to 224 bp; {0, 0}: the instance for any batch.
+struct LookupShape { uint32_t maxWin, k; };
+constexpr bool operator==(LookupShape a, LookupShape b) { return a.maxWin == b.maxWin && a.k == b.k; }
+constexpr LookupShape lookup_shape(bool windowsPerRead, uint32_t uniformWindows, uint32_t maxCand)
+{
+    const bool fixed = !windowsPerRead && (uniformWindows == 2u || uniformWindows == 3u) && (maxCand == 1u || maxCand == 2u);
+    return fixed ? LookupShape{uniformWindows, maxCand} : LookupShape{0u, 0u};
+}
+// the name under which mc_timing_get counts the launches of the picked instance (tests look at it; no kernel is timed under it)
+constexpr const char* lookup_shape_name(LookupShape f)
+{
+    return f.maxWin == 3u ? (f.k == 2u ? "gw_filter_lookup_w3_k2" : "gw_filter_lookup_w3_k1")
+         : f.maxWin == 2u ? (f.k == 2u ? "gw_filter_lookup_w2_k2" : "gw_filter_lookup_w2_k1") : "gw_filter_lookup_any";
+}
+
 // ---- the work lists' counters as the host knows them ----
 // small batches take one look at the work lists and launch only the kernels with work (a launch costs as much as such a batch's kernel:
 // 0.37 -> 0.32 ms per 65 536 reads); large ones skip the round trip and launch everything.  MC_DEFER_TAIL: no look either -- the caller has
