@@ -9,6 +9,7 @@ import pytest
 
 import table_info_ref as ref
 from metacache_amd import api, synth
+from table_model import Table, as_pairs, check_table      # noqa: F401 (the model of a table's arrays, shared with the builder's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,47 +27,6 @@ def mix32(x):
 
 def home_bucket(keys, nbuckets):
     return (mix32(keys) * np.uint64(nbuckets)) >> np.uint64(32)
-
-
-class Table:
-    """the arrays of one table: keys[n] (distinct), sizes[n] (1 .. 255), vals[sum sizes, 2] = {win, tgt} in file order"""
-
-    def __init__(self, keys, sizes, vals):
-        self.keys = np.asarray(keys, dtype=np.uint32)
-        self.sizes = np.asarray(sizes, dtype=np.uint8)
-        self.vals = np.ascontiguousarray(vals, dtype=np.uint32).reshape(-1, 2)
-        assert len(np.unique(self.keys)) == len(self.keys) and int(self.sizes.astype(np.int64).sum()) == len(self.vals) and self.sizes.min() >= 1
-        self.first = np.concatenate([[0], np.cumsum(self.sizes.astype(np.int64))])[:-1]
-
-    def stored(self, max_locs=0, rm_over=0):
-        """the sizes after the load-time rules (0: not stored)"""
-        eff = self.sizes.astype(np.int64)
-        if rm_over:
-            eff = np.where(eff > rm_over, 0, eff)
-        if max_locs:
-            eff = np.minimum(eff, max_locs)
-        return eff
-
-    def features(self, **rules):
-        eff = self.stored(**rules)
-        order = np.argsort(self.keys, kind="stable")
-        order = order[eff[order] > 0]
-        return self.keys[order], eff[order].astype(np.uint32)
-
-    def lookup(self, queries, **rules):
-        """-> (offsets[n + 1], locs[total, 2]) of the model"""
-        eff = self.stored(**rules)
-        queries = np.asarray(queries, dtype=np.uint32)
-        order = np.argsort(self.keys, kind="stable")
-        pos = np.searchsorted(self.keys[order], queries)
-        pos = np.minimum(pos, len(order) - 1)
-        idx = order[pos]
-        found = self.keys[idx] == queries
-        n = np.where(found, eff[idx], 0)
-        offsets = np.concatenate([[0], np.cumsum(n)]).astype(np.uint64)
-        total = int(offsets[-1])
-        flat = np.repeat(self.first[idx], n) + (np.arange(total) - np.repeat(offsets[:-1].astype(np.int64), n))
-        return offsets, self.vals[flat]
 
 
 def load(table, layout, **cfg_kw):
@@ -113,25 +73,6 @@ def load(table, layout, **cfg_kw):
     except Exception:
         db.close()
         raise
-
-
-def as_pairs(locs):
-    return np.stack([locs["win"], locs["tgt"]], axis=1)
-
-
-def check_table(db, table, queries, **rules):
-    """histogram, enumeration and lookups of a loaded table against the model"""
-    keys, sizes = table.features(**rules)
-    hist, dead = db.table_histogram()
-    assert hist.dtype == np.uint64 and np.array_equal(hist, np.bincount(sizes, minlength=256)) and hist[0] == 0
-    assert dead == len(table.keys) - len(keys)
-    gk, gs = db.table_features()
-    assert np.array_equal(gk, keys) and np.array_equal(gs, sizes)
-    for q in (queries, keys, keys[::-1]):
-        off, locs = db.table_lookup(q)
-        eoff, elocs = table.lookup(q, **rules)
-        assert np.array_equal(off, eoff)
-        assert np.array_equal(as_pairs(locs), elocs)
 
 
 def edge_table(rng, nbuckets=None):
